@@ -11,14 +11,16 @@ backward -> (DDP gradient all-reduce over RCCL, overlapped with backward) -> gra
 into the libwft multi-tensor AdamW — driven by the product's own `model_utils.train_step` (per-micro-batch loss.item(),
 scheduler step included).  68 clips per GPU per step by default (180 GiB of the 288 GB HBM).
 Weights: random init of the whisper-large-v3 architecture; data: synthetic (no network).
-Rank 0 prints ONE JSON line (contract in the task statement); it also carries
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times the K steps and prints that
+line: "roofline" and "cpu_baseline" are null there and nothing else is measured.  `--full` adds everything below (the
+`--no-roofline`, `--no-cpu-baseline` and `--no-extras` switches trim a `--full` run):
   "roofline":     the dominant kernel (the NT GEMM family with the most time — gemm_nt4w_kernel since round 4: the
                   Linear / logits forward and backward-data GEMMs), algorithmic FLOPs (2*M*N*K) / HIP-event time of its launches
                   during one instrumented step that follows the timed region; "traffic" = HBM-side
                   bytes per launch from the committed rocprofv3 PMC passes of this command (profiles/);
   "cpu_baseline": the CPU oracle (oracle/whisper_oracle.py, torch fp32) forward+backward on a
                   bounded sample, timed on this box's host cores (N=1 only);
-and, on the default (headline) invocation, extra keys measured in the same process after the headline:
+and, on the `--full` headline invocation, extra keys measured in the same process after the headline:
   "hand_rolled_ms_per_step": round 1's hand-written loop on the same state (cross-check of the product loop),
   "reference_yaml_shapes":   the reference YAML's batch 32 at S = 128 and at the S = 448 stress length,
   "configs2_lora_muon":      BASELINE configs[2] (LoRA r16 + Muon + stochastic depth + deep SpecAugment, B = 32) with
@@ -33,7 +35,12 @@ and, on the default (headline) invocation, extra keys measured in the same proce
                              launches), with and without a side-stream kernel that holds CUs and moves the ring's bytes,
   "cpu_baseline_small_models": the oracle's step for whisper-tiny / whisper-base (B = 2) on all host cores and on one.
 `ms_per_step` is the mean over the K timed steps (the contract's clock); `ms_per_step_median` is the median of the per-step
-wall times inside that region (train_step ends with loss.item()).  `--no-extras` prints the headline only.
+wall times inside that region (train_step ends with loss.item()).  Multi-GPU `--full` runs add the "ddp" object (the no_sync twin).
+
+`--dump-outputs DIR` (rank 0) writes what the last timed step handed its caller, after the timed region: loss.npy (float64, the
+step's loss as train_step returned it) and, for the model after that step's update, params_sample.npy plus one
+opt_<state>_sample.npy per floating optimizer state (exp_avg, exp_avg_sq for AdamW), float32.  Every parameter tensor
+contributes the same fixed, seeded element sample (all of it when it is small), in named_parameters() order; 64 MB at most.
 """
 from __future__ import annotations
 
@@ -271,9 +278,10 @@ class Case:
             return (2.0 * (f_fwd - f_att) + 3.0 * f_att + 3.0 * lora_flops_per_clip(self.dims, S, 16)) * B
         return 3.0 * f_fwd * B
 
-    def measure(self, B, S, steps, warmup, roofline=True, hand_rolled_steps=0, ddp_twin=True):
+    def measure(self, B, S, steps, warmup, roofline=True, hand_rolled_steps=0, ddp_twin=True, dump_dir=None):
         """-> dict(value, ms_per_step, ...) for `B` clips per GPU and decoder length S; max over ranks of the wall time of
-        exactly `steps` optimizer steps between barrier + synchronize."""
+        exactly `steps` optimizer steps between barrier + synchronize.  dump_dir: rank 0 writes the last timed step's outputs
+        there (dump_outputs) before anything else runs on the model."""
         import whisper_finetune.runtime as rt
         from whisper_finetune.engine import kernels as K
         from whisper_finetune.model.model_utils import train_step
@@ -320,6 +328,8 @@ class Case:
             t = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = t.item()
+        if dump_dir is not None and rank == 0:
+            self.dump_outputs(dump_dir, loss)
         res = {"batch": B, "seq_len": S, "ms_per_step": round(dt / steps * 1e3, 2),
                "ms_per_step_median": round(sorted(per_step)[len(per_step) // 2] * 1e3, 2),
                "value": round(B * self.world * steps * 30.0 / dt, 1), "final_loss": round(float(loss), 4)}
@@ -401,6 +411,36 @@ class Case:
         rt.IS_DISTRIBUTED = False
         del audio
         return res
+
+    def dump_outputs(self, out_dir, loss, max_bytes=64_000_000, per_tensor=2048):
+        """The last step's loss (float64) and a fixed sample of the updated parameters and optimizer states (float32).  The
+        sample of a parameter depends only on its position in named_parameters() and its size, so two builds of the project
+        draw the same elements."""
+        import numpy as np
+
+        out = Path(out_dir)
+        out.mkdir(parents=True, exist_ok=True)
+        np.save(out / "loss.npy", np.array([float(loss)], dtype=np.float64))
+        params = [p for _, p in self.model.named_parameters()]
+        keys = sorted({k for p in params for k, v in self.opt.state.get(p, {}).items()
+                       if torch.is_tensor(v) and v.is_floating_point() and v.numel() == p.numel()})
+        per_tensor = min(per_tensor, max_bytes // (4 * (1 + len(keys)) * len(params)))
+        cols = {"params": []}
+        cols.update({f"opt_{k}": [] for k in keys})
+        for i, p in enumerate(params):
+            n = p.numel()
+            idx = None
+            if n > per_tensor:
+                g = torch.Generator().manual_seed(i)
+                idx = torch.randint(0, n, (per_tensor,), generator=g).to(p.device)
+            st = self.opt.state.get(p, {})
+            for name, t in [("params", p)] + [(f"opt_{k}", st.get(k)) for k in keys]:
+                if t is None:
+                    continue
+                flat = t.detach().reshape(-1)
+                cols[name].append((flat if idx is None else flat[idx]).float().cpu())
+        for name, parts in cols.items():
+            np.save(out / f"{name}_sample.npy", torch.cat(parts).numpy().astype(np.float32))
 
     def release(self):
         self.net = self.model = self.opt = self.sched = None
@@ -527,11 +567,18 @@ def main():
     ap.add_argument("--stochastic-depth", type=float, default=0.0)
     ap.add_argument("--deep-spec-augment", action="store_true")
     ap.add_argument("--hip-graph", action="store_true", help="training.wft_hip_graph: the micro-batch as one captured HIP graph (small models)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, also measure the roofline step, the CPU baselines, the DDP no_sync twin and (default "
+                         "headline configuration, one GPU) the extras: hand-rolled loop, reference-YAML shapes, BASELINE configs "
+                         "sub-benches, DDP-mode block, entrypoint loop")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and a fixed sample of the updated parameters / optimizer states "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the instrumented roofline step")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the headline line: skip the reference-YAML shapes (B=32 at S=128 / S=448), the hand-rolled-loop "
-                         "cross-check and the LoRA+Muon (configs[2]) sub-bench")
+                    help="with --full: skip the reference-YAML shapes (B=32 at S=128 / S=448), the hand-rolled-loop "
+                         "cross-check and the configuration sub-benches")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", 0))
@@ -560,12 +607,14 @@ def main():
     B, S = args.batch, args.seq
     headline_default = args.model == "large-v3" and not (args.lora or args.muon or args.stochastic_depth > 0 or args.deep_spec_augment)
     # the extra lines are single-GPU measurements (the driver's N > 1 runs time the headline only: weak scaling of ONE workload)
-    extras = headline_default and not args.no_extras and world == 1
+    extras = args.full and headline_default and not args.no_extras and world == 1
+    roofline = args.full and not args.no_roofline
     case = Case(args, device, rank, local_rank, world, ddp, lora=args.lora, muon=args.muon, sd=args.stochastic_depth,
                 dsa=args.deep_spec_augment)
     if args.hip_graph:
         case.t_cfg["wft_hip_graph"] = True
-    head = case.measure(B, S, args.steps, args.warmup, roofline=not args.no_roofline, hand_rolled_steps=3 if extras else 0)
+    head = case.measure(B, S, args.steps, args.warmup, roofline=roofline, hand_rolled_steps=3 if extras else 0,
+                        ddp_twin=args.full, dump_dir=args.dump_outputs)
     hbm_peak = round(torch.cuda.max_memory_allocated() / 2**30, 1)
     other = []
     lora_line = None
@@ -583,7 +632,7 @@ def main():
         case.release()
         # BASELINE configs[2]: large-v3 LoRA r16 + Muon/AuxAdam + stochastic depth 0.1 + deep SpecAugment at the YAML's B = 32
         c2 = Case(args, device, rank, local_rank, world, ddp, lora=True, muon=True, sd=0.1, dsa=True)
-        lora_line = c2.measure(32, 128, 4, 2, roofline=not args.no_roofline)
+        lora_line = c2.measure(32, 128, 4, 2, roofline=roofline)
         lora_line["workload"] = f"whisper-large-v3 {c2.mode()}, 32 clips per GPU per step, S=128 (BASELINE configs[2] shape)"
         c2.release()
         # BASELINE configs[1]: whisper-base full fine-tune, 8 clips (host-bound: 810 launches of 13 ms of kernels per step)
@@ -592,7 +641,7 @@ def main():
         c1 = Case(args, device, rank, local_rank, world, ddp, model_name="base")
         eager = c1.measure(8, 128, 20, 5, roofline=False)
         c1.t_cfg["wft_hip_graph"] = True
-        base_line = c1.measure(8, 128, 30, 8, roofline=not args.no_roofline)
+        base_line = c1.measure(8, 128, 30, 8, roofline=roofline)
         base_line["eager_ms_per_step"], base_line["eager_ms_per_step_median"] = eager["ms_per_step"], eager["ms_per_step_median"]
         from whisper_finetune.engine import graph as _G
         gm = _G.graphed_for(c1.model)
@@ -602,7 +651,7 @@ def main():
         c1.release()
         # BASELINE configs[4]'s per-GPU workload: large-v3-turbo (4-layer decoder), LoRA r16, prompt + timestamp targets, B = 64
         c4 = Case(args, device, rank, local_rank, world, ddp, lora=True, model_name="large-v3-turbo", prompt_ts=True)
-        turbo_line = c4.measure(64, 128, 4, 2, roofline=not args.no_roofline)
+        turbo_line = c4.measure(64, 128, 4, 2, roofline=roofline)
         turbo_line["workload"] = (f"whisper-large-v3-turbo {c4.mode()}, 64 clips per GPU per step, 64-token prompt (-100 targets) + 128 "
                                   "transcript positions with a timestamp token every 16th (BASELINE configs[4] per-GPU shape)")
         c4.release()
@@ -656,7 +705,7 @@ def main():
             out["configs4_turbo_lora"] = turbo_line
         if entry_line is not None:
             out["entrypoint_loop"] = entry_line
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.model if args.model in ("tiny", "base", "small", "large-v3", "large-v3-turbo") else "large-v3", S)
             except Exception as exc:  # the baseline is informative; never lose the GPU number over it

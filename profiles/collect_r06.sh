@@ -2,7 +2,7 @@
 # Run ON THE GPU BOX from the repo root:  bash profiles/collect_r06.sh <tag> [what]
 #   what = all (default) | bench | stats | pmc | lora | mfma | base
 # Round 6 (headline batch 96).  Produces under gpurun_out/<tag>/ :
-#   bench.json.log            the default bench.py invocation (headline + extras: reference-YAML shapes, configs[1] / [2] / [4],
+#   bench.json.log            the `bench.py --full` invocation (headline + extras: reference-YAML shapes, configs[1] / [2] / [4],
 #                             entrypoint loop)
 #   stats/                    rocprofv3 --kernel-trace --stats of the headline configuration (--no-extras)
 #   pmc_summary.json          FETCH_SIZE / WRITE_SIZE per kernel of the headline (separate --pmc passes)  -> roofline.traffic
@@ -21,12 +21,12 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 cd $R
-HEAD="--no-cpu-baseline --no-extras"
+HEAD="--full --no-cpu-baseline --no-extras"
 LORA="--lora --muon --stochastic-depth 0.1 --deep-spec-augment --batch 32 --no-cpu-baseline --no-extras"
 want() { [ "$WHAT" = all ] || [ "$WHAT" = "$1" ]; }
 
 if want bench; then
-  python3 bench.py > $OUT/bench.json.log 2> $OUT/bench.err.log
+  python3 bench.py --full > $OUT/bench.json.log 2> $OUT/bench.err.log
   tail -1 $OUT/bench.json.log | cut -c1-400
 fi
 if want stats; then

@@ -18,7 +18,8 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 def test_bench_prints_one_json_line_last(force_ddp):
     env = dict(os.environ, WFT_BENCH_FORCE_DDP="1" if force_ddp else "0", MASTER_PORT="29577")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--model", "base", "--batch", "4", "--seq", "32", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, env=env, cwd=str(ROOT), timeout=600)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"],
+                       capture_output=True, text=True, env=env, cwd=str(ROOT), timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
     out = json.loads(lines[-1])  # the JSON object is the last line even when RCCL prints its banners
@@ -45,10 +46,30 @@ def test_bench_through_the_drivers_launcher_line():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "1", "--model", "base", "--batch", "4", "--seq", "32",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=str(ROOT), timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1
     out = json.loads(lines[-1])
     assert REQUIRED <= set(out) and out["n_gpus"] == 1 and out["value"] > 0 and out["config"]["parallelism"] == "dp1"
+
+
+def test_plain_run_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps, measures nothing beside them, and --dump-outputs writes the last
+    timed step's loss and the sampled model / optimizer state as float32 / float64 .npy files, 64 MB at most."""
+    import numpy as np
+
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--model", "base", "--batch", "4", "--seq", "32", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, cwd=str(ROOT), timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.strip()][-1])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["roofline"] is None and out["cpu_baseline"] is None and "hand_rolled_ms_per_step" not in out
+    files = {f.name: np.load(f) for f in (tmp_path / "out").glob("*.npy")}
+    assert {"loss.npy", "params_sample.npy", "opt_exp_avg_sample.npy", "opt_exp_avg_sq_sample.npy"} <= set(files)
+    assert files["loss.npy"].dtype == np.float64 and abs(files["loss.npy"][0] - out["final_loss"]) < 1e-3
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+    assert files["params_sample.npy"].shape == files["opt_exp_avg_sample.npy"].shape
+    assert sum(f.stat().st_size for f in (tmp_path / "out").iterdir()) <= 64_000_000
