@@ -293,6 +293,10 @@ int64_t wft_gemm_nt_aux8_bytes(const wft_gemm_args* args);
  *  Uses the same wft_gemm_args: M:=P, N:=Q, K:=R; bias/residual/aux ignored.
  *  batch > 1 sums over the batch as extra reduction (conv weight grads).     */
 int wft_gemm_tn_bf16(const wft_gemm_args* args, void* stream);
+/* Which kernel wft_gemm_tn_bf16 dispatches these arguments to: 4 (gemm_tn4w_kernel, one wave per SIMD), 256 (gemm_tn256_kernel, the
+ * 8-wave ping-pong 256x256 kernel) or 128 (the 128-tile kernel and its rank-r form).  Pure host function from the launcher's own
+ * predicates, workspace fields included (a split-K plan without its workspace runs on the 8-wave kernel); tests assert the dispatch. */
+int wft_gemm_tn_variant(const wft_gemm_args* args);
 /* Two independent rank-r products (p_valid > 0) in ONE launch of the load-stream kernels — the backward of an adapted Linear
  * group in the reference's parametrization (src/whisper_finetune/model/lora.py:30-71 via minLoRA; loss.backward() at
  * model/model_utils.py:63-72) needs {u = x (sA*m)^T, du = dy (sB)} and then {dA = du^T x, dB^T = u^T dy}: each pair is one call.

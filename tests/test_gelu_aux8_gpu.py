@@ -15,36 +15,13 @@ from whisper_finetune.engine import kernels as K  # noqa: E402
 from whisper_finetune.engine import lib as L  # noqa: E402
 from whisper_finetune.engine import ops  # noqa: E402
 
+from tests._gelu_codes import _code_index, _decode, _dgelu  # noqa: E402
+
 DEV = "cuda:0"
 
 
 def bf(x):
     return x.to(torch.bfloat16)
-
-
-def _dgelu(x):
-    x = x.double()
-    return 0.5 * (1 + torch.erf(x / 2 ** 0.5)) + x * torch.exp(-x * x / 2) / (2 * torch.pi) ** 0.5
-
-
-def _code_index(M, N):
-    """byte offset of element (m, n) in the fragment-ordered buffer (wft.h / gemm_nt4w.hip): int64 [M, N]"""
-    m = torch.arange(M, device=DEV).view(-1, 1)
-    n = torch.arange(N, device=DEV).view(1, -1)
-    tiles_n = N // 256
-    tm, r = m // 256, m % 256
-    tn, c = n // 256, n % 256
-    wave = (r // 128) * 2 + c // 128
-    fx, mr = (r % 128) // 16, r % 16
-    cc = c % 128
-    u, q, e = cc // 32, (cc % 32) // 8, cc % 8
-    up, hh = u // 2, u % 2
-    lane = q * 16 + mr
-    return ((tm * tiles_n + tn) * 4 + wave) * 16384 + (up * 8 + fx) * 1024 + lane * 16 + hh * 8 + e
-
-
-def _decode(codes, M, N):
-    return (codes[_code_index(M, N)].float() - 26.0) / 200.0
 
 
 @pytest.mark.parametrize("M,N,Kd", [(8192 + 112, 1024, 768), (4500, 5120, 1280), (33000, 1536, 384)])

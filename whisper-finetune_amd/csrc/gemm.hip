@@ -2025,6 +2025,21 @@ extern "C" int64_t wft_gemm_tn_workspace_bytes(const wft_gemm_args* a) {
   return (nsplit > 1 || tn_needs_reduce(a)) ? (int64_t)nsplit * tn_ws_rows(a) * a->N * 4 : 0;
 }
 
+// Which kernel wft_gemm_tn_bf16 below serves these arguments with (pure host function, like wft_gemm_nt_variant: the launcher's own
+// predicates in the launcher's order, nothing launched): 4 gemm_tn4w_kernel, 256 gemm_tn256_kernel, 128 the 128-tile kernel and its
+// rank-r load-stream form
+extern "C" int wft_gemm_tn_variant(const wft_gemm_args* a) {
+  if (!a || !tn_uses_256(a)) return 128;
+  if (g_tn_variant != 1 && a->variant == 0 && wft_tn4w_eligible(a)) {
+    int nsplit, per;
+    wft_tn4w_plan(a, &nsplit, &per);
+    const bool use_ws = (nsplit > 1 || a->tn_seg_count > 0) && a->workspace && a->workspace_bytes >= (int64_t)nsplit * a->M * a->N * 4 &&
+                        (((uintptr_t)a->workspace) & 15) == 0;
+    if (nsplit == 1 || use_ws) return 4;  // (split without a workspace: the ping-pong kernel's atomic path)
+  }
+  return 256;
+}
+
 extern "C" int wft_gemm_tn_bf16(const wft_gemm_args* a, void* stream) {
   WFT_CHECK_ARG(a && a->A && a->B && a->C, "null pointer");
   WFT_CHECK_ARG(a->M >= 128 && a->N >= 128 && a->K >= 1 && a->batch >= 1, "bad shape");

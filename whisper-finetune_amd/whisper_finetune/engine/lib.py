@@ -109,6 +109,7 @@ SIGNATURES = {
     "wft_gemm_nt_splitk_workspace_bytes": [C.POINTER(GemmArgs)],
     "wft_gemm_nt_aux8_bytes": [C.POINTER(GemmArgs)],
     "wft_gemm_tn_bf16": [C.POINTER(GemmArgs), c_vp],
+    "wft_gemm_tn_variant": [C.POINTER(GemmArgs)],
     "wft_gemm_nt_rank_pair_bf16": [C.POINTER(GemmArgs), C.POINTER(GemmArgs), c_vp],
     "wft_gemm_tn_rank_pair_bf16": [C.POINTER(GemmArgs), C.POINTER(GemmArgs), c_vp],
     "wft_gemm_tn_workspace_bytes": [C.POINTER(GemmArgs)],
