@@ -393,6 +393,59 @@ int wft_ce_bwd(const wft_bf16* logits, int64_t ld, const int64_t* targets,
 int wft_token_stats(const wft_bf16* logits, int64_t ld, const int64_t* targets,
                     int64_t rows, int64_t V, float* out4, int64_t* argmax, void* stream);
 
+/* -------------------------------------------------------- Greedy decoding */
+/* KV-cached greedy decoding (csrc/decode.hip): the single-token shapes of upstream's `whisper.decoding.GreedyDecoder` /
+ * `DecodingTask._main_loop` with `DecodingOptions(without_timestamps=True)` and the `kv_cache` hooks of
+ * whisper.model.MultiHeadAttention.forward (none of it is in the reference tree, whose evaluator is teacher-forced:
+ * eval/evaluator.py:70-73).  Everything that changes from token to token is DEVICE state — len i32 [B] (tokens a row holds,
+ * prompt included), tokens i64 [B, ld_tokens], finished i32 [B], sum_logprob f32 [B] — so no argument depends on the step.
+ *
+ * Single-token attention, head_dim 64: o[b, h] = softmax(q[b, h] . K[b, :n, h] * scale) V[b, :n, h], fp32 softmax.
+ *  q: bf16, row b at q + b*ldq, head h at + h*64; o likewise (ldo);
+ *  cache: key t of sequence b at k_cache + b*cache_bs + t*ld_cache + h*64, values at v_cache + the same offsets (one buffer
+ *    of [B, Tk, 2d] rows {k | v} serves both: v_cache = k_cache + d, ld_cache = 2d);
+ *  self-attention form (len != NULL): n = len[b] (clamped to 1..Tk, Tk = the cache's capacity); the step's k / v rows
+ *    (k_new / v_new + b*ld_new: the k and v thirds of the fused [B, 3d] projection output) are WRITTEN to cache row len[b] - 1
+ *    and take part as key len[b] - 1 — the append is fused, no other byte of the cache changes;
+ *  cross-attention form (len == NULL): n = Tk for every sequence, the cache is only read;
+ *  q_prescaled: as in wft_attn_args (q already carries scale * log2(e); `scale` is still required);
+ *  workspace: wft_attn_decode_workspace_bytes(args) bytes (0: none needed) — when B*H alone does not fill the chip the keys
+ *    are split over several workgroups whose partial (max, sum, o) are merged by a second kernel in split order.  No atomics:
+ *    the same arguments give the same bits.  The split depends on B, H and Tk only.                                          */
+typedef struct {
+  const wft_bf16* q; int64_t ldq;
+  const wft_bf16* k_new; const wft_bf16* v_new; int64_t ld_new;
+  wft_bf16* k_cache; wft_bf16* v_cache; int64_t ld_cache; int64_t cache_bs;
+  wft_bf16* o; int64_t ldo;
+  const int32_t* len;
+  int B; int H; int Tk; float scale; int q_prescaled;
+  void* workspace; int64_t workspace_bytes;
+} wft_attn_decode_args;
+int wft_attn_decode_bf16(const wft_attn_decode_args* args, void* stream);
+int64_t wft_attn_decode_workspace_bytes(const wft_attn_decode_args* args);
+/* out[b, :] = emb[tokens[b, len[b] - 1], :] + pos[len[b] - 1, :] (bf16): wft_embed_fwd for ONE token per sequence at the
+ * position device memory names (TextDecoder.forward's `offset` under a kv_cache upstream).  Same bits as wft_embed_fwd.   */
+int wft_decode_embed(const int64_t* tokens, int64_t ld_tokens, const int32_t* len, const float* emb, const float* pos,
+                     wft_bf16* out, int B, int n_ctx, int d, int64_t V, void* stream);
+/* Greedy pick for every sequence from its bf16 logits row (logits + b*ld; only the first V columns are read):
+ *  columns with suppress[col] != 0 are removed (u8 [V] or NULL: upstream's SuppressTokens); suppress_first (u8 [V] or NULL)
+ *    removes more for a row's FIRST generated token only, i.e. while len[b] == first_len[b] (upstream's SuppressBlank);
+ *  pick = argmax of what is left, lowest index on ties (the rule of wft_ce_fwd / wft_token_stats); logprob = its
+ *    log-probability under the softmax of the SUPPRESSED logits (upstream's GreedyDecoder.update runs after the filters);
+ *  an unfinished row: tokens[b, len[b]] = pick, sum_logprob[b] += logprob, len[b] += 1,
+ *    finished[b] = pick == eot || len[b] == max_len.  A finished row is frozen: nothing of its state changes (upstream stops
+ *    adding log-probabilities once the last token is eot).  unfinished[0] = number of rows still unfinished after the update.
+ *  pick_out i64 [B] / logprob_out f32 [B] (optional): what the step computed for every row, finished or not.                */
+typedef struct {
+  const wft_bf16* logits; int64_t ld; int64_t V;
+  const uint8_t* suppress; const uint8_t* suppress_first; const int32_t* first_len;
+  int64_t* tokens; int64_t ld_tokens;
+  int32_t* len; int32_t* finished; float* sum_logprob; int32_t* unfinished;
+  int64_t* pick_out; float* logprob_out;
+  int B; int eot; int max_len;
+} wft_decode_pick_args;
+int wft_decode_pick(const wft_decode_pick_args* args, void* stream);
+
 /* ------------------------------------------------- Log-mel + SpecAugment */
 /* whisper.audio.log_mel_spectrogram (data/data_loader.py:278; SURVEY.md App.
  * A.2): reflect-pad 200, Hann-400 STFT hop 160, |.|^2, mel filterbank,

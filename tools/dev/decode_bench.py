@@ -1,0 +1,226 @@
+"""Measurements behind the greedy-decoding rows of DESIGN.md (large-v3 shapes: H = 20, d = 1280, 32 layers), HIP events, warmed up.
+
+  attn   wft_attn_decode_bf16 against the same work through wft_attn_fwd_bf16 with Tq = 1, causal = 0, Tk = the common length,
+         alternating the two in one process (median / min / spread over the rounds), and as achieved bytes/s over the K/V bytes
+         the shape needs.  Every arm walks the 32 layers' buffers in rotation, as a decoding step does: a single buffer of a
+         small batch would sit in the Infinity Cache and time the cache, not the memory.
+  gemm   every wft_gemm_nt_bf16 call of one cached step at M = B: the kernel wft_gemm_nt_variant reports, time, and time over
+         (weight bytes / HBM rate) — the price list for a weight-streaming small-M GEMM.  Recorded, not acted on.
+  e2e    tokens/s of Whisper.greedy_decode against a loop of model.logits(tokens, xa) re-forwards (same prompts, 64 new tokens).
+
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e] [--batches 1,8,32] [--out FILE]
+"""
+import argparse
+import ctypes as C
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parents[2]
+for p in (str(ROOT / "whisper-finetune_amd"), str(ROOT)):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from whisper_finetune.engine import kernels as K  # noqa: E402
+from whisper_finetune.engine import lib as L  # noqa: E402
+from whisper_finetune.engine.whisper_model import MODEL_DIMS, Whisper  # noqa: E402
+
+DEV = torch.device("cuda:0")
+BF = torch.bfloat16
+H, D, LAYERS, CAP, TA = 20, 1280, 32, 448, 1500
+HBM = 6.3e12  # achievable HBM rate of the MI355X, bytes/s (8.0e12 on the data sheet)
+OUT = []
+
+
+def emit(rec):
+    OUT.append(rec)
+    print(json.dumps(rec), flush=True)
+
+
+def timed(fn, iters):
+    """ms per call of fn() over `iters` back-to-back calls between two events (the launches are queued ahead of the GPU where
+    the kernel is longer than a launch; where it is not, the figure is the launch rate — said in the table)."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def ab(arms, rounds=7, iters=8):
+    """arms: {name: fn}; alternating rounds in one process -> {name: (median, min, spread)} in ms; spread = (max - min) / median."""
+    for fn in arms.values():
+        fn(); fn()
+    ts = {n: [] for n in arms}
+    for _ in range(rounds):
+        for n, fn in arms.items():
+            ts[n].append(timed(fn, iters))
+    return {n: (statistics.median(v), min(v), (max(v) - min(v)) / statistics.median(v)) for n, v in ts.items()}
+
+
+def bench_attn(batches):
+    lib = L.load()
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for B in batches:
+        for form, Tk in (("self", 8), ("self", 224), ("self", 448), ("cross", TA)):
+            cap = CAP if form == "self" else TA
+            caches = [torch.randn(B, cap, 2 * D, device=DEV, generator=g).to(BF) for _ in range(LAYERS)]
+            qkv = torch.randn(B, 3 * D, device=DEV, generator=g).to(BF) * 0.3
+            lens = torch.full((B,), Tk, dtype=torch.int32, device=DEV)
+            new, old, keep = [], [], []
+            for c in caches:
+                if form == "self":
+                    a, o = K.attn_decode(qkv[:, :D], c, H, 0.125, new_kv=(qkv[:, D:2 * D], qkv[:, 2 * D:]), lens=lens, _args_only=True)
+                else:
+                    a, o = K.attn_decode(qkv[:, :D], c, H, 0.125, _args_only=True)
+                new.append(a); keep.append(o)
+                # the parent commit's way through the same ABI: one query row per sequence, no mask, one key count for the batch
+                # (it does not append the step's k / v: the self-attention comparison flatters it by that copy)
+                b = L.AttnArgs()
+                o2 = torch.empty(B, 1, D, dtype=BF, device=DEV); lse = torch.empty(B, H, 1, dtype=torch.float32, device=DEV)
+                b.q, b.ldq, b.q_bs = qkv.data_ptr(), 3 * D, 3 * D
+                b.k, b.ldk, b.k_bs = c.data_ptr(), 2 * D, cap * 2 * D
+                b.v, b.ldv, b.v_bs = c.data_ptr() + 2 * D, 2 * D, cap * 2 * D
+                b.o, b.ldo, b.o_bs = o2.data_ptr(), D, D
+                b.lse = lse.data_ptr()
+                b.B, b.H, b.Tq, b.Tk, b.causal, b.scale = B, H, 1, Tk, 0, 0.125
+                old.append(b); keep += [o2, lse]
+            st = L.stream_ptr()
+
+            def run_new():
+                for a in new:
+                    lib.wft_attn_decode_bf16(C.byref(a), st)
+
+            def run_old():
+                for b in old:
+                    lib.wft_attn_fwd_bf16(C.byref(b), st)
+
+            L.check(lib.wft_attn_decode_bf16(C.byref(new[0]), st), "wft_attn_decode_bf16")
+            L.check(lib.wft_attn_fwd_bf16(C.byref(old[0]), st), "wft_attn_fwd_bf16")
+            # same function: outputs agree to bf16 resolution at the size timed
+            # (self form: the first call appended the step's k / v at row Tk - 1, which is what the other arm then reads)
+            err = (keep[0].float() - keep[1].view(B, D).float()).abs().max().item()
+            res = ab({"decode": run_new, "fwd_tq1": run_old})
+            kv_bytes = B * H * Tk * 2 * 64 * 2
+            rec = dict(part="attn", B=B, form=form, Tk=Tk, kv_MB=round(kv_bytes / 1e6, 2), max_abs_diff=err,
+                       workspace_bytes=int(lib.wft_attn_decode_workspace_bytes(C.byref(new[0]))))
+            for n, (med, mn, spread) in res.items():
+                rec[n + "_us"] = round(med * 1e3 / LAYERS, 2)
+                rec[n + "_min_us"] = round(mn * 1e3 / LAYERS, 2)
+                rec[n + "_spread"] = round(spread, 3)
+                rec[n + "_GBps"] = round(kv_bytes / (med * 1e-3 / LAYERS) / 1e9, 1)
+            rec["speedup"] = round(res["fwd_tq1"][0] / res["decode"][0], 2)
+            emit(rec)
+            del caches, new, old, keep
+
+
+def bench_gemm(batches):
+    lib = L.load()
+    g = torch.Generator(device="cuda").manual_seed(1)
+    shapes = [("self q/k/v", 3 * D, D, LAYERS, L.EPI_NONE), ("self out", D, D, LAYERS, L.EPI_NONE), ("cross q", D, D, LAYERS, L.EPI_NONE),
+              ("cross out", D, D, LAYERS, L.EPI_NONE), ("mlp.0 + GELU", 4 * D, D, LAYERS, L.EPI_GELU), ("mlp.2", D, 4 * D, LAYERS, L.EPI_NONE),
+              ("tied logits", K.round_up(51866, 128), D, 4, L.EPI_NONE)]
+    for B in batches:
+        for name, N, Kd, copies, epi in shapes:
+            ws = [torch.randn(N, Kd, device=DEV, generator=g).to(BF) * 0.02 for _ in range(copies)]
+            x = torch.randn(B, Kd, device=DEV, generator=g).to(BF)
+            bias = torch.zeros(N, device=DEV)
+            calls, keep = [], []
+            for w in ws:
+                a, out = K.gemm_nt(x, w, bias=bias, epilogue=epi, _args_only=True)
+                calls.append(a); keep.append(out)
+            st = L.stream_ptr()
+
+            def run():
+                for a in calls:
+                    lib.wft_gemm_nt_bf16(C.byref(a), st)
+
+            L.check(lib.wft_gemm_nt_bf16(C.byref(calls[0]), st), "wft_gemm_nt_bf16")
+            med, mn, spread = ab({"nt": run})["nt"]
+            us = med * 1e3 / copies
+            floor_us = N * Kd * 2 / HBM * 1e6
+            emit(dict(part="gemm", B=B, call=name, N=N, K=Kd, kernel=int(lib.wft_gemm_nt_variant(C.byref(calls[0]))), us=round(us, 2),
+                      min_us=round(mn * 1e3 / copies, 2), spread=round(spread, 3), weight_MB=round(N * Kd * 2 / 1e6, 2),
+                      weight_floor_us=round(floor_us, 2), times_floor=round(us / floor_us, 1)))
+            del ws, calls, keep
+
+
+def bench_e2e(batches, new_tokens=64):
+    dims = MODEL_DIMS["large-v3"]
+    with torch.device(DEV):
+        m = Whisper(dims)
+    with torch.no_grad():
+        for n, p in m.named_parameters():
+            if p.dim() >= 2:
+                p.normal_(0, 0.02)
+            elif n.endswith("weight"):
+                p.fill_(1.0)
+            else:
+                p.zero_()
+    m.eval()
+    eot = 50257
+    for B in batches:
+        g = torch.Generator(device="cuda").manual_seed(B)
+        mel = torch.randn(B, dims.n_mels, 2 * dims.n_audio_ctx, device=DEV, generator=g)
+        prompt = torch.tensor([[50258, 50261, 50360, 50364]], device=DEV).expand(B, 4).contiguous()
+        max_len = 4 + new_tokens
+
+        def cached():
+            # eot suppressed: every row generates exactly new_tokens tokens
+            return m.greedy_decode(mel, prompt, None, eot=eot, max_len=max_len, suppress=[eot])
+
+        def reforward():
+            with torch.no_grad():
+                xa = m.embed_audio(mel)
+                toks = prompt
+                for _ in range(new_tokens):
+                    lg = m.logits(toks, xa)[:, -1]
+                    lg[:, eot] = float("-inf")
+                    toks = torch.cat([toks, lg.argmax(-1, keepdim=True)], 1)
+                return toks
+
+        res = {}
+        for name, fn in (("greedy_decode", cached), ("reforward", reforward)):
+            fn()  # warm-up: shadows, workspaces, code objects
+        for rnd in range(2):
+            for name, fn in (("greedy_decode", cached), ("reforward", reforward)):
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                out = fn()
+                torch.cuda.synchronize(); res.setdefault(name, []).append(time.perf_counter() - t0)
+                res[name + "_out"] = out
+        a, b = res["greedy_decode_out"][0][:, :max_len], res["reforward_out"]
+        emit(dict(part="e2e", B=B, new_tokens=new_tokens, greedy_decode_s=[round(t, 4) for t in res["greedy_decode"]],
+                  reforward_s=[round(t, 4) for t in res["reforward"]],
+                  greedy_decode_tok_s=round(B * new_tokens / min(res["greedy_decode"]), 1),
+                  reforward_tok_s=round(B * new_tokens / min(res["reforward"]), 1),
+                  speedup=round(min(res["reforward"]) / min(res["greedy_decode"]), 2),
+                  same_tokens_share=round((a == b).float().mean().item(), 4),
+                  note="both timings include the encoder pass; tokens differ only where two bf16 evaluations break a near-tie"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parts", default="attn,gemm,e2e")
+    ap.add_argument("--batches", default="1,8,32")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("decode_bench.py measures on the GPU: no device found (there is no CPU fallback)")
+    batches = [int(b) for b in a.batches.split(",")]
+    emit(dict(part="env", device=torch.cuda.get_device_name(0), lib=L.load().wft_version().decode(), torch=torch.__version__))
+    for part in a.parts.split(","):
+        {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e}[part](batches)
+    if a.out:
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))
+
+
+if __name__ == "__main__":
+    main()

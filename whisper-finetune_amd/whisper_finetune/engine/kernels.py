@@ -554,6 +554,88 @@ def attn_bwd(q, k, v, o, lse, do, n_head: int, causal: bool, scale: float, dq=No
     return dq, dk, dv
 
 
+# --------------------------------------------------------------------------- greedy decoding (csrc/decode.hip)
+def attn_decode(q, cache, n_head: int, scale: float, *, new_kv=None, lens=None, q_prescaled: bool = False, out=None, _args_only=False):
+    """Single-token attention (wft_attn_decode_bf16).  q bf16 [B, H*64] (any row stride); cache bf16 [B, Tk, 2*H*64], rows {k | v}.
+    Self-attention form: new_kv = (k, v) bf16 [B, H*64] views of the step's fused projection output and lens i32 [B] — the rows
+    are written to cache[b, lens[b] - 1] and attended over keys 0 .. lens[b] - 1.  Cross-attention form (neither given): all Tk
+    keys, the cache is only read.  -> o bf16 [B, H*64]."""
+    _chk(q, BF16, "q"); _chk(cache, BF16, "cache")
+    B, D = q.shape
+    if D != n_head * 64 or cache.dim() != 3 or cache.shape[0] != B or cache.shape[2] != 2 * D or q.stride(1) != 1 or cache.stride(2) != 1:
+        raise ValueError(f"attn_decode: q {tuple(q.shape)} / cache {tuple(cache.shape)} do not fit {n_head} heads of 64")
+    if (new_kv is None) != (lens is None):
+        raise ValueError("attn_decode: the self-attention form needs both new_kv and lens")
+    o = torch.empty((B, D), dtype=BF16, device=q.device) if out is None else out
+    a = L.AttnDecodeArgs()
+    a.q, a.ldq = q.data_ptr(), q.stride(0)
+    a.k_cache, a.v_cache = cache.data_ptr(), cache.data_ptr() + 2 * D
+    a.ld_cache, a.cache_bs = cache.stride(1), cache.stride(0)
+    a.o, a.ldo = o.data_ptr(), o.stride(0)
+    if new_kv is not None:
+        k, v = new_kv
+        _chk(k, BF16, "k_new"); _chk(v, BF16, "v_new")
+        _chk_flag(lens, B, "lens")
+        if k.shape != (B, D) or v.shape != (B, D) or k.stride() != v.stride() or k.stride(1) != 1:
+            raise ValueError("attn_decode: k_new / v_new must be [B, H*64] views with one row stride")
+        a.k_new, a.v_new, a.ld_new, a.len = k.data_ptr(), v.data_ptr(), k.stride(0), lens.data_ptr()
+    a.B, a.H, a.Tk, a.scale, a.q_prescaled = B, n_head, cache.shape[1], scale, int(bool(q_prescaled))
+    need = L.load().wft_attn_decode_workspace_bytes(C.byref(a))
+    if need > 0:
+        ws = _tn_workspace(q.device, need, slot="attn_decode")
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    if _args_only:  # (timing tools replay one argument struct)
+        return a, o
+    L.check(L.load().wft_attn_decode_bf16(C.byref(a), L.stream_ptr()), "wft_attn_decode_bf16")
+    return o
+
+
+def decode_embed(tokens, lens, emb, pos):
+    """out[b] = emb[tokens[b, lens[b] - 1]] + pos[lens[b] - 1] -> bf16 [B, d]; tokens i64 [B, n_ctx], lens i32 [B] on the device."""
+    _chk(tokens, torch.int64, "tokens"); _chk(emb, F32, "emb"); _chk(pos, F32, "pos")
+    B = tokens.shape[0]
+    _chk_flag(lens, B, "lens")
+    V, d = emb.shape
+    n_ctx = pos.shape[0]
+    if tokens.dim() != 2 or tokens.stride(1) != 1 or tokens.shape[1] < n_ctx or not emb.is_contiguous() or not pos.is_contiguous():
+        raise ValueError("decode_embed: tokens must be [B, >= n_ctx] with contiguous rows, emb / pos contiguous")
+    out = torch.empty((B, d), dtype=BF16, device=emb.device)
+    L.check(L.load().wft_decode_embed(_p(tokens), tokens.stride(0), _p(lens), _p(emb), _p(pos), _p(out), B, n_ctx, d, V, L.stream_ptr()),
+            "wft_decode_embed")
+    return out
+
+
+def decode_pick(logits, V: int, tokens, lens, finished, sum_logprob, unfinished, *, eot: int, max_len: int, suppress=None,
+                suppress_first=None, first_len=None, want_pick: bool = False):
+    """Greedy pick + state update (wft_decode_pick; include/wft.h).  logits bf16 [B, ld >= V]; suppress / suppress_first u8 [V] or None.
+    want_pick -> (pick i64 [B], logprob f32 [B]) as computed for EVERY row, finished or not."""
+    _chk(logits, BF16, "logits"); _chk(tokens, torch.int64, "tokens"); _chk(sum_logprob, F32, "sum_logprob")
+    B = logits.shape[0]
+    assert logits.dim() == 2 and logits.stride(1) == 1 and tokens.dim() == 2 and tokens.stride(1) == 1 and tokens.shape[0] == B
+    _chk_flag(lens, B, "lens"); _chk_flag(finished, B, "finished"); _chk_flag(unfinished, 1, "unfinished")
+    a = L.DecodePickArgs()
+    a.logits, a.ld, a.V = logits.data_ptr(), logits.stride(0), V
+    for name, m in (("suppress", suppress), ("suppress_first", suppress_first)):
+        if m is not None:
+            _chk(m, torch.uint8, name)
+            if m.numel() != V or not m.is_contiguous():
+                raise ValueError(f"{name}: expected a contiguous uint8 mask of {V} entries")
+            setattr(a, name, m.data_ptr())
+    if first_len is not None:
+        _chk_flag(first_len, B, "first_len")
+        a.first_len = first_len.data_ptr()
+    a.tokens, a.ld_tokens = tokens.data_ptr(), tokens.stride(0)
+    a.len, a.finished, a.sum_logprob, a.unfinished = lens.data_ptr(), finished.data_ptr(), sum_logprob.data_ptr(), unfinished.data_ptr()
+    pick = lp = None
+    if want_pick:
+        pick = torch.empty(B, dtype=torch.int64, device=logits.device)
+        lp = torch.empty(B, dtype=F32, device=logits.device)
+        a.pick_out, a.logprob_out = pick.data_ptr(), lp.data_ptr()
+    a.B, a.eot, a.max_len = B, int(eot), int(max_len)
+    L.check(L.load().wft_decode_pick(C.byref(a), L.stream_ptr()), "wft_decode_pick")
+    return pick, lp
+
+
 # --------------------------------------------------------------------------- embedding / CE
 def embed_fwd(tokens, emb, pos):
     _chk(tokens, torch.int64, "tokens"); _chk(emb, F32, "emb"); _chk(pos, F32, "pos")

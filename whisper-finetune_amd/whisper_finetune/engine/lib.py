@@ -74,6 +74,33 @@ class GemmF32Args(C.Structure):
     ]
 
 
+class AttnDecodeArgs(C.Structure):
+    """Mirror of wft_attn_decode_args (include/wft.h): single-token attention over a KV cache."""
+
+    _fields_ = [
+        ("q", c_vp), ("ldq", c_i64),
+        ("k_new", c_vp), ("v_new", c_vp), ("ld_new", c_i64),
+        ("k_cache", c_vp), ("v_cache", c_vp), ("ld_cache", c_i64), ("cache_bs", c_i64),
+        ("o", c_vp), ("ldo", c_i64),
+        ("len", c_vp),
+        ("B", C.c_int), ("H", C.c_int), ("Tk", C.c_int), ("scale", C.c_float), ("q_prescaled", C.c_int),
+        ("workspace", c_vp), ("workspace_bytes", c_i64),
+    ]
+
+
+class DecodePickArgs(C.Structure):
+    """Mirror of wft_decode_pick_args (include/wft.h): the greedy pick and the per-row decoding state it advances."""
+
+    _fields_ = [
+        ("logits", c_vp), ("ld", c_i64), ("V", c_i64),
+        ("suppress", c_vp), ("suppress_first", c_vp), ("first_len", c_vp),
+        ("tokens", c_vp), ("ld_tokens", c_i64),
+        ("len", c_vp), ("finished", c_vp), ("sum_logprob", c_vp), ("unfinished", c_vp),
+        ("pick_out", c_vp), ("logprob_out", c_vp),
+        ("B", C.c_int), ("eot", C.c_int), ("max_len", C.c_int),
+    ]
+
+
 EPI_NONE, EPI_GELU, EPI_DGELU, EPI_GELU_GRAD, EPI_MUL_AUX, EPI_GELU_GRAD8, EPI_MUL_AUX8 = 0, 1, 2, 3, 4, 5, 6
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); this table is also what
@@ -117,6 +144,10 @@ SIGNATURES = {
     "wft_attn_bwd_bf16": [C.POINTER(AttnArgs), c_vp],
     "wft_attn_bwd_colsum_workspace_bytes": [C.POINTER(AttnArgs)],
     "wft_attn_variant": [C.POINTER(AttnArgs), C.c_int],
+    "wft_attn_decode_bf16": [C.POINTER(AttnDecodeArgs), c_vp],
+    "wft_attn_decode_workspace_bytes": [C.POINTER(AttnDecodeArgs)],
+    "wft_decode_embed": [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_i64, c_vp],
+    "wft_decode_pick": [C.POINTER(DecodePickArgs), c_vp],
     "wft_embed_fwd": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_int, c_i64, c_vp],
     "wft_embed_bwd": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_int, c_i64, c_vp],
     "wft_ce_fwd": [c_vp, c_i64, c_vp, c_i64, c_i64, C.c_float, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -153,7 +184,7 @@ SIGNATURES = {
 }
 _RESTYPES = {"wft_last_error": C.c_char_p, "wft_version": C.c_char_p, "wft_layernorm_bwd_workspace": c_i64,
              "wft_gemm_tn_workspace_bytes": c_i64, "wft_gemm_nt_colsum_workspace_bytes": c_i64, "wft_gemm_nt_splitk_workspace_bytes": c_i64, "wft_gemm_nt_aux8_bytes": c_i64, "wft_colsum_workspace_bytes": c_i64,
-             "wft_attn_bwd_colsum_workspace_bytes": c_i64}
+             "wft_attn_bwd_colsum_workspace_bytes": c_i64, "wft_attn_decode_workspace_bytes": c_i64}
 
 _lib = None
 

@@ -26,6 +26,7 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
 
+from . import decode as _decode
 from . import draws
 from . import kernels as K
 from . import ops
@@ -173,7 +174,10 @@ class MultiHeadAttention(nn.Module):
         => causal (the decoder's -inf upper-triangular buffer).  Returns (out, None) like upstream;
         `residual` (engine extension) is added inside the out-projection epilogue."""
         if kv_cache:
-            raise NotImplementedError("kv_cache is an inference feature; the training/eval path is teacher-forced")
+            if not isinstance(kv_cache, _decode.KVCache):
+                raise NotImplementedError("kv_cache must be an engine.decode.KVCache (Whisper.greedy_decode builds one); upstream's "
+                                          "hook-filled dict is not supported")
+            return self._forward_cached(x, xa, kv_cache, residual)
         B, T, d = x.shape
         if self.wft_fp32:  # fp32 mode: separate projections, strided per-head GEMMs, materialised probabilities
             src = x if xa is None else xa
@@ -198,6 +202,45 @@ class MultiHeadAttention(nn.Module):
             kv = ops.linear(_as2d(_to_bf16(xa)), self._kv_group, [m.base_weight() for m in lin], [m.bias for m in lin],
                             [m.lora_spec() for m in lin], dx_accum=acc)
             o = ops.CrossAttnFn.apply(q.view(B, T, d), kv.view(B, Ta, 2 * d), self.n_head)
+        out = self.out(o.view(B * T, d), residual=None if residual is None else _as2d(residual))
+        return out.view(B, T, d), None
+
+    def _forward_cached(self, x: Tensor, xa: Optional[Tensor], cache: "_decode.KVCache", residual: Optional[Tensor]):
+        """Inference with a KVCache (engine/decode.py).  T > 1: the prefill — the teacher-forced kernels over the right-padded prompts,
+        the k / v rows stored into the cache.  T = 1: a cached step on the single-token kernel (csrc/decode.hip), which appends
+        the step's k / v itself.  Cross-attention keys / values are projected once per audio batch."""
+        if self.wft_fp32:
+            raise NotImplementedError("KV-cached decoding runs in the bf16 compute mode only (model.set_compute_dtype('bf16'))")
+        if torch.is_grad_enabled():
+            raise RuntimeError("a KVCache is an inference object: call the decoder under torch.no_grad()")
+        B, T, d = x.shape
+        x2 = _as2d(_to_bf16(x))
+        scale = 64 ** -0.5
+        if not cache.is_cross(self):
+            lin = [self.query, self.key, self.value]
+            qkv = ops.linear(x2, self._qkv_group, [m.base_weight() for m in lin], [m.bias for m in lin], [m.lora_spec() for m in lin])
+            prescaled = self._qkv_group.fwd_scales is not None
+            store = cache.self_kv[self]
+            if T > 1:
+                if cache.prefilled:
+                    raise RuntimeError("this KVCache already holds a prefix: only single-token steps may follow the prefill")
+                qkv3 = qkv.view(B, T, 3 * d)
+                o = ops.SelfAttnFn.apply(qkv3, self.n_head, True, prescaled)
+                store[:, :T].copy_(qkv3[..., d:])
+            else:
+                o = K.attn_decode(qkv[:, :d], store, self.n_head, scale, new_kv=(qkv[:, d:2 * d], qkv[:, 2 * d:]), lens=cache.len,
+                                  q_prescaled=prescaled)
+        else:
+            kv = cache.cross_kv[self]
+            if kv is None:
+                if xa is None:
+                    raise RuntimeError("the first call with a KVCache (the prefill) needs the encoder output")
+                lin = [self.key, self.value]
+                kv = ops.linear(_as2d(_to_bf16(xa)), self._kv_group, [m.base_weight() for m in lin], [m.bias for m in lin],
+                                [m.lora_spec() for m in lin]).view(B, xa.shape[1], 2 * d)
+                cache.cross_kv[self] = kv
+            q = self.query(x2)
+            o = ops.CrossAttnFn.apply(q.view(B, T, d), kv, self.n_head) if T > 1 else K.attn_decode(q, kv, self.n_head, scale)
         out = self.out(o.view(B * T, d), residual=None if residual is None else _as2d(residual))
         return out.view(B, T, d), None
 
@@ -295,8 +338,18 @@ class TextDecoder(nn.Module):
             return ops32.EmbedFn.apply(tokens, self.token_embedding.weight, self.positional_embedding)
         return ops.EmbedFn.apply(tokens, self.token_embedding.weight, self.positional_embedding)
 
+    def embed_cached(self, tokens: Optional[Tensor], kv_cache) -> Tensor:
+        """Embedding under a KVCache: the prompt block from position 0 (T > 1), or — a cached step, `tokens` None or [B, 1] — the
+        token at len[b] - 1 of every row, token AND position read from the cache's device state (the values of `tokens` are not)."""
+        if self.wft_fp32:
+            raise NotImplementedError("KV-cached decoding runs in the bf16 compute mode only (model.set_compute_dtype('bf16'))")
+        if tokens is not None and tokens.shape[-1] > 1:
+            return self.embed(tokens)
+        return K.decode_embed(kv_cache.tokens, kv_cache.len, self.token_embedding.weight.detach(),
+                              self.positional_embedding.detach()).view(kv_cache.batch, 1, -1)
+
     def hidden(self, x: Tensor, xa: Tensor, kv_cache: Optional[dict] = None) -> Tensor:
-        x = self.embed(x)
+        x = self.embed_cached(x, kv_cache) if kv_cache else self.embed(x)
         for block in self.blocks:
             x = block(x, xa, mask=self.mask, kv_cache=kv_cache)
         return self.ln(x)
@@ -402,6 +455,15 @@ class Whisper(nn.Module):
 
     def logits(self, tokens: Tensor, audio_features: Tensor):
         return self.decoder(tokens, audio_features)
+
+    def greedy_decode(self, mel: Tensor, prompt: Tensor, prompt_len=None, *, eot: int, max_len: Optional[int] = None,
+                      suppress=(), suppress_first=(), sync_every: int = 8):
+        """KV-cached greedy decoding, token ids in and out (engine/decode.py; upstream: whisper.decoding's greedy path with
+        DecodingOptions(without_timestamps=True)).  mel f32 [B, n_mels, 2 * n_audio_ctx]; prompt i64 [B, T] right-padded, prompt_len [B]
+        (None: all T long) -> (tokens i64 [B, L] padded with `eot` behind each row's end, lengths [B], sum_logprob f32 [B]).
+        eval() semantics, no gradients; the host looks at the unfinished-row counter every `sync_every` steps only."""
+        return _decode.greedy_decode(self, mel, prompt, prompt_len, eot=eot, max_len=max_len, suppress=suppress,
+                                     suppress_first=suppress_first, sync_every=sync_every)
 
     def forward(self, mel: Tensor, tokens: Tensor, targets: Optional[Tensor] = None, label_smoothing: float = 0.0) -> Tensor:
         """logits f32 [B, S, V] — or, when `targets` is given (engine extension used by train_step, also

@@ -15,7 +15,7 @@ import torch
 import whisper_finetune.runtime as rt
 from whisper_finetune.eval.metrics import (DatasetMetrics, PerUtteranceMetrics, aggregate_dataset_metrics, cer,
                                            compute_macro_average, compute_token_metrics, token_metrics_from_stats, wer)
-from whisper_finetune.eval.utils import VOCAB_SPECS, normalize_text
+from whisper_finetune.eval.utils import VOCAB_SPECS, decode_prefix_len, normalize_text
 
 
 def _default_tokenizer():
@@ -40,6 +40,30 @@ def _batch_token_stats(model, x, y_in, y_out):
     return None
 
 
+def _greedy_predictions(model, tokenizer, x, y_in) -> List[List[int]]:
+    """t_config["wft_eval_decode"] = "greedy": every utterance's predicted ids from KV-cached greedy decoding
+    (Whisper.greedy_decode) instead of the teacher-forced argmax.  The decoding prefix of a row is its y_in up to and including
+    the start-of-transcript sequence; every special token but eot is suppressed (upstream's notimestamps decoding plus its
+    SuppressTokens list of specials; `tokenizer.non_speech_tokens` too when the tokenizer has them), eot and the blank for a
+    row's first token (upstream's SuppressBlank); at most n_text_ctx // 2 new tokens (upstream's sample_len)."""
+    if not hasattr(model, "greedy_decode"):
+        raise RuntimeError('wft_eval_decode: "greedy" needs a model with greedy_decode (the engine\'s Whisper)')
+    eot = int(tokenizer.eot)
+    rows = y_in.cpu().tolist()
+    plen = [decode_prefix_len(r, int(tokenizer.sot), int(tokenizer.no_timestamps)) for r in rows]
+    width = max(plen)
+    prompt = torch.full((len(rows), width), eot, dtype=torch.int64)
+    for i, (r, n) in enumerate(zip(rows, plen)):
+        prompt[i, :n] = torch.tensor(r[:n], dtype=torch.int64)
+    suppress = sorted((set(int(t) for t in tokenizer.special_tokens.values()) | set(int(t) for t in getattr(tokenizer, "non_speech_tokens", ()))) - {eot})
+    blank = [int(t) for t in tokenizer.encode(" ")] if hasattr(tokenizer, "encode") else []
+    n_ctx = getattr(getattr(model, "dims", None), "n_text_ctx", 448)
+    tokens, lengths, _ = model.greedy_decode(x, prompt.to(x.device), torch.tensor(plen), eot=eot, max_len=min(n_ctx, width + n_ctx // 2),
+                                             suppress=suppress, suppress_first=[eot] + blank)
+    tokens, lengths = tokens.cpu().tolist(), lengths.cpu().tolist()
+    return [tokens[i][plen[i]:lengths[i]] for i in range(len(rows))]
+
+
 @torch.no_grad()
 def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict, tokenizer=None) -> DatasetMetrics:
     model = rt.unwrap_model(model)
@@ -62,6 +86,9 @@ def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict
     specials = set(tokenizer.special_tokens.values())
     spec = VOCAB_SPECS["v0"]
     per_utt: List[PerUtteranceMetrics] = []
+    decode_mode = t_config.get("wft_eval_decode")
+    if decode_mode not in (None, "greedy"):
+        raise ValueError(f'wft_eval_decode: the only value is "greedy" (absent = the teacher-forced argmax), got {decode_mode!r}')
 
     for x, y_in, y_out in dataloader:
         x = x.to(device, non_blocking=True)
@@ -74,8 +101,11 @@ def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict
                 pred = torch.argmax(logits, dim=-1)
         y_host = y_out.cpu().numpy()
         pred_host = fused[0] if fused is not None else pred.cpu().numpy()
+        # prediction TEXT from autoregressive decoding when asked for; NLL / entropy / ECE below stay teacher-forced
+        decoded = _greedy_predictions(model, tokenizer, x, y_in) if decode_mode == "greedy" else None
         for i in range(y_host.shape[0]):
-            pred_tokens = [t for t in pred_host[i].tolist() if t not in specials and t != -100]
+            pred_ids = pred_host[i].tolist() if decoded is None else decoded[i]
+            pred_tokens = [t for t in pred_ids if t not in specials and t != -100]
             true_tokens = [t for t in y_host[i].tolist() if t not in specials and t != -100]
             true_text = tokenizer.decode(true_tokens)
             if true_text.strip() == "":

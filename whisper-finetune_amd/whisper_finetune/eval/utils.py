@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import re
 import string
-from typing import Dict, Set
+from typing import Dict, Sequence, Set
 
 _SPACES = re.compile(r"[ \t]+")
 
@@ -35,3 +35,18 @@ def normalize_text(text: str, char_vocab: Set[str], char_lookup: Dict[str, str],
     text = _SPACES.sub(" ", text)
     text = "".join(ch for ch in text if ch in char_vocab)
     return _SPACES.sub(" ", text).strip()
+
+
+def decode_prefix_len(y_in: Sequence[int], sot: int, no_timestamps: int) -> int:
+    """Length of the decoding prefix of one teacher-forcing input row: everything up to and including its start-of-transcript
+    sequence — an optional prompt, then `sot`, language, task, and `no_timestamps` when it follows (a `no_speech` marker is not
+    part of it).  The writer it agrees with: data/data_loader.py AudioDataset._get_special_tokens (prompt + specials + text)."""
+    y = [int(t) for t in y_in]
+    if sot not in y:
+        raise ValueError("no start-of-transcript token in the decoder input")
+    n = y.index(sot) + 3  # sot, <|language|>, <|task|>: a prompt holds text and sot_prev only, so the first sot is THE sot
+    if n > len(y):
+        raise ValueError("the decoder input ends inside its start-of-transcript sequence")
+    if n < len(y) and y[n] == no_timestamps:
+        n += 1
+    return n

@@ -331,7 +331,7 @@ class CheckpointedStochasticTextDecoder(StochasticDepthMixin, TextDecoder):
         self.stochastic_depth_prob = stochastic_depth_prob
 
     def hidden(self, x: Tensor, xa: Tensor, kv_cache: Optional[dict] = None) -> Tensor:
-        x = self.embed(x)
+        x = self.embed_cached(x, kv_cache) if kv_cache else self.embed(x)
         for block in self.blocks:
             x = self.stochastic_depth(x, partial(block, xa=xa, mask=self.mask, kv_cache=kv_cache), self.stochastic_depth_prob)
         return self.ln(x)
