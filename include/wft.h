@@ -286,6 +286,19 @@ int64_t wft_gemm_nt_splitk_workspace_bytes(const wft_gemm_args* args);
 /* Size of the one-byte gelu' buffer of WFT_EPI_GELU_GRAD8 / WFT_EPI_MUL_AUX8 for these arguments, or 0 if the call would not be
  * served in that form (not a gemm_nt4w_kernel problem).  Pure host function.                                                */
 int64_t wft_gemm_nt_aux8_bytes(const wft_gemm_args* args);
+/* Weight-streaming form of the same product for the projections of a KV-cached decoding step (csrc/gemm_stream.hip; whisper.decoding's
+ * per-token decoder forward, M = batch): K is split over the whole chip as a function of (N, K) and the CU count only — never of M, so row m
+ * of C does not depend on the batch it sat in —, every weight byte is read once straight into registers, fp32 partials go to `workspace`
+ * [split][M][N] and a second launch sums them in split order and applies the epilogue (bitwise reproducible, no atomics).
+ * Served (wft_gemm_nt_stream_ok = 1): 1 <= M <= 32, batch 1, bf16 C, alpha 1, the plain epilogue or the gelu one of the enum above
+ * (aux NULL or the pre-activation), optional f32 bias, optional bf16 residual added AFTER the epilogue (residual_first 0, beta 1),
+ * N % 128 == 0, K % 64 == 0, the alignment rules of wft_gemm_nt_bf16 (bias 16-byte, residual / aux 8-byte aligned, ldr / ldaux % 4 == 0).
+ * Everything else — an f32 or accumulated C, batch > 1, colsum, p_valid, valid_rows_period, the other epilogues, larger M — is refused
+ * with WFT_ERR_UNSUPPORTED before any device call; wft_gemm_nt_bf16 takes those calls.  `workspace` must hold
+ * wft_gemm_nt_stream_workspace_bytes(args) bytes (0 = not served), 16-byte aligned.  Both queries are pure host functions.       */
+int wft_gemm_nt_stream_bf16(const wft_gemm_args* args, void* stream);
+int wft_gemm_nt_stream_ok(const wft_gemm_args* args);
+int64_t wft_gemm_nt_stream_workspace_bytes(const wft_gemm_args* args);
 /* C[p, q] (+)= alpha * sum_r A[r, p] * B[r, q]   (weight gradients dW = dY^T X:
  * what autograd's mm-backward computes for whisper.model.Linear).
  *  A bf16 [R, P] (row r at A + r*lda, P contiguous), B bf16 [R, Q];

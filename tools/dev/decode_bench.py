@@ -7,8 +7,13 @@
   gemm   every wft_gemm_nt_bf16 call of one cached step at M = B: the kernel wft_gemm_nt_variant reports, time, and time over
          (weight bytes / HBM rate) — the price list for a weight-streaming small-M GEMM.  Recorded, not acted on.
   e2e    tokens/s of Whisper.greedy_decode against a loop of model.logits(tokens, xa) re-forwards (same prompts, 64 new tokens).
+  gemm_stream  the same seven calls through wft_gemm_nt_stream_bf16 (csrc/gemm_stream.hip) against wft_gemm_nt_bf16 on the same
+         arguments, alternating, 32 distinct weight buffers in rotation; max difference of the two outputs at the size timed.
+         The table wft_gemm_nt_stream_ok's rule is set from (arm = "stream_vs_nt").
+  e2e_step     greedy_decode's four step arms, alternating: step="eager" (the baseline), eager steps on the streaming GEMMs, the
+         captured step on the old GEMMs, step="graph"; tokens/s, ms per token, launches per step, share of equal tokens.
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e] [--batches 1,8,32] [--out FILE]
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -152,6 +157,143 @@ def bench_gemm(batches):
             del ws, calls, keep
 
 
+def bench_gemm_stream(batches):
+    lib = L.load()
+    g = torch.Generator(device="cuda").manual_seed(1)
+    shapes = [("self q/k/v", 3 * D, D, LAYERS, L.EPI_NONE), ("self out", D, D, LAYERS, L.EPI_NONE), ("cross q", D, D, LAYERS, L.EPI_NONE),
+              ("cross out", D, D, LAYERS, L.EPI_NONE), ("mlp.0 + GELU", 4 * D, D, LAYERS, L.EPI_GELU), ("mlp.2", D, 4 * D, LAYERS, L.EPI_NONE),
+              ("tied logits", K.round_up(51866, 128), D, 4, L.EPI_NONE)]
+    for B in batches:
+        for name, N, Kd, copies, epi in shapes:
+            ws = [torch.randn(N, Kd, device=DEV, generator=g).to(BF) * 0.02 for _ in range(copies)]
+            x = torch.randn(B, Kd, device=DEV, generator=g).to(BF)
+            bias = torch.zeros(N, device=DEV)
+            old, new, keep = [], [], []
+            for w in ws:
+                a, out = K.gemm_nt(x, w, bias=bias, epilogue=epi, _args_only=True)
+                served = K.gemm_nt_stream(x, w, bias=bias, epilogue=epi, _args_only=True)
+                if served is None:
+                    break
+                old.append(a); new.append(served[0]); keep += [out, served[1]]
+            if not new:
+                emit(dict(part="gemm_stream", arm="stream_vs_nt", B=B, call=name, N=N, K=Kd, served=0))
+                continue
+            st = L.stream_ptr()
+
+            def run_old():
+                for a in old:
+                    lib.wft_gemm_nt_bf16(C.byref(a), st)
+
+            def run_new():
+                for a in new:
+                    lib.wft_gemm_nt_stream_bf16(C.byref(a), st)
+
+            L.check(lib.wft_gemm_nt_bf16(C.byref(old[0]), st), "wft_gemm_nt_bf16")
+            L.check(lib.wft_gemm_nt_stream_bf16(C.byref(new[0]), st), "wft_gemm_nt_stream_bf16")
+            diff = (keep[0].float() - keep[1].float()).abs().max().item()
+            res = ab({"nt": run_old, "stream": run_new})
+            floor_us = N * Kd * 2 / HBM * 1e6
+            us_old, us_new = res["nt"][0] * 1e3 / copies, res["stream"][0] * 1e3 / copies
+            emit(dict(part="gemm_stream", arm="stream_vs_nt", B=B, call=name, N=N, K=Kd, served=1, nt_us=round(us_old, 2), nt_spread=round(res["nt"][2], 3),
+                      stream_us=round(us_new, 2), stream_spread=round(res["stream"][2], 3), ratio=round(us_old / us_new, 2),
+                      stream_TBps=round(N * Kd * 2 / (us_new * 1e-6) / 1e12, 3), weight_floor_us=round(floor_us, 2),
+                      stream_times_floor=round(us_new / floor_us, 1), nt_times_floor=round(us_old / floor_us, 1), max_abs_diff=diff,
+                      workspace_bytes=int(lib.wft_gemm_nt_stream_workspace_bytes(C.byref(new[0])))))
+            del ws, old, new, keep
+
+
+def _random_large_v3():
+    dims = MODEL_DIMS["large-v3"]
+    with torch.device(DEV):
+        m = Whisper(dims)
+    with torch.no_grad():
+        for n, p in m.named_parameters():
+            if p.dim() >= 2:
+                p.normal_(0, 0.02)
+            elif n.endswith("weight"):
+                p.fill_(1.0)
+            else:
+                p.zero_()
+    return m.eval(), dims
+
+
+def bench_e2e_step(batches, new_tokens=64, runs=3):
+    from whisper_finetune.engine import decode as Dm
+
+    m, dims = _random_large_v3()
+    lib = L.load()
+    eot = 50257
+    arms = {"eager": dict(), "eager_stream": dict(step="graph", _capture=False), "graph_nt": dict(step="graph", _stream_gemm=False),
+            "graph": dict(step="graph")}
+    for B in batches:
+        g = torch.Generator(device="cuda").manual_seed(B)
+        mel = torch.randn(B, dims.n_mels, 2 * dims.n_audio_ctx, device=DEV, generator=g)
+        prompt = torch.tensor([[50258, 50261, 50360, 50364]], device=DEV).expand(B, 4).contiguous()
+        max_len = 4 + new_tokens
+        # library calls of one cached step + pick per GEMM route (every call that takes a stream enqueues at least one kernel;
+        # a streaming GEMM is two: kernel + reduce).  The graph arms issue the same work as ONE graph launch per step.
+        counts = {}
+        for route in (False, True):
+            cache = Dm.KVCache(m.decoder, B, device=DEV)
+            with torch.no_grad():
+                cache.start(prompt, None, eot=eot, max_len=max_len, suppress=[eot], n_vocab=dims.n_vocab)
+                lg = Dm.prefill(m.decoder, cache, m.encoder(mel)); Dm.pick(m.decoder, cache, lg)
+                with _CountCalls() as cc, Dm.stream_gemm(route):
+                    lg = Dm.step(m.decoder, cache); Dm.pick(m.decoder, cache, lg)
+            counts[route] = (sum(cc.n.values()), cc.n.get("wft_gemm_nt_stream_bf16", 0), cc.n.get("wft_gemm_nt_bf16", 0))
+            del cache
+        route_of = {"eager": False, "eager_stream": True, "graph_nt": False, "graph": True}
+        times, outs = {a: [] for a in arms}, {}
+        for a, kw in arms.items():  # warm-up: shadows, workspaces, code objects, the capture
+            m.greedy_decode(mel, prompt, None, eot=eot, max_len=max_len, suppress=[eot], **kw)
+        for rnd in range(runs):
+            for a, kw in arms.items():
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                outs[a] = m.greedy_decode(mel, prompt, None, eot=eot, max_len=max_len, suppress=[eot], **kw)
+                torch.cuda.synchronize(); times[a].append(time.perf_counter() - t0)
+        # the encoder + prefill share of a call, to report the per-token figure of the cached steps alone
+        pre = []
+        for rnd in range(runs):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            m.greedy_decode(mel, prompt, None, eot=eot, max_len=5, suppress=[eot])
+            torch.cuda.synchronize(); pre.append(time.perf_counter() - t0)
+        pre_s = statistics.median(pre)
+        for a in arms:
+            med = statistics.median(times[a])
+            emit(dict(part="e2e_step", arm=a, B=B, new_tokens=new_tokens, runs_s=[round(t, 4) for t in times[a]], median_s=round(med, 4),
+                      spread=round((max(times[a]) - min(times[a])) / med, 3), tok_s=round(B * new_tokens / med, 1),
+                      encoder_prefill_s=round(pre_s, 4), ms_per_step=round((med - pre_s) / (new_tokens - 1) * 1e3, 3),
+                      library_calls_per_step=counts[route_of[a]][0], stream_gemm_calls=counts[route_of[a]][1],
+                      nt_gemm_calls=counts[route_of[a]][2], host_launches_per_step=1 if a.startswith("graph") else counts[route_of[a]][0],
+                      same_tokens_as_eager=round((outs[a][0] == outs["eager"][0]).float().mean().item(), 4),
+                      speedup_vs_eager=round(statistics.median(times["eager"]) / med, 2)))
+        Dm.release_graphs(m)
+
+
+class _CountCalls:
+    """Counts, per entry point, the libwft calls that enqueue work (the ones whose last argument is the stream)."""
+
+    def __enter__(self):
+        self.n, self.real = {}, {}
+        lib = L.load()
+        for name, argtypes in L.SIGNATURES.items():
+            if argtypes and argtypes[-1] is L.c_vp and name.startswith("wft_") and not name.endswith("_bytes"):
+                fn = getattr(lib, name)
+                self.real[name] = fn
+
+                def counted(*a, _fn=fn, _name=name):
+                    self.n[_name] = self.n.get(_name, 0) + 1
+                    return _fn(*a)
+
+                setattr(lib, name, counted)
+        return self
+
+    def __exit__(self, *exc):
+        lib = L.load()
+        for name, fn in self.real.items():
+            setattr(lib, name, fn)
+
+
 def bench_e2e(batches, new_tokens=64):
     dims = MODEL_DIMS["large-v3"]
     with torch.device(DEV):
@@ -216,7 +358,7 @@ def main():
     batches = [int(b) for b in a.batches.split(",")]
     emit(dict(part="env", device=torch.cuda.get_device_name(0), lib=L.load().wft_version().decode(), torch=torch.__version__))
     for part in a.parts.split(","):
-        {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e}[part](batches)
+        {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": bench_gemm_stream, "e2e_step": bench_e2e_step}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

@@ -372,6 +372,51 @@ def gemm_nt(a, b, *, M=None, N=None, K=None, lda=None, ldb=None, out=None, out_f
     return out
 
 
+def gemm_nt_stream(a, b, *, M=None, N=None, K=None, lda=None, ldb=None, out=None, bias=None, residual=None, aux=None,
+                   epilogue=L.EPI_NONE, ldc=None, ldaux=None, ldr=None, _args_only=False):
+    """C[M,N] = A[M,K] @ B[N,K]^T (+bias) (gelu) (+residual) on the weight-streaming kernel for M <= 32 (csrc/gemm_stream.hip,
+    wft_gemm_nt_stream_bf16): the keywords of `gemm_nt` that apply.  Returns None — nothing launched — when the library does not
+    serve the call in that form (wft_gemm_nt_stream_ok): the caller sends it to `gemm_nt`.  The fp32 partials live in a scratch
+    slot of their own ("nt_stream")."""
+    _chk(a, BF16, "A"); _chk(b, BF16, "B")
+    if M is None:
+        M = a.shape[0]
+    if K is None:
+        K = a.shape[-1]
+    if N is None:
+        N = b.shape[0]
+    args = L.GemmArgs()
+    args.A, args.lda = a.data_ptr(), (a.stride(-2) if a.dim() >= 2 else K) if lda is None else lda
+    args.B, args.ldb = b.data_ptr(), b.stride(-2) if ldb is None else ldb
+    args.M, args.N, args.K, args.batch = M, N, K, 1
+    args.epilogue, args.alpha, args.beta = epilogue, 1.0, 1.0
+    args.bias = 0 if bias is None else bias.data_ptr()
+    if residual is not None:
+        _chk(residual, BF16, "residual")
+        args.residual, args.ldr = residual.data_ptr(), (residual.stride(-2) if ldr is None else ldr)
+    if aux is not None:
+        _chk(aux, BF16, "aux")
+        args.aux, args.ldaux = aux.data_ptr(), (aux.stride(-2) if ldaux is None else ldaux)
+    if out is not None:
+        _chk(out, BF16, "out")
+        args.C, args.ldc = out.data_ptr(), out.stride(-2) if ldc is None else ldc
+    else:
+        args.C, args.ldc = 1 << 20, N  # (a placeholder with the alignment a fresh tensor has: nothing is allocated for a refused call)
+    lib = L.load()
+    need = lib.wft_gemm_nt_stream_workspace_bytes(C.byref(args))
+    if need <= 0:
+        return None
+    if out is None:
+        out = torch.empty((M, N), dtype=BF16, device=a.device)
+        args.C, args.ldc = out.data_ptr(), out.stride(-2)
+    ws = _tn_workspace(a.device, need, slot="nt_stream")
+    args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    if _args_only:
+        return args, out
+    L.check(lib.wft_gemm_nt_stream_bf16(C.byref(args), L.stream_ptr()), "wft_gemm_nt_stream_bf16")
+    return out
+
+
 def gemm_nt_aux8_bytes(M: int, N: int, K: int, device, epilogue=None, colsum: bool = False) -> int:
     """Bytes of the one-byte gelu' buffer if an [M, K] x [N, K]^T product with the GELU_GRAD8 / MUL_AUX8 epilogue is served by
     gemm_nt4w_kernel (wft_gemm_nt_aux8_bytes), else 0.  Shapes only — the pointers are placeholders with the alignment real operands have."""

@@ -18,6 +18,7 @@ import torch
 from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from .. import runtime as _rt
+from . import decode as _decode
 from . import kernels as K
 from . import lib as L
 
@@ -901,6 +902,14 @@ def linear(x, group: LinearGroup, weights, biases, loras=None, residual=None, ge
     consuming Linear as gelu_pre / gelu_codes.  gelu_next_n (with gelu_out): out-features of that consumer — lets the pair use the
     one-byte form when both of its GEMMs qualify."""
     loras = list(loras) if loras is not None else [None] * len(weights)
+    if _decode.stream_gemm_active() and not torch.is_grad_enabled() and not (gelu_out and residual is not None):
+        # a cached decoding step (decode.stream_gemm): the weight-streaming kernel where the library serves the call; there is no
+        # backward, so the GELU call stores no gelu' and the stand-ins for the pre-activation are None
+        has_lora = any(sp is not None for sp in loras)
+        W, _, bias = group.shadows(weights, biases, need_t=False, loras=loras if has_lora else None)
+        y = K.gemm_nt_stream(x, W, bias=bias, residual=residual, epilogue=L.EPI_GELU if gelu_out else L.EPI_NONE)
+        if y is not None:
+            return (None, y, None) if gelu_out else y
     cfg = _LinearCfg(group, len(weights), tuple(b is not None for b in biases), tuple(loras), gelu_out,
                      gelu_pre is not None, sum(w.shape[0] for w in weights), dx_accum, int(gelu_next_n), gelu_codes)
     params = list(weights) + [b for b in biases if b is not None]
@@ -1184,6 +1193,16 @@ class TiedLogitsFn(torch.autograd.Function):
         dx = K.gemm_nt(dl, WT, launch=ctx.launch) if ctx.needs_input_grad[0] else None
         dE = K.gemm_tn(dl, x)[: emb.shape[0], : emb.shape[1]] if ctx.needs_input_grad[1] else None
         return dx, dE, None
+
+
+def tied_logits(x, emb, group: LinearGroup):
+    """Front door of TiedLogitsFn; under decode.stream_gemm() and no_grad the product goes to the weight-streaming kernel where served."""
+    if _decode.stream_gemm_active() and not torch.is_grad_enabled():
+        W, _, _ = group.shadows([emb], [None], need_t=True)
+        y = K.gemm_nt_stream(x, W)
+        if y is not None:
+            return y
+    return TiedLogitsFn.apply(x, emb, group)
 
 
 class FusedCEFn(torch.autograd.Function):

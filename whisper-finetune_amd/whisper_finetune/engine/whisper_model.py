@@ -358,7 +358,7 @@ class TextDecoder(nn.Module):
         """bf16 [B*S, V rounded up to 128] (columns >= V are zero-weight padding); fp32 mode: f32 [B*S, V]."""
         if self.wft_fp32:
             return ops32.TiedLogitsFn.apply(h, self.token_embedding.weight)
-        return ops.TiedLogitsFn.apply(_as2d(h), self.token_embedding.weight, self._logit_group)
+        return ops.tied_logits(_as2d(h), self.token_embedding.weight, self._logit_group)
 
     def logits_from_hidden(self, h: Tensor) -> Tensor:
         B, S, _ = h.shape
@@ -457,13 +457,18 @@ class Whisper(nn.Module):
         return self.decoder(tokens, audio_features)
 
     def greedy_decode(self, mel: Tensor, prompt: Tensor, prompt_len=None, *, eot: int, max_len: Optional[int] = None,
-                      suppress=(), suppress_first=(), sync_every: int = 8):
+                      suppress=(), suppress_first=(), sync_every: int = 8, step: str = "eager", _capture: bool = True,
+                      _stream_gemm: bool = True):
         """KV-cached greedy decoding, token ids in and out (engine/decode.py; upstream: whisper.decoding's greedy path with
         DecodingOptions(without_timestamps=True)).  mel f32 [B, n_mels, 2 * n_audio_ctx]; prompt i64 [B, T] right-padded, prompt_len [B]
         (None: all T long) -> (tokens i64 [B, L] padded with `eot` behind each row's end, lengths [B], sum_logprob f32 [B]).
-        eval() semantics, no gradients; the host looks at the unfinished-row counter every `sync_every` steps only."""
+        eval() semantics, no gradients; the host looks at the unfinished-row counter every `sync_every` steps only.
+        step="graph": the cached steps run on the weight-streaming small-M GEMMs (csrc/gemm_stream.hip) and are replayed from one
+        captured HIP graph per (batch, device) — engine/decode.py; `decode.release_graphs(model)` frees what that pins.  "eager"
+        (default): every step launch by launch on the kernels of the prefill.  (`_capture` / `_stream_gemm`: decode.greedy_decode's two private A/B keywords.)"""
         return _decode.greedy_decode(self, mel, prompt, prompt_len, eot=eot, max_len=max_len, suppress=suppress,
-                                     suppress_first=suppress_first, sync_every=sync_every)
+                                     suppress_first=suppress_first, sync_every=sync_every, step=step,
+                                     _capture=_capture, _stream_gemm=_stream_gemm)
 
     def forward(self, mel: Tensor, tokens: Tensor, targets: Optional[Tensor] = None, label_smoothing: float = 0.0) -> Tensor:
         """logits f32 [B, S, V] — or, when `targets` is given (engine extension used by train_step, also
