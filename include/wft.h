@@ -459,6 +459,74 @@ typedef struct {
 } wft_decode_pick_args;
 int wft_decode_pick(const wft_decode_pick_args* args, void* stream);
 
+/* ---------------------------------------------------------- Beam search */
+/* Beam-search decoding on a KV cache shared between the beams (csrc/decode.hip; DESIGN.md §3 "Beam-search layouts"): upstream's
+ * `BeamSearchDecoder` + `MaximumLikelihoodRanker` with `without_timestamps=True`, restated in engine/decode.py (neither is in the
+ * reference tree and openai-whisper is not a dependency: parity with the upstream binary is unpinned).  W = beam size (1..8);
+ * audio a owns the R = B*W slot rows r = a*W + j.
+ *
+ * Single-token attention for beams; q / o / scale / q_prescaled / head_dim 64 as in wft_attn_decode_args.
+ *  self form (len != NULL; anc != NULL; group must be 1): R hypotheses over a cache of R slot rows.  Key t < len[r] - 1 of row r
+ *    is read at slot anc[r*ld_anc + t] (i32; a value outside 0..R-1 reads slot r), i.e. at k_cache + slot*cache_bs + t*ld_cache;
+ *    the step's k / v rows (k_new / v_new + r*ld_new) are written to slot r at position len[r] - 1 and take part as that key;
+ *    anc[r, len[r] - 1] is not used.  Nothing else is written: a beam reorder permutes rows of `anc`, keys never move.  Same
+ *    key-to-lane dealing, split and merge order as wft_attn_decode_bf16: the output is bit-identical to that call on a cache
+ *    gathered by `anc`.
+ *  cross form (len == NULL; anc ignored): R = A*group query rows over a read-only cache of A = R/group audios, the `group`
+ *    consecutive rows of an audio share its keys / values.  One workgroup per (audio, head, split) reads each K / V block once
+ *    and runs the online softmax of all `group` rows against it.  Split rule: the keys of an (audio, head) are cut in
+ *    nsplit = clamp(ceil(256 / (A*H)), 1, min(ceil(Tk / 512), 16)) — the rule of wft_attn_decode_bf16 with its B set to A, the
+ *    number of AUDIOS.  Per query row the arithmetic order is that of wft_attn_decode_bf16 at the same split: wherever this
+ *    nsplit equals the one that call takes at B = R rows, the output is bit-identical to it on a group-times replicated cache.
+ *  workspace: wft_attn_decode_beam_workspace_bytes(args) bytes (0: none needed).  No atomics: reruns are bit-identical.        */
+typedef struct {
+  const wft_bf16* q; int64_t ldq;
+  const wft_bf16* k_new; const wft_bf16* v_new; int64_t ld_new;
+  wft_bf16* k_cache; wft_bf16* v_cache; int64_t ld_cache; int64_t cache_bs;
+  wft_bf16* o; int64_t ldo;
+  const int32_t* len;
+  const int32_t* anc; int64_t ld_anc;
+  int R; int H; int Tk; int group; float scale; int q_prescaled;
+  void* workspace; int64_t workspace_bytes;
+} wft_attn_decode_beam_args;
+int wft_attn_decode_beam_bf16(const wft_attn_decode_beam_args* args, void* stream);
+int64_t wft_attn_decode_beam_workspace_bytes(const wft_attn_decode_beam_args* args);
+/* The k = W + 1 best continuations of every logits row (bf16, logits + i*ld; only the first V columns are read), i = 0..rows-1.
+ * Logits row i belongs to state row r = i*row_step (row_step = 1: one logits row per hypothesis; row_step = W: the prefill's one
+ * row per audio).  Masks exactly as wft_decode_pick: `suppress` always, `suppress_first` while len[r] == first_len[r].
+ *  cand_logp[r*k + c] = log-softmax over the live columns of the c-th largest live logit, cand_tok[r*k + c] = its column;
+ *  descending, ties to the lower column.  Fewer than k live columns: the rest is (-1, -inf).  2 <= k <= 9.                   */
+typedef struct {
+  const wft_bf16* logits; int64_t ld; int64_t V;
+  const uint8_t* suppress; const uint8_t* suppress_first; const int32_t* first_len; const int32_t* len;
+  int32_t* cand_tok; float* cand_logp;
+  int rows; int row_step; int k;
+} wft_decode_topk_args;
+int wft_decode_topk(const wft_decode_topk_args* args, void* stream);
+/* One beam-search step for every audio that is not done, from the candidate lists of wft_decode_topk (k = W + 1 per row):
+ *  candidates (j, i), j = beam, i = list position, score = sum_logprob[a*W + j] + cand_logp[a*W + j][i] (one fp32 add); `first`
+ *    != 0: only j = 0 contributes (the W copies of the prompt are one hypothesis).  Order: score descending, ties to the lower
+ *    j, then the lower i (ranked by counting).  Walked in that order: an `eot` candidate is a newly finished sequence (beam j's
+ *    tokens + eot, that score), any other one becomes the next beam slot s = 0, 1, .. until W are saved; eot candidates below
+ *    that point are dropped.  Newly finished sequences are appended in walk order while the audio's list holds fewer than C.
+ *  written per audio: tokens[a*W + s, :len] = old row of the source beam, tokens[.., len] = the token, sum_logprob = the score,
+ *    len + 1 on all W rows; anc rows permuted the same way IN PLACE and anc[a*W + s, len - 1] = a*W + source j (the slot whose
+ *    step wrote that position); fin_tokens[a, p, :] (i64, row stride ld_tokens; padded with eot), fin_len[a, p] (eot counted),
+ *    fin_score[a, p], fin_n[a]; done[a] = fin_n[a] == C || new len == max_len.  A done audio is frozen: nothing of it changes.
+ *  unfinished[0] = number of audios not done after the update.  src_out i32 [B*W] (optional): the source beam j of every new
+ *    slot of an audio that was updated (others untouched).                                                                    */
+typedef struct {
+  const int32_t* cand_tok; const float* cand_logp;
+  int64_t* tokens; int64_t ld_tokens;
+  int32_t* anc; int64_t ld_anc;
+  int32_t* len; float* sum_logprob;
+  int32_t* done; int32_t* unfinished;
+  int64_t* fin_tokens; int32_t* fin_len; float* fin_score; int32_t* fin_n;
+  int32_t* src_out;
+  int B; int W; int C; int eot; int max_len; int first;
+} wft_beam_update_args;
+int wft_beam_update(const wft_beam_update_args* args, void* stream);
+
 /* ------------------------------------------------- Log-mel + SpecAugment */
 /* whisper.audio.log_mel_spectrogram (data/data_loader.py:278; SURVEY.md App.
  * A.2): reflect-pad 200, Hann-400 STFT hop 160, |.|^2, mel filterbank,

@@ -13,7 +13,13 @@
   e2e_step     greedy_decode's four step arms, alternating: step="eager" (the baseline), eager steps on the streaming GEMMs, the
          captured step on the old GEMMs, step="graph"; tokens/s, ms per token, launches per step, share of equal tokens.
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step] [--batches 1,8,32] [--out FILE]
+  beam   beam search at W = 5 (--batches = audios, e.g. 1,4,6): (i) the self form of wft_attn_decode_beam_bf16 (identity and
+         scrambled ancestry table) against wft_attn_decode_bf16 at the same rows and keys — the price of the indirection; (ii) its
+         grouped cross form at R = B * W rows against wft_attn_decode_bf16 at R rows on W-times replicated caches: us, K/V bytes,
+         achieved TB/s; (iii) wft_decode_topk + wft_beam_update against wft_decode_pick at R rows; (iv) beam_decode(W = 5) against
+         greedy_decode at batch = R, eager and graph: tokens/s, ms per step, ratio.
+
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,beam] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -347,6 +353,148 @@ def bench_e2e(batches, new_tokens=64):
                   note="both timings include the encoder pass; tokens differ only where two bf16 evaluations break a near-tie"))
 
 
+def bench_beam(batches, W=5, new_tokens=64, runs=3):
+    from whisper_finetune.engine import decode as Dm
+
+    lib = L.load()
+    st = L.stream_ptr()
+    g = torch.Generator(device="cuda").manual_seed(2)
+
+    def rec_times(rec, res):
+        for n, (med, mn, spread) in res.items():
+            rec[n + "_us"] = round(med * 1e3 / LAYERS, 2)
+            rec[n + "_min_us"] = round(mn * 1e3 / LAYERS, 2)
+            rec[n + "_spread"] = round(spread, 3)
+
+    def runner(fn, calls):
+        def run():
+            for a in calls:
+                fn(C.byref(a), st)
+        return run
+
+    for B in batches:
+        R = B * W
+        # (i) the self form against the existing kernel, same rows and keys
+        for Tk in (8, 224, 448):
+            caches = [torch.randn(R, CAP, 2 * D, device=DEV, generator=g).to(BF) for _ in range(LAYERS)]
+            qkv = torch.randn(R, 3 * D, device=DEV, generator=g).to(BF) * 0.3
+            lens = torch.full((R,), Tk, dtype=torch.int32, device=DEV)
+            ident = torch.arange(R, dtype=torch.int32, device=DEV)[:, None].expand(-1, CAP).contiguous()
+            # every entry names a random beam of the row's own audio, as a run that reorders at every step would leave it
+            scr = (torch.arange(R, device=DEV)[:, None] // W * W + torch.randint(0, W, (R, CAP), device=DEV, generator=g)).to(torch.int32)
+            old, new_i, new_s, keep = [], [], [], []
+            for c in caches:
+                kw = dict(new_kv=(qkv[:, D:2 * D], qkv[:, 2 * D:]), lens=lens, _args_only=True)
+                a, o = K.attn_decode(qkv[:, :D], c, H, 0.125, **kw); old.append(a); keep.append(o)
+                a, o = K.attn_decode_beam(qkv[:, :D], c, H, 0.125, anc=ident, **kw); new_i.append(a); keep.append(o)
+                a, o = K.attn_decode_beam(qkv[:, :D], c, H, 0.125, anc=scr, **kw); new_s.append(a); keep.append(o)
+            L.check(lib.wft_attn_decode_bf16(C.byref(old[0]), st), "wft_attn_decode_bf16")
+            L.check(lib.wft_attn_decode_beam_bf16(C.byref(new_i[0]), st), "wft_attn_decode_beam_bf16")
+            same = bool(torch.equal(keep[0].view(torch.int16), keep[1].view(torch.int16)))
+            res = ab({"decode": runner(lib.wft_attn_decode_bf16, old), "beam_identity": runner(lib.wft_attn_decode_beam_bf16, new_i),
+                      "beam_scrambled": runner(lib.wft_attn_decode_beam_bf16, new_s)})
+            rec = dict(part="beam", arm="self", B=B, W=W, rows=R, Tk=Tk, kv_MB=round(R * H * Tk * 2 * 64 * 2 / 1e6, 2), identity_bits_equal=same)
+            rec_times(rec, res)
+            rec["identity_vs_decode"] = round(res["beam_identity"][0] / res["decode"][0], 3)
+            rec["scrambled_vs_decode"] = round(res["beam_scrambled"][0] / res["decode"][0], 3)
+            emit(rec)
+            del caches, old, new_i, new_s, keep
+        # (ii) the grouped cross form against the existing kernel at R rows on replicated caches
+        caches = [torch.randn(B, TA, 2 * D, device=DEV, generator=g).to(BF) for _ in range(LAYERS)]
+        reps = [c.repeat_interleave(W, 0) for c in caches]
+        q = torch.randn(R, D, device=DEV, generator=g).to(BF) * 0.3
+        old, new, keep = [], [], []
+        for c, r in zip(caches, reps):
+            a, o = K.attn_decode(q, r, H, 0.125, _args_only=True); old.append(a); keep.append(o)
+            a, o = K.attn_decode_beam(q, c, H, 0.125, group=W, _args_only=True); new.append(a); keep.append(o)
+        L.check(lib.wft_attn_decode_bf16(C.byref(old[0]), st), "wft_attn_decode_bf16")
+        L.check(lib.wft_attn_decode_beam_bf16(C.byref(new[0]), st), "wft_attn_decode_beam_bf16")
+        diff = (keep[0].float() - keep[1].float()).abs().max().item()
+        res = ab({"decode_replicated": runner(lib.wft_attn_decode_bf16, old), "beam_grouped": runner(lib.wft_attn_decode_beam_bf16, new)})
+        rec = dict(part="beam", arm="cross", B=B, W=W, rows=R, Tk=TA, max_abs_diff=diff, bits_equal=bool(torch.equal(keep[0].view(torch.int16), keep[1].view(torch.int16))),
+                   replicated_kv_MB=round(R * H * TA * 256 / 1e6, 2), grouped_kv_MB=round(B * H * TA * 256 / 1e6, 2),
+                   grouped_workspace_bytes=int(lib.wft_attn_decode_beam_workspace_bytes(C.byref(new[0]))),
+                   replicated_workspace_bytes=int(lib.wft_attn_decode_workspace_bytes(C.byref(old[0]))))
+        rec_times(rec, res)
+        rec["decode_replicated_TBps"] = round(R * H * TA * 256 / (res["decode_replicated"][0] * 1e-3 / LAYERS) / 1e12, 3)
+        rec["beam_grouped_TBps"] = round(B * H * TA * 256 / (res["beam_grouped"][0] * 1e-3 / LAYERS) / 1e12, 3)
+        rec["speedup"] = round(res["decode_replicated"][0] / res["beam_grouped"][0], 2)
+        emit(rec)
+        del caches, reps, old, new, keep
+        # (iii) top-k + update against the greedy pick, both at R rows (32 rotating logits buffers)
+        V, n_ctx = 51866, CAP
+        ld = K.round_up(V, 128)
+        logits = [(torch.randn(R, ld, device=DEV, generator=g) * 3).to(BF) for _ in range(LAYERS)]
+        tokens = torch.zeros(R, n_ctx, dtype=torch.int64, device=DEV)
+        i32 = dict(dtype=torch.int32, device=DEV)
+        sup = torch.zeros(V, dtype=torch.uint8, device=DEV); sup[50257:] = 1
+        state = dict(lens=torch.full((R,), 100, **i32), fin=torch.zeros(R, **i32), slp=torch.zeros(R, device=DEV), unf=torch.zeros(1, **i32),
+                     anc=torch.zeros(R, n_ctx, **i32), done=torch.zeros(B, **i32), ct=torch.zeros(R, W + 1, **i32), cl=torch.zeros(R, W + 1, device=DEV),
+                     ft=torch.zeros(B, W, n_ctx, dtype=torch.int64, device=DEV), fl=torch.zeros(B, W, **i32), fs=torch.zeros(B, W, device=DEV),
+                     fn=torch.zeros(B, **i32))
+
+        def reset():
+            state["lens"].fill_(100); state["fin"].zero_(); state["done"].zero_(); state["fn"].zero_()
+
+        def run_pick():
+            reset()
+            for lg in logits:
+                K.decode_pick(lg, V, tokens, state["lens"], state["fin"], state["slp"], state["unf"], eot=50257, max_len=n_ctx, suppress=sup,
+                              first_len=state["lens"])
+
+        def run_topk():
+            reset()
+            for lg in logits:
+                K.decode_topk(lg, V, state["ct"], state["cl"], lens=state["lens"], first_len=state["lens"], suppress=sup)
+
+        def run_beam():
+            reset()
+            for lg in logits:
+                K.decode_topk(lg, V, state["ct"], state["cl"], lens=state["lens"], first_len=state["lens"], suppress=sup)
+                K.beam_update(state["ct"], state["cl"], tokens, state["anc"], state["lens"], state["slp"], state["done"], state["unf"], state["ft"],
+                              state["fl"], state["fs"], state["fn"], eot=50257, max_len=n_ctx)
+
+        res = ab({"pick": run_pick, "topk": run_topk, "topk_update": run_beam}, iters=2)
+        rec = dict(part="beam", arm="pick", B=B, W=W, rows=R, V=V, logits_MB=round(R * V * 2 / 1e6, 2),
+                   note="one call per rotating logits buffer, issued through the Python wrappers (their host time is in every arm)")
+        rec_times(rec, res)
+        rec["topk_update_vs_pick"] = round(res["topk_update"][0] / res["pick"][0], 2)
+        emit(rec)
+        del logits
+
+    # (iv) end to end: beam_decode(W) over B audios against greedy_decode at batch = B * W, eager and graph
+    m, dims = _random_large_v3()
+    eot = 50257
+    for B in batches:
+        R = B * W
+        gm = torch.Generator(device="cuda").manual_seed(B)
+        mel = torch.randn(R, dims.n_mels, 2 * dims.n_audio_ctx, device=DEV, generator=gm)
+        prompt = torch.tensor([[50258, 50261, 50360, 50364]], device=DEV).expand(R, 4).contiguous()
+        max_len = 4 + new_tokens
+        arms = {}
+        for mode in ("eager", "graph"):
+            arms["beam_" + mode] = lambda n=5, mode=mode, max_len=max_len: m.beam_decode(mel[:B], prompt[:B], None, beam_size=W, eot=eot, max_len=max_len if n else 5,
+                                                                                        suppress=[eot], step=mode)
+            arms["greedy_" + mode] = lambda n=5, mode=mode, max_len=max_len: m.greedy_decode(mel, prompt, None, eot=eot, max_len=max_len if n else 5, suppress=[eot],
+                                                                                            step=mode)
+        times, pre = {a: [] for a in arms}, {a: [] for a in arms}
+        for fn in arms.values():
+            fn()  # warm-up: shadows, workspaces, code objects, the capture
+        for rnd in range(runs):
+            for a, fn in arms.items():
+                torch.cuda.synchronize(); t0 = time.perf_counter(); fn(); torch.cuda.synchronize(); times[a].append(time.perf_counter() - t0)
+                torch.cuda.synchronize(); t0 = time.perf_counter(); fn(0); torch.cuda.synchronize(); pre[a].append(time.perf_counter() - t0)
+        for a in arms:
+            med, pre_s = statistics.median(times[a]), statistics.median(pre[a])
+            other = statistics.median(times[a.replace("beam_", "greedy_")])
+            emit(dict(part="beam", arm="e2e_" + a, B=B, W=W, rows=R, new_tokens=new_tokens, runs_s=[round(t, 4) for t in times[a]], median_s=round(med, 4),
+                      spread=round((max(times[a]) - min(times[a])) / med, 3), encoder_prefill_s=round(pre_s, 4),
+                      ms_per_step=round((med - pre_s) / (new_tokens - 1) * 1e3, 3),
+                      tok_s=round((B if a.startswith("beam") else R) * new_tokens / med, 1), hypothesis_tok_s=round(R * new_tokens / med, 1),
+                      time_vs_greedy_at_R_rows=round(med / other, 3)))
+        Dm.release_graphs(m)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="attn,gemm,e2e")
@@ -358,7 +506,8 @@ def main():
     batches = [int(b) for b in a.batches.split(",")]
     emit(dict(part="env", device=torch.cuda.get_device_name(0), lib=L.load().wft_version().decode(), torch=torch.__version__))
     for part in a.parts.split(","):
-        {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": bench_gemm_stream, "e2e_step": bench_e2e_step}[part](batches)
+        {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": bench_gemm_stream, "e2e_step": bench_e2e_step,
+         "beam": bench_beam}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

@@ -1,4 +1,4 @@
-// decode.hip — the single-token kernels of KV-cached greedy decoding (include/wft.h "Greedy decoding").
+// decode.hip — the single-token kernels of KV-cached greedy and beam-search decoding (include/wft.h "Greedy decoding", "Beam search").
 //
 // A cached decoding step runs ONE query row per (sequence, head) against a key/value cache that grows by one row per step.  Nothing
 // here depends on the step: the position of every sequence lives in device memory (`len`), so a step is a fixed launch sequence.
@@ -6,6 +6,9 @@
 //  attn_decode_kernel / attn_decode_merge_kernel   softmax(q K^T) V for one query row, HBM-bound K/V read
 //  decode_embed_kernel                             token + positional embedding at the device-side position
 //  decode_pick_kernel / decode_count_kernel        suppress, arg-max, log-probability, state update, unfinished-row count
+//  attn_decode_beam_kernel                         the same attention for beams: self keys through the ancestry table, cross keys
+//                                                  read once per audio for all of its beams
+//  decode_topk_kernel / beam_update_kernel         the W + 1 best continuations per hypothesis; one beam-search step per audio
 #include "common.h"
 
 // ----------------------------------------------------------------------------- single-token attention
@@ -204,15 +207,16 @@ __global__ __launch_bounds__(64) void attn_decode_merge_kernel(const float* ws, 
   o[(long)b * ldo + h * 64 + i] = f2bf(acc / l);
 }
 
-static int dec_nsplit(const wft_attn_decode_args* a) {
+static int dec_nsplit_of(long B, long H, long Tk) {
   // enough workgroups to cover the chip when B * H alone does not, in splits of about DEC_MIN_SPLIT_KEYS keys or more
-  const long bh = (long)a->B * a->H;
+  const long bh = B * H;
   long want = (DEC_TARGET_WGS + bh - 1) / bh;
-  const long most = (a->Tk + DEC_MIN_SPLIT_KEYS - 1) / DEC_MIN_SPLIT_KEYS;
+  const long most = (Tk + DEC_MIN_SPLIT_KEYS - 1) / DEC_MIN_SPLIT_KEYS;
   if (want > most) want = most;
   if (want > 16) want = 16;
   return want < 1 ? 1 : (int)want;
 }
+static int dec_nsplit(const wft_attn_decode_args* a) { return dec_nsplit_of(a->B, a->H, a->Tk); }
 
 extern "C" int64_t wft_attn_decode_workspace_bytes(const wft_attn_decode_args* a) {
   if (!a || a->B < 1 || a->H < 1 || a->Tk < 1) return 0;
@@ -393,6 +397,501 @@ extern "C" int wft_decode_pick(const wft_decode_pick_args* a, void* stream) {
   WFT_CHECK_ARG(!a->suppress_first || a->first_len, "suppress_first needs first_len");
   hipLaunchKernelGGL(decode_pick_kernel, dim3((unsigned)a->B), dim3(PICK_THREADS), 0, (hipStream_t)stream, *a);
   hipLaunchKernelGGL(decode_count_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int*)a->finished, a->B, a->unfinished);
+  WFT_CHECK_LAUNCH();
+  return WFT_OK;
+}
+
+// ----------------------------------------------------------------------------- single-token attention for beams
+// attn_decode_kernel's work split, key-to-lane dealing, two-blocks-in-flight loads and merge order, for two new shapes.
+//  SELF (W = 1): hypothesis r reads key t at cache slot anc[r, t] — keys are never copied when beams are reordered, only rows of
+//    `anc` are.  The 4 slot indices of a block are fetched ONE BLOCK AHEAD of its keys (iA / iB below: when the K / V loads of block
+//    j + 1 are issued their indices are already in registers, and the indices of block j + 2 are in flight), so the indirection adds
+//    one dependent load at the head of a row and none to the K / V stream.
+//  cross (W = group): one workgroup per (audio, head, split) loads each K / V block ONCE and runs the online softmax of the audio's W
+//    query rows against it: W states per lane, the arithmetic of one query exactly that of attn_decode_kernel.
+template <int W, bool SELF>
+__global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_beam_kernel(wft_attn_decode_beam_args a, int nsplit, float qk_alpha) {
+  __shared__ float red[DEC_WAVES][W][DEC_PART];
+  const int ah = blockIdx.x, sp = blockIdx.y;
+  const int au = ah / a.H, h = ah - au * a.H;  // au: the slot row (SELF) or the audio
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 3, c = lane & 7;
+  const int r0 = au * W;  // first query row
+
+  int n = a.Tk;
+  int p_new = -1;
+  if (SELF) {
+    n = a.len[au];
+    n = n < 1 ? 1 : (n > a.Tk ? a.Tk : n);
+    p_new = n - 1;
+  }
+  const long hoff = h * 64 + c * 8;
+  const unsigned short* kc = a.k_cache + hoff + (SELF ? 0 : (long)au * a.cache_bs);
+  const unsigned short* vc = a.v_cache + hoff + (SELF ? 0 : (long)au * a.cache_bs);
+  const unsigned short* kn = SELF ? a.k_new + (long)au * a.ld_new + hoff : kc;
+  const unsigned short* vn = SELF ? a.v_new + (long)au * a.ld_new + hoff : vc;
+  const int* anc = SELF ? a.anc + (long)au * a.ld_anc : nullptr;
+
+  if (SELF && sp == 0 && wave == 0 && lane < 16) {
+    // the append into the row's OWN slot at position p_new.  No lane of this launch reads position p_new of any slot (whoever owns
+    // key p_new takes it from k_new / v_new), and no `anc` entry of an earlier position points at it: nothing to order.
+    const u32x4 r = *(const u32x4*)(g == 0 ? kn : vn);
+    unsigned short* dst = (g == 0 ? a.k_cache : a.v_cache) + (long)au * a.cache_bs + (long)p_new * a.ld_cache + hoff;
+    *(u32x4*)dst = r;
+  }
+
+  float q[W][8];
+#pragma unroll
+  for (int j = 0; j < W; ++j) dec_unpack8(*(const u32x4*)(a.q + (long)(r0 + j) * a.ldq + hoff), q[j]);
+
+  dec_state st[W];
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    st[j].m = DEC_NEG;
+    st[j].l = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) st[j].o[i] = 0.f;
+  }
+
+  auto ldidx = [&](int blk, int* ix) {
+    if (SELF) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        int t = blk * DEC_BLOCK_KEYS + g + u * 8;
+        t = t < n ? t : n - 1;
+        int s = au;
+        if (t != p_new) s = anc[t];
+        ix[u] = (unsigned)s < (unsigned)a.R ? s : au;  // (an in-bounds slot whatever the table holds)
+      }
+    }
+  };
+  auto load = [&](int blk, const int* ix, u32x4* kr, u32x4* vr) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      int t = blk * DEC_BLOCK_KEYS + g + u * 8;
+      t = t < n ? t : n - 1;  // (a clamped, in-bounds address; the value is discarded)
+      const bool fresh = t == p_new;
+      const long off = (SELF ? (long)ix[u] * a.cache_bs : 0) + (long)t * a.ld_cache;
+      kr[u] = *(const u32x4*)(fresh ? kn : kc + off);
+      vr[u] = *(const u32x4*)(fresh ? vn : vc + off);
+    }
+  };
+  auto consume = [&](int blk, const u32x4* kr, const u32x4* vr) {
+    bool ok[4];
+    float kf[4][8], vf[4][8];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      ok[u] = blk * DEC_BLOCK_KEYS + g + u * 8 < n;
+      dec_unpack8(kr[u], kf[u]);
+      dec_unpack8(vr[u], vf[u]);
+    }
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      float s[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        float d = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d = fmaf(q[j][i], kf[u][i], d);
+        d += __shfl_xor(d, 1, 64);
+        d += __shfl_xor(d, 2, 64);
+        d += __shfl_xor(d, 4, 64);
+        s[u] = ok[u] ? d * qk_alpha : DEC_NEG;
+      }
+      const float mn = fmaxf(fmaxf(st[j].m, fmaxf(s[0], s[1])), fmaxf(s[2], s[3]));
+      const float resc = __builtin_amdgcn_exp2f(st[j].m - mn);
+      st[j].m = mn;
+      st[j].l *= resc;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) st[j].o[i] *= resc;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float p = ok[u] ? __builtin_amdgcn_exp2f(s[u] - mn) : 0.f;
+        st[j].l += p;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) st[j].o[i] = fmaf(p, vf[u][i], st[j].o[i]);
+      }
+    }
+  };
+  const int stride = nsplit * DEC_WAVES;
+  int blk = sp * DEC_WAVES + wave;
+  u32x4 kA[4], vA[4], kB[4], vB[4];
+  int iA[4] = {0, 0, 0, 0}, iB[4] = {0, 0, 0, 0};
+  ldidx(blk, iA);
+  ldidx(blk + stride, iB);
+  load(blk, iA, kA, vA);
+  while (blk * DEC_BLOCK_KEYS < n) {
+    ldidx(blk + 2 * stride, iA);
+    load(blk + stride, iB, kB, vB);
+    consume(blk, kA, vA);
+    blk += stride;
+    if (!(blk * DEC_BLOCK_KEYS < n)) break;
+    ldidx(blk + 2 * stride, iB);
+    load(blk + stride, iA, kA, vA);
+    consume(blk, kB, vB);
+    blk += stride;
+  }
+
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    // the 8 key groups of the wave (butterfly over lane bits 3..5; group 0's copy is the one used)
+#pragma unroll
+    for (int off = 8; off < 64; off <<= 1) {
+      const float bm = __shfl_xor(st[j].m, off, 64), bl = __shfl_xor(st[j].l, off, 64);
+      float bo[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) bo[i] = __shfl_xor(st[j].o[i], off, 64);
+      dec_merge(st[j], bm, bl, bo);
+    }
+    if (g == 0) {
+      if (c == 0) {
+        red[wave][j][0] = st[j].m;
+        red[wave][j][1] = st[j].l;
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) red[wave][j][2 + c * 8 + i] = st[j].o[i];
+    }
+  }
+  __syncthreads();
+  if (wave == 0 && g == 0) {
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+      // the 4 waves, in wave order
+      for (int w = 1; w < DEC_WAVES; ++w) {
+        float bo[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) bo[i] = red[w][j][2 + c * 8 + i];
+        dec_merge(st[j], red[w][j][0], red[w][j][1], bo);
+      }
+      const long rh = (long)(r0 + j) * a.H + h;
+      if (nsplit == 1) {
+        const float inv = 1.0f / st[j].l;
+        u32x4 r;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = pack2bf(st[j].o[2 * i] * inv, st[j].o[2 * i + 1] * inv);
+        *(u32x4*)(a.o + (long)(r0 + j) * a.ldo + hoff) = r;
+      } else {
+        float* part = (float*)a.workspace + (rh * nsplit + sp) * DEC_PART;  // the layout attn_decode_merge_kernel reads, per query row
+        if (c == 0) {
+          part[0] = st[j].m;
+          part[1] = st[j].l;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) part[2 + c * 8 + i] = st[j].o[i];
+      }
+    }
+  }
+}
+
+static int beam_nsplit(const wft_attn_decode_beam_args* a) {
+  return dec_nsplit_of(a->len ? a->R : a->R / a->group, a->H, a->Tk);  // (the cross form: per AUDIO — the rule stated in wft.h)
+}
+
+static bool beam_shape_ok(const wft_attn_decode_beam_args* a) {
+  return a && a->R >= 1 && a->H >= 1 && a->Tk >= 1 && a->group >= 1 && a->group <= 8 && a->R % a->group == 0 && (!a->len || a->group == 1);
+}
+
+extern "C" int64_t wft_attn_decode_beam_workspace_bytes(const wft_attn_decode_beam_args* a) {
+  if (!beam_shape_ok(a)) return 0;
+  const int ns = beam_nsplit(a);
+  return ns == 1 ? 0 : (int64_t)a->R * a->H * ns * DEC_PART * (int64_t)sizeof(float);
+}
+
+extern "C" int wft_attn_decode_beam_bf16(const wft_attn_decode_beam_args* a, void* stream) {
+  WFT_CHECK_ARG(a && a->q && a->k_cache && a->v_cache && a->o, "null pointer");
+  WFT_CHECK_ARG(a->R >= 1 && a->H >= 1 && a->Tk >= 1 && (long)a->R * a->H <= 0x7fffffffL, "bad shape");
+  WFT_CHECK_ARG(a->group >= 1 && a->group <= 8 && a->R % a->group == 0, "group must lie in 1..8 and divide the rows");
+  const long d = (long)a->H * 64;
+  WFT_CHECK_ARG(a->ldq >= d && a->ldo >= d && a->ld_cache >= d, "leading dimensions must cover H * 64 = d");
+  WFT_CHECK_ARG(a->ldq % 8 == 0 && a->ldo % 8 == 0 && a->ld_cache % 8 == 0 && a->cache_bs % 8 == 0, "ld / batch strides must be multiples of 8");
+  WFT_CHECK_ARG(a->cache_bs >= (int64_t)(a->Tk - 1) * a->ld_cache + d, "cache capacity: a slot's Tk rows must fit its batch stride");
+  WFT_CHECK_ARG(((((uintptr_t)a->q) | ((uintptr_t)a->k_cache) | ((uintptr_t)a->v_cache) | ((uintptr_t)a->o)) & 15) == 0, "16-byte alignment");
+  if (a->len) {
+    WFT_CHECK_ARG(a->group == 1, "the self form (len given) takes group = 1");
+    WFT_CHECK_ARG(a->anc && a->ld_anc >= a->Tk, "the self form needs the ancestry table, ld_anc >= Tk");
+    WFT_CHECK_ARG(a->k_new && a->v_new, "self-attention form (len given) needs the step's k / v rows");
+    WFT_CHECK_ARG(a->ld_new >= d && a->ld_new % 8 == 0 && ((((uintptr_t)a->k_new) | ((uintptr_t)a->v_new)) & 15) == 0, "k_new / v_new layout");
+  }
+  WFT_CHECK_ARG(a->scale > 0.f, "scale");
+  const int ns = beam_nsplit(a);
+  if (ns > 1)
+    WFT_CHECK_ARG(a->workspace && a->workspace_bytes >= wft_attn_decode_beam_workspace_bytes(a) && (((uintptr_t)a->workspace) & 15) == 0,
+                  "workspace of wft_attn_decode_beam_workspace_bytes(args) bytes");
+  const float alpha = a->q_prescaled ? 1.0f : a->scale * 1.4426950408889634f;
+  const dim3 grid((unsigned)((a->R / a->group) * a->H), (unsigned)ns), block(DEC_WAVES * 64);
+  hipStream_t s = (hipStream_t)stream;
+#define BEAM_LAUNCH(W_, SELF_) hipLaunchKernelGGL((attn_decode_beam_kernel<W_, SELF_>), grid, block, 0, s, *a, ns, alpha)
+  if (a->len) {
+    BEAM_LAUNCH(1, true);
+  } else {
+    switch (a->group) {
+      case 1: BEAM_LAUNCH(1, false); break;
+      case 2: BEAM_LAUNCH(2, false); break;
+      case 3: BEAM_LAUNCH(3, false); break;
+      case 4: BEAM_LAUNCH(4, false); break;
+      case 5: BEAM_LAUNCH(5, false); break;
+      case 6: BEAM_LAUNCH(6, false); break;
+      case 7: BEAM_LAUNCH(7, false); break;
+      default: BEAM_LAUNCH(8, false); break;
+    }
+  }
+#undef BEAM_LAUNCH
+  if (ns > 1)
+    hipLaunchKernelGGL(attn_decode_merge_kernel, dim3((unsigned)(a->R * a->H)), dim3(64), 0, s, (const float*)a->workspace, ns, a->o,
+                       (long)a->ldo, a->H);
+  WFT_CHECK_LAUNCH();
+  return WFT_OK;
+}
+
+// ----------------------------------------------------------------------------- the W + 1 best continuations of a row
+// One workgroup per logits row, decode_pick_kernel's 16-byte row reads and masks.  Pass 1: every thread keeps the TOPK_MAX best
+// (value, column) of ITS columns as a sorted list in registers (columns come in ascending order, so a tie stays behind the lower
+// column).  Merge: k rounds, each the workgroup's best list head under (value desc, column asc) — a fixed-order tree, no atomics —
+// after which the one thread that owns that column pops it.  Pass 2 (the row is L2-resident): decode_pick_kernel's sum of
+// exp(x - max), in its order; log p = (x - max) - log(sum).  A live column whose logit is -inf can never be a candidate.
+#define TOPK_MAX 9
+#define TOPK_NONE 0x7fffffff
+
+__global__ __launch_bounds__(PICK_THREADS) void decode_topk_kernel(wft_decode_topk_args a) {
+  __shared__ float s_v[PICK_THREADS / 64];
+  __shared__ int s_i[PICK_THREADS / 64];
+  __shared__ float s_sum[PICK_THREADS / 64];
+  __shared__ float s_wv[TOPK_MAX];
+  __shared__ int s_wi[TOPK_MAX];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long r = (long)blockIdx.x * a.row_step;
+  const unsigned short* row = a.logits + (long)blockIdx.x * a.ld;
+  const int V = (int)a.V;
+  const unsigned char* m1 = a.suppress;
+  const unsigned char* m2 = (a.suppress_first && a.first_len && a.len && a.len[r] == a.first_len[r]) ? a.suppress_first : nullptr;
+
+  float lv[TOPK_MAX];
+  int li[TOPK_MAX];
+#pragma unroll
+  for (int p = 0; p < TOPK_MAX; ++p) {
+    lv[p] = -INFINITY;
+    li[p] = TOPK_NONE;
+  }
+  for (int c0 = tid * 8; c0 < V; c0 += PICK_THREADS * 8) {
+    float f[8];
+    dec_unpack8(*(const u32x4*)(row + c0), f);  // (ld % 8 == 0 and ld >= V rounded up to 8: in bounds)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int col = c0 + j;
+      const bool live = col < V && !(m1 && m1[col]) && !(m2 && m2[col]);
+      if (live && f[j] > lv[TOPK_MAX - 1]) {
+        lv[TOPK_MAX - 1] = f[j];
+        li[TOPK_MAX - 1] = col;
+#pragma unroll
+        for (int p = TOPK_MAX - 1; p > 0; --p) {
+          if (lv[p] > lv[p - 1]) {  // strict: an equal value stays behind the earlier (lower) column
+            const float tv = lv[p]; lv[p] = lv[p - 1]; lv[p - 1] = tv;
+            const int ti = li[p]; li[p] = li[p - 1]; li[p - 1] = ti;
+          }
+        }
+      }
+    }
+  }
+
+  for (int rnd = 0; rnd < a.k; ++rnd) {
+    float best = lv[0];
+    int bi = li[0];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(best, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (pick_better(ov, oi, best, bi)) {
+        best = ov;
+        bi = oi;
+      }
+    }
+    if (lane == 0) {
+      s_v[wave] = best;
+      s_i[wave] = bi;
+    }
+    __syncthreads();
+    best = s_v[0];
+    bi = s_i[0];
+    for (int w = 1; w < PICK_THREADS / 64; ++w)
+      if (pick_better(s_v[w], s_i[w], best, bi)) {
+        best = s_v[w];
+        bi = s_i[w];
+      }
+    if (bi != TOPK_NONE && li[0] == bi) {  // the owner of that column pops it
+#pragma unroll
+      for (int p = 0; p < TOPK_MAX - 1; ++p) {
+        lv[p] = lv[p + 1];
+        li[p] = li[p + 1];
+      }
+      lv[TOPK_MAX - 1] = -INFINITY;
+      li[TOPK_MAX - 1] = TOPK_NONE;
+    }
+    if (tid == 0) {
+      s_wv[rnd] = best;
+      s_wi[rnd] = bi;
+    }
+    __syncthreads();
+  }
+  const float top = s_wv[0];
+  const bool any = s_wi[0] != TOPK_NONE;
+
+  float sum = 0.f;
+  if (any) {
+    for (int c0 = tid * 8; c0 < V; c0 += PICK_THREADS * 8) {
+      float f[8];
+      dec_unpack8(*(const u32x4*)(row + c0), f);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int col = c0 + j;
+        const bool live = col < V && !(m1 && m1[col]) && !(m2 && m2[col]);
+        sum += live ? __expf(f[j] - top) : 0.f;
+      }
+    }
+  }
+  sum = wave_sum(sum);
+  if (lane == 0) s_sum[wave] = sum;
+  __syncthreads();
+  if (tid < a.k) {
+    float tot = s_sum[0];
+    for (int w = 1; w < PICK_THREADS / 64; ++w) tot += s_sum[w];
+    const bool have = s_wi[tid] != TOPK_NONE;
+    a.cand_tok[r * a.k + tid] = have ? s_wi[tid] : -1;
+    a.cand_logp[r * a.k + tid] = have ? (s_wv[tid] - top) - __logf(tot) : -INFINITY;
+  }
+}
+
+extern "C" int wft_decode_topk(const wft_decode_topk_args* a, void* stream) {
+  WFT_CHECK_ARG(a && a->logits && a->cand_tok && a->cand_logp, "null pointer");
+  WFT_CHECK_ARG(a->rows >= 1 && a->row_step >= 1 && a->V >= 1 && a->V <= 0x7ffffff0L, "bad shape");
+  WFT_CHECK_ARG(a->k >= 2 && a->k <= TOPK_MAX, "k = beam size + 1 must lie in 2..9");
+  WFT_CHECK_ARG(a->ld % 8 == 0 && a->ld >= (a->V + 7) / 8 * 8 && (((uintptr_t)a->logits) & 15) == 0, "logits rows: 16-byte aligned, ld >= V rounded up to 8");
+  WFT_CHECK_ARG(!a->suppress_first || (a->first_len && a->len), "suppress_first needs len and first_len");
+  hipLaunchKernelGGL(decode_topk_kernel, dim3((unsigned)a->rows), dim3(PICK_THREADS), 0, (hipStream_t)stream, *a);
+  WFT_CHECK_LAUNCH();
+  return WFT_OK;
+}
+
+// ----------------------------------------------------------------------------- one beam-search step per audio
+// One workgroup per audio (include/wft.h wft_beam_update).  The <= 72 candidates are ranked by counting, thread 0 walks the order,
+// then the rows of `tokens` and `anc` are permuted in place: a permutation of rows touches one column at a time, so the thread that
+// owns column t reads its W values into registers and writes them back permuted — no scratch copy, nothing to order between threads.
+#define BEAM_MAX_W 8
+#define BEAM_THREADS 256
+#define BEAM_MAX_CAND (BEAM_MAX_W * (BEAM_MAX_W + 1))
+
+template <typename T>
+__device__ __forceinline__ T beam_sel(const T* v, int j) {
+  T out = v[0];
+#pragma unroll
+  for (int i = 1; i < BEAM_MAX_W; ++i) out = j == i ? v[i] : out;
+  return out;
+}
+
+__global__ __launch_bounds__(BEAM_THREADS) void beam_update_kernel(wft_beam_update_args a) {
+  __shared__ float s_score[BEAM_MAX_CAND];
+  __shared__ int s_tok[BEAM_MAX_CAND];
+  __shared__ int s_order[BEAM_MAX_CAND];
+  __shared__ int s_src[BEAM_MAX_W], s_ntok[BEAM_MAX_W], s_fsrc[BEAM_MAX_W];
+  __shared__ float s_nscore[BEAM_MAX_W], s_fscore[BEAM_MAX_W];
+  __shared__ int s_nfin;
+  const int au = blockIdx.x, tid = threadIdx.x, W = a.W, k = W + 1;
+  if (a.done[au]) return;  // a done audio is frozen
+  const int r0 = au * W;
+  const int L = a.len[r0];
+  const int have = a.fin_n[au];
+  if (L < 1 || L >= a.max_len || have < 0 || have >= a.C) {  // (nothing can be appended: the audio ends here)
+    if (tid == 0) a.done[au] = 1;
+    return;
+  }
+  const int nc = (a.first ? 1 : W) * k;
+  if (tid < nc) {
+    const int j = tid / k, i = tid - j * k;
+    const int tok = a.cand_tok[(long)(r0 + j) * k + i];
+    float sc = __fadd_rn(a.sum_logprob[r0 + j], a.cand_logp[(long)(r0 + j) * k + i]);
+    sc = (tok >= 0 && sc == sc) ? sc : -INFINITY;
+    s_tok[tid] = tok;
+    s_score[tid] = sc;
+  }
+  __syncthreads();
+  if (tid < nc) {
+    const float sc = s_score[tid];
+    int rank = 0;
+    for (int o = 0; o < nc; ++o) {
+      const float so = s_score[o];
+      rank += (so > sc || (so == sc && o < tid)) ? 1 : 0;
+    }
+    s_order[rank] = tid;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int ns = 0, nf = 0;
+    for (int p = 0; p < nc && ns < W; ++p) {
+      const int cnd = s_order[p], tok = s_tok[cnd], j = cnd / k;
+      if (tok < 0) continue;
+      if (tok == a.eot) {
+        if (have + nf < a.C) {
+          s_fsrc[nf] = j;
+          s_fscore[nf] = s_score[cnd];
+          ++nf;
+        }
+      } else {
+        s_src[ns] = j;
+        s_ntok[ns] = tok;
+        s_nscore[ns] = s_score[cnd];
+        ++ns;
+      }
+    }
+    for (; ns < W; ++ns) {  // (not reached while W non-eot candidates exist, which the host checks)
+      s_src[ns] = ns;
+      s_ntok[ns] = a.eot;
+      s_nscore[ns] = -INFINITY;
+    }
+    s_nfin = nf;
+  }
+  __syncthreads();
+  const int nf = s_nfin;
+  for (int t = tid; t < (int)a.ld_tokens; t += BEAM_THREADS) {
+    long v[BEAM_MAX_W];
+    int w[BEAM_MAX_W];
+#pragma unroll
+    for (int j = 0; j < BEAM_MAX_W; ++j) {
+      v[j] = (j < W && t < L) ? a.tokens[(long)(r0 + j) * a.ld_tokens + t] : 0;
+      w[j] = (j < W && t < L - 1) ? a.anc[(long)(r0 + j) * a.ld_anc + t] : 0;
+    }
+    for (int e = 0; e < nf; ++e)
+      a.fin_tokens[((long)au * a.C + have + e) * a.ld_tokens + t] = t < L ? beam_sel(v, s_fsrc[e]) : (long)a.eot;
+    if (t <= L) {
+      for (int s = 0; s < W; ++s) {
+        const int j = s_src[s];
+        a.tokens[(long)(r0 + s) * a.ld_tokens + t] = t < L ? beam_sel(v, j) : (long)s_ntok[s];
+        if (t < L) a.anc[(long)(r0 + s) * a.ld_anc + t] = t < L - 1 ? beam_sel(w, j) : r0 + j;
+      }
+    }
+  }
+  if (tid < W) {
+    a.sum_logprob[r0 + tid] = s_nscore[tid];
+    a.len[r0 + tid] = L + 1;
+    if (a.src_out) a.src_out[r0 + tid] = s_src[tid];
+  }
+  if (tid == 0) {
+    for (int e = 0; e < nf; ++e) {
+      a.fin_len[(long)au * a.C + have + e] = L + 1;
+      a.fin_score[(long)au * a.C + have + e] = s_fscore[e];
+    }
+    a.fin_n[au] = have + nf;
+    a.done[au] = (have + nf >= a.C || L + 1 >= a.max_len) ? 1 : 0;
+  }
+}
+
+extern "C" int wft_beam_update(const wft_beam_update_args* a, void* stream) {
+  WFT_CHECK_ARG(a && a->cand_tok && a->cand_logp && a->tokens && a->anc && a->len && a->sum_logprob && a->done && a->unfinished, "null pointer");
+  WFT_CHECK_ARG(a->fin_tokens && a->fin_len && a->fin_score && a->fin_n, "null pointer (finished lists)");
+  WFT_CHECK_ARG(a->B >= 1 && a->W >= 1 && a->W <= BEAM_MAX_W, "beam size must lie in 1..8");
+  WFT_CHECK_ARG(a->C >= 1, "the finished lists hold C >= 1 entries");
+  WFT_CHECK_ARG(a->max_len >= 1 && a->max_len <= a->ld_tokens && a->max_len <= a->ld_anc, "max_len must fit the token buffer and the ancestry table");
+  WFT_CHECK_ARG(a->eot >= 0, "eot outside the vocabulary");
+  hipLaunchKernelGGL(beam_update_kernel, dim3((unsigned)a->B), dim3(BEAM_THREADS), 0, (hipStream_t)stream, *a);
+  hipLaunchKernelGGL(decode_count_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int*)a->done, a->B, a->unfinished);
   WFT_CHECK_LAUNCH();
   return WFT_OK;
 }

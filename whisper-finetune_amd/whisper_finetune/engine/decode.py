@@ -1,8 +1,9 @@
-"""KV-cached greedy decoding on the engine's decoder: token ids in, token ids out.
+"""KV-cached greedy and beam-search decoding on the engine's decoder: token ids in, token ids out.
 
 The greedy path of upstream's `whisper.decoding` (`DecodingTask._main_loop` with `GreedyDecoder`, `SuppressTokens`,
-`SuppressBlank`, `DecodingOptions(without_timestamps=True)`); no tokenizer, beam search, temperature fallback, timestamp rules
-or language detection.
+`SuppressBlank`, `DecodingOptions(without_timestamps=True)`) and, in the second half of this file, its `BeamSearchDecoder` +
+`MaximumLikelihoodRanker` on a KV cache that the beams of an audio share (`BeamCache`, `beam_decode`); no tokenizer, temperature
+fallback, timestamp rules or language detection.
 
 Everything that changes from token to token lives in device memory (`KVCache`: len / tokens / finished / sum_logprob), so a
 step is a fixed sequence of launches whose arguments never change: LayerNorm and every projection through the existing
@@ -154,6 +155,8 @@ MAX_SESSIONS = 2  # graph sessions kept per model (one per (batch, device)); the
 # model -> OrderedDict[(batch, device) -> _GraphSession].  Kept OFF the module, like engine/graph.py's registry: CUDAGraph objects
 # neither pickle nor deep-copy, and a dropped model drops its sessions.
 _SESSIONS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
+# the same for beam search, in a table of its own: model -> OrderedDict[(audios, beam, candidates, device) -> _BeamGraphSession]
+_BEAM_SESSIONS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 
 
 def _groups(decoder):
@@ -173,8 +176,13 @@ class _GraphSession:
     weight shadows and stacked biases of every Linear group, the scratch slots — is referenced by `keep` and named in the
     fingerprint that is compared after every prefill: any difference recaptures, a mismatch never replays."""
 
+    who = "greedy_decode"
+
     def __init__(self, decoder, batch: int, device):
         self.cache = KVCache(decoder, batch, device=device)
+        self._init_static(decoder, device)
+
+    def _init_static(self, decoder, device):
         self.cross = {}      # attn module -> static bf16 [B, n_audio_ctx, 2d]
         V = decoder.token_embedding.weight.shape[0]
         self.suppress = torch.zeros(V, dtype=torch.uint8, device=device)
@@ -202,6 +210,12 @@ class _GraphSession:
             elif m is not buf:
                 buf.copy_(m)
             setattr(c, name, buf)
+
+    def _body(self, decoder):
+        """What one replay runs, on the static buffers of self.cache."""
+        logits = step(decoder, self.cache)
+        pick(decoder, self.cache, logits)
+        return logits
 
     def _fingerprint(self, decoder, stream: bool, slots=None):
         c = self.cache
@@ -242,16 +256,15 @@ class _GraphSession:
             with torch.cuda.stream(side):
                 with torch.cuda.graph(g, stream=side):
                     with stream_gemm(stream):
-                        logits = step(decoder, c)
-                        pick(decoder, c, logits)
+                        logits = self._body(decoder)
         except Exception as exc:
             # (tensors first allocated inside a failed capture must not be used: nothing of this session survives)
             self.graph = None
-            raise RuntimeError(f"greedy_decode(step='graph'): capturing the decoding step failed ({type(exc).__name__}: {exc}); "
+            raise RuntimeError(f"{self.who}(step='graph'): capturing the decoding step failed ({type(exc).__name__}: {exc}); "
                                "use step='eager'") from exc
         cur.wait_stream(side)
         if self._fingerprint(decoder, stream)[0] != fp:
-            raise RuntimeError("greedy_decode(step='graph'): a buffer of the decoding step was replaced DURING its capture (a scratch slot "
+            raise RuntimeError(f"{self.who}(step='graph'): a buffer of the decoding step was replaced DURING its capture (a scratch slot "
                                "or a weight shadow that the warm-up step should have created); use step='eager'")
         self.graph, self.fingerprint, self.keep, self.slots = g, fp, keep + [logits], slots
         self.captures += 1
@@ -284,9 +297,10 @@ def sessions(model) -> dict:
 def release_graphs(model) -> None:
     """Drop every captured decoding step of `model` with the static buffers it pins (self-attention cache, cross keys / values,
     the graph's private pool).  The evaluator calls it when a dataset is done, so nothing stays pinned during training."""
-    reg = _SESSIONS.pop(model, None)
-    if reg:
-        reg.clear()
+    for table in (_SESSIONS, _BEAM_SESSIONS):
+        reg = table.pop(model, None)
+        if reg:
+            reg.clear()
 
 
 STEP_MODES = ("eager", "graph")
@@ -349,5 +363,311 @@ def greedy_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=Non
         tokens = cache.tokens[:, :L].clone()
         tokens.masked_fill_(torch.arange(L, device=tokens.device)[None, :] >= lengths[:, None], cache.eot)
         return tokens, lengths, cache.sum_logprob.clone()
+    finally:
+        model.train(was_training)
+
+
+# ============================================================================= beam search
+# Upstream's `BeamSearchDecoder` + `MaximumLikelihoodRanker` under `without_timestamps=True`, restated (neither is in the reference
+# tree and openai-whisper is not a dependency: parity with the upstream binary is unpinned).  W = beam_size; audio a owns the rows
+# r = a*W + j; all rows of an audio hold the same `len`; C = round(W * patience) finished sequences end an audio.  One step, per
+# audio that is not done (csrc/decode.hip: wft_decode_topk, wft_beam_update; include/wft.h states the order rules):
+#   the W + 1 most probable continuations of every beam -> candidates scored sum_logprob + logp -> walked in descending order: an
+#   `eot` candidate joins the audio's finished list (while that holds fewer than C), any other becomes the next beam, until W beams.
+# What makes it cheap (DESIGN.md §3 "Beam-search layouts"): the cross keys / values exist once per AUDIO and are read once per step
+# for all of its beams; self-attention keys are never moved — a beam reorder permutes rows of the i32 ancestry table `anc`.
+MAX_BEAM = 8
+
+
+def beam_candidates(beam_size: int, patience: float = 1.0) -> int:
+    """C = round(beam_size * patience) with Python's round — how many finished sequences end an audio.  Raises ValueError on a bad
+    beam size or patience."""
+    if isinstance(beam_size, bool) or not isinstance(beam_size, int) or not 1 <= beam_size <= MAX_BEAM:
+        raise ValueError(f"beam_size must be an integer in [1, {MAX_BEAM}], got {beam_size!r}")
+    if isinstance(patience, bool) or not isinstance(patience, (int, float)) or not patience > 0 or patience != patience or patience == float("inf"):
+        raise ValueError(f"patience must be a positive finite number, got {patience!r}")
+    C = round(beam_size * patience)
+    if C < 1:
+        raise ValueError(f"round(beam_size * patience) = {C}: patience={patience!r} leaves no room for a finished sequence")
+    return C
+
+
+def _check_live_columns(beam_size: int, n_vocab: int, suppress: Sequence[int], suppress_first: Sequence[int]) -> None:
+    """At least W + 1 columns stay live under suppress | suppress_first: then every step has >= W candidates that are not `eot`."""
+    dead = {int(t) for t in suppress} | {int(t) for t in suppress_first}
+    if dead and (min(dead) < 0 or max(dead) >= n_vocab):
+        raise ValueError("suppressed token ids must lie inside the vocabulary")
+    if n_vocab - len(dead) < beam_size + 1:
+        raise ValueError(f"beam_size={beam_size} needs at least {beam_size + 1} un-suppressed columns, {n_vocab - len(dead)} of {n_vocab} are left")
+
+
+class BeamCache:
+    """Keys / values plus the beam-search state of `audios` audios x `beam_size` hypotheses (R = audios * beam_size slot rows).
+
+    Handed to the decoder as `kv_cache=` like a KVCache: a call with T > 1 tokens is the prefill — ONE row per audio through the
+    teacher-forced kernels, its k / v stored into slot row a*W —, a call with T = 1 a cached step of all R rows.
+      self_kv[attn]  bf16 [R, n_text_ctx, 2d]   slot rows; hypothesis r reads position t at slot anc[r, t]
+      anc            i32 [R, n_text_ctx]         the ancestry table: keys never move, a beam reorder permutes these rows
+      cross_kv[attn] bf16 [audios, n_audio_ctx, 2d]   one copy per audio, shared by its beams
+      tokens i64 [R, n_ctx], len / first_len i32 [R], sum_logprob f32 [R], done i32 [audios], unfinished i32 [1]
+      cand_tok i32 / cand_logp f32 [R, W + 1]    the step's candidates;  src i32 [R]: the source beam of every slot's last update
+      fin_tokens i64 [audios, C, n_ctx], fin_len i32 / fin_score f32 [audios, C], fin_n i32 [audios]   the finished lists"""
+
+    def __init__(self, decoder, audios: int, beam_size: int, candidates: Optional[int] = None, device=None):
+        pos = decoder.positional_embedding
+        device = pos.device if device is None else device
+        self.n_ctx, d = pos.shape
+        W = int(beam_size)
+        C = beam_candidates(W) if candidates is None else int(candidates)
+        if not 1 <= W <= MAX_BEAM or C < 1:
+            raise ValueError(f"beam_size must lie in [1, {MAX_BEAM}] and candidates be >= 1")
+        self.audios, self.beam, self.cands = int(audios), W, C
+        R = self.batch = self.audios * W  # rows of a cached step (the name the decoder reads)
+        self.self_kv = {blk.attn: torch.empty((R, self.n_ctx, 2 * d), dtype=BF16, device=device) for blk in decoder.blocks}
+        self.cross_kv = {blk.cross_attn: None for blk in decoder.blocks}
+        i32 = dict(dtype=torch.int32, device=device)
+        f32 = dict(dtype=torch.float32, device=device)
+        self.anc = torch.zeros((R, self.n_ctx), **i32)
+        self.tokens = torch.zeros((R, self.n_ctx), dtype=torch.int64, device=device)
+        self.len = torch.ones(R, **i32)
+        self.first_len = torch.ones(R, **i32)
+        self.sum_logprob = torch.zeros(R, **f32)
+        self.done = torch.zeros(self.audios, **i32)
+        self.unfinished = torch.full((1,), self.audios, **i32)
+        self.cand_tok = torch.full((R, W + 1), -1, **i32)
+        self.cand_logp = torch.zeros((R, W + 1), **f32)
+        self.src = torch.zeros(R, **i32)
+        self.fin_tokens = torch.zeros((self.audios, C, self.n_ctx), dtype=torch.int64, device=device)
+        self.fin_len = torch.zeros((self.audios, C), **i32)
+        self.fin_score = torch.zeros((self.audios, C), **f32)
+        self.fin_n = torch.zeros(self.audios, **i32)
+        self.prompt_T = 0
+        self.prefilled = False
+        self.eot, self.max_len = 0, self.n_ctx
+        self.suppress = self.suppress_first = None
+
+    def is_cross(self, attn) -> bool:
+        return attn in self.cross_kv
+
+    def start(self, prompt: torch.Tensor, prompt_len: Optional[torch.Tensor], *, eot: int, max_len: Optional[int] = None,
+              suppress: Sequence[int] = (), suppress_first: Sequence[int] = (), n_vocab: int) -> None:
+        """Load the prompts (i64 [audios, T], right-padded; prompt_len [audios] or None) into all W rows of every audio and reset
+        the state.  The checks of KVCache.start plus the live-column count."""
+        B, T = prompt.shape
+        W = self.beam
+        max_len = self.n_ctx if max_len is None else int(max_len)
+        if B != self.audios or not 1 <= T <= self.n_ctx:
+            raise ValueError(f"prompt {tuple(prompt.shape)} does not fit a cache of {self.audios} x {self.n_ctx}")
+        if not T <= max_len <= self.n_ctx:
+            raise ValueError(f"max_len={max_len} must lie in [prompt width {T}, n_text_ctx {self.n_ctx}]")
+        if not 0 <= int(eot) < n_vocab:
+            raise ValueError(f"eot={eot} is outside the vocabulary")
+        _check_live_columns(W, n_vocab, suppress, suppress_first)
+        dev = self.tokens.device
+        if prompt_len is None:
+            pl = torch.full((B,), T, dtype=torch.int32)
+        else:
+            pl = torch.as_tensor(prompt_len).to(device="cpu", dtype=torch.int32).reshape(B)
+            if int(pl.min()) < 1 or int(pl.max()) > T:
+                raise ValueError("prompt_len must lie in [1, prompt width]")
+        self.tokens.fill_(int(eot))
+        self.tokens.view(B, W, self.n_ctx)[:, :, :T].copy_(prompt.to(dev)[:, None, :])
+        self.len.copy_(pl.to(dev).repeat_interleave(W))
+        self.first_len.copy_(self.len)
+        self.anc.copy_((torch.arange(B, dtype=torch.int32, device=dev) * W).repeat_interleave(W)[:, None].expand(-1, self.n_ctx))
+        self.done.copy_((pl >= max_len).to(torch.int32))
+        self.unfinished.copy_((self.done == 0).sum().to(torch.int32).reshape(1))
+        self.sum_logprob.zero_()
+        self.cand_tok.fill_(-1); self.cand_logp.zero_(); self.src.zero_()
+        self.fin_tokens.fill_(int(eot)); self.fin_len.zero_(); self.fin_score.zero_(); self.fin_n.zero_()
+        self.prompt_T, self.prefilled = T, False
+        self.eot, self.max_len = int(eot), max_len
+        self.suppress = _mask(suppress, n_vocab, dev)
+        self.suppress_first = _mask(suppress_first, n_vocab, dev)
+        for key in self.cross_kv:
+            self.cross_kv[key] = None
+
+
+def beam_prefill(decoder, cache: BeamCache, xa: torch.Tensor) -> torch.Tensor:
+    """The prompts, ONE row per audio, through the teacher-forced kernels (k / v stored into slot row a*W, cross k / v computed once
+    per audio) -> padded bf16 logits [audios, Vpad] of every audio's last prompt position."""
+    B, W = cache.audios, cache.beam
+    T = min(max(cache.prompt_T, 2), cache.n_ctx)  # (a one-token prompt block is widened by a pad column: T = 1 means "cached step")
+    h = decoder.hidden(cache.tokens[::W, :T], xa, kv_cache=cache)  # [B, T, d]
+    rows = torch.arange(B, device=h.device) * T + (cache.len[::W].long() - 1)
+    last = h.reshape(B * T, -1).index_select(0, rows)
+    cache.prefilled = True
+    return decoder.padded_logits(last.view(B, 1, -1))
+
+
+def beam_step(decoder, cache: BeamCache) -> torch.Tensor:
+    """One cached step: the token at len[r] - 1 of every hypothesis through the decoder -> padded bf16 logits [R, Vpad]."""
+    return decoder.padded_logits(decoder.hidden(None, None, kv_cache=cache))
+
+
+def beam_topk(decoder, cache: BeamCache, logits: torch.Tensor, first: bool = False) -> None:
+    """cand_tok / cand_logp <- the W + 1 best continuations per logits row (wft_decode_topk).  first: `logits` are the prefill's,
+    one row per audio, and fill the candidate row of beam 0."""
+    V = decoder.token_embedding.weight.shape[0]
+    K.decode_topk(logits, V, cache.cand_tok, cache.cand_logp, lens=cache.len, first_len=cache.first_len, suppress=cache.suppress,
+                  suppress_first=cache.suppress_first, row_step=cache.beam if first else 1)
+
+
+def beam_update(cache: BeamCache, first: bool = False) -> None:
+    """One beam-search step of every audio that is not done, from cand_tok / cand_logp (wft_beam_update)."""
+    K.beam_update(cache.cand_tok, cache.cand_logp, cache.tokens, cache.anc, cache.len, cache.sum_logprob, cache.done, cache.unfinished,
+                  cache.fin_tokens, cache.fin_len, cache.fin_score, cache.fin_n, eot=cache.eot, max_len=cache.max_len, first=first,
+                  src_out=cache.src)
+
+
+def beam_rank(entries, length_penalty: Optional[float] = None) -> int:
+    """entries: [(n generated tokens without the final eot, sum_logprob)] in list order -> index of the first maximum of
+    sum_logprob / n, or / ((5 + n) / 6) ** length_penalty; n = 0 ranks as -inf."""
+    best, best_i = None, 0
+    for i, (n, slp) in enumerate(entries):
+        score = beam_score(n, slp, length_penalty)
+        if best is None or score > best:
+            best, best_i = score, i
+    return best_i
+
+
+def beam_score(n: int, sum_logprob: float, length_penalty: Optional[float] = None) -> float:
+    if n <= 0:
+        return float("-inf")
+    return float(sum_logprob) / (float(n) if length_penalty is None else ((5.0 + n) / 6.0) ** float(length_penalty))
+
+
+def beam_finalize(cache: BeamCache, length_penalty: Optional[float] = None):
+    """End of decoding, on the host (one small read-back): an audio with fewer than W finished entries receives its current beams in
+    descending sum_logprob (ties to the lower j) until it holds W; the entries are ranked by beam_score; the first maximum in list
+    order wins.  -> per audio the list of (tokens incl. prompt and a final eot if the hypothesis ended with one, sum_logprob, score),
+    in LIST order, and the winner's index."""
+    B, W = cache.audios, cache.beam
+    fin_tokens, fin_len, fin_score, fin_n = cache.fin_tokens.cpu(), cache.fin_len.cpu().tolist(), cache.fin_score.cpu(), cache.fin_n.cpu().tolist()
+    tokens, lens, first, slp = cache.tokens.cpu(), cache.len.cpu().tolist(), cache.first_len.cpu().tolist(), cache.sum_logprob.cpu()
+    out = []
+    for a in range(B):
+        r0 = a * W
+        entries = [(fin_tokens[a, p, :fin_len[a][p]].tolist(), float(fin_score[a, p]), fin_len[a][p] - first[r0] - 1) for p in range(fin_n[a])]
+        order = sorted(range(W), key=lambda j: -float(slp[r0 + j]))  # (stable: ties to the lower j)
+        for j in order:
+            if len(entries) >= W:
+                break
+            entries.append((tokens[r0 + j, :lens[r0 + j]].tolist(), float(slp[r0 + j]), lens[r0 + j] - first[r0 + j]))
+        win = beam_rank([(n, s) for _, s, n in entries], length_penalty)
+        out.append(([(t, s, beam_score(n, s, length_penalty)) for t, s, n in entries], win))
+    return out
+
+
+class _BeamGraphSession(_GraphSession):
+    """One HIP graph = beam_step + beam_topk + beam_update on the static buffers of ONE BeamCache (the first update of a decode, fed
+    by the prefill, stays outside).  Fingerprint, warm-up and failure handling are _GraphSession's."""
+
+    who = "beam_decode"
+
+    def __init__(self, decoder, audios: int, beam_size: int, candidates: int, device):
+        self.cache = BeamCache(decoder, audios, beam_size, candidates, device=device)
+        self._init_static(decoder, device)
+
+    def _body(self, decoder):
+        logits = beam_step(decoder, self.cache)
+        beam_topk(decoder, self.cache, logits)
+        beam_update(self.cache)
+        return logits
+
+    def _fingerprint(self, decoder, stream: bool, slots=None):
+        fp, keep, slots = super()._fingerprint(decoder, stream, slots)
+        return fp + (("beam", self.cache.beam, self.cache.cands),), keep, slots
+
+
+def _beam_session(model, audios: int, beam_size: int, candidates: int, device) -> _BeamGraphSession:
+    reg = _BEAM_SESSIONS.get(model)
+    if reg is None:
+        reg = _BEAM_SESSIONS[model] = OrderedDict()
+    key = (int(audios), int(beam_size), int(candidates), str(device))
+    sess = reg.get(key)
+    if sess is None:
+        while len(reg) >= MAX_SESSIONS:
+            reg.popitem(last=False)
+        sess = reg[key] = _BeamGraphSession(model.decoder, audios, beam_size, candidates, device)
+    else:
+        reg.move_to_end(key)
+    return sess
+
+
+def beam_sessions(model) -> dict:
+    """{(audios, beam_size, candidates, device): session} of `model`: the captured beam steps (kept apart from `sessions(model)`)."""
+    return dict(_BEAM_SESSIONS.get(model) or {})
+
+
+@torch.no_grad()
+def beam_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None, *, beam_size: int, patience: float = 1.0,
+                length_penalty: Optional[float] = None, eot: int, max_len: Optional[int] = None, suppress: Sequence[int] = (),
+                suppress_first: Sequence[int] = (), sync_every: int = 8, step: str = "eager", return_all: bool = False,
+                _capture: bool = True, _stream_gemm: bool = True):
+    """Beam search -> (tokens i64 [B, L], lengths i64 [B], sum_logprob f32 [B]) of the winning hypothesis per audio, in greedy_decode's
+    layout: prompt included, the `eot` that ended the hypothesis included (one that ran into `max_len` has none), padded with `eot`.
+    return_all: a fourth value, per audio the list of (tokens, sum_logprob, score) of all its entries, best score first (stable).
+
+    beam_size 1..8; an audio ends once round(beam_size * patience) sequences have finished or at `max_len`; the winner maximises
+    sum_logprob / n over the generated tokens (n without the final eot), or sum_logprob / ((5 + n) / 6) ** length_penalty.
+    Argument errors are raised before any device work.  `step`, `sync_every`, `_capture`, `_stream_gemm`: as greedy_decode; the
+    captured beam steps live in their own sessions (`beam_sessions`), freed by `release_graphs` too."""
+    if step not in STEP_MODES:
+        raise ValueError(f"step must be one of {STEP_MODES}, got {step!r}")
+    C = beam_candidates(beam_size, patience)
+    if length_penalty is not None and (isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float))):
+        raise ValueError(f"length_penalty must be None or a number, got {length_penalty!r}")
+    _check_live_columns(beam_size, model.dims.n_vocab, suppress, suppress_first)
+    if getattr(model, "compute_dtype", "bf16") != "bf16":
+        raise NotImplementedError("beam_decode runs in the bf16 compute mode only: the single-token kernels (csrc/decode.hip) are bf16; "
+                                  "call model.set_compute_dtype('bf16') to decode")
+    if sync_every < 1:
+        raise ValueError("sync_every must be >= 1")
+    graph = step == "graph" and _capture
+    stream = step == "graph" and _stream_gemm
+    was_training = model.training
+    model.eval()
+    try:
+        dec = model.decoder
+        B = prompt.shape[0]
+        sess = _beam_session(model, B, beam_size, C, mel.device) if graph else None
+        cache = sess.cache if graph else BeamCache(dec, B, beam_size, C, device=mel.device)
+        cache.start(prompt, prompt_len, eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first, n_vocab=model.dims.n_vocab)
+        most = cache.max_len - int(cache.first_len.min())
+        if most > 0:
+            logits = beam_prefill(dec, cache, model.encoder(mel))
+            if graph:
+                sess.adopt_prefill()
+            beam_topk(dec, cache, logits, first=True)
+            beam_update(cache, first=True)
+            ready = graph and sess.valid(dec, stream)
+            warmed = False
+            for i in range(1, most):
+                if i % sync_every == 0 and int(cache.unfinished.item()) == 0:
+                    break
+                if graph and not ready and warmed:
+                    sess.capture(dec, stream)
+                    ready = True
+                if ready:
+                    sess.replay()
+                    continue
+                with stream_gemm(stream):
+                    logits = beam_step(dec, cache)
+                    beam_topk(dec, cache, logits)
+                    beam_update(cache)
+                warmed = True
+        ranked = beam_finalize(cache, length_penalty)
+        wins = [entries[win] for entries, win in ranked]
+        L = max(len(t) for t, _, _ in wins)
+        tokens = torch.full((B, L), cache.eot, dtype=torch.int64)
+        for a, (t, _, _) in enumerate(wins):
+            tokens[a, :len(t)] = torch.tensor(t, dtype=torch.int64)
+        dev = cache.tokens.device
+        res = (tokens.to(dev), torch.tensor([len(t) for t, _, _ in wins], dtype=torch.int64, device=dev),
+               torch.tensor([s for _, s, _ in wins], dtype=torch.float32, device=dev))
+        if return_all:
+            res += ([sorted(entries, key=lambda e: -e[2]) for entries, _ in ranked],)
+        return res
     finally:
         model.train(was_training)

@@ -681,6 +681,111 @@ def decode_pick(logits, V: int, tokens, lens, finished, sum_logprob, unfinished,
     return pick, lp
 
 
+# --------------------------------------------------------------------------- beam-search decoding (csrc/decode.hip)
+def attn_decode_beam(q, cache, n_head: int, scale: float, *, new_kv=None, lens=None, anc=None, group: int = 1, q_prescaled: bool = False,
+                     out=None, _args_only=False):
+    """Single-token attention for beams (wft_attn_decode_beam_bf16).  q bf16 [R, H*64] (any row stride).
+    Self form (new_kv, lens, anc given): cache bf16 [R, Tk, 2*H*64] of slot rows; key t of row r is read at slot anc[r, t] (i32
+    [R, >= Tk]), the step's k / v rows are written to cache[r, lens[r] - 1].  Cross form: cache bf16 [R // group, Tk, 2*H*64], read
+    only, shared by the `group` consecutive rows of an audio.  -> o bf16 [R, H*64]."""
+    _chk(q, BF16, "q"); _chk(cache, BF16, "cache")
+    R, D = q.shape
+    self_form = lens is not None
+    if (new_kv is None) != (lens is None) or (anc is None) != (lens is None):
+        raise ValueError("attn_decode_beam: the self form needs new_kv, lens and anc together")
+    if not 1 <= int(group) <= 8 or R % int(group) or (self_form and group != 1):
+        raise ValueError(f"attn_decode_beam: group={group} must lie in 1..8 and divide the {R} rows (1 in the self form)")
+    if D != n_head * 64 or cache.dim() != 3 or cache.shape[0] != R // group or cache.shape[2] != 2 * D or q.stride(1) != 1 or cache.stride(2) != 1:
+        raise ValueError(f"attn_decode_beam: q {tuple(q.shape)} / cache {tuple(cache.shape)} do not fit {n_head} heads of 64 at group {group}")
+    o = torch.empty((R, D), dtype=BF16, device=q.device) if out is None else out
+    a = L.AttnDecodeBeamArgs()
+    a.q, a.ldq = q.data_ptr(), q.stride(0)
+    a.k_cache, a.v_cache = cache.data_ptr(), cache.data_ptr() + 2 * D
+    a.ld_cache, a.cache_bs = cache.stride(1), cache.stride(0)
+    a.o, a.ldo = o.data_ptr(), o.stride(0)
+    if self_form:
+        k, v = new_kv
+        _chk(k, BF16, "k_new"); _chk(v, BF16, "v_new"); _chk(anc, torch.int32, "anc")
+        _chk_flag(lens, R, "lens")
+        if k.shape != (R, D) or v.shape != (R, D) or k.stride() != v.stride() or k.stride(1) != 1:
+            raise ValueError("attn_decode_beam: k_new / v_new must be [R, H*64] views with one row stride")
+        if anc.dim() != 2 or anc.shape[0] != R or anc.shape[1] < cache.shape[1] or anc.stride(1) != 1:
+            raise ValueError(f"attn_decode_beam: anc must be i32 [R, >= {cache.shape[1]}] with contiguous rows")
+        a.k_new, a.v_new, a.ld_new, a.len = k.data_ptr(), v.data_ptr(), k.stride(0), lens.data_ptr()
+        a.anc, a.ld_anc = anc.data_ptr(), anc.stride(0)
+    a.R, a.H, a.Tk, a.group, a.scale, a.q_prescaled = R, n_head, cache.shape[1], int(group), scale, int(bool(q_prescaled))
+    need = L.load().wft_attn_decode_beam_workspace_bytes(C.byref(a))
+    if need > 0:
+        ws = _tn_workspace(q.device, need, slot="attn_decode_beam")
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    if _args_only:
+        return a, o
+    L.check(L.load().wft_attn_decode_beam_bf16(C.byref(a), L.stream_ptr()), "wft_attn_decode_beam_bf16")
+    return o
+
+
+def decode_topk(logits, V: int, cand_tok, cand_logp, *, lens=None, first_len=None, suppress=None, suppress_first=None, row_step: int = 1):
+    """The k best continuations per logits row (wft_decode_topk).  logits bf16 [rows, ld >= V]; logits row i belongs to state row
+    i * row_step of lens / first_len / cand_tok i32 [R, k] / cand_logp f32 [R, k], which receive (token, log-probability) in
+    descending order, ties to the lower token."""
+    _chk(logits, BF16, "logits"); _chk(cand_tok, torch.int32, "cand_tok"); _chk(cand_logp, F32, "cand_logp")
+    rows = logits.shape[0]
+    if logits.dim() != 2 or logits.stride(1) != 1 or cand_tok.dim() != 2 or cand_tok.shape != cand_logp.shape or not cand_tok.is_contiguous() \
+            or not cand_logp.is_contiguous() or row_step < 1 or (rows - 1) * row_step >= cand_tok.shape[0]:
+        raise ValueError("decode_topk: logits [rows, ld], cand_tok / cand_logp contiguous [R, k] with (rows - 1) * row_step < R")
+    R, k = cand_tok.shape
+    a = L.DecodeTopkArgs()
+    a.logits, a.ld, a.V = logits.data_ptr(), logits.stride(0), V
+    for name, m in (("suppress", suppress), ("suppress_first", suppress_first)):
+        if m is not None:
+            _chk(m, torch.uint8, name)
+            if m.numel() != V or not m.is_contiguous():
+                raise ValueError(f"{name}: expected a contiguous uint8 mask of {V} entries")
+            setattr(a, name, m.data_ptr())
+    if lens is not None:
+        _chk_flag(lens, R, "lens")
+        a.len = lens.data_ptr()
+    if first_len is not None:
+        _chk_flag(first_len, R, "first_len")
+        a.first_len = first_len.data_ptr()
+    a.cand_tok, a.cand_logp = cand_tok.data_ptr(), cand_logp.data_ptr()
+    a.rows, a.row_step, a.k = rows, int(row_step), k
+    L.check(L.load().wft_decode_topk(C.byref(a), L.stream_ptr()), "wft_decode_topk")
+
+
+def beam_update(cand_tok, cand_logp, tokens, anc, lens, sum_logprob, done, unfinished, fin_tokens, fin_len, fin_score, fin_n, *, eot: int,
+                max_len: int, first: bool = False, src_out=None):
+    """One beam-search step per audio (wft_beam_update; include/wft.h).  cand_* [R, W + 1]; tokens i64 / anc i32 [R, n_ctx]; lens i32 /
+    sum_logprob f32 [R]; done i32 [B], unfinished i32 [1]; fin_tokens i64 [B, C, n_ctx], fin_len i32 / fin_score f32 [B, C], fin_n i32
+    [B].  Everything is updated in place."""
+    _chk(cand_tok, torch.int32, "cand_tok"); _chk(cand_logp, F32, "cand_logp"); _chk(tokens, torch.int64, "tokens"); _chk(anc, torch.int32, "anc")
+    _chk(sum_logprob, F32, "sum_logprob"); _chk(fin_tokens, torch.int64, "fin_tokens"); _chk(fin_score, F32, "fin_score")
+    R, k = cand_tok.shape
+    W, B = k - 1, done.numel()
+    if W < 1 or R != B * W or fin_tokens.dim() != 3 or fin_tokens.shape[0] != B:
+        raise ValueError(f"beam_update: {R} candidate rows of {k} do not fit {B} audios")
+    Cn = fin_tokens.shape[1]
+    ok = (cand_tok.is_contiguous() and cand_logp.is_contiguous() and cand_logp.shape == (R, k) and tokens.dim() == 2 and tokens.shape[0] == R
+          and tokens.stride(1) == 1 and anc.dim() == 2 and anc.shape[0] == R and anc.stride(1) == 1 and fin_tokens.is_contiguous()
+          and fin_tokens.shape[2] == tokens.stride(0) and fin_len.is_contiguous() and fin_score.is_contiguous()
+          and tuple(fin_len.shape) == (B, Cn) and tuple(fin_score.shape) == (B, Cn)
+          and max_len <= tokens.shape[1] and max_len <= anc.shape[1])
+    if not ok:
+        raise ValueError("beam_update: buffer layouts do not match (see the docstring)")
+    _chk_flag(lens, R, "lens"); _chk_flag(done, B, "done"); _chk_flag(unfinished, 1, "unfinished"); _chk_flag(fin_n, B, "fin_n")
+    _chk(fin_len, torch.int32, "fin_len")
+    a = L.BeamUpdateArgs()
+    a.cand_tok, a.cand_logp = cand_tok.data_ptr(), cand_logp.data_ptr()
+    a.tokens, a.ld_tokens, a.anc, a.ld_anc = tokens.data_ptr(), tokens.stride(0), anc.data_ptr(), anc.stride(0)
+    a.len, a.sum_logprob, a.done, a.unfinished = lens.data_ptr(), sum_logprob.data_ptr(), done.data_ptr(), unfinished.data_ptr()
+    a.fin_tokens, a.fin_len, a.fin_score, a.fin_n = fin_tokens.data_ptr(), fin_len.data_ptr(), fin_score.data_ptr(), fin_n.data_ptr()
+    if src_out is not None:
+        _chk_flag(src_out, R, "src_out")
+        a.src_out = src_out.data_ptr()
+    a.B, a.W, a.C, a.eot, a.max_len, a.first = B, W, Cn, int(eot), int(max_len), int(bool(first))
+    L.check(L.load().wft_beam_update(C.byref(a), L.stream_ptr()), "wft_beam_update")
+
+
 # --------------------------------------------------------------------------- embedding / CE
 def embed_fwd(tokens, emb, pos):
     _chk(tokens, torch.int64, "tokens"); _chk(emb, F32, "emb"); _chk(pos, F32, "pos")

@@ -101,6 +101,48 @@ class DecodePickArgs(C.Structure):
     ]
 
 
+class AttnDecodeBeamArgs(C.Structure):
+    """Mirror of wft_attn_decode_beam_args (include/wft.h): single-token attention for beams — self keys through the ancestry
+    table, cross keys shared by the `group` rows of an audio."""
+
+    _fields_ = [
+        ("q", c_vp), ("ldq", c_i64),
+        ("k_new", c_vp), ("v_new", c_vp), ("ld_new", c_i64),
+        ("k_cache", c_vp), ("v_cache", c_vp), ("ld_cache", c_i64), ("cache_bs", c_i64),
+        ("o", c_vp), ("ldo", c_i64),
+        ("len", c_vp),
+        ("anc", c_vp), ("ld_anc", c_i64),
+        ("R", C.c_int), ("H", C.c_int), ("Tk", C.c_int), ("group", C.c_int), ("scale", C.c_float), ("q_prescaled", C.c_int),
+        ("workspace", c_vp), ("workspace_bytes", c_i64),
+    ]
+
+
+class DecodeTopkArgs(C.Structure):
+    """Mirror of wft_decode_topk_args (include/wft.h): the W + 1 best continuations of every logits row."""
+
+    _fields_ = [
+        ("logits", c_vp), ("ld", c_i64), ("V", c_i64),
+        ("suppress", c_vp), ("suppress_first", c_vp), ("first_len", c_vp), ("len", c_vp),
+        ("cand_tok", c_vp), ("cand_logp", c_vp),
+        ("rows", C.c_int), ("row_step", C.c_int), ("k", C.c_int),
+    ]
+
+
+class BeamUpdateArgs(C.Structure):
+    """Mirror of wft_beam_update_args (include/wft.h): one beam-search step per audio on the device-side state."""
+
+    _fields_ = [
+        ("cand_tok", c_vp), ("cand_logp", c_vp),
+        ("tokens", c_vp), ("ld_tokens", c_i64),
+        ("anc", c_vp), ("ld_anc", c_i64),
+        ("len", c_vp), ("sum_logprob", c_vp),
+        ("done", c_vp), ("unfinished", c_vp),
+        ("fin_tokens", c_vp), ("fin_len", c_vp), ("fin_score", c_vp), ("fin_n", c_vp),
+        ("src_out", c_vp),
+        ("B", C.c_int), ("W", C.c_int), ("C", C.c_int), ("eot", C.c_int), ("max_len", C.c_int), ("first", C.c_int),
+    ]
+
+
 EPI_NONE, EPI_GELU, EPI_DGELU, EPI_GELU_GRAD, EPI_MUL_AUX, EPI_GELU_GRAD8, EPI_MUL_AUX8 = 0, 1, 2, 3, 4, 5, 6
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); this table is also what
@@ -151,6 +193,10 @@ SIGNATURES = {
     "wft_attn_decode_workspace_bytes": [C.POINTER(AttnDecodeArgs)],
     "wft_decode_embed": [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_i64, c_vp],
     "wft_decode_pick": [C.POINTER(DecodePickArgs), c_vp],
+    "wft_attn_decode_beam_bf16": [C.POINTER(AttnDecodeBeamArgs), c_vp],
+    "wft_attn_decode_beam_workspace_bytes": [C.POINTER(AttnDecodeBeamArgs)],
+    "wft_decode_topk": [C.POINTER(DecodeTopkArgs), c_vp],
+    "wft_beam_update": [C.POINTER(BeamUpdateArgs), c_vp],
     "wft_embed_fwd": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_int, c_i64, c_vp],
     "wft_embed_bwd": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_int, c_i64, c_vp],
     "wft_ce_fwd": [c_vp, c_i64, c_vp, c_i64, c_i64, C.c_float, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -188,7 +234,7 @@ SIGNATURES = {
 _RESTYPES = {"wft_last_error": C.c_char_p, "wft_version": C.c_char_p, "wft_layernorm_bwd_workspace": c_i64,
              "wft_gemm_tn_workspace_bytes": c_i64, "wft_gemm_nt_colsum_workspace_bytes": c_i64, "wft_gemm_nt_splitk_workspace_bytes": c_i64, "wft_gemm_nt_aux8_bytes": c_i64, "wft_colsum_workspace_bytes": c_i64,
              "wft_attn_bwd_colsum_workspace_bytes": c_i64, "wft_attn_decode_workspace_bytes": c_i64,
-             "wft_gemm_nt_stream_workspace_bytes": c_i64}
+             "wft_gemm_nt_stream_workspace_bytes": c_i64, "wft_attn_decode_beam_workspace_bytes": c_i64}
 
 _lib = None
 

@@ -174,9 +174,9 @@ class MultiHeadAttention(nn.Module):
         => causal (the decoder's -inf upper-triangular buffer).  Returns (out, None) like upstream;
         `residual` (engine extension) is added inside the out-projection epilogue."""
         if kv_cache:
-            if not isinstance(kv_cache, _decode.KVCache):
-                raise NotImplementedError("kv_cache must be an engine.decode.KVCache (Whisper.greedy_decode builds one); upstream's "
-                                          "hook-filled dict is not supported")
+            if not isinstance(kv_cache, (_decode.KVCache, _decode.BeamCache)):
+                raise NotImplementedError("kv_cache must be an engine.decode.KVCache or BeamCache (Whisper.greedy_decode / beam_decode "
+                                          "build one); upstream's hook-filled dict is not supported")
             return self._forward_cached(x, xa, kv_cache, residual)
         B, T, d = x.shape
         if self.wft_fp32:  # fp32 mode: separate projections, strided per-head GEMMs, materialised probabilities
@@ -208,7 +208,9 @@ class MultiHeadAttention(nn.Module):
     def _forward_cached(self, x: Tensor, xa: Optional[Tensor], cache: "_decode.KVCache", residual: Optional[Tensor]):
         """Inference with a KVCache (engine/decode.py).  T > 1: the prefill — the teacher-forced kernels over the right-padded prompts,
         the k / v rows stored into the cache.  T = 1: a cached step on the single-token kernel (csrc/decode.hip), which appends
-        the step's k / v itself.  Cross-attention keys / values are projected once per audio batch."""
+        the step's k / v itself.  Cross-attention keys / values are projected once per audio batch.
+        With a BeamCache the prefill carries ONE row per audio (stored into slot row a*W) and a step all audios * W hypotheses: self
+        keys are read through the ancestry table, cross keys once per audio for its W rows (wft_attn_decode_beam_bf16)."""
         if self.wft_fp32:
             raise NotImplementedError("KV-cached decoding runs in the bf16 compute mode only (model.set_compute_dtype('bf16'))")
         if torch.is_grad_enabled():
@@ -216,6 +218,7 @@ class MultiHeadAttention(nn.Module):
         B, T, d = x.shape
         x2 = _as2d(_to_bf16(x))
         scale = 64 ** -0.5
+        beam = isinstance(cache, _decode.BeamCache)
         if not cache.is_cross(self):
             lin = [self.query, self.key, self.value]
             qkv = ops.linear(x2, self._qkv_group, [m.base_weight() for m in lin], [m.bias for m in lin], [m.lora_spec() for m in lin])
@@ -226,7 +229,10 @@ class MultiHeadAttention(nn.Module):
                     raise RuntimeError("this KVCache already holds a prefix: only single-token steps may follow the prefill")
                 qkv3 = qkv.view(B, T, 3 * d)
                 o = ops.SelfAttnFn.apply(qkv3, self.n_head, True, prescaled)
-                store[:, :T].copy_(qkv3[..., d:])
+                (store.view(B, cache.beam, -1, 2 * d)[:, 0] if beam else store)[:, :T].copy_(qkv3[..., d:])
+            elif beam:
+                o = K.attn_decode_beam(qkv[:, :d], store, self.n_head, scale, new_kv=(qkv[:, d:2 * d], qkv[:, 2 * d:]), lens=cache.len,
+                                       anc=cache.anc, q_prescaled=prescaled)
             else:
                 o = K.attn_decode(qkv[:, :d], store, self.n_head, scale, new_kv=(qkv[:, d:2 * d], qkv[:, 2 * d:]), lens=cache.len,
                                   q_prescaled=prescaled)
@@ -240,7 +246,12 @@ class MultiHeadAttention(nn.Module):
                                 [m.lora_spec() for m in lin]).view(B, xa.shape[1], 2 * d)
                 cache.cross_kv[self] = kv
             q = self.query(x2)
-            o = ops.CrossAttnFn.apply(q.view(B, T, d), kv, self.n_head) if T > 1 else K.attn_decode(q, kv, self.n_head, scale)
+            if T > 1:
+                o = ops.CrossAttnFn.apply(q.view(B, T, d), kv, self.n_head)
+            elif beam:
+                o = K.attn_decode_beam(q, kv, self.n_head, scale, group=cache.beam)
+            else:
+                o = K.attn_decode(q, kv, self.n_head, scale)
         out = self.out(o.view(B * T, d), residual=None if residual is None else _as2d(residual))
         return out.view(B, T, d), None
 
@@ -469,6 +480,17 @@ class Whisper(nn.Module):
         return _decode.greedy_decode(self, mel, prompt, prompt_len, eot=eot, max_len=max_len, suppress=suppress,
                                      suppress_first=suppress_first, sync_every=sync_every, step=step,
                                      _capture=_capture, _stream_gemm=_stream_gemm)
+
+    def beam_decode(self, mel: Tensor, prompt: Tensor, prompt_len=None, *, beam_size: int, patience: float = 1.0, length_penalty=None,
+                    eot: int, max_len: Optional[int] = None, suppress=(), suppress_first=(), sync_every: int = 8, step: str = "eager",
+                    return_all: bool = False, _capture: bool = True, _stream_gemm: bool = True):
+        """KV-cached beam search (engine/decode.py beam_decode; upstream: whisper.decoding's BeamSearchDecoder + MaximumLikelihoodRanker
+        with DecodingOptions(without_timestamps=True), restated there — parity with the upstream binary is unpinned).  Arguments and
+        result layout as greedy_decode, for the winning hypothesis of every audio; beam_size 1..8; the beams of an audio share its
+        cross keys / values and no self-attention key is ever copied.  return_all adds every audio's ranked hypotheses."""
+        return _decode.beam_decode(self, mel, prompt, prompt_len, beam_size=beam_size, patience=patience, length_penalty=length_penalty,
+                                   eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first, sync_every=sync_every,
+                                   step=step, return_all=return_all, _capture=_capture, _stream_gemm=_stream_gemm)
 
     def forward(self, mel: Tensor, tokens: Tensor, targets: Optional[Tensor] = None, label_smoothing: float = 0.0) -> Tensor:
         """logits f32 [B, S, V] — or, when `targets` is given (engine extension used by train_step, also

@@ -40,14 +40,18 @@ def _batch_token_stats(model, x, y_in, y_out):
     return None
 
 
-def _greedy_predictions(model, tokenizer, x, y_in, step: str = "eager") -> List[List[int]]:
+def _greedy_predictions(model, tokenizer, x, y_in, step: str = "eager", beam: dict = None) -> List[List[int]]:
     """t_config["wft_eval_decode"] = "greedy": every utterance's predicted ids from KV-cached greedy decoding
     (Whisper.greedy_decode) instead of the teacher-forced argmax.  The decoding prefix of a row is its y_in up to and including
     the start-of-transcript sequence; every special token but eot is suppressed (upstream's notimestamps decoding plus its
     SuppressTokens list of specials; `tokenizer.non_speech_tokens` too when the tokenizer has them), eot and the blank for a
     row's first token (upstream's SuppressBlank); at most n_text_ctx // 2 new tokens (upstream's sample_len).
-    `step` is t_config["wft_eval_decode_step"]: "graph" = the captured step on the weight-streaming GEMMs (engine/decode.py)."""
-    if not hasattr(model, "greedy_decode"):
+    `step` is t_config["wft_eval_decode_step"]: "graph" = the captured step on the weight-streaming GEMMs (engine/decode.py).
+    `beam` = {"beam_size", "patience"} (t_config["wft_eval_decode"] = "beam_search"): the same prefix, suppression and length rules
+    through Whisper.beam_decode, the winning hypothesis of every utterance."""
+    if beam is not None and not hasattr(model, "beam_decode"):
+        raise RuntimeError('wft_eval_decode: "beam_search" needs a model with beam_decode (the engine\'s Whisper)')
+    if beam is None and not hasattr(model, "greedy_decode"):
         raise RuntimeError('wft_eval_decode: "greedy" needs a model with greedy_decode (the engine\'s Whisper)')
     eot = int(tokenizer.eot)
     rows = y_in.cpu().tolist()
@@ -59,8 +63,13 @@ def _greedy_predictions(model, tokenizer, x, y_in, step: str = "eager") -> List[
     suppress = sorted((set(int(t) for t in tokenizer.special_tokens.values()) | set(int(t) for t in getattr(tokenizer, "non_speech_tokens", ()))) - {eot})
     blank = [int(t) for t in tokenizer.encode(" ")] if hasattr(tokenizer, "encode") else []
     n_ctx = getattr(getattr(model, "dims", None), "n_text_ctx", 448)
-    tokens, lengths, _ = model.greedy_decode(x, prompt.to(x.device), torch.tensor(plen), eot=eot, max_len=min(n_ctx, width + n_ctx // 2),
-                                             suppress=suppress, suppress_first=[eot] + blank, **({} if step == "eager" else {"step": step}))
+    kw = dict(eot=eot, max_len=min(n_ctx, width + n_ctx // 2), suppress=suppress, suppress_first=[eot] + blank,
+              **({} if step == "eager" else {"step": step}))
+    if beam is None:
+        tokens, lengths, _ = model.greedy_decode(x, prompt.to(x.device), torch.tensor(plen), **kw)
+    else:
+        tokens, lengths, _ = model.beam_decode(x, prompt.to(x.device), torch.tensor(plen), beam_size=beam["beam_size"],
+                                               patience=beam["patience"], **kw)
     tokens, lengths = tokens.cpu().tolist(), lengths.cpu().tolist()
     return [tokens[i][plen[i]:lengths[i]] for i in range(len(rows))]
 
@@ -88,8 +97,16 @@ def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict
     spec = VOCAB_SPECS["v0"]
     per_utt: List[PerUtteranceMetrics] = []
     decode_mode = t_config.get("wft_eval_decode")
-    if decode_mode not in (None, "greedy"):
-        raise ValueError(f'wft_eval_decode: the only value is "greedy" (absent = the teacher-forced argmax), got {decode_mode!r}')
+    if decode_mode not in (None, "greedy", "beam_search"):
+        raise ValueError(f'wft_eval_decode: "greedy" or "beam_search" (absent = the teacher-forced argmax), got {decode_mode!r}')
+    beam = None
+    if decode_mode == "beam_search":
+        beam = {"beam_size": t_config.get("wft_eval_decode_beam_size", 5), "patience": t_config.get("wft_eval_decode_patience", 1.0)}
+        bs, pat = beam["beam_size"], beam["patience"]
+        if isinstance(bs, bool) or not isinstance(bs, int) or not 1 <= bs <= 8:
+            raise ValueError(f"wft_eval_decode_beam_size: an integer in [1, 8], got {bs!r}")
+        if isinstance(pat, bool) or not isinstance(pat, (int, float)) or not 0 < pat < float("inf") or round(bs * pat) < 1:
+            raise ValueError(f"wft_eval_decode_patience: a positive number with round(beam_size * patience) >= 1, got {pat!r}")
     decode_step = t_config.get("wft_eval_decode_step")
     if decode_step not in (None, "eager", "graph"):
         raise ValueError(f'wft_eval_decode_step: "eager" (the default) or "graph", got {decode_step!r}')
@@ -107,7 +124,7 @@ def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict
         y_host = y_out.cpu().numpy()
         pred_host = fused[0] if fused is not None else pred.cpu().numpy()
         # prediction TEXT from autoregressive decoding when asked for; NLL / entropy / ECE below stay teacher-forced
-        decoded = _greedy_predictions(model, tokenizer, x, y_in, decode_step) if decode_mode == "greedy" else None
+        decoded = _greedy_predictions(model, tokenizer, x, y_in, decode_step, beam) if decode_mode is not None else None
         for i in range(y_host.shape[0]):
             pred_ids = pred_host[i].tolist() if decoded is None else decoded[i]
             pred_tokens = [t for t in pred_ids if t not in specials and t != -100]
@@ -123,7 +140,7 @@ def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict
                 nll, lp, ent, conf, ok = compute_token_metrics(logits[i], y_out[i], pred[i])
             per_utt.append(PerUtteranceMetrics(pred_n, true_n, wer(true_n, pred_n) if true_n else 0.0,
                                                cer(true_n, pred_n) if true_n else 0.0, nll, lp, ent, conf, ok))
-    if decode_mode == "greedy" and decode_step == "graph":
+    if decode_mode is not None and decode_step == "graph":
         # the captured steps pin a KV cache and the cross keys / values per batch size: nothing of that stays behind for training
         from whisper_finetune.engine import decode as _decode
 
