@@ -33,13 +33,15 @@ static inline const char* wft_dev_getenv(const char*) { return nullptr; }
 #define WFT_BUILD_KIND ""
 #endif
 
-#define WFT_CHECK_ARG(cond, msg)                                   \
+// (who: the entry point an error is reported for, where a helper checks the arguments of several)
+#define WFT_CHECK_ARG_AS(who, cond, msg)                           \
   do {                                                             \
     if (!(cond)) {                                                 \
-      wft_set_error("%s: %s (%s)", __func__, msg, #cond);          \
+      wft_set_error("%s: %s (%s)", who, msg, #cond);               \
       return WFT_ERR_ARG;                                          \
     }                                                              \
   } while (0)
+#define WFT_CHECK_ARG(cond, msg) WFT_CHECK_ARG_AS(__func__, cond, msg)
 
 #define WFT_CHECK_LAUNCH()                                         \
   do {                                                             \

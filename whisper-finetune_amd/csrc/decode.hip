@@ -4,10 +4,11 @@
 // here depends on the step: the position of every sequence lives in device memory (`len`), so a step is a fixed launch sequence.
 //
 //  attn_decode_kernel / attn_decode_merge_kernel   softmax(q K^T) V for one query row, HBM-bound K/V read
+//  attn_decode_beam_kernel<W, SELF>                the same attention for beams: self keys through the ancestry table, cross keys
+//                                                  read once per audio for all of its beams.  Kept apart from attn_decode_kernel on
+//                                                  purpose (see the note above it); the host side of the two entry points is one.
 //  decode_embed_kernel                             token + positional embedding at the device-side position
 //  decode_pick_kernel / decode_count_kernel        suppress, arg-max, log-probability, state update, unfinished-row count
-//  attn_decode_beam_kernel                         the same attention for beams: self keys through the ancestry table, cross keys
-//                                                  read once per audio for all of its beams
 //  decode_topk_kernel / beam_update_kernel         the W + 1 best continuations per hypothesis; one beam-search step per audio
 #include "common.h"
 
@@ -191,216 +192,6 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(wft_attn_de
   }
 }
 
-// the `nsplit` partials of one (sequence, head), in split order: one wave, one lane per output dim
-__global__ __launch_bounds__(64) void attn_decode_merge_kernel(const float* ws, int nsplit, unsigned short* o, long ldo, int H) {
-  const int bh = blockIdx.x, b = bh / H, h = bh - b * H, i = threadIdx.x;
-  const float* part = ws + (long)bh * nsplit * DEC_PART;
-  float m = part[0], l = part[1], acc = part[2 + i];
-  for (int s = 1; s < nsplit; ++s) {
-    const float* q = part + (long)s * DEC_PART;
-    const float M = fmaxf(m, q[0]);
-    const float wa = __builtin_amdgcn_exp2f(m - M), wb = __builtin_amdgcn_exp2f(q[0] - M);
-    l = l * wa + q[1] * wb;
-    acc = acc * wa + q[2 + i] * wb;
-    m = M;
-  }
-  o[(long)b * ldo + h * 64 + i] = f2bf(acc / l);
-}
-
-static int dec_nsplit_of(long B, long H, long Tk) {
-  // enough workgroups to cover the chip when B * H alone does not, in splits of about DEC_MIN_SPLIT_KEYS keys or more
-  const long bh = B * H;
-  long want = (DEC_TARGET_WGS + bh - 1) / bh;
-  const long most = (Tk + DEC_MIN_SPLIT_KEYS - 1) / DEC_MIN_SPLIT_KEYS;
-  if (want > most) want = most;
-  if (want > 16) want = 16;
-  return want < 1 ? 1 : (int)want;
-}
-static int dec_nsplit(const wft_attn_decode_args* a) { return dec_nsplit_of(a->B, a->H, a->Tk); }
-
-extern "C" int64_t wft_attn_decode_workspace_bytes(const wft_attn_decode_args* a) {
-  if (!a || a->B < 1 || a->H < 1 || a->Tk < 1) return 0;
-  const int ns = dec_nsplit(a);
-  return ns == 1 ? 0 : (int64_t)a->B * a->H * ns * DEC_PART * (int64_t)sizeof(float);
-}
-
-extern "C" int wft_attn_decode_bf16(const wft_attn_decode_args* a, void* stream) {
-  WFT_CHECK_ARG(a && a->q && a->k_cache && a->v_cache && a->o, "null pointer");
-  WFT_CHECK_ARG(a->B >= 1 && a->H >= 1 && a->Tk >= 1 && (long)a->B * a->H <= 0x7fffffffL, "bad shape");
-  const long d = (long)a->H * 64;
-  WFT_CHECK_ARG(a->ldq >= d && a->ldo >= d && a->ld_cache >= d, "leading dimensions must cover H * 64 = d");
-  WFT_CHECK_ARG(a->ldq % 8 == 0 && a->ldo % 8 == 0 && a->ld_cache % 8 == 0 && a->cache_bs % 8 == 0, "ld / batch strides must be multiples of 8");
-  WFT_CHECK_ARG(a->cache_bs >= (int64_t)(a->Tk - 1) * a->ld_cache + d, "cache capacity: a sequence's Tk rows must fit its batch stride");
-  WFT_CHECK_ARG(((((uintptr_t)a->q) | ((uintptr_t)a->k_cache) | ((uintptr_t)a->v_cache) | ((uintptr_t)a->o)) & 15) == 0, "16-byte alignment");
-  if (a->len) {
-    WFT_CHECK_ARG(a->k_new && a->v_new, "self-attention form (len given) needs the step's k / v rows");
-    WFT_CHECK_ARG(a->ld_new >= d && a->ld_new % 8 == 0 && ((((uintptr_t)a->k_new) | ((uintptr_t)a->v_new)) & 15) == 0, "k_new / v_new layout");
-  }
-  WFT_CHECK_ARG(a->scale > 0.f, "scale");
-  const int ns = dec_nsplit(a);
-  if (ns > 1)
-    WFT_CHECK_ARG(a->workspace && a->workspace_bytes >= wft_attn_decode_workspace_bytes(a) && (((uintptr_t)a->workspace) & 15) == 0,
-                  "workspace of wft_attn_decode_workspace_bytes(args) bytes");
-  const float alpha = a->q_prescaled ? 1.0f : a->scale * 1.4426950408889634f;
-  hipLaunchKernelGGL(attn_decode_kernel, dim3((unsigned)(a->B * a->H), (unsigned)ns), dim3(DEC_WAVES * 64), 0, (hipStream_t)stream, *a, ns, alpha);
-  if (ns > 1)
-    hipLaunchKernelGGL(attn_decode_merge_kernel, dim3((unsigned)(a->B * a->H)), dim3(64), 0, (hipStream_t)stream, (const float*)a->workspace,
-                       ns, a->o, (long)a->ldo, a->H);
-  WFT_CHECK_LAUNCH();
-  return WFT_OK;
-}
-
-// ----------------------------------------------------------------------------- embedding at the device-side position
-// out[b] = emb[tokens[b, len[b] - 1]] + pos[len[b] - 1]: the arithmetic of embed_fwd_kernel (misc.hip), one fp32 add and one rounding.
-__global__ __launch_bounds__(256) void decode_embed_kernel(const long* tokens, long ld_tokens, const int* len, const float* emb,
-                                                            const float* pos, unsigned short* out, int B, int n_ctx, int d, long V) {
-  const int dv = d >> 3;
-  const long total = (long)B * dv;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int b = (int)(i / dv);
-    const int c = (int)(i - (long)b * dv) * 8;
-    int p = len[b] - 1;
-    p = p < 0 ? 0 : (p >= n_ctx ? n_ctx - 1 : p);
-    long tok = tokens[(long)b * ld_tokens + p];
-    tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);
-    const float* e = emb + tok * d + c;
-    const float* pp = pos + (long)p * d + c;
-    const f32x4 a0 = *(const f32x4*)e, a1 = *(const f32x4*)(e + 4);
-    const f32x4 b0 = *(const f32x4*)pp, b1 = *(const f32x4*)(pp + 4);
-    u32x4 o = {pack2bf(a0[0] + b0[0], a0[1] + b0[1]), pack2bf(a0[2] + b0[2], a0[3] + b0[3]),
-               pack2bf(a1[0] + b1[0], a1[1] + b1[1]), pack2bf(a1[2] + b1[2], a1[3] + b1[3])};
-    *(u32x4*)(out + (long)b * d + c) = o;
-  }
-}
-
-extern "C" int wft_decode_embed(const int64_t* tokens, int64_t ld_tokens, const int32_t* len, const float* emb, const float* pos,
-                                wft_bf16* out, int B, int n_ctx, int d, int64_t V, void* stream) {
-  WFT_CHECK_ARG(tokens && len && emb && pos && out, "null pointer");
-  WFT_CHECK_ARG(B >= 1 && n_ctx >= 1 && ld_tokens >= n_ctx && d >= 8 && d % 8 == 0 && V >= 1, "bad shape");
-  WFT_CHECK_ARG(((((uintptr_t)emb) | ((uintptr_t)pos) | ((uintptr_t)out)) & 15) == 0, "16-byte alignment");
-  const long total = (long)B * (d / 8);
-  const unsigned grid = (unsigned)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256);
-  hipLaunchKernelGGL(decode_embed_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const long*)tokens, (long)ld_tokens, len, emb, pos,
-                     out, B, n_ctx, d, (long)V);
-  WFT_CHECK_LAUNCH();
-  return WFT_OK;
-}
-
-// ----------------------------------------------------------------------------- greedy pick
-// One workgroup per sequence.  Pass 1: maximum of the un-suppressed logits with its LOWEST index (each thread scans its columns in
-// ascending order with a strict compare; the tree compares (value, index) pairs).  Pass 2 (the row is L2-resident): sum of
-// exp(x - max) over the same columns, so log p(pick) = -log(sum).  Thread 0 then advances the row's state unless it is finished.
-#define PICK_THREADS 256
-
-__device__ __forceinline__ bool pick_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-
-__global__ __launch_bounds__(PICK_THREADS) void decode_pick_kernel(wft_decode_pick_args a) {
-  __shared__ float s_v[PICK_THREADS / 64];
-  __shared__ int s_i[PICK_THREADS / 64];
-  __shared__ float s_sum[PICK_THREADS / 64];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned short* row = a.logits + (long)b * a.ld;
-  const int V = (int)a.V;
-  const int L = a.len[b];
-  const unsigned char* m1 = a.suppress;
-  const unsigned char* m2 = (a.suppress_first && a.first_len && L == a.first_len[b]) ? a.suppress_first : nullptr;
-
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int c0 = tid * 8; c0 < V; c0 += PICK_THREADS * 8) {
-    float f[8];
-    dec_unpack8(*(const u32x4*)(row + c0), f);  // (ld % 8 == 0 and ld >= V rounded up to 8: in bounds)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int col = c0 + j;
-      const bool live = col < V && !(m1 && m1[col]) && !(m2 && m2[col]);
-      if (live && f[j] > best) {
-        best = f[j];
-        bi = col;
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (pick_better(ov, oi, best, bi)) {
-      best = ov;
-      bi = oi;
-    }
-  }
-  if (lane == 0) {
-    s_v[wave] = best;
-    s_i[wave] = bi;
-  }
-  __syncthreads();
-  best = s_v[0];
-  bi = s_i[0];
-  for (int w = 1; w < PICK_THREADS / 64; ++w)
-    if (pick_better(s_v[w], s_i[w], best, bi)) {
-      best = s_v[w];
-      bi = s_i[w];
-    }
-  const bool any = bi != 0x7fffffff;
-
-  float sum = 0.f;
-  if (any) {
-    for (int c0 = tid * 8; c0 < V; c0 += PICK_THREADS * 8) {
-      float f[8];
-      dec_unpack8(*(const u32x4*)(row + c0), f);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int col = c0 + j;
-        const bool live = col < V && !(m1 && m1[col]) && !(m2 && m2[col]);
-        sum += live ? __expf(f[j] - best) : 0.f;
-      }
-    }
-  }
-  sum = wave_sum(sum);
-  if (lane == 0) s_sum[wave] = sum;
-  __syncthreads();
-  if (tid == 0) {
-    float tot = s_sum[0];
-    for (int w = 1; w < PICK_THREADS / 64; ++w) tot += s_sum[w];
-    const long pick = any ? bi : a.eot;  // (every column suppressed: the row ends)
-    const float lp = any ? -__logf(tot) : 0.f;
-    if (a.pick_out) a.pick_out[b] = pick;
-    if (a.logprob_out) a.logprob_out[b] = lp;
-    if (!a.finished[b]) {  // a finished row is frozen
-      if (L >= 0 && L < a.max_len) {
-        a.tokens[(long)b * a.ld_tokens + L] = pick;
-        a.sum_logprob[b] += lp;
-        a.len[b] = L + 1;
-      }
-      a.finished[b] = (pick == a.eot || L + 1 >= a.max_len) ? 1 : 0;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void decode_count_kernel(const int* finished, int B, int* unfinished) {
-  __shared__ int s[4];
-  int n = 0;
-  for (int i = threadIdx.x; i < B; i += 256) n += finished[i] ? 0 : 1;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) unfinished[0] = s[0] + s[1] + s[2] + s[3];
-}
-
-extern "C" int wft_decode_pick(const wft_decode_pick_args* a, void* stream) {
-  WFT_CHECK_ARG(a && a->logits && a->tokens && a->len && a->finished && a->sum_logprob && a->unfinished, "null pointer");
-  WFT_CHECK_ARG(a->B >= 1 && a->V >= 1 && a->V <= 0x7ffffff0L, "bad shape");
-  WFT_CHECK_ARG(a->ld % 8 == 0 && a->ld >= (a->V + 7) / 8 * 8 && (((uintptr_t)a->logits) & 15) == 0, "logits rows: 16-byte aligned, ld >= V rounded up to 8");
-  WFT_CHECK_ARG(a->max_len >= 1 && a->max_len <= a->ld_tokens, "max_len must fit the token buffer");
-  WFT_CHECK_ARG(a->eot >= 0 && a->eot < a->V, "eot outside the vocabulary");
-  WFT_CHECK_ARG(!a->suppress_first || a->first_len, "suppress_first needs first_len");
-  hipLaunchKernelGGL(decode_pick_kernel, dim3((unsigned)a->B), dim3(PICK_THREADS), 0, (hipStream_t)stream, *a);
-  hipLaunchKernelGGL(decode_count_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int*)a->finished, a->B, a->unfinished);
-  WFT_CHECK_LAUNCH();
-  return WFT_OK;
-}
-
 // ----------------------------------------------------------------------------- single-token attention for beams
 // attn_decode_kernel's work split, key-to-lane dealing, two-blocks-in-flight loads and merge order, for two new shapes.
 //  SELF (W = 1): hypothesis r reads key t at cache slot anc[r, t] — keys are never copied when beams are reordered, only rows of
@@ -409,6 +200,11 @@ extern "C" int wft_decode_pick(const wft_decode_pick_args* a, void* stream) {
 //    one dependent load at the head of a row and none to the K / V stream.
 //  cross (W = group): one workgroup per (audio, head, split) loads each K / V block ONCE and runs the online softmax of the audio's W
 //    query rows against it: W states per lane, the arithmetic of one query exactly that of attn_decode_kernel.
+// Why this template is not also the greedy kernel.  A three-mode form of it (own slot / ancestry / cross) compiles without scratch, but
+// hipcc does not give its W = 1 instantiations attn_decode_kernel's schedule: there the next block's 8 loads are issued before the
+// current block is consumed under s_waitcnt vmcnt(14) .. (8); in the template's instantiations they sink below the loop's exit test
+// and are waited for at once (vmcnt(6) .. (0)), about one block in flight; dropping the index plumbing outside the ancestry mode
+// does not bring it back (checked from the ISA).  Greedy decoding runs every step; it keeps the kernel with the measured schedule.
 template <int W, bool SELF>
 __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_beam_kernel(wft_attn_decode_beam_args a, int nsplit, float qk_alpha) {
   __shared__ float red[DEC_WAVES][W][DEC_PART];
@@ -583,48 +379,85 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_beam_kernel(wft_at
   }
 }
 
-static int beam_nsplit(const wft_attn_decode_beam_args* a) {
-  return dec_nsplit_of(a->len ? a->R : a->R / a->group, a->H, a->Tk);  // (the cross form: per AUDIO — the rule stated in wft.h)
-}
-
-static bool beam_shape_ok(const wft_attn_decode_beam_args* a) {
-  return a && a->R >= 1 && a->H >= 1 && a->Tk >= 1 && a->group >= 1 && a->group <= 8 && a->R % a->group == 0 && (!a->len || a->group == 1);
-}
-
-extern "C" int64_t wft_attn_decode_beam_workspace_bytes(const wft_attn_decode_beam_args* a) {
-  if (!beam_shape_ok(a)) return 0;
-  const int ns = beam_nsplit(a);
-  return ns == 1 ? 0 : (int64_t)a->R * a->H * ns * DEC_PART * (int64_t)sizeof(float);
-}
-
-extern "C" int wft_attn_decode_beam_bf16(const wft_attn_decode_beam_args* a, void* stream) {
-  WFT_CHECK_ARG(a && a->q && a->k_cache && a->v_cache && a->o, "null pointer");
-  WFT_CHECK_ARG(a->R >= 1 && a->H >= 1 && a->Tk >= 1 && (long)a->R * a->H <= 0x7fffffffL, "bad shape");
-  WFT_CHECK_ARG(a->group >= 1 && a->group <= 8 && a->R % a->group == 0, "group must lie in 1..8 and divide the rows");
-  const long d = (long)a->H * 64;
-  WFT_CHECK_ARG(a->ldq >= d && a->ldo >= d && a->ld_cache >= d, "leading dimensions must cover H * 64 = d");
-  WFT_CHECK_ARG(a->ldq % 8 == 0 && a->ldo % 8 == 0 && a->ld_cache % 8 == 0 && a->cache_bs % 8 == 0, "ld / batch strides must be multiples of 8");
-  WFT_CHECK_ARG(a->cache_bs >= (int64_t)(a->Tk - 1) * a->ld_cache + d, "cache capacity: a slot's Tk rows must fit its batch stride");
-  WFT_CHECK_ARG(((((uintptr_t)a->q) | ((uintptr_t)a->k_cache) | ((uintptr_t)a->v_cache) | ((uintptr_t)a->o)) & 15) == 0, "16-byte alignment");
-  if (a->len) {
-    WFT_CHECK_ARG(a->group == 1, "the self form (len given) takes group = 1");
-    WFT_CHECK_ARG(a->anc && a->ld_anc >= a->Tk, "the self form needs the ancestry table, ld_anc >= Tk");
-    WFT_CHECK_ARG(a->k_new && a->v_new, "self-attention form (len given) needs the step's k / v rows");
-    WFT_CHECK_ARG(a->ld_new >= d && a->ld_new % 8 == 0 && ((((uintptr_t)a->k_new) | ((uintptr_t)a->v_new)) & 15) == 0, "k_new / v_new layout");
+// the `nsplit` partials of one (query row, head), in split order: one wave, one lane per output dim
+__global__ __launch_bounds__(64) void attn_decode_merge_kernel(const float* ws, int nsplit, unsigned short* o, long ldo, int H) {
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H, i = threadIdx.x;
+  const float* part = ws + (long)bh * nsplit * DEC_PART;
+  float m = part[0], l = part[1], acc = part[2 + i];
+  for (int s = 1; s < nsplit; ++s) {
+    const float* q = part + (long)s * DEC_PART;
+    const float M = fmaxf(m, q[0]);
+    const float wa = __builtin_amdgcn_exp2f(m - M), wb = __builtin_amdgcn_exp2f(q[0] - M);
+    l = l * wa + q[1] * wb;
+    acc = acc * wa + q[2 + i] * wb;
+    m = M;
   }
-  WFT_CHECK_ARG(a->scale > 0.f, "scale");
-  const int ns = beam_nsplit(a);
-  if (ns > 1)
-    WFT_CHECK_ARG(a->workspace && a->workspace_bytes >= wft_attn_decode_beam_workspace_bytes(a) && (((uintptr_t)a->workspace) & 15) == 0,
-                  "workspace of wft_attn_decode_beam_workspace_bytes(args) bytes");
-  const float alpha = a->q_prescaled ? 1.0f : a->scale * 1.4426950408889634f;
-  const dim3 grid((unsigned)((a->R / a->group) * a->H), (unsigned)ns), block(DEC_WAVES * 64);
-  hipStream_t s = (hipStream_t)stream;
-#define BEAM_LAUNCH(W_, SELF_) hipLaunchKernelGGL((attn_decode_beam_kernel<W_, SELF_>), grid, block, 0, s, *a, ns, alpha)
-  if (a->len) {
+  o[(long)b * ldo + h * 64 + i] = f2bf(acc / l);
+}
+
+// Host side.  Both entry points work on the beam struct: greedy decoding is its group = 1 case without an ancestry table.
+static wft_attn_decode_beam_args dec_from_greedy(const wft_attn_decode_args* a) {
+  wft_attn_decode_beam_args b = {};
+  b.q = a->q, b.ldq = a->ldq, b.k_new = a->k_new, b.v_new = a->v_new, b.ld_new = a->ld_new;
+  b.k_cache = a->k_cache, b.v_cache = a->v_cache, b.ld_cache = a->ld_cache, b.cache_bs = a->cache_bs;
+  b.o = a->o, b.ldo = a->ldo, b.len = a->len;
+  b.R = a->B, b.H = a->H, b.Tk = a->Tk, b.group = 1, b.scale = a->scale, b.q_prescaled = a->q_prescaled;
+  b.workspace = a->workspace, b.workspace_bytes = a->workspace_bytes;
+  return b;
+}
+
+static int dec_nsplit(const wft_attn_decode_beam_args& a) {
+  // enough workgroups to cover the chip when the (sequence, head) or — cross form — (audio, head) pairs alone do not, in splits of
+  // about DEC_MIN_SPLIT_KEYS keys or more (the rule stated in wft.h)
+  const long bh = (long)(a.len ? a.R : a.R / a.group) * a.H;
+  long want = (DEC_TARGET_WGS + bh - 1) / bh;
+  const long most = ((long)a.Tk + DEC_MIN_SPLIT_KEYS - 1) / DEC_MIN_SPLIT_KEYS;
+  if (want > most) want = most;
+  if (want > 16) want = 16;
+  return want < 1 ? 1 : (int)want;
+}
+
+static int64_t dec_workspace_bytes(const wft_attn_decode_beam_args& a) {
+  if (a.R < 1 || a.H < 1 || a.Tk < 1 || a.group < 1 || a.group > 8 || a.R % a.group != 0 || (a.len && a.group != 1)) return 0;
+  const int ns = dec_nsplit(a);
+  return ns == 1 ? 0 : (int64_t)a.R * a.H * ns * DEC_PART * (int64_t)sizeof(float);
+}
+
+// the argument checks of both entry points (`who`: the one that reports); use_anc: the self form reads keys through `anc`
+static int dec_check(const wft_attn_decode_beam_args& a, bool use_anc, const char* who) {
+  WFT_CHECK_ARG_AS(who, a.q && a.k_cache && a.v_cache && a.o, "null pointer");
+  WFT_CHECK_ARG_AS(who, a.R >= 1 && a.H >= 1 && a.Tk >= 1 && (long)a.R * a.H <= 0x7fffffffL, "bad shape");
+  WFT_CHECK_ARG_AS(who, a.group >= 1 && a.group <= 8 && a.R % a.group == 0, "group must lie in 1..8 and divide the rows");
+  const long d = (long)a.H * 64;
+  WFT_CHECK_ARG_AS(who, a.ldq >= d && a.ldo >= d && a.ld_cache >= d, "leading dimensions must cover H * 64 = d");
+  WFT_CHECK_ARG_AS(who, a.ldq % 8 == 0 && a.ldo % 8 == 0 && a.ld_cache % 8 == 0 && a.cache_bs % 8 == 0, "ld / batch strides must be multiples of 8");
+  WFT_CHECK_ARG_AS(who, a.cache_bs >= (int64_t)(a.Tk - 1) * a.ld_cache + d, "cache capacity: the Tk rows of a sequence or slot must fit its batch stride");
+  WFT_CHECK_ARG_AS(who, ((((uintptr_t)a.q) | ((uintptr_t)a.k_cache) | ((uintptr_t)a.v_cache) | ((uintptr_t)a.o)) & 15) == 0, "16-byte alignment");
+  if (a.len) {
+    WFT_CHECK_ARG_AS(who, a.group == 1, "the self form (len given) takes group = 1");
+    WFT_CHECK_ARG_AS(who, !use_anc || (a.anc && a.ld_anc >= a.Tk), "the self form needs the ancestry table, ld_anc >= Tk");
+    WFT_CHECK_ARG_AS(who, a.k_new && a.v_new, "self-attention form (len given) needs the step's k / v rows");
+    WFT_CHECK_ARG_AS(who, a.ld_new >= d && a.ld_new % 8 == 0 && ((((uintptr_t)a.k_new) | ((uintptr_t)a.v_new)) & 15) == 0, "k_new / v_new layout");
+  }
+  WFT_CHECK_ARG_AS(who, a.scale > 0.f, "scale");
+  if (dec_nsplit(a) > 1)
+    WFT_CHECK_ARG_AS(who, a.workspace && a.workspace_bytes >= dec_workspace_bytes(a) && (((uintptr_t)a.workspace) & 15) == 0,
+              "workspace of as many bytes as the entry point's _workspace_bytes function returns");
+  return WFT_OK;
+}
+
+// the main kernel the (checked) arguments select — `greedy`: the caller's own struct when it is wft_attn_decode_bf16 — and the merge
+static int dec_launch(const wft_attn_decode_beam_args& a, const wft_attn_decode_args* greedy, hipStream_t s) {
+  const int ns = dec_nsplit(a);
+  const float alpha = a.q_prescaled ? 1.0f : a.scale * 1.4426950408889634f;
+  const dim3 grid((unsigned)((a.R / a.group) * a.H), (unsigned)ns), block(DEC_WAVES * 64);
+#define BEAM_LAUNCH(W_, SELF_) hipLaunchKernelGGL((attn_decode_beam_kernel<W_, SELF_>), grid, block, 0, s, a, ns, alpha)
+  if (greedy) {
+    hipLaunchKernelGGL(attn_decode_kernel, grid, block, 0, s, *greedy, ns, alpha);
+  } else if (a.len) {
     BEAM_LAUNCH(1, true);
   } else {
-    switch (a->group) {
+    switch (a.group) {
       case 1: BEAM_LAUNCH(1, false); break;
       case 2: BEAM_LAUNCH(2, false); break;
       case 3: BEAM_LAUNCH(3, false); break;
@@ -637,8 +470,187 @@ extern "C" int wft_attn_decode_beam_bf16(const wft_attn_decode_beam_args* a, voi
   }
 #undef BEAM_LAUNCH
   if (ns > 1)
-    hipLaunchKernelGGL(attn_decode_merge_kernel, dim3((unsigned)(a->R * a->H)), dim3(64), 0, s, (const float*)a->workspace, ns, a->o,
-                       (long)a->ldo, a->H);
+    hipLaunchKernelGGL(attn_decode_merge_kernel, dim3((unsigned)(a.R * a.H)), dim3(64), 0, s, (const float*)a.workspace, ns, a.o, (long)a.ldo,
+                       a.H);
+  WFT_CHECK_LAUNCH();
+  return WFT_OK;
+}
+
+extern "C" int64_t wft_attn_decode_workspace_bytes(const wft_attn_decode_args* a) { return a ? dec_workspace_bytes(dec_from_greedy(a)) : 0; }
+extern "C" int64_t wft_attn_decode_beam_workspace_bytes(const wft_attn_decode_beam_args* a) { return a ? dec_workspace_bytes(*a) : 0; }
+
+extern "C" int wft_attn_decode_bf16(const wft_attn_decode_args* a, void* stream) {
+  WFT_CHECK_ARG(a, "null pointer");
+  const wft_attn_decode_beam_args b = dec_from_greedy(a);
+  const int rc = dec_check(b, false, __func__);
+  return rc != WFT_OK ? rc : dec_launch(b, a, (hipStream_t)stream);
+}
+
+extern "C" int wft_attn_decode_beam_bf16(const wft_attn_decode_beam_args* a, void* stream) {
+  WFT_CHECK_ARG(a, "null pointer");
+  const int rc = dec_check(*a, true, __func__);
+  return rc != WFT_OK ? rc : dec_launch(*a, nullptr, (hipStream_t)stream);
+}
+
+// ----------------------------------------------------------------------------- embedding at the device-side position
+// out[b] = emb[tokens[b, len[b] - 1]] + pos[len[b] - 1]: the arithmetic of embed_fwd_kernel (misc.hip), one fp32 add and one rounding.
+__global__ __launch_bounds__(256) void decode_embed_kernel(const long* tokens, long ld_tokens, const int* len, const float* emb,
+                                                            const float* pos, unsigned short* out, int B, int n_ctx, int d, long V) {
+  const int dv = d >> 3;
+  const long total = (long)B * dv;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int b = (int)(i / dv);
+    const int c = (int)(i - (long)b * dv) * 8;
+    int p = len[b] - 1;
+    p = p < 0 ? 0 : (p >= n_ctx ? n_ctx - 1 : p);
+    long tok = tokens[(long)b * ld_tokens + p];
+    tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);
+    const float* e = emb + tok * d + c;
+    const float* pp = pos + (long)p * d + c;
+    const f32x4 a0 = *(const f32x4*)e, a1 = *(const f32x4*)(e + 4);
+    const f32x4 b0 = *(const f32x4*)pp, b1 = *(const f32x4*)(pp + 4);
+    u32x4 o = {pack2bf(a0[0] + b0[0], a0[1] + b0[1]), pack2bf(a0[2] + b0[2], a0[3] + b0[3]),
+               pack2bf(a1[0] + b1[0], a1[1] + b1[1]), pack2bf(a1[2] + b1[2], a1[3] + b1[3])};
+    *(u32x4*)(out + (long)b * d + c) = o;
+  }
+}
+
+extern "C" int wft_decode_embed(const int64_t* tokens, int64_t ld_tokens, const int32_t* len, const float* emb, const float* pos,
+                                wft_bf16* out, int B, int n_ctx, int d, int64_t V, void* stream) {
+  WFT_CHECK_ARG(tokens && len && emb && pos && out, "null pointer");
+  WFT_CHECK_ARG(B >= 1 && n_ctx >= 1 && ld_tokens >= n_ctx && d >= 8 && d % 8 == 0 && V >= 1, "bad shape");
+  WFT_CHECK_ARG(((((uintptr_t)emb) | ((uintptr_t)pos) | ((uintptr_t)out)) & 15) == 0, "16-byte alignment");
+  const long total = (long)B * (d / 8);
+  const unsigned grid = (unsigned)((total + 255) / 256 > 1024 ? 1024 : (total + 255) / 256);
+  hipLaunchKernelGGL(decode_embed_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const long*)tokens, (long)ld_tokens, len, emb, pos,
+                     out, B, n_ctx, d, (long)V);
+  WFT_CHECK_LAUNCH();
+  return WFT_OK;
+}
+
+// ----------------------------------------------------------------------------- greedy pick
+// One workgroup per sequence.  Pass 1: maximum of the un-suppressed logits with its LOWEST index (each thread scans its columns in
+// ascending order with a strict compare; the tree compares (value, index) pairs).  Pass 2 (the row is L2-resident): sum of
+// exp(x - max) over the same columns, so log p(pick) = -log(sum).  Thread 0 then advances the row's state unless it is finished.
+// The row scan, the arg-best reduce and the sum pass are shared with decode_topk_kernel below.
+#define PICK_THREADS 256
+#define PICK_WAVES (PICK_THREADS / 64)
+#define PICK_NONE 0x7fffffff
+
+__device__ __forceinline__ bool pick_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+// f(x, col) for the live columns of a logits row — col < V, neither mask set — that this thread owns: 16-byte reads, ascending columns
+template <typename F>
+__device__ __forceinline__ void pick_scan(const unsigned short* row, int V, const unsigned char* m1, const unsigned char* m2, F f) {
+  for (int c0 = threadIdx.x * 8; c0 < V; c0 += PICK_THREADS * 8) {
+    float x[8];
+    dec_unpack8(*(const u32x4*)(row + c0), x);  // (ld % 8 == 0 and ld >= V rounded up to 8: in bounds)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int col = c0 + j;
+      if (col < V && !(m1 && m1[col]) && !(m2 && m2[col])) f(x[j], col);
+    }
+  }
+}
+
+// the workgroup's best (value, lowest index) in every thread: the wave butterfly, then the waves in wave order.  s_v / s_i: one
+// entry per wave; the caller puts a barrier between two calls.
+__device__ __forceinline__ void pick_wg_best(float& best, int& bi, float* s_v, int* s_i) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (pick_better(ov, oi, best, bi)) {
+      best = ov;
+      bi = oi;
+    }
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_v[threadIdx.x >> 6] = best;
+    s_i[threadIdx.x >> 6] = bi;
+  }
+  __syncthreads();
+  best = s_v[0];
+  bi = s_i[0];
+  for (int w = 1; w < PICK_WAVES; ++w)
+    if (pick_better(s_v[w], s_i[w], best, bi)) {
+      best = s_v[w];
+      bi = s_i[w];
+    }
+}
+
+// sum of exp(x - top) over the live columns of the row (0 when `any` is false), in every thread: per thread in column order, the
+// wave butterfly, then the waves in wave order
+__device__ __forceinline__ float pick_wg_sumexp(const unsigned short* row, int V, const unsigned char* m1, const unsigned char* m2, float top,
+                                                bool any, float* s_sum) {
+  float sum = 0.f;
+  if (any) pick_scan(row, V, m1, m2, [&](float x, int) { sum += __expf(x - top); });
+  sum = wave_sum(sum);
+  if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = sum;
+  __syncthreads();
+  float tot = s_sum[0];
+  for (int w = 1; w < PICK_WAVES; ++w) tot += s_sum[w];
+  return tot;
+}
+
+__global__ __launch_bounds__(PICK_THREADS) void decode_pick_kernel(wft_decode_pick_args a) {
+  __shared__ float s_v[PICK_WAVES];
+  __shared__ int s_i[PICK_WAVES];
+  __shared__ float s_sum[PICK_WAVES];
+  const int b = blockIdx.x;
+  const unsigned short* row = a.logits + (long)b * a.ld;
+  const int V = (int)a.V;
+  const int L = a.len[b];
+  const unsigned char* m1 = a.suppress;
+  const unsigned char* m2 = (a.suppress_first && a.first_len && L == a.first_len[b]) ? a.suppress_first : nullptr;
+
+  float best = -INFINITY;
+  int bi = PICK_NONE;
+  pick_scan(row, V, m1, m2, [&](float x, int col) {
+    if (x > best) {
+      best = x;
+      bi = col;
+    }
+  });
+  pick_wg_best(best, bi, s_v, s_i);
+  const bool any = bi != PICK_NONE;
+  const float tot = pick_wg_sumexp(row, V, m1, m2, best, any, s_sum);
+  if (threadIdx.x == 0) {
+    const long pick = any ? bi : a.eot;  // (every column suppressed: the row ends)
+    const float lp = any ? -__logf(tot) : 0.f;
+    if (a.pick_out) a.pick_out[b] = pick;
+    if (a.logprob_out) a.logprob_out[b] = lp;
+    if (!a.finished[b]) {  // a finished row is frozen
+      if (L >= 0 && L < a.max_len) {
+        a.tokens[(long)b * a.ld_tokens + L] = pick;
+        a.sum_logprob[b] += lp;
+        a.len[b] = L + 1;
+      }
+      a.finished[b] = (pick == a.eot || L + 1 >= a.max_len) ? 1 : 0;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void decode_count_kernel(const int* finished, int B, int* unfinished) {
+  __shared__ int s[4];
+  int n = 0;
+  for (int i = threadIdx.x; i < B; i += 256) n += finished[i] ? 0 : 1;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) unfinished[0] = s[0] + s[1] + s[2] + s[3];
+}
+
+extern "C" int wft_decode_pick(const wft_decode_pick_args* a, void* stream) {
+  WFT_CHECK_ARG(a && a->logits && a->tokens && a->len && a->finished && a->sum_logprob && a->unfinished, "null pointer");
+  WFT_CHECK_ARG(a->B >= 1 && a->V >= 1 && a->V <= 0x7ffffff0L, "bad shape");
+  WFT_CHECK_ARG(a->ld % 8 == 0 && a->ld >= (a->V + 7) / 8 * 8 && (((uintptr_t)a->logits) & 15) == 0, "logits rows: 16-byte aligned, ld >= V rounded up to 8");
+  WFT_CHECK_ARG(a->max_len >= 1 && a->max_len <= a->ld_tokens, "max_len must fit the token buffer");
+  WFT_CHECK_ARG(a->eot >= 0 && a->eot < a->V, "eot outside the vocabulary");
+  WFT_CHECK_ARG(!a->suppress_first || a->first_len, "suppress_first needs first_len");
+  hipLaunchKernelGGL(decode_pick_kernel, dim3((unsigned)a->B), dim3(PICK_THREADS), 0, (hipStream_t)stream, *a);
+  hipLaunchKernelGGL(decode_count_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int*)a->finished, a->B, a->unfinished);
   WFT_CHECK_LAUNCH();
   return WFT_OK;
 }
@@ -650,15 +662,14 @@ extern "C" int wft_attn_decode_beam_bf16(const wft_attn_decode_beam_args* a, voi
 // after which the one thread that owns that column pops it.  Pass 2 (the row is L2-resident): decode_pick_kernel's sum of
 // exp(x - max), in its order; log p = (x - max) - log(sum).  A live column whose logit is -inf can never be a candidate.
 #define TOPK_MAX 9
-#define TOPK_NONE 0x7fffffff
 
 __global__ __launch_bounds__(PICK_THREADS) void decode_topk_kernel(wft_decode_topk_args a) {
-  __shared__ float s_v[PICK_THREADS / 64];
-  __shared__ int s_i[PICK_THREADS / 64];
-  __shared__ float s_sum[PICK_THREADS / 64];
+  __shared__ float s_v[PICK_WAVES];
+  __shared__ int s_i[PICK_WAVES];
+  __shared__ float s_sum[PICK_WAVES];
   __shared__ float s_wv[TOPK_MAX];
   __shared__ int s_wi[TOPK_MAX];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const long r = (long)blockIdx.x * a.row_step;
   const unsigned short* row = a.logits + (long)blockIdx.x * a.ld;
   const int V = (int)a.V;
@@ -670,61 +681,34 @@ __global__ __launch_bounds__(PICK_THREADS) void decode_topk_kernel(wft_decode_to
 #pragma unroll
   for (int p = 0; p < TOPK_MAX; ++p) {
     lv[p] = -INFINITY;
-    li[p] = TOPK_NONE;
+    li[p] = PICK_NONE;
   }
-  for (int c0 = tid * 8; c0 < V; c0 += PICK_THREADS * 8) {
-    float f[8];
-    dec_unpack8(*(const u32x4*)(row + c0), f);  // (ld % 8 == 0 and ld >= V rounded up to 8: in bounds)
+  pick_scan(row, V, m1, m2, [&](float x, int col) {
+    if (x > lv[TOPK_MAX - 1]) {
+      lv[TOPK_MAX - 1] = x;
+      li[TOPK_MAX - 1] = col;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int col = c0 + j;
-      const bool live = col < V && !(m1 && m1[col]) && !(m2 && m2[col]);
-      if (live && f[j] > lv[TOPK_MAX - 1]) {
-        lv[TOPK_MAX - 1] = f[j];
-        li[TOPK_MAX - 1] = col;
-#pragma unroll
-        for (int p = TOPK_MAX - 1; p > 0; --p) {
-          if (lv[p] > lv[p - 1]) {  // strict: an equal value stays behind the earlier (lower) column
-            const float tv = lv[p]; lv[p] = lv[p - 1]; lv[p - 1] = tv;
-            const int ti = li[p]; li[p] = li[p - 1]; li[p - 1] = ti;
-          }
+      for (int p = TOPK_MAX - 1; p > 0; --p) {
+        if (lv[p] > lv[p - 1]) {  // strict: an equal value stays behind the earlier (lower) column
+          const float tv = lv[p]; lv[p] = lv[p - 1]; lv[p - 1] = tv;
+          const int ti = li[p]; li[p] = li[p - 1]; li[p - 1] = ti;
         }
       }
     }
-  }
+  });
 
   for (int rnd = 0; rnd < a.k; ++rnd) {
     float best = lv[0];
     int bi = li[0];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (pick_better(ov, oi, best, bi)) {
-        best = ov;
-        bi = oi;
-      }
-    }
-    if (lane == 0) {
-      s_v[wave] = best;
-      s_i[wave] = bi;
-    }
-    __syncthreads();
-    best = s_v[0];
-    bi = s_i[0];
-    for (int w = 1; w < PICK_THREADS / 64; ++w)
-      if (pick_better(s_v[w], s_i[w], best, bi)) {
-        best = s_v[w];
-        bi = s_i[w];
-      }
-    if (bi != TOPK_NONE && li[0] == bi) {  // the owner of that column pops it
+    pick_wg_best(best, bi, s_v, s_i);
+    if (bi != PICK_NONE && li[0] == bi) {  // the owner of that column pops it
 #pragma unroll
       for (int p = 0; p < TOPK_MAX - 1; ++p) {
         lv[p] = lv[p + 1];
         li[p] = li[p + 1];
       }
       lv[TOPK_MAX - 1] = -INFINITY;
-      li[TOPK_MAX - 1] = TOPK_NONE;
+      li[TOPK_MAX - 1] = PICK_NONE;
     }
     if (tid == 0) {
       s_wv[rnd] = best;
@@ -733,28 +717,9 @@ __global__ __launch_bounds__(PICK_THREADS) void decode_topk_kernel(wft_decode_to
     __syncthreads();
   }
   const float top = s_wv[0];
-  const bool any = s_wi[0] != TOPK_NONE;
-
-  float sum = 0.f;
-  if (any) {
-    for (int c0 = tid * 8; c0 < V; c0 += PICK_THREADS * 8) {
-      float f[8];
-      dec_unpack8(*(const u32x4*)(row + c0), f);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int col = c0 + j;
-        const bool live = col < V && !(m1 && m1[col]) && !(m2 && m2[col]);
-        sum += live ? __expf(f[j] - top) : 0.f;
-      }
-    }
-  }
-  sum = wave_sum(sum);
-  if (lane == 0) s_sum[wave] = sum;
-  __syncthreads();
+  const float tot = pick_wg_sumexp(row, V, m1, m2, top, s_wi[0] != PICK_NONE, s_sum);
   if (tid < a.k) {
-    float tot = s_sum[0];
-    for (int w = 1; w < PICK_THREADS / 64; ++w) tot += s_sum[w];
-    const bool have = s_wi[tid] != TOPK_NONE;
+    const bool have = s_wi[tid] != PICK_NONE;
     a.cand_tok[r * a.k + tid] = have ? s_wi[tid] : -1;
     a.cand_logp[r * a.k + tid] = have ? (s_wv[tid] - top) - __logf(tot) : -INFINITY;
   }

@@ -50,26 +50,22 @@ def stream_gemm(enabled: bool = True):
         _TLS.stream_gemm = old
 
 
-class KVCache:
-    """Keys / values of every decoder layer plus the per-row decoding state, for `batch` sequences.
+class _Cache:
+    """What KVCache and BeamCache share: the key / value buffers of every decoder layer for `rows` cached rows, the state every
+    decode keeps, and the argument checks of start().  The attention modules ask the cache to store the prefill's rows and to run a
+    step (store_prefill / self_step / cross_step), so only the cache knows its layout."""
 
-    Handed to the decoder as `kv_cache=`: a call with T > 1 tokens is the prefill (the teacher-forced kernels over the
-    right-padded prompts; k / v rows stored), a call with T = 1 is a cached step on the single-token kernels."""
-
-    def __init__(self, decoder, batch: int, device=None):
+    def __init__(self, decoder, rows: int, audios: int, device=None):
         pos = decoder.positional_embedding
         device = pos.device if device is None else device
         self.n_ctx, d = pos.shape
-        self.batch = int(batch)
-        self.self_kv = {blk.attn: torch.empty((batch, self.n_ctx, 2 * d), dtype=BF16, device=device) for blk in decoder.blocks}
+        self.batch = int(rows)  # rows of a cached step (the name the decoder reads)
+        self.self_kv = {blk.attn: torch.empty((rows, self.n_ctx, 2 * d), dtype=BF16, device=device) for blk in decoder.blocks}
         self.cross_kv = {blk.cross_attn: None for blk in decoder.blocks}
-        i32 = dict(dtype=torch.int32, device=device)
-        self.tokens = torch.zeros((batch, self.n_ctx), dtype=torch.int64, device=device)
-        self.len = torch.ones(batch, **i32)
-        self.prompt_len = torch.ones(batch, **i32)
-        self.finished = torch.zeros(batch, **i32)
-        self.unfinished = torch.full((1,), batch, **i32)
-        self.sum_logprob = torch.zeros(batch, dtype=torch.float32, device=device)
+        self.tokens = torch.zeros((rows, self.n_ctx), dtype=torch.int64, device=device)
+        self.len = torch.ones(rows, dtype=torch.int32, device=device)
+        self.sum_logprob = torch.zeros(rows, dtype=torch.float32, device=device)
+        self.unfinished = torch.full((1,), audios, dtype=torch.int32, device=device)
         self.prompt_T = 0       # width of the right-padded prompt block (host constant of this decode)
         self.prefilled = False
         self.eot, self.max_len = 0, self.n_ctx
@@ -78,37 +74,64 @@ class KVCache:
     def is_cross(self, attn) -> bool:
         return attn in self.cross_kv
 
-    def start(self, prompt: torch.Tensor, prompt_len: Optional[torch.Tensor], *, eot: int, max_len: Optional[int] = None,
-              suppress: Sequence[int] = (), suppress_first: Sequence[int] = (), n_vocab: int) -> None:
-        """Load the prompts (i64 [B, T], right-padded; prompt_len [B] or None = all T long) and reset the state."""
+    def _start(self, audios: int, prompt: torch.Tensor, prompt_len, eot: int, max_len: Optional[int], suppress, suppress_first, n_vocab: int):
+        """The checks and resets of both start()s -> (prompt width T, the prompt lengths as i32 [audios] on the host)."""
         B, T = prompt.shape
         max_len = self.n_ctx if max_len is None else int(max_len)
-        if B != self.batch or not 1 <= T <= self.n_ctx:
-            raise ValueError(f"prompt {tuple(prompt.shape)} does not fit a cache of {self.batch} x {self.n_ctx}")
+        if B != audios or not 1 <= T <= self.n_ctx:
+            raise ValueError(f"prompt {tuple(prompt.shape)} does not fit a cache of {audios} x {self.n_ctx}")
         if not T <= max_len <= self.n_ctx:
             raise ValueError(f"max_len={max_len} must lie in [prompt width {T}, n_text_ctx {self.n_ctx}]")
         if not 0 <= int(eot) < n_vocab:
             raise ValueError(f"eot={eot} is outside the vocabulary")
-        dev = self.tokens.device
-        self.tokens.fill_(int(eot))
-        self.tokens[:, :T].copy_(prompt.to(dev))
         if prompt_len is None:
-            self.len.fill_(T)
+            pl = torch.full((B,), T, dtype=torch.int32)
         else:
-            pl = torch.as_tensor(prompt_len).to(device=dev, dtype=torch.int32).reshape(B)
+            pl = torch.as_tensor(prompt_len).to(device="cpu", dtype=torch.int32).reshape(B)
             if int(pl.min()) < 1 or int(pl.max()) > T:
                 raise ValueError("prompt_len must lie in [1, prompt width]")
-            self.len.copy_(pl)
-        self.prompt_len.copy_(self.len)
-        self.finished.copy_((self.len >= max_len).to(torch.int32))
-        self.unfinished.copy_((self.finished == 0).sum().to(torch.int32).reshape(1))
-        self.sum_logprob.zero_()
-        self.prompt_T, self.prefilled = T, False
-        self.eot, self.max_len = int(eot), max_len
+        dev = self.tokens.device
         self.suppress = _mask(suppress, n_vocab, dev)
         self.suppress_first = _mask(suppress_first, n_vocab, dev)
+        self.prompt_T, self.prefilled = T, False
+        self.eot, self.max_len = int(eot), max_len
+        self.tokens.fill_(int(eot))
+        self.sum_logprob.zero_()
         for key in self.cross_kv:
             self.cross_kv[key] = None
+        return T, pl
+
+
+class KVCache(_Cache):
+    """Keys / values of every decoder layer plus the per-row decoding state, for `batch` sequences.
+
+    Handed to the decoder as `kv_cache=`: a call with T > 1 tokens is the prefill (the teacher-forced kernels over the
+    right-padded prompts; k / v rows stored), a call with T = 1 is a cached step on the single-token kernels."""
+
+    def __init__(self, decoder, batch: int, device=None):
+        super().__init__(decoder, batch, batch, device)
+        self.prompt_len = torch.ones_like(self.len)
+        self.finished = torch.zeros_like(self.len)
+
+    def start(self, prompt: torch.Tensor, prompt_len: Optional[torch.Tensor], *, eot: int, max_len: Optional[int] = None,
+              suppress: Sequence[int] = (), suppress_first: Sequence[int] = (), n_vocab: int) -> None:
+        """Load the prompts (i64 [B, T], right-padded; prompt_len [B] or None = all T long) and reset the state."""
+        T, pl = self._start(self.batch, prompt, prompt_len, eot, max_len, suppress, suppress_first, n_vocab)
+        self.tokens[:, :T].copy_(prompt.to(self.tokens.device))
+        self.len.copy_(pl)
+        self.prompt_len.copy_(self.len)
+        self.finished.copy_((self.len >= self.max_len).to(torch.int32))
+        self.unfinished.copy_((self.finished == 0).sum().to(torch.int32).reshape(1))
+
+    def store_prefill(self, attn, kv: torch.Tensor) -> None:
+        """kv bf16 [B, T, 2d]: the {k | v} rows of the prompt block."""
+        self.self_kv[attn][:, :kv.shape[1]].copy_(kv)
+
+    def self_step(self, attn, q, k, v, n_head: int, scale: float, q_prescaled: bool) -> torch.Tensor:
+        return K.attn_decode(q, self.self_kv[attn], n_head, scale, new_kv=(k, v), lens=self.len, q_prescaled=q_prescaled)
+
+    def cross_step(self, attn, q, n_head: int, scale: float) -> torch.Tensor:
+        return K.attn_decode(q, self.cross_kv[attn], n_head, scale)
 
 
 def _mask(ids: Sequence[int], n_vocab: int, device) -> Optional[torch.Tensor]:
@@ -133,13 +156,11 @@ def prefill(decoder, cache: KVCache, xa: torch.Tensor) -> torch.Tensor:
     return decoder.padded_logits(last.view(cache.batch, 1, -1))
 
 
-def step(decoder, cache: KVCache) -> torch.Tensor:
-    """One cached step: the token at len[b] - 1 of every row through the decoder -> padded bf16 logits [B, Vpad]."""
-    h = decoder.hidden(None, None, kv_cache=cache)  # [B, 1, d]
+def step(decoder, cache) -> torch.Tensor:
+    """One cached step: the token at len[r] - 1 of every row (KVCache) or hypothesis (BeamCache) through the decoder -> padded bf16
+    logits [rows, Vpad]."""
+    h = decoder.hidden(None, None, kv_cache=cache)  # [rows, 1, d]
     return decoder.padded_logits(h)
-
-
-_cached_step = step  # (greedy_decode has a keyword of that name)
 
 
 def pick(decoder, cache: KVCache, logits: torch.Tensor, want_pick: bool = False):
@@ -150,12 +171,18 @@ def pick(decoder, cache: KVCache, logits: torch.Tensor, want_pick: bool = False)
                          first_len=cache.prompt_len, want_pick=want_pick)
 
 
+def _greedy_body(decoder, cache: KVCache) -> torch.Tensor:
+    logits = step(decoder, cache)
+    pick(decoder, cache, logits)
+    return logits
+
+
 # ----------------------------------------------------------------------------- the captured step
-MAX_SESSIONS = 2  # graph sessions kept per model (one per (batch, device)); the oldest is evicted
-# model -> OrderedDict[(batch, device) -> _GraphSession].  Kept OFF the module, like engine/graph.py's registry: CUDAGraph objects
-# neither pickle nor deep-copy, and a dropped model drops its sessions.
+MAX_SESSIONS = 2  # graph sessions kept per model and kind of decoding; the oldest is evicted
+# model -> OrderedDict[key -> _GraphSession], one table per kind, so greedy and beam sessions are counted and evicted apart:
+# key = (batch, device), or (audios, beam, candidates, device) for beam search.  Kept OFF the module, like engine/graph.py's
+# registry: CUDAGraph objects neither pickle nor deep-copy, and a dropped model drops its sessions.
 _SESSIONS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
-# the same for beam search, in a table of its own: model -> OrderedDict[(audios, beam, candidates, device) -> _BeamGraphSession]
 _BEAM_SESSIONS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 
 
@@ -169,20 +196,18 @@ def _groups(decoder):
 
 
 class _GraphSession:
-    """One HIP graph = step(dec, cache) + pick(dec, cache, logits) on the static buffers of ONE KVCache, replayed once per token.
+    """One HIP graph = body(decoder, cache) — a cached step and its state update — on the static buffers of ONE cache, replayed once
+    per token (the first update of a decode, fed by the prefill, stays outside).
 
-    Everything a step reads that changes between tokens or between decodes lives in buffers this session owns (the KVCache, the
+    Everything a step reads that changes between tokens or between decodes lives in buffers this session owns (the cache, the
     cross keys / values, the two suppression masks); everything else whose ADDRESS the graph holds — decoder parameters, the bf16
     weight shadows and stacked biases of every Linear group, the scratch slots — is referenced by `keep` and named in the
-    fingerprint that is compared after every prefill: any difference recaptures, a mismatch never replays."""
+    fingerprint that is compared after every prefill: any difference recaptures, a mismatch never replays.  `extra`: what the
+    caller adds to the fingerprint; `who` names the caller in error messages."""
 
-    who = "greedy_decode"
-
-    def __init__(self, decoder, batch: int, device):
-        self.cache = KVCache(decoder, batch, device=device)
-        self._init_static(decoder, device)
-
-    def _init_static(self, decoder, device):
+    def __init__(self, decoder, cache, body, extra: tuple, who: str):
+        self.cache, self._body, self._extra, self.who = cache, body, tuple(extra), who
+        device = cache.tokens.device
         self.cross = {}      # attn module -> static bf16 [B, n_audio_ctx, 2d]
         V = decoder.token_embedding.weight.shape[0]
         self.suppress = torch.zeros(V, dtype=torch.uint8, device=device)
@@ -211,12 +236,6 @@ class _GraphSession:
                 buf.copy_(m)
             setattr(c, name, buf)
 
-    def _body(self, decoder):
-        """What one replay runs, on the static buffers of self.cache."""
-        logits = step(decoder, self.cache)
-        pick(decoder, self.cache, logits)
-        return logits
-
     def _fingerprint(self, decoder, stream: bool, slots=None):
         c = self.cache
         dev = c.tokens.device
@@ -236,7 +255,7 @@ class _GraphSession:
         for name in slots:
             ws = K._TN_WS.get((dev.type, dev.index, name))
             fp.append((name, None if ws is None else ws.data_ptr())); keep.append(ws)
-        return tuple(fp), keep, tuple(slots)
+        return tuple(fp) + self._extra, keep, tuple(slots)
 
     def valid(self, decoder, stream: bool) -> bool:
         return self.graph is not None and self.fingerprint == self._fingerprint(decoder, stream, self.slots)[0]
@@ -256,7 +275,7 @@ class _GraphSession:
             with torch.cuda.stream(side):
                 with torch.cuda.graph(g, stream=side):
                     with stream_gemm(stream):
-                        logits = self._body(decoder)
+                        logits = self._body(decoder, c)
         except Exception as exc:
             # (tensors first allocated inside a failed capture must not be used: nothing of this session survives)
             self.graph = None
@@ -274,16 +293,16 @@ class _GraphSession:
         self.replays += 1
 
 
-def _session(model, batch: int, device) -> _GraphSession:
-    reg = _SESSIONS.get(model)
+def _session(table, model, key: tuple, make) -> _GraphSession:
+    """The session of `model` under `key` in `table`, most recently used last; make() builds a missing one once the oldest is gone."""
+    reg = table.get(model)
     if reg is None:
-        reg = _SESSIONS[model] = OrderedDict()
-    key = (int(batch), str(device))
+        reg = table[model] = OrderedDict()
     sess = reg.get(key)
     if sess is None:
         while len(reg) >= MAX_SESSIONS:
             reg.popitem(last=False)
-        sess = reg[key] = _GraphSession(model.decoder, batch, device)
+        sess = reg[key] = make()
     else:
         reg.move_to_end(key)
     return sess
@@ -292,6 +311,11 @@ def _session(model, batch: int, device) -> _GraphSession:
 def sessions(model) -> dict:
     """{(batch, device): session} of `model` (tests and tools read the capture / replay counters)."""
     return dict(_SESSIONS.get(model) or {})
+
+
+def beam_sessions(model) -> dict:
+    """{(audios, beam_size, candidates, device): session} of `model`: the captured beam steps (kept apart from `sessions(model)`)."""
+    return dict(_BEAM_SESSIONS.get(model) or {})
 
 
 def release_graphs(model) -> None:
@@ -304,6 +328,57 @@ def release_graphs(model) -> None:
 
 
 STEP_MODES = ("eager", "graph")
+
+
+def _check_mode(model, who: str, step: str, sync_every: int) -> None:
+    if step not in STEP_MODES:
+        raise ValueError(f"step must be one of {STEP_MODES}, got {step!r}")
+    if getattr(model, "compute_dtype", "bf16") != "bf16":
+        raise NotImplementedError(f"{who} runs in the bf16 compute mode only: the single-token kernels (csrc/decode.hip) are bf16; "
+                                  "call model.set_compute_dtype('bf16') to decode")
+    if sync_every < 1:
+        raise ValueError("sync_every must be >= 1")
+
+
+def _decode(model, mel: torch.Tensor, start: dict, *, who: str, table, key: tuple, make_cache, prefill, first, body, readout, extra=(),
+            graph: bool, stream: bool, sync_every: int):
+    """The loop of greedy_decode and beam_decode -> readout(cache) after the last step (read while the model is still in eval mode).  make_cache(decoder) builds the cache (kept in a
+    graph session of `table` under key + (device,) when `graph`), start: the arguments of its start(); prefill(decoder, cache, xa)
+    -> logits, first(decoder, cache, logits): the update they feed, body(decoder, cache): one cached step with its update.
+    Host reads: the fingerprint check once after the prefill, the `unfinished` counter every `sync_every` steps."""
+    was_training = model.training
+    model.eval()
+    try:
+        dec = model.decoder
+        sess = None
+        if graph:
+            sess = _session(table, model, key + (str(mel.device),), lambda: _GraphSession(dec, make_cache(dec), body, extra, who))
+        cache = sess.cache if graph else make_cache(dec)
+        cache.start(**start, n_vocab=model.dims.n_vocab)
+        # updates until the shortest prompt reaches max_len (start() has just set len to the prompt lengths; nothing ran since)
+        most = cache.max_len - int(cache.len.min())
+        if most > 0:
+            logits = prefill(dec, cache, model.encoder(mel))
+            if graph:
+                sess.adopt_prefill()
+            first(dec, cache, logits)
+            ready = graph and sess.valid(dec, stream)  # (the fingerprint check a replay cannot make: once per decode, after the prefill)
+            warmed = False
+            for i in range(1, most):
+                if i % sync_every == 0 and int(cache.unfinished.item()) == 0:
+                    break
+                if graph and not ready and warmed:
+                    sess.capture(dec, stream)
+                    ready = True
+                if ready:
+                    sess.replay()
+                    continue
+                with stream_gemm(stream):
+                    body(dec, cache)
+                warmed = True
+        return readout(cache)
+    finally:
+        model.train(was_training)
 
 
 @torch.no_grad()
@@ -320,51 +395,20 @@ def greedy_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=Non
     has no valid graph runs eagerly, the second is captured; at most MAX_SESSIONS sessions per model, `release_graphs(model)` frees
     them.  The prefill and the encoder keep their kernels in both modes.  `_capture=False` / `_stream_gemm=False` switch off one
     half each (tests and the A/B bench only)."""
-    if step not in STEP_MODES:
-        raise ValueError(f"step must be one of {STEP_MODES}, got {step!r}")
-    if getattr(model, "compute_dtype", "bf16") != "bf16":
-        raise NotImplementedError("greedy_decode runs in the bf16 compute mode only: the single-token kernels (csrc/decode.hip) are bf16; "
-                                  "call model.set_compute_dtype('bf16') to decode")
-    if sync_every < 1:
-        raise ValueError("sync_every must be >= 1")
-    graph = step == "graph" and _capture
-    stream = step == "graph" and _stream_gemm
-    was_training = model.training
-    model.eval()
-    try:
-        dec = model.decoder
-        B = prompt.shape[0]
-        sess = _session(model, B, mel.device) if graph else None
-        cache = sess.cache if graph else KVCache(dec, B, device=mel.device)
-        cache.start(prompt, prompt_len, eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first, n_vocab=model.dims.n_vocab)
-        most = cache.max_len - int(cache.prompt_len.min())  # picks until the shortest prompt reaches max_len
-        if most > 0:
-            logits = prefill(dec, cache, model.encoder(mel))
-            if graph:
-                sess.adopt_prefill()
-            pick(dec, cache, logits)
-            ready = graph and sess.valid(dec, stream)  # (the fingerprint check a replay cannot make: once per decode, after the prefill)
-            warmed = False
-            for i in range(1, most):
-                if i % sync_every == 0 and int(cache.unfinished.item()) == 0:
-                    break
-                if graph and not ready and warmed:
-                    sess.capture(dec, stream)
-                    ready = True
-                if ready:
-                    sess.replay()
-                    continue
-                with stream_gemm(stream):
-                    logits = _cached_step(dec, cache)
-                    pick(dec, cache, logits)
-                warmed = True
+    _check_mode(model, "greedy_decode", step, sync_every)
+    B = prompt.shape[0]
+
+    def readout(cache):
         lengths = cache.len.long()
         L = int(lengths.max())
         tokens = cache.tokens[:, :L].clone()
         tokens.masked_fill_(torch.arange(L, device=tokens.device)[None, :] >= lengths[:, None], cache.eot)
         return tokens, lengths, cache.sum_logprob.clone()
-    finally:
-        model.train(was_training)
+
+    return _decode(model, mel, dict(prompt=prompt, prompt_len=prompt_len, eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first),
+                   who="greedy_decode", table=_SESSIONS, key=(int(B),), make_cache=lambda dec: KVCache(dec, B, device=mel.device),
+                   prefill=prefill, first=pick, body=_greedy_body, readout=readout, graph=step == "graph" and _capture,
+                   stream=step == "graph" and _stream_gemm, sync_every=sync_every)
 
 
 # ============================================================================= beam search
@@ -401,7 +445,7 @@ def _check_live_columns(beam_size: int, n_vocab: int, suppress: Sequence[int], s
         raise ValueError(f"beam_size={beam_size} needs at least {beam_size + 1} un-suppressed columns, {n_vocab - len(dead)} of {n_vocab} are left")
 
 
-class BeamCache:
+class BeamCache(_Cache):
     """Keys / values plus the beam-search state of `audios` audios x `beam_size` hypotheses (R = audios * beam_size slot rows).
 
     Handed to the decoder as `kv_cache=` like a KVCache: a call with T > 1 tokens is the prefill — ONE row per audio through the
@@ -414,26 +458,19 @@ class BeamCache:
       fin_tokens i64 [audios, C, n_ctx], fin_len i32 / fin_score f32 [audios, C], fin_n i32 [audios]   the finished lists"""
 
     def __init__(self, decoder, audios: int, beam_size: int, candidates: Optional[int] = None, device=None):
-        pos = decoder.positional_embedding
-        device = pos.device if device is None else device
-        self.n_ctx, d = pos.shape
         W = int(beam_size)
         C = beam_candidates(W) if candidates is None else int(candidates)
         if not 1 <= W <= MAX_BEAM or C < 1:
             raise ValueError(f"beam_size must lie in [1, {MAX_BEAM}] and candidates be >= 1")
         self.audios, self.beam, self.cands = int(audios), W, C
-        R = self.batch = self.audios * W  # rows of a cached step (the name the decoder reads)
-        self.self_kv = {blk.attn: torch.empty((R, self.n_ctx, 2 * d), dtype=BF16, device=device) for blk in decoder.blocks}
-        self.cross_kv = {blk.cross_attn: None for blk in decoder.blocks}
+        R = self.audios * W
+        super().__init__(decoder, R, self.audios, device)
+        device = self.tokens.device
         i32 = dict(dtype=torch.int32, device=device)
         f32 = dict(dtype=torch.float32, device=device)
         self.anc = torch.zeros((R, self.n_ctx), **i32)
-        self.tokens = torch.zeros((R, self.n_ctx), dtype=torch.int64, device=device)
-        self.len = torch.ones(R, **i32)
         self.first_len = torch.ones(R, **i32)
-        self.sum_logprob = torch.zeros(R, **f32)
         self.done = torch.zeros(self.audios, **i32)
-        self.unfinished = torch.full((1,), self.audios, **i32)
         self.cand_tok = torch.full((R, W + 1), -1, **i32)
         self.cand_logp = torch.zeros((R, W + 1), **f32)
         self.src = torch.zeros(R, **i32)
@@ -441,51 +478,34 @@ class BeamCache:
         self.fin_len = torch.zeros((self.audios, C), **i32)
         self.fin_score = torch.zeros((self.audios, C), **f32)
         self.fin_n = torch.zeros(self.audios, **i32)
-        self.prompt_T = 0
-        self.prefilled = False
-        self.eot, self.max_len = 0, self.n_ctx
-        self.suppress = self.suppress_first = None
-
-    def is_cross(self, attn) -> bool:
-        return attn in self.cross_kv
 
     def start(self, prompt: torch.Tensor, prompt_len: Optional[torch.Tensor], *, eot: int, max_len: Optional[int] = None,
               suppress: Sequence[int] = (), suppress_first: Sequence[int] = (), n_vocab: int) -> None:
         """Load the prompts (i64 [audios, T], right-padded; prompt_len [audios] or None) into all W rows of every audio and reset
         the state.  The checks of KVCache.start plus the live-column count."""
-        B, T = prompt.shape
-        W = self.beam
-        max_len = self.n_ctx if max_len is None else int(max_len)
-        if B != self.audios or not 1 <= T <= self.n_ctx:
-            raise ValueError(f"prompt {tuple(prompt.shape)} does not fit a cache of {self.audios} x {self.n_ctx}")
-        if not T <= max_len <= self.n_ctx:
-            raise ValueError(f"max_len={max_len} must lie in [prompt width {T}, n_text_ctx {self.n_ctx}]")
-        if not 0 <= int(eot) < n_vocab:
-            raise ValueError(f"eot={eot} is outside the vocabulary")
+        B, W = self.audios, self.beam
         _check_live_columns(W, n_vocab, suppress, suppress_first)
+        T, pl = self._start(B, prompt, prompt_len, eot, max_len, suppress, suppress_first, n_vocab)
         dev = self.tokens.device
-        if prompt_len is None:
-            pl = torch.full((B,), T, dtype=torch.int32)
-        else:
-            pl = torch.as_tensor(prompt_len).to(device="cpu", dtype=torch.int32).reshape(B)
-            if int(pl.min()) < 1 or int(pl.max()) > T:
-                raise ValueError("prompt_len must lie in [1, prompt width]")
-        self.tokens.fill_(int(eot))
         self.tokens.view(B, W, self.n_ctx)[:, :, :T].copy_(prompt.to(dev)[:, None, :])
         self.len.copy_(pl.to(dev).repeat_interleave(W))
         self.first_len.copy_(self.len)
         self.anc.copy_((torch.arange(B, dtype=torch.int32, device=dev) * W).repeat_interleave(W)[:, None].expand(-1, self.n_ctx))
-        self.done.copy_((pl >= max_len).to(torch.int32))
+        self.done.copy_((pl >= self.max_len).to(torch.int32))
         self.unfinished.copy_((self.done == 0).sum().to(torch.int32).reshape(1))
-        self.sum_logprob.zero_()
         self.cand_tok.fill_(-1); self.cand_logp.zero_(); self.src.zero_()
         self.fin_tokens.fill_(int(eot)); self.fin_len.zero_(); self.fin_score.zero_(); self.fin_n.zero_()
-        self.prompt_T, self.prefilled = T, False
-        self.eot, self.max_len = int(eot), max_len
-        self.suppress = _mask(suppress, n_vocab, dev)
-        self.suppress_first = _mask(suppress_first, n_vocab, dev)
-        for key in self.cross_kv:
-            self.cross_kv[key] = None
+
+    def store_prefill(self, attn, kv: torch.Tensor) -> None:
+        """kv bf16 [audios, T, 2d]: the {k | v} rows of the prompt block, into slot row a*W of every audio."""
+        B, T = kv.shape[:2]
+        self.self_kv[attn].view(B, self.beam, -1, kv.shape[2])[:, 0, :T].copy_(kv)
+
+    def self_step(self, attn, q, k, v, n_head: int, scale: float, q_prescaled: bool) -> torch.Tensor:
+        return K.attn_decode_beam(q, self.self_kv[attn], n_head, scale, new_kv=(k, v), lens=self.len, anc=self.anc, q_prescaled=q_prescaled)
+
+    def cross_step(self, attn, q, n_head: int, scale: float) -> torch.Tensor:
+        return K.attn_decode_beam(q, self.cross_kv[attn], n_head, scale, group=self.beam)
 
 
 def beam_prefill(decoder, cache: BeamCache, xa: torch.Tensor) -> torch.Tensor:
@@ -500,9 +520,7 @@ def beam_prefill(decoder, cache: BeamCache, xa: torch.Tensor) -> torch.Tensor:
     return decoder.padded_logits(last.view(B, 1, -1))
 
 
-def beam_step(decoder, cache: BeamCache) -> torch.Tensor:
-    """One cached step: the token at len[r] - 1 of every hypothesis through the decoder -> padded bf16 logits [R, Vpad]."""
-    return decoder.padded_logits(decoder.hidden(None, None, kv_cache=cache))
+beam_step = step
 
 
 def beam_topk(decoder, cache: BeamCache, logits: torch.Tensor, first: bool = False) -> None:
@@ -518,6 +536,18 @@ def beam_update(cache: BeamCache, first: bool = False) -> None:
     K.beam_update(cache.cand_tok, cache.cand_logp, cache.tokens, cache.anc, cache.len, cache.sum_logprob, cache.done, cache.unfinished,
                   cache.fin_tokens, cache.fin_len, cache.fin_score, cache.fin_n, eot=cache.eot, max_len=cache.max_len, first=first,
                   src_out=cache.src)
+
+
+def _beam_first(decoder, cache: BeamCache, logits: torch.Tensor) -> None:
+    beam_topk(decoder, cache, logits, first=True)
+    beam_update(cache, first=True)
+
+
+def _beam_body(decoder, cache: BeamCache) -> torch.Tensor:
+    logits = beam_step(decoder, cache)
+    beam_topk(decoder, cache, logits)
+    beam_update(cache)
+    return logits
 
 
 def beam_rank(entries, length_penalty: Optional[float] = None) -> int:
@@ -559,47 +589,6 @@ def beam_finalize(cache: BeamCache, length_penalty: Optional[float] = None):
     return out
 
 
-class _BeamGraphSession(_GraphSession):
-    """One HIP graph = beam_step + beam_topk + beam_update on the static buffers of ONE BeamCache (the first update of a decode, fed
-    by the prefill, stays outside).  Fingerprint, warm-up and failure handling are _GraphSession's."""
-
-    who = "beam_decode"
-
-    def __init__(self, decoder, audios: int, beam_size: int, candidates: int, device):
-        self.cache = BeamCache(decoder, audios, beam_size, candidates, device=device)
-        self._init_static(decoder, device)
-
-    def _body(self, decoder):
-        logits = beam_step(decoder, self.cache)
-        beam_topk(decoder, self.cache, logits)
-        beam_update(self.cache)
-        return logits
-
-    def _fingerprint(self, decoder, stream: bool, slots=None):
-        fp, keep, slots = super()._fingerprint(decoder, stream, slots)
-        return fp + (("beam", self.cache.beam, self.cache.cands),), keep, slots
-
-
-def _beam_session(model, audios: int, beam_size: int, candidates: int, device) -> _BeamGraphSession:
-    reg = _BEAM_SESSIONS.get(model)
-    if reg is None:
-        reg = _BEAM_SESSIONS[model] = OrderedDict()
-    key = (int(audios), int(beam_size), int(candidates), str(device))
-    sess = reg.get(key)
-    if sess is None:
-        while len(reg) >= MAX_SESSIONS:
-            reg.popitem(last=False)
-        sess = reg[key] = _BeamGraphSession(model.decoder, audios, beam_size, candidates, device)
-    else:
-        reg.move_to_end(key)
-    return sess
-
-
-def beam_sessions(model) -> dict:
-    """{(audios, beam_size, candidates, device): session} of `model`: the captured beam steps (kept apart from `sessions(model)`)."""
-    return dict(_BEAM_SESSIONS.get(model) or {})
-
-
 @torch.no_grad()
 def beam_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None, *, beam_size: int, patience: float = 1.0,
                 length_penalty: Optional[float] = None, eot: int, max_len: Optional[int] = None, suppress: Sequence[int] = (),
@@ -613,50 +602,14 @@ def beam_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None,
     sum_logprob / n over the generated tokens (n without the final eot), or sum_logprob / ((5 + n) / 6) ** length_penalty.
     Argument errors are raised before any device work.  `step`, `sync_every`, `_capture`, `_stream_gemm`: as greedy_decode; the
     captured beam steps live in their own sessions (`beam_sessions`), freed by `release_graphs` too."""
-    if step not in STEP_MODES:
-        raise ValueError(f"step must be one of {STEP_MODES}, got {step!r}")
     C = beam_candidates(beam_size, patience)
     if length_penalty is not None and (isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float))):
         raise ValueError(f"length_penalty must be None or a number, got {length_penalty!r}")
     _check_live_columns(beam_size, model.dims.n_vocab, suppress, suppress_first)
-    if getattr(model, "compute_dtype", "bf16") != "bf16":
-        raise NotImplementedError("beam_decode runs in the bf16 compute mode only: the single-token kernels (csrc/decode.hip) are bf16; "
-                                  "call model.set_compute_dtype('bf16') to decode")
-    if sync_every < 1:
-        raise ValueError("sync_every must be >= 1")
-    graph = step == "graph" and _capture
-    stream = step == "graph" and _stream_gemm
-    was_training = model.training
-    model.eval()
-    try:
-        dec = model.decoder
-        B = prompt.shape[0]
-        sess = _beam_session(model, B, beam_size, C, mel.device) if graph else None
-        cache = sess.cache if graph else BeamCache(dec, B, beam_size, C, device=mel.device)
-        cache.start(prompt, prompt_len, eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first, n_vocab=model.dims.n_vocab)
-        most = cache.max_len - int(cache.first_len.min())
-        if most > 0:
-            logits = beam_prefill(dec, cache, model.encoder(mel))
-            if graph:
-                sess.adopt_prefill()
-            beam_topk(dec, cache, logits, first=True)
-            beam_update(cache, first=True)
-            ready = graph and sess.valid(dec, stream)
-            warmed = False
-            for i in range(1, most):
-                if i % sync_every == 0 and int(cache.unfinished.item()) == 0:
-                    break
-                if graph and not ready and warmed:
-                    sess.capture(dec, stream)
-                    ready = True
-                if ready:
-                    sess.replay()
-                    continue
-                with stream_gemm(stream):
-                    logits = beam_step(dec, cache)
-                    beam_topk(dec, cache, logits)
-                    beam_update(cache)
-                warmed = True
+    _check_mode(model, "beam_decode", step, sync_every)
+    B = prompt.shape[0]
+
+    def readout(cache):
         ranked = beam_finalize(cache, length_penalty)
         wins = [entries[win] for entries, win in ranked]
         L = max(len(t) for t, _, _ in wins)
@@ -669,5 +622,9 @@ def beam_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None,
         if return_all:
             res += ([sorted(entries, key=lambda e: -e[2]) for entries, _ in ranked],)
         return res
-    finally:
-        model.train(was_training)
+
+    return _decode(model, mel, dict(prompt=prompt, prompt_len=prompt_len, eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first),
+                   who="beam_decode", table=_BEAM_SESSIONS, key=(int(B), int(beam_size), int(C)),
+                   make_cache=lambda dec: BeamCache(dec, B, beam_size, C, device=mel.device), prefill=beam_prefill, first=_beam_first,
+                   body=_beam_body, readout=readout, extra=(("beam", beam_size, C),), graph=step == "graph" and _capture,
+                   stream=step == "graph" and _stream_gemm, sync_every=sync_every)

@@ -600,19 +600,15 @@ def attn_bwd(q, k, v, o, lse, do, n_head: int, causal: bool, scale: float, dq=No
 
 
 # --------------------------------------------------------------------------- greedy decoding (csrc/decode.hip)
-def attn_decode(q, cache, n_head: int, scale: float, *, new_kv=None, lens=None, q_prescaled: bool = False, out=None, _args_only=False):
-    """Single-token attention (wft_attn_decode_bf16).  q bf16 [B, H*64] (any row stride); cache bf16 [B, Tk, 2*H*64], rows {k | v}.
-    Self-attention form: new_kv = (k, v) bf16 [B, H*64] views of the step's fused projection output and lens i32 [B] — the rows
-    are written to cache[b, lens[b] - 1] and attended over keys 0 .. lens[b] - 1.  Cross-attention form (neither given): all Tk
-    keys, the cache is only read.  -> o bf16 [B, H*64]."""
+def _attn_decode_call(a, stem: str, q, cache, n_head: int, scale: float, new_kv, lens, q_prescaled: bool, out, args_only: bool, group: int = 1):
+    """What AttnDecodeArgs and AttnDecodeBeamArgs share: the layout checks, q / cache / o, the step's k / v rows with `lens`, the
+    workspace slot and the call of `stem`_bf16.  The caller has set the fields of its own struct (rows, group, anc) before."""
+    who = stem[4:]  # (also the workspace slot)
     _chk(q, BF16, "q"); _chk(cache, BF16, "cache")
-    B, D = q.shape
-    if D != n_head * 64 or cache.dim() != 3 or cache.shape[0] != B or cache.shape[2] != 2 * D or q.stride(1) != 1 or cache.stride(2) != 1:
-        raise ValueError(f"attn_decode: q {tuple(q.shape)} / cache {tuple(cache.shape)} do not fit {n_head} heads of 64")
-    if (new_kv is None) != (lens is None):
-        raise ValueError("attn_decode: the self-attention form needs both new_kv and lens")
-    o = torch.empty((B, D), dtype=BF16, device=q.device) if out is None else out
-    a = L.AttnDecodeArgs()
+    R, D = q.shape
+    if D != n_head * 64 or cache.dim() != 3 or cache.shape[0] != R // group or cache.shape[2] != 2 * D or q.stride(1) != 1 or cache.stride(2) != 1:
+        raise ValueError(f"{who}: q {tuple(q.shape)} / cache {tuple(cache.shape)} do not fit {n_head} heads of 64 at group {group}")
+    o = torch.empty((R, D), dtype=BF16, device=q.device) if out is None else out
     a.q, a.ldq = q.data_ptr(), q.stride(0)
     a.k_cache, a.v_cache = cache.data_ptr(), cache.data_ptr() + 2 * D
     a.ld_cache, a.cache_bs = cache.stride(1), cache.stride(0)
@@ -620,19 +616,32 @@ def attn_decode(q, cache, n_head: int, scale: float, *, new_kv=None, lens=None, 
     if new_kv is not None:
         k, v = new_kv
         _chk(k, BF16, "k_new"); _chk(v, BF16, "v_new")
-        _chk_flag(lens, B, "lens")
-        if k.shape != (B, D) or v.shape != (B, D) or k.stride() != v.stride() or k.stride(1) != 1:
-            raise ValueError("attn_decode: k_new / v_new must be [B, H*64] views with one row stride")
+        _chk_flag(lens, R, "lens")
+        if k.shape != (R, D) or v.shape != (R, D) or k.stride() != v.stride() or k.stride(1) != 1:
+            raise ValueError(f"{who}: k_new / v_new must be [rows, H*64] views with one row stride")
         a.k_new, a.v_new, a.ld_new, a.len = k.data_ptr(), v.data_ptr(), k.stride(0), lens.data_ptr()
-    a.B, a.H, a.Tk, a.scale, a.q_prescaled = B, n_head, cache.shape[1], scale, int(bool(q_prescaled))
-    need = L.load().wft_attn_decode_workspace_bytes(C.byref(a))
+    a.H, a.Tk, a.scale, a.q_prescaled = n_head, cache.shape[1], scale, int(bool(q_prescaled))
+    need = getattr(L.load(), stem + "_workspace_bytes")(C.byref(a))
     if need > 0:
-        ws = _tn_workspace(q.device, need, slot="attn_decode")
+        ws = _tn_workspace(q.device, need, slot=who)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-    if _args_only:  # (timing tools replay one argument struct)
+    if args_only:  # (timing tools replay one argument struct)
         return a, o
-    L.check(L.load().wft_attn_decode_bf16(C.byref(a), L.stream_ptr()), "wft_attn_decode_bf16")
+    L.check(getattr(L.load(), stem + "_bf16")(C.byref(a), L.stream_ptr()), stem + "_bf16")
     return o
+
+
+def attn_decode(q, cache, n_head: int, scale: float, *, new_kv=None, lens=None, q_prescaled: bool = False, out=None, _args_only=False):
+    """Single-token attention (wft_attn_decode_bf16).  q bf16 [B, H*64] (any row stride); cache bf16 [B, Tk, 2*H*64], rows {k | v}.
+    Self-attention form: new_kv = (k, v) bf16 [B, H*64] views of the step's fused projection output and lens i32 [B] — the rows
+    are written to cache[b, lens[b] - 1] and attended over keys 0 .. lens[b] - 1.  Cross-attention form (neither given): all Tk
+    keys, the cache is only read.  -> o bf16 [B, H*64]."""
+    if (new_kv is None) != (lens is None):
+        raise ValueError("attn_decode: the self-attention form needs both new_kv and lens")
+    _chk(q, BF16, "q")
+    a = L.AttnDecodeArgs()
+    a.B = q.shape[0]
+    return _attn_decode_call(a, "wft_attn_decode", q, cache, n_head, scale, new_kv, lens, q_prescaled, out, _args_only)
 
 
 def decode_embed(tokens, lens, emb, pos):
@@ -650,6 +659,16 @@ def decode_embed(tokens, lens, emb, pos):
     return out
 
 
+def _set_suppress(a, V: int, suppress, suppress_first) -> None:
+    """The two suppression masks (u8 [V] or None) of DecodePickArgs / DecodeTopkArgs."""
+    for name, m in (("suppress", suppress), ("suppress_first", suppress_first)):
+        if m is not None:
+            _chk(m, torch.uint8, name)
+            if m.numel() != V or not m.is_contiguous():
+                raise ValueError(f"{name}: expected a contiguous uint8 mask of {V} entries")
+            setattr(a, name, m.data_ptr())
+
+
 def decode_pick(logits, V: int, tokens, lens, finished, sum_logprob, unfinished, *, eot: int, max_len: int, suppress=None,
                 suppress_first=None, first_len=None, want_pick: bool = False):
     """Greedy pick + state update (wft_decode_pick; include/wft.h).  logits bf16 [B, ld >= V]; suppress / suppress_first u8 [V] or None.
@@ -660,12 +679,7 @@ def decode_pick(logits, V: int, tokens, lens, finished, sum_logprob, unfinished,
     _chk_flag(lens, B, "lens"); _chk_flag(finished, B, "finished"); _chk_flag(unfinished, 1, "unfinished")
     a = L.DecodePickArgs()
     a.logits, a.ld, a.V = logits.data_ptr(), logits.stride(0), V
-    for name, m in (("suppress", suppress), ("suppress_first", suppress_first)):
-        if m is not None:
-            _chk(m, torch.uint8, name)
-            if m.numel() != V or not m.is_contiguous():
-                raise ValueError(f"{name}: expected a contiguous uint8 mask of {V} entries")
-            setattr(a, name, m.data_ptr())
+    _set_suppress(a, V, suppress, suppress_first)
     if first_len is not None:
         _chk_flag(first_len, B, "first_len")
         a.first_len = first_len.data_ptr()
@@ -689,39 +703,19 @@ def attn_decode_beam(q, cache, n_head: int, scale: float, *, new_kv=None, lens=N
     [R, >= Tk]), the step's k / v rows are written to cache[r, lens[r] - 1].  Cross form: cache bf16 [R // group, Tk, 2*H*64], read
     only, shared by the `group` consecutive rows of an audio.  -> o bf16 [R, H*64]."""
     _chk(q, BF16, "q"); _chk(cache, BF16, "cache")
-    R, D = q.shape
-    self_form = lens is not None
+    R = q.shape[0]
     if (new_kv is None) != (lens is None) or (anc is None) != (lens is None):
         raise ValueError("attn_decode_beam: the self form needs new_kv, lens and anc together")
-    if not 1 <= int(group) <= 8 or R % int(group) or (self_form and group != 1):
+    if not 1 <= int(group) <= 8 or R % int(group) or (lens is not None and group != 1):
         raise ValueError(f"attn_decode_beam: group={group} must lie in 1..8 and divide the {R} rows (1 in the self form)")
-    if D != n_head * 64 or cache.dim() != 3 or cache.shape[0] != R // group or cache.shape[2] != 2 * D or q.stride(1) != 1 or cache.stride(2) != 1:
-        raise ValueError(f"attn_decode_beam: q {tuple(q.shape)} / cache {tuple(cache.shape)} do not fit {n_head} heads of 64 at group {group}")
-    o = torch.empty((R, D), dtype=BF16, device=q.device) if out is None else out
     a = L.AttnDecodeBeamArgs()
-    a.q, a.ldq = q.data_ptr(), q.stride(0)
-    a.k_cache, a.v_cache = cache.data_ptr(), cache.data_ptr() + 2 * D
-    a.ld_cache, a.cache_bs = cache.stride(1), cache.stride(0)
-    a.o, a.ldo = o.data_ptr(), o.stride(0)
-    if self_form:
-        k, v = new_kv
-        _chk(k, BF16, "k_new"); _chk(v, BF16, "v_new"); _chk(anc, torch.int32, "anc")
-        _chk_flag(lens, R, "lens")
-        if k.shape != (R, D) or v.shape != (R, D) or k.stride() != v.stride() or k.stride(1) != 1:
-            raise ValueError("attn_decode_beam: k_new / v_new must be [R, H*64] views with one row stride")
-        if anc.dim() != 2 or anc.shape[0] != R or anc.shape[1] < cache.shape[1] or anc.stride(1) != 1:
-            raise ValueError(f"attn_decode_beam: anc must be i32 [R, >= {cache.shape[1]}] with contiguous rows")
-        a.k_new, a.v_new, a.ld_new, a.len = k.data_ptr(), v.data_ptr(), k.stride(0), lens.data_ptr()
+    a.R, a.group = R, int(group)
+    if anc is not None:
+        _chk(anc, torch.int32, "anc")
+        if anc.dim() != 2 or anc.shape[0] != R or cache.dim() != 3 or anc.shape[1] < cache.shape[1] or anc.stride(1) != 1:
+            raise ValueError(f"attn_decode_beam: anc must be i32 [R, >= {cache.shape[1] if cache.dim() == 3 else 'Tk'}] with contiguous rows")
         a.anc, a.ld_anc = anc.data_ptr(), anc.stride(0)
-    a.R, a.H, a.Tk, a.group, a.scale, a.q_prescaled = R, n_head, cache.shape[1], int(group), scale, int(bool(q_prescaled))
-    need = L.load().wft_attn_decode_beam_workspace_bytes(C.byref(a))
-    if need > 0:
-        ws = _tn_workspace(q.device, need, slot="attn_decode_beam")
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-    if _args_only:
-        return a, o
-    L.check(L.load().wft_attn_decode_beam_bf16(C.byref(a), L.stream_ptr()), "wft_attn_decode_beam_bf16")
-    return o
+    return _attn_decode_call(a, "wft_attn_decode_beam", q, cache, n_head, scale, new_kv, lens, q_prescaled, out, _args_only, group=int(group))
 
 
 def decode_topk(logits, V: int, cand_tok, cand_logp, *, lens=None, first_len=None, suppress=None, suppress_first=None, row_step: int = 1):
@@ -736,12 +730,7 @@ def decode_topk(logits, V: int, cand_tok, cand_logp, *, lens=None, first_len=Non
     R, k = cand_tok.shape
     a = L.DecodeTopkArgs()
     a.logits, a.ld, a.V = logits.data_ptr(), logits.stride(0), V
-    for name, m in (("suppress", suppress), ("suppress_first", suppress_first)):
-        if m is not None:
-            _chk(m, torch.uint8, name)
-            if m.numel() != V or not m.is_contiguous():
-                raise ValueError(f"{name}: expected a contiguous uint8 mask of {V} entries")
-            setattr(a, name, m.data_ptr())
+    _set_suppress(a, V, suppress, suppress_first)
     if lens is not None:
         _chk_flag(lens, R, "lens")
         a.len = lens.data_ptr()

@@ -209,8 +209,8 @@ class MultiHeadAttention(nn.Module):
         """Inference with a KVCache (engine/decode.py).  T > 1: the prefill — the teacher-forced kernels over the right-padded prompts,
         the k / v rows stored into the cache.  T = 1: a cached step on the single-token kernel (csrc/decode.hip), which appends
         the step's k / v itself.  Cross-attention keys / values are projected once per audio batch.
-        With a BeamCache the prefill carries ONE row per audio (stored into slot row a*W) and a step all audios * W hypotheses: self
-        keys are read through the ancestry table, cross keys once per audio for its W rows (wft_attn_decode_beam_bf16)."""
+        The cache hides its layout (store_prefill / self_step / cross_step): with a BeamCache the prefill carries ONE row per audio
+        and a step all audios * W hypotheses — self keys through the ancestry table, cross keys once per audio for its W rows."""
         if self.wft_fp32:
             raise NotImplementedError("KV-cached decoding runs in the bf16 compute mode only (model.set_compute_dtype('bf16'))")
         if torch.is_grad_enabled():
@@ -218,24 +218,18 @@ class MultiHeadAttention(nn.Module):
         B, T, d = x.shape
         x2 = _as2d(_to_bf16(x))
         scale = 64 ** -0.5
-        beam = isinstance(cache, _decode.BeamCache)
         if not cache.is_cross(self):
             lin = [self.query, self.key, self.value]
             qkv = ops.linear(x2, self._qkv_group, [m.base_weight() for m in lin], [m.bias for m in lin], [m.lora_spec() for m in lin])
             prescaled = self._qkv_group.fwd_scales is not None
-            store = cache.self_kv[self]
             if T > 1:
                 if cache.prefilled:
                     raise RuntimeError("this KVCache already holds a prefix: only single-token steps may follow the prefill")
                 qkv3 = qkv.view(B, T, 3 * d)
                 o = ops.SelfAttnFn.apply(qkv3, self.n_head, True, prescaled)
-                (store.view(B, cache.beam, -1, 2 * d)[:, 0] if beam else store)[:, :T].copy_(qkv3[..., d:])
-            elif beam:
-                o = K.attn_decode_beam(qkv[:, :d], store, self.n_head, scale, new_kv=(qkv[:, d:2 * d], qkv[:, 2 * d:]), lens=cache.len,
-                                       anc=cache.anc, q_prescaled=prescaled)
+                cache.store_prefill(self, qkv3[..., d:])
             else:
-                o = K.attn_decode(qkv[:, :d], store, self.n_head, scale, new_kv=(qkv[:, d:2 * d], qkv[:, 2 * d:]), lens=cache.len,
-                                  q_prescaled=prescaled)
+                o = cache.self_step(self, qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], self.n_head, scale, prescaled)
         else:
             kv = cache.cross_kv[self]
             if kv is None:
@@ -248,10 +242,8 @@ class MultiHeadAttention(nn.Module):
             q = self.query(x2)
             if T > 1:
                 o = ops.CrossAttnFn.apply(q.view(B, T, d), kv, self.n_head)
-            elif beam:
-                o = K.attn_decode_beam(q, kv, self.n_head, scale, group=cache.beam)
             else:
-                o = K.attn_decode(q, kv, self.n_head, scale)
+                o = cache.cross_step(self, q, self.n_head, scale)
         out = self.out(o.view(B * T, d), residual=None if residual is None else _as2d(residual))
         return out.view(B, T, d), None
 
