@@ -41,11 +41,14 @@ def _view(cache):
     return dv
 
 
-def drive(m, oracle, mel, prompt, plen, steps, *, beam, cands, eot, max_len, suppress=(), suppress_first=(), compare_teacher=True):
+def drive(m, oracle, mel, prompt, plen, steps, *, beam, cands, eot, max_len, suppress=(), suppress_first=(), compare_teacher=True,
+          check_steps=None):
     """`steps` beam-search steps from the pieces beam_decode is made of.  Per step: (a) the logits of every live row against the
-    teacher-forced engine and the fp32 oracle on that row's own prefix, worst row; (b) the oracle replay on the engine's candidates."""
+    teacher-forced engine and the fp32 oracle on that row's own prefix, worst row; (b) the oracle replay on the engine's candidates.
+    check_steps(i, lens of the live rows) -> bool restricts (a) to chosen steps (None: every step; rec["checked"] lists them); (b)
+    runs after every step regardless."""
     V, nB = m.dims.n_vocab, prompt.shape[0]
-    rec = dict(rel_teacher=[], rel_oracle=[], done_at={}, first_cands=None, rows=0)
+    rec = dict(rel_teacher=[], rel_oracle=[], done_at={}, first_cands=None, rows=0, checked=[])
     m.eval()
     with torch.no_grad():
         xa = m.encoder(mel)
@@ -64,6 +67,8 @@ def drive(m, oracle, mel, prompt, plen, steps, *, beam, cands, eot, max_len, sup
             if live:
                 sel = torch.tensor([state_rows[k] for k in live])
                 toks, lens = cache.tokens.cpu()[sel], cache.len.cpu()[sel]
+            if live and (check_steps is None or check_steps(i, lens.tolist())):
+                rec["checked"].append(i)
                 got = logits[:, :V].float().cpu()[live]
                 rec["rows"] += len(live)
                 if oracle is not None:

@@ -11,7 +11,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests import _beam_oracle as BO  # noqa: E402
-from tests.test_decode_kernels_gpu import _ref_decode, close  # noqa: E402
+from tests.test_decode_kernels_gpu import ALL_LONG, PER_HEAD_TOL, _ref_decode, close, close_per_head  # noqa: E402
 from whisper_finetune.engine import kernels as K  # noqa: E402
 from whisper_finetune.engine import lib as L  # noqa: E402
 
@@ -157,6 +157,26 @@ class _DevState:
         self.fin_n = torch.zeros(B, **I32)
         self.src = torch.full((R,), -1, **I32)
 
+    def load_history(self, st, rng, vocab):
+        """Replace the state of a fresh start() by one in the middle of a decode, on the device and in the oracle `st` alike: every
+        beam has its own tokens (drawn from `vocab`, which must not hold eot), its own score on the coarse grid of _random_cands,
+        and an ancestry row that names other slots of its audio — so a row permutation moves values that tell the rows apart in
+        EVERY column, and the steps that follow are ordinary ones (first = False)."""
+        W = self.W
+        tokens, anc, slp = self.tokens.cpu(), self.anc.cpu(), self.slp.cpu()
+        for au in st.audios:
+            n = au.first_len
+            for j, b in enumerate(au.beams):
+                r = au.a * W + j
+                b.tokens = [int(t) for t in rng.choice(vocab, size=n)]
+                b.anc = [au.a * W + int(s) for s in rng.integers(0, W, size=n)]  # (entry n - 1 is never read: the step that appends overwrites it)
+                b.slp = np.float32(-0.125 * int(rng.integers(0, 40)))
+                tokens[r, :n] = torch.tensor(b.tokens)
+                anc[r, :n - 1] = torch.tensor(b.anc[:n - 1], dtype=torch.int32)
+                slp[r] = float(b.slp)
+            au.first = False
+        self.tokens.copy_(tokens); self.anc.copy_(anc); self.slp.copy_(slp)
+
     def update(self, cand_tok, cand_logp, first):
         K.beam_update(cand_tok.to(DEV), cand_logp.to(DEV), self.tokens, self.anc, self.len, self.slp, self.done, self.unfinished,
                       self.fin_tokens, self.fin_len, self.fin_score, self.fin_n, eot=self.eot, max_len=self.max_len, first=first,
@@ -193,9 +213,10 @@ def _random_cands(rng, R, W, vocab, eot, p_eot):
     on a coarse grid, so equal scores happen."""
     tok = np.zeros((R, W + 1), dtype=np.int32)
     lp = np.zeros((R, W + 1), dtype=np.float32)
+    p_eot = np.broadcast_to(np.asarray(p_eot, dtype=np.float64), (R,))  # (one probability, or one per row)
     for r in range(R):
         t = rng.choice(vocab, size=W + 1, replace=False)
-        if rng.random() < p_eot:
+        if rng.random() < p_eot[r]:
             t[rng.integers(0, W + 1)] = eot
         tok[r] = t
         lp[r] = -np.sort(rng.integers(1, 24, size=W + 1)).astype(np.float32) * np.float32(0.125)
@@ -232,6 +253,48 @@ def test_beam_update_follows_the_oracle_on_the_same_candidates(W, patience, p_eo
         assert any(len(au.fin) == C for au in st.audios), "no finished list filled: the case does not test what it says"
     if p_eot == 0.0:
         assert all(len(au.fin) == 0 for au in st.audios)
+
+
+@pytest.mark.parametrize("W", [5, 8])
+def test_beam_update_permutes_columns_beyond_256(W):
+    """The token buffer at its full width (n_ctx = max_len = 448): the kernel permutes rows of `tokens` and `anc` one column per
+    thread, 256 threads, so columns 256 and up are the SECOND trip of that loop.  Prompts of 3, 250, 255, 256, 257, 440, 447 and 448
+    tokens, loaded as a decode in progress (_DevState.load_history: per-beam tokens, scores and ancestry), random candidates until
+    every audio is done, the whole state compared with the oracle after every step as in the test above.  Which audio sees eot when
+    is arranged so that both ends are reached behind column 256: the 3-token audio sees none for 300 steps and then fills its
+    finished list (the copy into fin_tokens runs over columns >= 256 too), the 250-token one never does and ends at max_len."""
+    eot, n_ctx, max_len = 3, 448, 448
+    plens = [3, 250, 255, 256, 257, 440, 447, 448]
+    B, C = len(plens), BO.candidates(W)
+    rng = np.random.default_rng(4480 + W)
+    vocab = np.array([t for t in range(10, 10 + 3 * W + 6)] + [0, 1, 2])
+    prompts = [[5] * n for n in plens]
+    st = BO.State(prompts, W, C, eot, max_len)
+    dv = _DevState(prompts, W, C, eot, max_len, n_ctx)
+    dv.load_history(st, rng, vocab)
+    assert st.audios[7].done and st.unfinished == B - 1
+    before = dv.tokens.cpu().clone()
+    moved_late = fin_late = 0
+    for i in range(max_len):
+        p = np.repeat([0.0 if i < 300 else 0.5, 0.0, 0.3, 0.05, 0.5, 0.3, 0.5, 0.5], W)
+        tok, lp = _random_cands(rng, B * W, W, vocab, eot, p)
+        dv.update(tok, lp, first=False)
+        BO.step_candidates(st, _as_lists(tok.numpy(), lp.numpy(), B, W))
+        dv.check(st, f"step {i}")
+        after = dv.tokens.cpu()
+        lens = dv.len.cpu().tolist()
+        for r in range(B * W):  # columns >= 256 inside the hypothesis (its newest token aside) whose value changed: a row really moved
+            moved_late += int((after[r, 256:max(lens[r] - 1, 256)] != before[r, 256:max(lens[r] - 1, 256)]).sum())
+        before = after.clone()
+        if st.unfinished == 0:
+            break
+    assert st.unfinished == 0
+    fin_late = sum(len(t) > 257 for au in st.audios for t, _ in au.fin)
+    ends = [len(au.beams[0].tokens) for au in st.audios]
+    print(f"W={W}: lengths at the end {ends}, finished {[len(au.fin) for au in st.audios]}; {moved_late} token values in columns >= 256 "
+          f"changed by a reorder, {fin_late} finished sequences longer than 257 tokens")
+    assert ends[1] == max_len and ends[7] == max_len and ends[0] > 300
+    assert moved_late > 0 and fin_late > 0 and len(st.audios[0].fin) == C
 
 
 def test_beam_update_crafted_ties_and_dropped_eot():
@@ -299,6 +362,34 @@ def test_self_form_is_bit_identical_to_the_gathered_cache(H, lens, prescaled):
     close(got, _ref_decode(qkv[:, :D], full[..., :D], full[..., D:], lens, H, math.log(2.0) if prescaled else scale), 2e-2, f"self form R*H={R * H}")
 
 
+@pytest.mark.parametrize("H", [6, 20])
+@pytest.mark.parametrize("prescaled", [False, True])
+def test_self_form_long_rows_per_head(H, prescaled):
+    """Every hypothesis between 225 and 448 keys behind a scrambled ancestry table (every wave owns keys, the index prefetch two
+    blocks ahead fetches live blocks): each (row, head) within 2^-7 of its own largest fp64 reference value (close_per_head), and
+    bit-identical to wft_attn_decode_bf16 on the gathered cache as above."""
+    lens = ALL_LONG
+    R, D, cap = len(lens), H * 64, 448
+    g = torch.Generator().manual_seed(R * 613 + H)
+    slots = torch.randn(R, cap, 2 * D, generator=g).to(BF)
+    qkv = torch.randn(R, 3 * D, generator=g).to(BF)
+    scale = 0.125
+    if prescaled:
+        qkv[:, :D] = (qkv[:, :D].float() * (scale * LOG2E)).to(BF)
+    anc = _scrambled_anc(R, cap, lens, g)
+    gathered = slots[anc.long(), torch.arange(cap)[None, :]]
+    full = gathered.clone()
+    for r, n in enumerate(lens):
+        full[r, n - 1] = qkv[r, D:]
+    ref = _ref_decode(qkv[:, :D], full[..., :D], full[..., D:], lens, H, math.log(2.0) if prescaled else scale, dtype=torch.float64)
+    lens_t = torch.tensor(lens, **I32)
+    qd = qkv.to(DEV)
+    got = K.attn_decode_beam(qd[:, :D], slots.to(DEV), H, scale, new_kv=(qd[:, D:2 * D], qd[:, 2 * D:]), lens=lens_t, anc=anc.to(DEV), q_prescaled=prescaled)
+    close_per_head(got, ref, PER_HEAD_TOL, f"self form, all rows long, H={H} prescaled={prescaled}")
+    want = K.attn_decode(qd[:, :D], gathered.to(DEV), H, scale, new_kv=(qd[:, D:2 * D], qd[:, 2 * D:]), lens=lens_t, q_prescaled=prescaled)
+    assert torch.equal(bits(got), bits(want))
+
+
 def test_self_form_over_a_split_cache():
     """Capacity > 512 keys at a small R * H: the split path with indirection, still bit-identical."""
     H, D, cap = 2, 128, 1100
@@ -315,6 +406,12 @@ def test_self_form_over_a_split_cache():
     assert args.workspace_bytes > 0
     got = K.attn_decode_beam(qkv[:, :D], slots.to(DEV), H, 0.125, new_kv=(qkv[:, D:2 * D], qkv[:, 2 * D:]), lens=lens_t, anc=anc.to(DEV))
     assert torch.equal(bits(got), bits(want))
+    # the rows of 600 and 1100 keys, each head against its own scale
+    full = gd.cpu().clone()
+    for r, n in enumerate(lens):
+        full[r, n - 1] = qkv[r, D:].cpu()
+    ref = _ref_decode(qkv[:, :D].cpu(), full[..., :D], full[..., D:], lens, H, 0.125, dtype=torch.float64)
+    close_per_head(got[2:], ref[2:], PER_HEAD_TOL, "self form over 3 splits, rows of 600 and 1100 keys")
 
 
 # ----------------------------------------------------------------------------- wft_attn_decode_beam_bf16, cross form
