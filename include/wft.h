@@ -503,6 +503,26 @@ typedef struct {
   int rows; int row_step; int k;
 } wft_decode_topk_args;
 int wft_decode_topk(const wft_decode_topk_args* args, void* stream);
+/* Timestamp rules: upstream's `whisper.decoding.ApplyTimestampRules`, restated (openai-whisper is not a dependency: parity with the
+ * upstream binary is unpinned).  Columns ts_begin .. V-1 are timestamps (eot < ts_begin < V); no_timestamps: a column or -1;
+ * max_initial: upstream's max_initial_timestamp_index, or -1 for none.  The SAMPLED tokens of state row r are
+ * tokens[r, first_len[r] : len[r]]; the kernels read them, there is no other rule state.  After the `suppress` / `suppress_first`
+ * masks, in upstream's order:
+ *  1. column no_timestamps is removed;
+ *  2. last_ts = the last sampled token is >= ts_begin; pen_ts = fewer than two sampled tokens, or the one before the last is >=
+ *     ts_begin.  last_ts && pen_ts: columns ts_begin..V-1 are removed; last_ts && !pen_ts: columns 0..eot-1 are removed;
+ *  3. t = the last sampled token that is a timestamp, if any: columns ts_begin..t-1 are removed, and t too unless last_ts && !pen_ts;
+ *  4. no sampled token yet: columns 0..ts_begin-1 are removed and, with max_initial >= 0, the columns above ts_begin + max_initial;
+ *  5. over what is still live: if logsumexp of the timestamp columns is STRICTLY greater than the largest log-probability of a
+ *     column below ts_begin (both under the softmax of the live row, so log sum_ts exp(x - m) > max_text - m; an empty side is
+ *     -inf), every column below ts_begin is removed.
+ * The pick / the candidates and their log-probabilities are taken under the softmax of the finally live columns, as with the
+ * static masks alone.  Every column removed: the pick is eot with log-probability 0, the candidates are (-1, -inf).  first_len and
+ * len are required.  wft_decode_topk_ts reads the token rows of the state rows r = i*row_step at tokens + r*ld_tokens.          */
+typedef struct { int ts_begin; int no_timestamps; int max_initial; } wft_ts_rules;
+int wft_decode_pick_ts(const wft_decode_pick_args* args, const wft_ts_rules* rules, void* stream);
+int wft_decode_topk_ts(const wft_decode_topk_args* args, const wft_ts_rules* rules, const int64_t* tokens, int64_t ld_tokens, int eot,
+                       void* stream);
 /* One beam-search step for every audio that is not done, from the candidate lists of wft_decode_topk (k = W + 1 per row):
  *  candidates (j, i), j = beam, i = list position, score = sum_logprob[a*W + j] + cand_logp[a*W + j][i] (one fp32 add); `first`
  *    != 0: only j = 0 contributes (the W copies of the prompt are one hypothesis).  Order: score descending, ties to the lower

@@ -19,7 +19,11 @@
          achieved TB/s; (iii) wft_decode_topk + wft_beam_update against wft_decode_pick at R rows; (iv) beam_decode(W = 5) against
          greedy_decode at batch = R, eager and graph: tokens/s, ms per step, ratio.
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,beam] [--batches 1,8,32] [--out FILE]
+  ts     the timestamp-rule forms of the pick and the top-k (wft_decode_pick_ts, wft_decode_topk_ts) against the plain kernels on the
+         same rows, V = 51 866, --batches = rows: histories of 100 sampled tokens ending in text, so every rule-5 pass runs (the
+         two arg-best pairs, the two sums, and for top-k the third scan).
+
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,beam,ts] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -495,6 +499,46 @@ def bench_beam(batches, W=5, new_tokens=64, runs=3):
         Dm.release_graphs(m)
 
 
+def bench_ts(batches):
+    """Pick / top-6 with and without the timestamp rules at R rows: 32 rotating logits buffers (a single one would sit in the
+    Infinity Cache), issued through the Python wrappers (their host time is in every arm)."""
+    V, n_ctx, tsb, eot, k = 51866, CAP, 50365, 50257, 6
+    ld = K.round_up(V, 128)
+    i32 = dict(dtype=torch.int32, device=DEV)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for R in batches:
+        logits = [(torch.randn(R, ld, device=DEV, generator=g) * 3).to(BF) for _ in range(LAYERS)]
+        tokens = torch.randint(0, eot, (R, n_ctx), device=DEV, generator=g)
+        tokens[:, 4] = tsb + 10  # the opening timestamp of every row; text behind it
+        sup = torch.zeros(V, dtype=torch.uint8, device=DEV); sup[eot + 1:tsb] = 1
+        first = torch.full((R,), 4, **i32)
+        st = dict(lens=torch.full((R,), 104, **i32), fin=torch.zeros(R, **i32), slp=torch.zeros(R, device=DEV), unf=torch.zeros(1, **i32),
+                  ct=torch.zeros(R, k, **i32), cl=torch.zeros(R, k, device=DEV))
+        rules = (tsb, tsb - 1, 50)
+
+        def pick(ru):
+            st["lens"].fill_(104); st["fin"].zero_()
+            for lg in logits:
+                st["lens"].fill_(104)
+                K.decode_pick(lg, V, tokens, st["lens"], st["fin"], st["slp"], st["unf"], eot=eot, max_len=n_ctx, suppress=sup, first_len=first, ts_rules=ru)
+
+        def topk(ru):
+            for lg in logits:
+                K.decode_topk(lg, V, st["ct"], st["cl"], lens=st["lens"], first_len=first, suppress=sup, ts_rules=ru, tokens=tokens, eot=eot)
+
+        res = ab({"pick": lambda: pick(None), "pick_ts": lambda: pick(rules), "topk": lambda: topk(None), "topk_ts": lambda: topk(rules)}, iters=2)
+        rec = dict(part="ts", rows=R, V=V, k=k, sampled_tokens=100, logits_MB=round(R * V * 2 / 1e6, 2),
+                   note="us per call; the pick arms include one fill_ of `len` per call")
+        for n, (med, mn, spread) in res.items():
+            rec[n + "_us"] = round(med * 1e3 / LAYERS, 2)
+            rec[n + "_min_us"] = round(mn * 1e3 / LAYERS, 2)
+            rec[n + "_spread"] = round(spread, 3)
+        rec["pick_ts_vs_pick"] = round(res["pick_ts"][0] / res["pick"][0], 2)
+        rec["topk_ts_vs_topk"] = round(res["topk_ts"][0] / res["topk"][0], 2)
+        emit(rec)
+        del logits
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="attn,gemm,e2e")
@@ -507,7 +551,7 @@ def main():
     emit(dict(part="env", device=torch.cuda.get_device_name(0), lib=L.load().wft_version().decode(), torch=torch.__version__))
     for part in a.parts.split(","):
         {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": bench_gemm_stream, "e2e_step": bench_e2e_step,
-         "beam": bench_beam}[part](batches)
+         "beam": bench_beam, "ts": bench_ts}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

@@ -10,6 +10,7 @@
 //  decode_embed_kernel                             token + positional embedding at the device-side position
 //  decode_pick_kernel / decode_count_kernel        suppress, arg-max, log-probability, state update, unfinished-row count
 //  decode_topk_kernel / beam_update_kernel         the W + 1 best continuations per hypothesis; one beam-search step per audio
+//  decode_pick_kernel<true> / decode_topk_kernel<true>   the same two under upstream's timestamp rules (ts_row_rules, ts_decide)
 #include "common.h"
 
 // ----------------------------------------------------------------------------- single-token attention
@@ -539,16 +540,21 @@ extern "C" int wft_decode_embed(const int64_t* tokens, int64_t ld_tokens, const 
 
 __device__ __forceinline__ bool pick_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
-// f(x, col) for the live columns of a logits row — col < V, neither mask set — that this thread owns: 16-byte reads, ascending columns
-template <typename F>
-__device__ __forceinline__ void pick_scan(const unsigned short* row, int V, const unsigned char* m1, const unsigned char* m2, F f) {
+// f(x, col) for the live columns of a logits row — col < V, live(col), neither mask set — that this thread owns: 16-byte reads,
+// ascending columns.  live: the per-row column predicate of the timestamp rules (ts_live below), pick_all where there are none.
+struct pick_all {
+  __device__ __forceinline__ bool operator()(int) const { return true; }
+};
+
+template <typename P, typename F>
+__device__ __forceinline__ void pick_scan(const unsigned short* row, int V, const unsigned char* m1, const unsigned char* m2, P live, F f) {
   for (int c0 = threadIdx.x * 8; c0 < V; c0 += PICK_THREADS * 8) {
     float x[8];
     dec_unpack8(*(const u32x4*)(row + c0), x);  // (ld % 8 == 0 and ld >= V rounded up to 8: in bounds)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int col = c0 + j;
-      if (col < V && !(m1 && m1[col]) && !(m2 && m2[col])) f(x[j], col);
+      if (col < V && live(col) && !(m1 && m1[col]) && !(m2 && m2[col])) f(x[j], col);
     }
   }
 }
@@ -579,12 +585,9 @@ __device__ __forceinline__ void pick_wg_best(float& best, int& bi, float* s_v, i
     }
 }
 
-// sum of exp(x - top) over the live columns of the row (0 when `any` is false), in every thread: per thread in column order, the
-// wave butterfly, then the waves in wave order
-__device__ __forceinline__ float pick_wg_sumexp(const unsigned short* row, int V, const unsigned char* m1, const unsigned char* m2, float top,
-                                                bool any, float* s_sum) {
-  float sum = 0.f;
-  if (any) pick_scan(row, V, m1, m2, [&](float x, int) { sum += __expf(x - top); });
+// the workgroup's sum of `sum` in every thread: the wave butterfly, then the waves in wave order.  s_sum: one entry per wave, not
+// reused without a barrier in between.
+__device__ __forceinline__ float pick_wg_sum(float sum, float* s_sum) {
   sum = wave_sum(sum);
   if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = sum;
   __syncthreads();
@@ -593,7 +596,121 @@ __device__ __forceinline__ float pick_wg_sumexp(const unsigned short* row, int V
   return tot;
 }
 
-__global__ __launch_bounds__(PICK_THREADS) void decode_pick_kernel(wft_decode_pick_args a) {
+// sum of exp(x - top) over the live columns of the row (0 when `any` is false), in every thread: per thread in column order, then
+// pick_wg_sum
+__device__ __forceinline__ float pick_wg_sumexp(const unsigned short* row, int V, const unsigned char* m1, const unsigned char* m2, float top,
+                                                bool any, float* s_sum) {
+  float sum = 0.f;
+  if (any) pick_scan(row, V, m1, m2, pick_all{}, [&](float x, int) { sum += __expf(x - top); });
+  return pick_wg_sum(sum, s_sum);
+}
+
+// ----------------------------------------------------------------------------- the timestamp rules (include/wft.h "Timestamp rules")
+// Upstream's `ApplyTimestampRules`, restated.  Rules 1-4 remove column RANGES that follow from three facts about the row's sampled
+// tokens tokens[r, F..L) — the last one, the one before it, the last timestamp among them — so they become four per-row scalars and
+// a live column is `col != no_ts && (col < ts_begin ? col >= text_lo : ts_lo <= col <= ts_hi)`:
+//   1  no_ts is removed                                                                       (no_ts = -1: nothing)
+//   2  last_ts && pen_ts: every timestamp is removed (ts_lo = V); last_ts && !pen_ts: columns 0..eot-1 are (text_lo = eot)
+//   3  t = the last sampled timestamp: ts_begin..t-1 are removed, and t itself unless last_ts && !pen_ts  (ts_lo = t or t + 1)
+//   4  no sampled token yet: all text is removed (text_lo = ts_begin), and timestamps above ts_begin + max_initial (ts_hi)
+// Rule 5 (the probability rule) needs the row's values and lives in the kernels: ts_decide below.
+// The facts are read from `tokens` by the workgroup itself — at most n_text_ctx i64 values, one strided read and a max-index
+// reduce — so there is no per-row rule state to keep, permute or reset, and nothing on the host depends on the step.
+struct ts_row {
+  int no_ts, ts_begin, text_lo, ts_lo, ts_hi;
+};
+
+__device__ __forceinline__ bool ts_live(const ts_row& t, int col) {
+  return col != t.no_ts && (col < t.ts_begin ? col >= t.text_lo : (col >= t.ts_lo && col <= t.ts_hi));
+}
+
+// the same ts_row in every thread.  tok: the row's tokens (ld_tokens of them are addressable), F / L: first_len / len of the row;
+// s_ts: one entry per wave, used by nothing else.
+__device__ __forceinline__ ts_row ts_row_rules(const wft_ts_rules& ru, const long* tok, long ld_tokens, int F, int L, int V, int eot,
+                                               int* s_ts) {
+  L = (int)min((long)max(L, 0), ld_tokens);
+  F = min(max(F, 0), L);
+  const int n = L - F;  // sampled tokens
+  int idx = -1;         // position of the last sampled timestamp (ascending positions per thread: the last hit is its largest)
+  for (int i = F + (int)threadIdx.x; i < L; i += PICK_THREADS)
+    if (tok[i] >= ru.ts_begin) idx = i;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) idx = max(idx, __shfl_xor(idx, o, 64));
+  if ((threadIdx.x & 63) == 0) s_ts[threadIdx.x >> 6] = idx;
+  __syncthreads();
+  idx = s_ts[0];
+  for (int w = 1; w < PICK_WAVES; ++w) idx = max(idx, s_ts[w]);
+  const bool last_ts = n >= 1 && tok[L - 1] >= ru.ts_begin;
+  const bool pen_ts = n < 2 || tok[L - 2] >= ru.ts_begin;
+  ts_row t;
+  t.no_ts = ru.no_timestamps;
+  t.ts_begin = ru.ts_begin;
+  t.text_lo = 0;
+  t.ts_lo = ru.ts_begin;
+  t.ts_hi = V - 1;
+  if (last_ts && pen_ts) t.ts_lo = V;
+  if (last_ts && !pen_ts) t.text_lo = eot;
+  if (idx >= 0) {
+    const long last = min(tok[idx], (long)V - 1);
+    t.ts_lo = max(t.ts_lo, (int)last + ((last_ts && !pen_ts) ? 0 : 1));
+  }
+  if (n == 0) {
+    t.text_lo = ru.ts_begin;
+    if (ru.max_initial >= 0) t.ts_hi = (int)min((long)V - 1, (long)ru.ts_begin + ru.max_initial);
+  }
+  return t;
+}
+
+// Rule 5 rides the two passes the kernels make anyway.  Pass 1 keeps TWO arg-best pairs, the best live text column (bt, it) and the
+// best live timestamp column (bs, is); pass 2 keeps two sums of exp(x - m), m = max(bt, bs), per thread in column order and reduced
+// by pick_wg_sum.  Both log-probabilities share the normaliser, so "logsumexp of the timestamps > the best text log-probability"
+// is log(sum_ts) > bt - m (an empty side is -inf: 0 timestamps never win, 0 text columns always lose to a live timestamp).
+struct ts_pass {
+  float bt, bs, m, st, ss;
+  int it, is;
+  bool wins;  // the timestamps win: every text column is removed
+};
+
+template <typename P>
+__device__ __forceinline__ ts_pass ts_decide(const unsigned short* row, int V, const unsigned char* m1, const unsigned char* m2, int ts_begin,
+                                             P live, float* s_v, int* s_i, float* s_sum, float* s_sum2) {
+  ts_pass p;
+  p.bt = p.bs = -INFINITY;
+  p.it = p.is = PICK_NONE;
+  pick_scan(row, V, m1, m2, live, [&](float x, int col) {
+    if (col < ts_begin) {
+      if (x > p.bt) {
+        p.bt = x;
+        p.it = col;
+      }
+    } else if (x > p.bs) {
+      p.bs = x;
+      p.is = col;
+    }
+  });
+  pick_wg_best(p.bt, p.it, s_v, s_i);
+  __syncthreads();
+  pick_wg_best(p.bs, p.is, s_v, s_i);
+  p.m = fmaxf(p.bt, p.bs);
+  p.st = p.ss = 0.f;
+  if (p.it != PICK_NONE || p.is != PICK_NONE) {
+    const float m = p.m;
+    pick_scan(row, V, m1, m2, live, [&](float x, int col) {
+      const float e = __expf(x - m);
+      if (col < ts_begin) p.st += e;
+      else p.ss += e;
+    });
+  }
+  p.st = pick_wg_sum(p.st, s_sum);
+  p.ss = pick_wg_sum(p.ss, s_sum2);
+  p.wins = __logf(p.ss) > p.bt - p.m;
+  return p;
+}
+
+// TS: the timestamp-rule form (wft_decode_pick_ts).  The timestamps win -> the best timestamp column under the normaliser sum_ts;
+// otherwise the better of the two pairs (value descending, the lower column on ties) under sum_ts + sum_text.
+template <bool TS>
+__global__ __launch_bounds__(PICK_THREADS) void decode_pick_kernel(wft_decode_pick_args a, wft_ts_rules ru) {
   __shared__ float s_v[PICK_WAVES];
   __shared__ int s_i[PICK_WAVES];
   __shared__ float s_sum[PICK_WAVES];
@@ -606,18 +723,30 @@ __global__ __launch_bounds__(PICK_THREADS) void decode_pick_kernel(wft_decode_pi
 
   float best = -INFINITY;
   int bi = PICK_NONE;
-  pick_scan(row, V, m1, m2, [&](float x, int col) {
-    if (x > best) {
-      best = x;
-      bi = col;
-    }
-  });
-  pick_wg_best(best, bi, s_v, s_i);
+  float lp;
+  if constexpr (TS) {
+    __shared__ int s_ts[PICK_WAVES];
+    __shared__ float s_sum2[PICK_WAVES];
+    const ts_row t = ts_row_rules(ru, a.tokens + (long)b * a.ld_tokens, a.ld_tokens, a.first_len[b], L, V, a.eot, s_ts);
+    const ts_pass p = ts_decide(row, V, m1, m2, t.ts_begin, [&](int col) { return ts_live(t, col); }, s_v, s_i, s_sum, s_sum2);
+    const bool ts = p.wins || pick_better(p.bs, p.is, p.bt, p.it);
+    best = ts ? p.bs : p.bt;
+    bi = ts ? p.is : p.it;
+    lp = p.wins ? (p.bs - p.m) - __logf(p.ss) : -__logf(p.st + p.ss);
+  } else {
+    pick_scan(row, V, m1, m2, pick_all{}, [&](float x, int col) {
+      if (x > best) {
+        best = x;
+        bi = col;
+      }
+    });
+    pick_wg_best(best, bi, s_v, s_i);
+    lp = -__logf(pick_wg_sumexp(row, V, m1, m2, best, bi != PICK_NONE, s_sum));
+  }
   const bool any = bi != PICK_NONE;
-  const float tot = pick_wg_sumexp(row, V, m1, m2, best, any, s_sum);
   if (threadIdx.x == 0) {
     const long pick = any ? bi : a.eot;  // (every column suppressed: the row ends)
-    const float lp = any ? -__logf(tot) : 0.f;
+    if (!any) lp = 0.f;
     if (a.pick_out) a.pick_out[b] = pick;
     if (a.logprob_out) a.logprob_out[b] = lp;
     if (!a.finished[b]) {  // a finished row is frozen
@@ -642,14 +771,36 @@ __global__ __launch_bounds__(256) void decode_count_kernel(const int* finished, 
   if (threadIdx.x == 0) unfinished[0] = s[0] + s[1] + s[2] + s[3];
 }
 
+static int pick_check(const wft_decode_pick_args* a, const char* who) {
+  WFT_CHECK_ARG_AS(who, a && a->logits && a->tokens && a->len && a->finished && a->sum_logprob && a->unfinished, "null pointer");
+  WFT_CHECK_ARG_AS(who, a->B >= 1 && a->V >= 1 && a->V <= 0x7ffffff0L, "bad shape");
+  WFT_CHECK_ARG_AS(who, a->ld % 8 == 0 && a->ld >= (a->V + 7) / 8 * 8 && (((uintptr_t)a->logits) & 15) == 0, "logits rows: 16-byte aligned, ld >= V rounded up to 8");
+  WFT_CHECK_ARG_AS(who, a->max_len >= 1 && a->max_len <= a->ld_tokens, "max_len must fit the token buffer");
+  WFT_CHECK_ARG_AS(who, a->eot >= 0 && a->eot < a->V, "eot outside the vocabulary");
+  WFT_CHECK_ARG_AS(who, !a->suppress_first || a->first_len, "suppress_first needs first_len");
+  return WFT_OK;
+}
+
+static int ts_check(const wft_ts_rules* ru, int eot, int64_t V, const char* who) {
+  WFT_CHECK_ARG_AS(who, ru, "null pointer");
+  WFT_CHECK_ARG_AS(who, ru->ts_begin > eot && ru->ts_begin < V, "ts_begin must lie in (eot, V)");
+  WFT_CHECK_ARG_AS(who, ru->no_timestamps >= -1 && ru->no_timestamps < V, "no_timestamps is -1 or a column");
+  return WFT_OK;
+}
+
 extern "C" int wft_decode_pick(const wft_decode_pick_args* a, void* stream) {
-  WFT_CHECK_ARG(a && a->logits && a->tokens && a->len && a->finished && a->sum_logprob && a->unfinished, "null pointer");
-  WFT_CHECK_ARG(a->B >= 1 && a->V >= 1 && a->V <= 0x7ffffff0L, "bad shape");
-  WFT_CHECK_ARG(a->ld % 8 == 0 && a->ld >= (a->V + 7) / 8 * 8 && (((uintptr_t)a->logits) & 15) == 0, "logits rows: 16-byte aligned, ld >= V rounded up to 8");
-  WFT_CHECK_ARG(a->max_len >= 1 && a->max_len <= a->ld_tokens, "max_len must fit the token buffer");
-  WFT_CHECK_ARG(a->eot >= 0 && a->eot < a->V, "eot outside the vocabulary");
-  WFT_CHECK_ARG(!a->suppress_first || a->first_len, "suppress_first needs first_len");
-  hipLaunchKernelGGL(decode_pick_kernel, dim3((unsigned)a->B), dim3(PICK_THREADS), 0, (hipStream_t)stream, *a);
+  if (int rc = pick_check(a, __func__)) return rc;
+  hipLaunchKernelGGL(decode_pick_kernel<false>, dim3((unsigned)a->B), dim3(PICK_THREADS), 0, (hipStream_t)stream, *a, wft_ts_rules{});
+  hipLaunchKernelGGL(decode_count_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int*)a->finished, a->B, a->unfinished);
+  WFT_CHECK_LAUNCH();
+  return WFT_OK;
+}
+
+extern "C" int wft_decode_pick_ts(const wft_decode_pick_args* a, const wft_ts_rules* ru, void* stream) {
+  if (int rc = pick_check(a, __func__)) return rc;
+  if (int rc = ts_check(ru, a->eot, a->V, __func__)) return rc;
+  WFT_CHECK_ARG(a->first_len, "the timestamp rules need first_len");
+  hipLaunchKernelGGL(decode_pick_kernel<true>, dim3((unsigned)a->B), dim3(PICK_THREADS), 0, (hipStream_t)stream, *a, *ru);
   hipLaunchKernelGGL(decode_count_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int*)a->finished, a->B, a->unfinished);
   WFT_CHECK_LAUNCH();
   return WFT_OK;
@@ -663,7 +814,15 @@ extern "C" int wft_decode_pick(const wft_decode_pick_args* a, void* stream) {
 // exp(x - max), in its order; log p = (x - max) - log(sum).  A live column whose logit is -inf can never be a candidate.
 #define TOPK_MAX 9
 
-__global__ __launch_bounds__(PICK_THREADS) void decode_topk_kernel(wft_decode_topk_args a) {
+// TS: the timestamp-rule form (wft_decode_topk_ts).  Rule 5 decides which columns are live, so it must precede the candidate
+// merge: ts_decide's two passes run first (the first one reads HBM, the second the L2-resident row), then the list pass above runs
+// unchanged under the FINAL predicate — a third scan, of a row that is still L2-resident — and the log-probabilities reuse
+// ts_decide's maximum and sums.  Chosen over two register lists per thread (text / timestamp, merged by rule 5's outcome): the
+// list insertion, the merge rounds and the pop stay the code of the plain kernel and 2 x 9 more (value, column) registers are not
+// held through the scan.  Neither form has been timed (DESIGN.md §3 "Timestamp rules").
+template <bool TS>
+__global__ __launch_bounds__(PICK_THREADS) void decode_topk_kernel(wft_decode_topk_args a, wft_ts_rules ru, const long* tokens, long ld_tokens,
+                                                                   int eot) {
   __shared__ float s_v[PICK_WAVES];
   __shared__ int s_i[PICK_WAVES];
   __shared__ float s_sum[PICK_WAVES];
@@ -676,6 +835,22 @@ __global__ __launch_bounds__(PICK_THREADS) void decode_topk_kernel(wft_decode_to
   const unsigned char* m1 = a.suppress;
   const unsigned char* m2 = (a.suppress_first && a.first_len && a.len && a.len[r] == a.first_len[r]) ? a.suppress_first : nullptr;
 
+  ts_row t = {};
+  float top = 0.f, tot = 0.f;
+  auto live = [&](int col) {
+    if constexpr (TS) return ts_live(t, col);
+    else return true;
+  };
+  if constexpr (TS) {
+    __shared__ int s_ts[PICK_WAVES];
+    __shared__ float s_sum2[PICK_WAVES];
+    t = ts_row_rules(ru, tokens + r * ld_tokens, ld_tokens, a.first_len[r], a.len[r], V, eot, s_ts);
+    const ts_pass p = ts_decide(row, V, m1, m2, t.ts_begin, live, s_v, s_i, s_sum, s_sum2);
+    if (p.wins) t.text_lo = t.ts_begin;
+    top = p.m;
+    tot = p.wins ? p.ss : p.st + p.ss;
+  }
+
   float lv[TOPK_MAX];
   int li[TOPK_MAX];
 #pragma unroll
@@ -683,7 +858,7 @@ __global__ __launch_bounds__(PICK_THREADS) void decode_topk_kernel(wft_decode_to
     lv[p] = -INFINITY;
     li[p] = PICK_NONE;
   }
-  pick_scan(row, V, m1, m2, [&](float x, int col) {
+  pick_scan(row, V, m1, m2, live, [&](float x, int col) {
     if (x > lv[TOPK_MAX - 1]) {
       lv[TOPK_MAX - 1] = x;
       li[TOPK_MAX - 1] = col;
@@ -716,8 +891,10 @@ __global__ __launch_bounds__(PICK_THREADS) void decode_topk_kernel(wft_decode_to
     }
     __syncthreads();
   }
-  const float top = s_wv[0];
-  const float tot = pick_wg_sumexp(row, V, m1, m2, top, s_wi[0] != PICK_NONE, s_sum);
+  if constexpr (!TS) {
+    top = s_wv[0];
+    tot = pick_wg_sumexp(row, V, m1, m2, top, s_wi[0] != PICK_NONE, s_sum);
+  }
   if (tid < a.k) {
     const bool have = s_wi[tid] != PICK_NONE;
     a.cand_tok[r * a.k + tid] = have ? s_wi[tid] : -1;
@@ -725,13 +902,32 @@ __global__ __launch_bounds__(PICK_THREADS) void decode_topk_kernel(wft_decode_to
   }
 }
 
+static int topk_check(const wft_decode_topk_args* a, const char* who) {
+  WFT_CHECK_ARG_AS(who, a && a->logits && a->cand_tok && a->cand_logp, "null pointer");
+  WFT_CHECK_ARG_AS(who, a->rows >= 1 && a->row_step >= 1 && a->V >= 1 && a->V <= 0x7ffffff0L, "bad shape");
+  WFT_CHECK_ARG_AS(who, a->k >= 2 && a->k <= TOPK_MAX, "k = beam size + 1 must lie in 2..9");
+  WFT_CHECK_ARG_AS(who, a->ld % 8 == 0 && a->ld >= (a->V + 7) / 8 * 8 && (((uintptr_t)a->logits) & 15) == 0, "logits rows: 16-byte aligned, ld >= V rounded up to 8");
+  WFT_CHECK_ARG_AS(who, !a->suppress_first || (a->first_len && a->len), "suppress_first needs len and first_len");
+  return WFT_OK;
+}
+
 extern "C" int wft_decode_topk(const wft_decode_topk_args* a, void* stream) {
-  WFT_CHECK_ARG(a && a->logits && a->cand_tok && a->cand_logp, "null pointer");
-  WFT_CHECK_ARG(a->rows >= 1 && a->row_step >= 1 && a->V >= 1 && a->V <= 0x7ffffff0L, "bad shape");
-  WFT_CHECK_ARG(a->k >= 2 && a->k <= TOPK_MAX, "k = beam size + 1 must lie in 2..9");
-  WFT_CHECK_ARG(a->ld % 8 == 0 && a->ld >= (a->V + 7) / 8 * 8 && (((uintptr_t)a->logits) & 15) == 0, "logits rows: 16-byte aligned, ld >= V rounded up to 8");
-  WFT_CHECK_ARG(!a->suppress_first || (a->first_len && a->len), "suppress_first needs len and first_len");
-  hipLaunchKernelGGL(decode_topk_kernel, dim3((unsigned)a->rows), dim3(PICK_THREADS), 0, (hipStream_t)stream, *a);
+  if (int rc = topk_check(a, __func__)) return rc;
+  hipLaunchKernelGGL(decode_topk_kernel<false>, dim3((unsigned)a->rows), dim3(PICK_THREADS), 0, (hipStream_t)stream, *a, wft_ts_rules{},
+                     (const long*)nullptr, 0L, 0);
+  WFT_CHECK_LAUNCH();
+  return WFT_OK;
+}
+
+extern "C" int wft_decode_topk_ts(const wft_decode_topk_args* a, const wft_ts_rules* ru, const int64_t* tokens, int64_t ld_tokens, int eot,
+                                  void* stream) {
+  if (int rc = topk_check(a, __func__)) return rc;
+  WFT_CHECK_ARG(eot >= 0 && eot < a->V, "eot outside the vocabulary");
+  if (int rc = ts_check(ru, eot, a->V, __func__)) return rc;
+  WFT_CHECK_ARG(a->first_len && a->len, "the timestamp rules need len and first_len");
+  WFT_CHECK_ARG(tokens && ld_tokens >= 1, "the timestamp rules need the token rows");
+  hipLaunchKernelGGL(decode_topk_kernel<true>, dim3((unsigned)a->rows), dim3(PICK_THREADS), 0, (hipStream_t)stream, *a, *ru,
+                     (const long*)tokens, (long)ld_tokens, eot);
   WFT_CHECK_LAUNCH();
   return WFT_OK;
 }

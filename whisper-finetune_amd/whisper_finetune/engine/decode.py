@@ -2,8 +2,9 @@
 
 The greedy path of upstream's `whisper.decoding` (`DecodingTask._main_loop` with `GreedyDecoder`, `SuppressTokens`,
 `SuppressBlank`, `DecodingOptions(without_timestamps=True)`) and, in the second half of this file, its `BeamSearchDecoder` +
-`MaximumLikelihoodRanker` on a KV cache that the beams of an audio share (`BeamCache`, `beam_decode`); no tokenizer, temperature
-fallback, timestamp rules or language detection.
+`MaximumLikelihoodRanker` on a KV cache that the beams of an audio share (`BeamCache`, `beam_decode`); with `timestamp_begin=` both
+decode under upstream's `ApplyTimestampRules` (restated in include/wft.h "Timestamp rules"; the pick / top-k kernels apply them,
+`timestamp_segments` reads the result); no tokenizer, temperature fallback or language detection.
 
 Everything that changes from token to token lives in device memory (`KVCache`: len / tokens / finished / sum_logprob), so a
 step is a fixed sequence of launches whose arguments never change: LayerNorm and every projection through the existing
@@ -70,12 +71,15 @@ class _Cache:
         self.prefilled = False
         self.eot, self.max_len = 0, self.n_ctx
         self.suppress = self.suppress_first = None
+        self.ts_rules = None    # (timestamp_begin, no_timestamps or None, max_initial_timestamp_index or None), or None: no rules
 
     def is_cross(self, attn) -> bool:
         return attn in self.cross_kv
 
-    def _start(self, audios: int, prompt: torch.Tensor, prompt_len, eot: int, max_len: Optional[int], suppress, suppress_first, n_vocab: int):
-        """The checks and resets of both start()s -> (prompt width T, the prompt lengths as i32 [audios] on the host)."""
+    def _start(self, audios: int, prompt: torch.Tensor, prompt_len, eot: int, max_len: Optional[int], suppress, suppress_first, n_vocab: int,
+               ts_rules=None):
+        """The checks and resets of both start()s -> (prompt width T, the prompt lengths as i32 [audios] on the host).  ts_rules: what
+        check_ts_rules returned."""
         B, T = prompt.shape
         max_len = self.n_ctx if max_len is None else int(max_len)
         if B != audios or not 1 <= T <= self.n_ctx:
@@ -95,6 +99,7 @@ class _Cache:
         self.suppress_first = _mask(suppress_first, n_vocab, dev)
         self.prompt_T, self.prefilled = T, False
         self.eot, self.max_len = int(eot), max_len
+        self.ts_rules = ts_rules
         self.tokens.fill_(int(eot))
         self.sum_logprob.zero_()
         for key in self.cross_kv:
@@ -114,9 +119,12 @@ class KVCache(_Cache):
         self.finished = torch.zeros_like(self.len)
 
     def start(self, prompt: torch.Tensor, prompt_len: Optional[torch.Tensor], *, eot: int, max_len: Optional[int] = None,
-              suppress: Sequence[int] = (), suppress_first: Sequence[int] = (), n_vocab: int) -> None:
-        """Load the prompts (i64 [B, T], right-padded; prompt_len [B] or None = all T long) and reset the state."""
-        T, pl = self._start(self.batch, prompt, prompt_len, eot, max_len, suppress, suppress_first, n_vocab)
+              suppress: Sequence[int] = (), suppress_first: Sequence[int] = (), n_vocab: int, timestamp_begin: Optional[int] = None,
+              no_timestamps: Optional[int] = None, max_initial_timestamp_index: Optional[int] = 50) -> None:
+        """Load the prompts (i64 [B, T], right-padded; prompt_len [B] or None = all T long) and reset the state.  timestamp_begin:
+        every pick of this decode runs under the timestamp rules (check_ts_rules)."""
+        rules = check_ts_rules(n_vocab, eot, suppress, suppress_first, timestamp_begin, no_timestamps, max_initial_timestamp_index)
+        T, pl = self._start(self.batch, prompt, prompt_len, eot, max_len, suppress, suppress_first, n_vocab, rules)
         self.tokens[:, :T].copy_(prompt.to(self.tokens.device))
         self.len.copy_(pl)
         self.prompt_len.copy_(self.len)
@@ -132,6 +140,53 @@ class KVCache(_Cache):
 
     def cross_step(self, attn, q, n_head: int, scale: float) -> torch.Tensor:
         return K.attn_decode(q, self.cross_kv[attn], n_head, scale)
+
+
+def check_ts_rules(n_vocab: int, eot: int, suppress: Sequence[int], suppress_first: Sequence[int], timestamp_begin: Optional[int],
+                   no_timestamps: Optional[int] = None, max_initial_timestamp_index: Optional[int] = 50, beam_size: Optional[int] = None):
+    """The constants of the timestamp rules (include/wft.h "Timestamp rules") -> (timestamp_begin, no_timestamps or None,
+    max_initial_timestamp_index or None), or None when timestamp_begin is None (no rules: the other two are not looked at).
+    ValueError: timestamp_begin outside (eot, n_vocab); no_timestamps outside the vocabulary; a negative max_initial_timestamp_index;
+    a suppressed id that is a timestamp (the rules own those columns); and for beam search (beam_size = W) what guarantees W
+    candidates that are not `eot` at every step, so that wft_beam_update never runs out of them:
+      first step: only beam 0 counts and rule 4 leaves it the timestamps 0..max_initial — W of them must exist;
+      later steps: all W beams count and each keeps a live column that is not eot.  Last token a timestamp after a timestamp
+      (or the only sampled token): every text column is live and rule 5 cannot fire (no live timestamp) — so at least W + 1 text
+      columns must survive suppress | suppress_first | {no_timestamps}, which also covers a text token behind which no timestamp
+      is left (t = V - 1).  Last token a timestamp after text: that timestamp t itself stays live (rule 3 keeps it, rule 5 only
+      ever removes text).  Otherwise text is live unless rule 5 removes it, which needs a live timestamp to win."""
+    if timestamp_begin is None:
+        return None
+    V, tsb = int(n_vocab), int(timestamp_begin)
+    if not int(eot) < tsb < V:
+        raise ValueError(f"timestamp_begin={timestamp_begin} must lie in (eot={eot}, n_vocab={V})")
+    if no_timestamps is not None and not 0 <= int(no_timestamps) < V:
+        raise ValueError(f"no_timestamps={no_timestamps} is outside the vocabulary")
+    if max_initial_timestamp_index is not None and (isinstance(max_initial_timestamp_index, bool) or int(max_initial_timestamp_index) < 0):
+        raise ValueError(f"max_initial_timestamp_index must be None or >= 0, got {max_initial_timestamp_index!r}")
+    dead = {int(t) for t in suppress} | {int(t) for t in suppress_first}
+    if dead and max(dead) >= tsb:
+        raise ValueError(f"suppress / suppress_first hold a timestamp id (>= timestamp_begin={tsb}): the timestamp rules own those columns")
+    no_ts = None if no_timestamps is None else int(no_timestamps)
+    max_initial = None if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
+    if beam_size is not None:
+        W = int(beam_size)
+        if max_initial is not None and max_initial < W - 1:
+            raise ValueError(f"beam_size={W} needs max_initial_timestamp_index >= {W - 1}: only the timestamps 0..max_initial are live at the first step")
+        last = V - 1 if max_initial is None else min(V - 1, tsb + max_initial)
+        first_live = last - tsb + 1 - (1 if no_ts is not None and tsb <= no_ts <= last else 0)
+        if first_live < W:
+            raise ValueError(f"beam_size={W} needs {W} live timestamps at the first step, {first_live} are left")
+        text_live = tsb - len({t for t in dead | ({no_ts} if no_ts is not None else set()) if 0 <= t < tsb})
+        if text_live < W + 1:
+            raise ValueError(f"beam_size={W} needs at least {W + 1} un-suppressed text columns under the timestamp rules, {text_live} are left")
+    return (tsb, no_ts, max_initial)
+
+
+def ts_extra(ts_rules) -> tuple:
+    """What the rule constants add to a graph session's fingerprint: the captured pick / top-k launch holds them BY VALUE, so a step
+    captured under other rules (or none) must never be replayed."""
+    return (("ts_rules",) + tuple(ts_rules),) if ts_rules is not None else ()
 
 
 def _mask(ids: Sequence[int], n_vocab: int, device) -> Optional[torch.Tensor]:
@@ -164,11 +219,12 @@ def step(decoder, cache) -> torch.Tensor:
 
 
 def pick(decoder, cache: KVCache, logits: torch.Tensor, want_pick: bool = False):
-    """Greedy pick from the padded logits and the state update of every unfinished row (wft_decode_pick)."""
+    """Greedy pick from the padded logits and the state update of every unfinished row (wft_decode_pick; wft_decode_pick_ts when
+    the cache was started with timestamp rules)."""
     V = decoder.token_embedding.weight.shape[0]
     return K.decode_pick(logits, V, cache.tokens, cache.len, cache.finished, cache.sum_logprob, cache.unfinished, eot=cache.eot,
                          max_len=cache.max_len, suppress=cache.suppress, suppress_first=cache.suppress_first,
-                         first_len=cache.prompt_len, want_pick=want_pick)
+                         first_len=cache.prompt_len, want_pick=want_pick, ts_rules=cache.ts_rules)
 
 
 def _greedy_body(decoder, cache: KVCache) -> torch.Tensor:
@@ -353,6 +409,7 @@ def _decode(model, mel: torch.Tensor, start: dict, *, who: str, table, key: tupl
         sess = None
         if graph:
             sess = _session(table, model, key + (str(mel.device),), lambda: _GraphSession(dec, make_cache(dec), body, extra, who))
+            sess._extra = tuple(extra)  # (a kept session may have been captured under other timestamp rules: then it recaptures)
         cache = sess.cache if graph else make_cache(dec)
         cache.start(**start, n_vocab=model.dims.n_vocab)
         # updates until the shortest prompt reaches max_len (start() has just set len to the prompt lengths; nothing ran since)
@@ -384,8 +441,14 @@ def _decode(model, mel: torch.Tensor, start: dict, *, who: str, table, key: tupl
 @torch.no_grad()
 def greedy_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None, *, eot: int, max_len: Optional[int] = None,
                   suppress: Sequence[int] = (), suppress_first: Sequence[int] = (), sync_every: int = 8, step: str = "eager",
-                  _capture: bool = True, _stream_gemm: bool = True):
+                  timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
+                  max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True, _stream_gemm: bool = True):
     """-> (tokens i64 [B, L] — prompt included, padded with `eot` behind each row's end —, lengths i64 [B], sum_logprob f32 [B]).
+
+    timestamp_begin (default None: no rules, today's path exactly): the first timestamp id; every pick then runs under upstream's
+    timestamp rules (include/wft.h "Timestamp rules") with `no_timestamps` removed and the first timestamp at most
+    `max_initial_timestamp_index` (None: unbounded); the log-probabilities are those of the rule-filtered rows.  Argument errors
+    (check_ts_rules) are raised before any device work.  `timestamp_segments` splits the result into timed segments.
 
     A row ends with the `eot` it picked (counted in its length) or at `max_len` tokens (default n_text_ctx).  `sum_logprob` sums
     the log-probabilities of the generated tokens, the `eot` included, under the softmax of the suppressed logits.
@@ -396,6 +459,8 @@ def greedy_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=Non
     them.  The prefill and the encoder keep their kernels in both modes.  `_capture=False` / `_stream_gemm=False` switch off one
     half each (tests and the A/B bench only)."""
     _check_mode(model, "greedy_decode", step, sync_every)
+    rules = check_ts_rules(model.dims.n_vocab, eot, suppress, suppress_first, timestamp_begin, no_timestamps, max_initial_timestamp_index)
+    ts_kw = dict(timestamp_begin=timestamp_begin, no_timestamps=no_timestamps, max_initial_timestamp_index=max_initial_timestamp_index)
     B = prompt.shape[0]
 
     def readout(cache):
@@ -405,9 +470,9 @@ def greedy_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=Non
         tokens.masked_fill_(torch.arange(L, device=tokens.device)[None, :] >= lengths[:, None], cache.eot)
         return tokens, lengths, cache.sum_logprob.clone()
 
-    return _decode(model, mel, dict(prompt=prompt, prompt_len=prompt_len, eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first),
+    return _decode(model, mel, dict(prompt=prompt, prompt_len=prompt_len, eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first, **ts_kw),
                    who="greedy_decode", table=_SESSIONS, key=(int(B),), make_cache=lambda dec: KVCache(dec, B, device=mel.device),
-                   prefill=prefill, first=pick, body=_greedy_body, readout=readout, graph=step == "graph" and _capture,
+                   prefill=prefill, first=pick, body=_greedy_body, readout=readout, extra=ts_extra(rules), graph=step == "graph" and _capture,
                    stream=step == "graph" and _stream_gemm, sync_every=sync_every)
 
 
@@ -480,12 +545,14 @@ class BeamCache(_Cache):
         self.fin_n = torch.zeros(self.audios, **i32)
 
     def start(self, prompt: torch.Tensor, prompt_len: Optional[torch.Tensor], *, eot: int, max_len: Optional[int] = None,
-              suppress: Sequence[int] = (), suppress_first: Sequence[int] = (), n_vocab: int) -> None:
+              suppress: Sequence[int] = (), suppress_first: Sequence[int] = (), n_vocab: int, timestamp_begin: Optional[int] = None,
+              no_timestamps: Optional[int] = None, max_initial_timestamp_index: Optional[int] = 50) -> None:
         """Load the prompts (i64 [audios, T], right-padded; prompt_len [audios] or None) into all W rows of every audio and reset
-        the state.  The checks of KVCache.start plus the live-column count."""
+        the state.  The checks of KVCache.start plus the live-column count (under timestamp rules: check_ts_rules' beam clauses)."""
         B, W = self.audios, self.beam
         _check_live_columns(W, n_vocab, suppress, suppress_first)
-        T, pl = self._start(B, prompt, prompt_len, eot, max_len, suppress, suppress_first, n_vocab)
+        rules = check_ts_rules(n_vocab, eot, suppress, suppress_first, timestamp_begin, no_timestamps, max_initial_timestamp_index, beam_size=W)
+        T, pl = self._start(B, prompt, prompt_len, eot, max_len, suppress, suppress_first, n_vocab, rules)
         dev = self.tokens.device
         self.tokens.view(B, W, self.n_ctx)[:, :, :T].copy_(prompt.to(dev)[:, None, :])
         self.len.copy_(pl.to(dev).repeat_interleave(W))
@@ -524,11 +591,13 @@ beam_step = step
 
 
 def beam_topk(decoder, cache: BeamCache, logits: torch.Tensor, first: bool = False) -> None:
-    """cand_tok / cand_logp <- the W + 1 best continuations per logits row (wft_decode_topk).  first: `logits` are the prefill's,
-    one row per audio, and fill the candidate row of beam 0."""
+    """cand_tok / cand_logp <- the W + 1 best continuations per logits row (wft_decode_topk; wft_decode_topk_ts when the cache was
+    started with timestamp rules — the kernel reads each hypothesis' sampled tokens from `tokens`, whose rows wft_beam_update
+    permutes with the beams).  first: `logits` are the prefill's, one row per audio, and fill the candidate row of beam 0."""
     V = decoder.token_embedding.weight.shape[0]
     K.decode_topk(logits, V, cache.cand_tok, cache.cand_logp, lens=cache.len, first_len=cache.first_len, suppress=cache.suppress,
-                  suppress_first=cache.suppress_first, row_step=cache.beam if first else 1)
+                  suppress_first=cache.suppress_first, row_step=cache.beam if first else 1, ts_rules=cache.ts_rules, tokens=cache.tokens,
+                  eot=cache.eot)
 
 
 def beam_update(cache: BeamCache, first: bool = False) -> None:
@@ -593,13 +662,16 @@ def beam_finalize(cache: BeamCache, length_penalty: Optional[float] = None):
 def beam_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None, *, beam_size: int, patience: float = 1.0,
                 length_penalty: Optional[float] = None, eot: int, max_len: Optional[int] = None, suppress: Sequence[int] = (),
                 suppress_first: Sequence[int] = (), sync_every: int = 8, step: str = "eager", return_all: bool = False,
-                _capture: bool = True, _stream_gemm: bool = True):
+                timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
+                max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True, _stream_gemm: bool = True):
     """Beam search -> (tokens i64 [B, L], lengths i64 [B], sum_logprob f32 [B]) of the winning hypothesis per audio, in greedy_decode's
     layout: prompt included, the `eot` that ended the hypothesis included (one that ran into `max_len` has none), padded with `eot`.
     return_all: a fourth value, per audio the list of (tokens, sum_logprob, score) of all its entries, best score first (stable).
 
     beam_size 1..8; an audio ends once round(beam_size * patience) sequences have finished or at `max_len`; the winner maximises
     sum_logprob / n over the generated tokens (n without the final eot), or sum_logprob / ((5 + n) / 6) ** length_penalty.
+    timestamp_begin / no_timestamps / max_initial_timestamp_index: as greedy_decode (default: no rules), every hypothesis under
+    its own history; beam search needs max_initial_timestamp_index >= beam_size - 1 or None (check_ts_rules says why).
     Argument errors are raised before any device work.  `step`, `sync_every`, `_capture`, `_stream_gemm`: as greedy_decode; the
     captured beam steps live in their own sessions (`beam_sessions`), freed by `release_graphs` too."""
     C = beam_candidates(beam_size, patience)
@@ -607,6 +679,9 @@ def beam_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None,
         raise ValueError(f"length_penalty must be None or a number, got {length_penalty!r}")
     _check_live_columns(beam_size, model.dims.n_vocab, suppress, suppress_first)
     _check_mode(model, "beam_decode", step, sync_every)
+    rules = check_ts_rules(model.dims.n_vocab, eot, suppress, suppress_first, timestamp_begin, no_timestamps, max_initial_timestamp_index,
+                           beam_size=beam_size)
+    ts_kw = dict(timestamp_begin=timestamp_begin, no_timestamps=no_timestamps, max_initial_timestamp_index=max_initial_timestamp_index)
     B = prompt.shape[0]
 
     def readout(cache):
@@ -623,8 +698,41 @@ def beam_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None,
             res += ([sorted(entries, key=lambda e: -e[2]) for entries, _ in ranked],)
         return res
 
-    return _decode(model, mel, dict(prompt=prompt, prompt_len=prompt_len, eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first),
+    return _decode(model, mel, dict(prompt=prompt, prompt_len=prompt_len, eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first, **ts_kw),
                    who="beam_decode", table=_BEAM_SESSIONS, key=(int(B), int(beam_size), int(C)),
                    make_cache=lambda dec: BeamCache(dec, B, beam_size, C, device=mel.device), prefill=beam_prefill, first=_beam_first,
-                   body=_beam_body, readout=readout, extra=(("beam", beam_size, C),), graph=step == "graph" and _capture,
+                   body=_beam_body, readout=readout, extra=(("beam", beam_size, C),) + ts_extra(rules), graph=step == "graph" and _capture,
                    stream=step == "graph" and _stream_gemm, sync_every=sync_every)
+
+
+# ============================================================================= timed segments
+def timestamp_segments(tokens, prompt_len, lengths, timestamp_begin: int, eot: int, time_precision: float = 0.02):
+    """The decoded rows of greedy_decode / beam_decode under timestamp rules -> per row [(start_s, end_s, [text token ids])].
+
+    The sampled tokens of a row are tokens[r][prompt_len[r]:lengths[r]], read up to the first `eot`.  A timestamp opens a segment,
+    the next one closes it; the timestamp right behind a closing one opens the next segment — the split at consecutive timestamp
+    pairs that upstream's `transcribe` makes.  Seconds = (id - timestamp_begin) * time_precision.  Text that is still open at the
+    end of the row (a row cut at max_len, or an eot inside a segment) ends at None, text before any opening timestamp starts at
+    None; a lone opening timestamp at the very end gives no segment; a pair with nothing in between gives one with no tokens.
+    Pure Python on the host, no tokenizer: tokens / prompt_len / lengths may be tensors or nested lists."""
+    as_list = lambda v: v.tolist() if hasattr(v, "tolist") else list(v)
+    rows, plen, lens = as_list(tokens), as_list(prompt_len), as_list(lengths)
+    tsb = int(timestamp_begin)
+    out = []
+    for row, p, n in zip(rows, plen, lens):
+        segs, start, is_open, text = [], None, False, []
+        for t in row[int(p):int(n)]:
+            t = int(t)
+            if t == int(eot):
+                break
+            if t < tsb:
+                text.append(t)
+            elif is_open or text:  # closes the open segment (or text that no timestamp opened)
+                segs.append((start, (t - tsb) * time_precision, text))
+                start, is_open, text = None, False, []
+            else:
+                start, is_open = (t - tsb) * time_precision, True
+        if text:
+            segs.append((start, None, text))
+        out.append(segs)
+    return out

@@ -669,10 +669,21 @@ def _set_suppress(a, V: int, suppress, suppress_first) -> None:
             setattr(a, name, m.data_ptr())
 
 
+def _ts_rules(ts_rules):
+    """(ts_begin, no_timestamps or None, max_initial or None) -> TsRules (None / a negative value: -1, "none")."""
+    ts_begin, no_ts, max_initial = ts_rules
+    ru = L.TsRules()
+    ru.ts_begin = int(ts_begin)
+    ru.no_timestamps = -1 if no_ts is None else int(no_ts)
+    ru.max_initial = -1 if max_initial is None else int(max_initial)
+    return ru
+
+
 def decode_pick(logits, V: int, tokens, lens, finished, sum_logprob, unfinished, *, eot: int, max_len: int, suppress=None,
-                suppress_first=None, first_len=None, want_pick: bool = False):
+                suppress_first=None, first_len=None, want_pick: bool = False, ts_rules=None):
     """Greedy pick + state update (wft_decode_pick; include/wft.h).  logits bf16 [B, ld >= V]; suppress / suppress_first u8 [V] or None.
-    want_pick -> (pick i64 [B], logprob f32 [B]) as computed for EVERY row, finished or not."""
+    want_pick -> (pick i64 [B], logprob f32 [B]) as computed for EVERY row, finished or not.
+    ts_rules = (ts_begin, no_timestamps or None, max_initial or None): the pick under the timestamp rules (wft_decode_pick_ts)."""
     _chk(logits, BF16, "logits"); _chk(tokens, torch.int64, "tokens"); _chk(sum_logprob, F32, "sum_logprob")
     B = logits.shape[0]
     assert logits.dim() == 2 and logits.stride(1) == 1 and tokens.dim() == 2 and tokens.stride(1) == 1 and tokens.shape[0] == B
@@ -691,7 +702,11 @@ def decode_pick(logits, V: int, tokens, lens, finished, sum_logprob, unfinished,
         lp = torch.empty(B, dtype=F32, device=logits.device)
         a.pick_out, a.logprob_out = pick.data_ptr(), lp.data_ptr()
     a.B, a.eot, a.max_len = B, int(eot), int(max_len)
-    L.check(L.load().wft_decode_pick(C.byref(a), L.stream_ptr()), "wft_decode_pick")
+    if ts_rules is not None:
+        ru = _ts_rules(ts_rules)
+        L.check(L.load().wft_decode_pick_ts(C.byref(a), C.byref(ru), L.stream_ptr()), "wft_decode_pick_ts")
+    else:
+        L.check(L.load().wft_decode_pick(C.byref(a), L.stream_ptr()), "wft_decode_pick")
     return pick, lp
 
 
@@ -718,10 +733,13 @@ def attn_decode_beam(q, cache, n_head: int, scale: float, *, new_kv=None, lens=N
     return _attn_decode_call(a, "wft_attn_decode_beam", q, cache, n_head, scale, new_kv, lens, q_prescaled, out, _args_only, group=int(group))
 
 
-def decode_topk(logits, V: int, cand_tok, cand_logp, *, lens=None, first_len=None, suppress=None, suppress_first=None, row_step: int = 1):
+def decode_topk(logits, V: int, cand_tok, cand_logp, *, lens=None, first_len=None, suppress=None, suppress_first=None, row_step: int = 1,
+                ts_rules=None, tokens=None, eot: Optional[int] = None):
     """The k best continuations per logits row (wft_decode_topk).  logits bf16 [rows, ld >= V]; logits row i belongs to state row
     i * row_step of lens / first_len / cand_tok i32 [R, k] / cand_logp f32 [R, k], which receive (token, log-probability) in
-    descending order, ties to the lower token."""
+    descending order, ties to the lower token.
+    ts_rules = (ts_begin, no_timestamps or None, max_initial or None) with tokens i64 [R, n_ctx] and eot: the candidates under the
+    timestamp rules (wft_decode_topk_ts)."""
     _chk(logits, BF16, "logits"); _chk(cand_tok, torch.int32, "cand_tok"); _chk(cand_logp, F32, "cand_logp")
     rows = logits.shape[0]
     if logits.dim() != 2 or logits.stride(1) != 1 or cand_tok.dim() != 2 or cand_tok.shape != cand_logp.shape or not cand_tok.is_contiguous() \
@@ -739,6 +757,16 @@ def decode_topk(logits, V: int, cand_tok, cand_logp, *, lens=None, first_len=Non
         a.first_len = first_len.data_ptr()
     a.cand_tok, a.cand_logp = cand_tok.data_ptr(), cand_logp.data_ptr()
     a.rows, a.row_step, a.k = rows, int(row_step), k
+    if ts_rules is not None:
+        if tokens is None or eot is None:
+            raise ValueError("decode_topk: the timestamp rules need tokens and eot")
+        _chk(tokens, torch.int64, "tokens")
+        if tokens.dim() != 2 or tokens.shape[0] != R or not tokens.is_contiguous():
+            raise ValueError(f"decode_topk: tokens must be contiguous i64 [{R}, n_ctx]")
+        ru = _ts_rules(ts_rules)
+        L.check(L.load().wft_decode_topk_ts(C.byref(a), C.byref(ru), tokens.data_ptr(), tokens.shape[1], int(eot), L.stream_ptr()),
+                "wft_decode_topk_ts")
+        return
     L.check(L.load().wft_decode_topk(C.byref(a), L.stream_ptr()), "wft_decode_topk")
 
 

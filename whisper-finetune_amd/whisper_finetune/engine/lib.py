@@ -128,6 +128,12 @@ class DecodeTopkArgs(C.Structure):
     ]
 
 
+class TsRules(C.Structure):
+    """Mirror of wft_ts_rules (include/wft.h "Timestamp rules"): the constants of upstream's ApplyTimestampRules."""
+
+    _fields_ = [("ts_begin", C.c_int), ("no_timestamps", C.c_int), ("max_initial", C.c_int)]
+
+
 class BeamUpdateArgs(C.Structure):
     """Mirror of wft_beam_update_args (include/wft.h): one beam-search step per audio on the device-side state."""
 
@@ -196,6 +202,8 @@ SIGNATURES = {
     "wft_attn_decode_beam_bf16": [C.POINTER(AttnDecodeBeamArgs), c_vp],
     "wft_attn_decode_beam_workspace_bytes": [C.POINTER(AttnDecodeBeamArgs)],
     "wft_decode_topk": [C.POINTER(DecodeTopkArgs), c_vp],
+    "wft_decode_pick_ts": [C.POINTER(DecodePickArgs), C.POINTER(TsRules), c_vp],
+    "wft_decode_topk_ts": [C.POINTER(DecodeTopkArgs), C.POINTER(TsRules), c_vp, c_i64, C.c_int, c_vp],
     "wft_beam_update": [C.POINTER(BeamUpdateArgs), c_vp],
     "wft_embed_fwd": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_int, c_i64, c_vp],
     "wft_embed_bwd": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_int, c_i64, c_vp],

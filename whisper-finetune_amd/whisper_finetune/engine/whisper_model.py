@@ -460,7 +460,8 @@ class Whisper(nn.Module):
         return self.decoder(tokens, audio_features)
 
     def greedy_decode(self, mel: Tensor, prompt: Tensor, prompt_len=None, *, eot: int, max_len: Optional[int] = None,
-                      suppress=(), suppress_first=(), sync_every: int = 8, step: str = "eager", _capture: bool = True,
+                      suppress=(), suppress_first=(), sync_every: int = 8, step: str = "eager", timestamp_begin: Optional[int] = None,
+                      no_timestamps: Optional[int] = None, max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True,
                       _stream_gemm: bool = True):
         """KV-cached greedy decoding, token ids in and out (engine/decode.py; upstream: whisper.decoding's greedy path with
         DecodingOptions(without_timestamps=True)).  mel f32 [B, n_mels, 2 * n_audio_ctx]; prompt i64 [B, T] right-padded, prompt_len [B]
@@ -468,21 +469,28 @@ class Whisper(nn.Module):
         eval() semantics, no gradients; the host looks at the unfinished-row counter every `sync_every` steps only.
         step="graph": the cached steps run on the weight-streaming small-M GEMMs (csrc/gemm_stream.hip) and are replayed from one
         captured HIP graph per (batch, device) — engine/decode.py; `decode.release_graphs(model)` frees what that pins.  "eager"
-        (default): every step launch by launch on the kernels of the prefill.  (`_capture` / `_stream_gemm`: decode.greedy_decode's two private A/B keywords.)"""
+        (default): every step launch by launch on the kernels of the prefill.  (`_capture` / `_stream_gemm`: decode.greedy_decode's two private A/B keywords.)
+        timestamp_begin (None: off): decode under upstream's timestamp rules, applied inside the pick kernel (include/wft.h
+        "Timestamp rules"); no_timestamps / max_initial_timestamp_index: that column is removed / the first timestamp is at most
+        this index.  `decode.timestamp_segments` turns the result into timed segments."""
         return _decode.greedy_decode(self, mel, prompt, prompt_len, eot=eot, max_len=max_len, suppress=suppress,
-                                     suppress_first=suppress_first, sync_every=sync_every, step=step,
+                                     suppress_first=suppress_first, sync_every=sync_every, step=step, timestamp_begin=timestamp_begin,
+                                     no_timestamps=no_timestamps, max_initial_timestamp_index=max_initial_timestamp_index,
                                      _capture=_capture, _stream_gemm=_stream_gemm)
 
     def beam_decode(self, mel: Tensor, prompt: Tensor, prompt_len=None, *, beam_size: int, patience: float = 1.0, length_penalty=None,
                     eot: int, max_len: Optional[int] = None, suppress=(), suppress_first=(), sync_every: int = 8, step: str = "eager",
-                    return_all: bool = False, _capture: bool = True, _stream_gemm: bool = True):
+                    return_all: bool = False, timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
+                    max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True, _stream_gemm: bool = True):
         """KV-cached beam search (engine/decode.py beam_decode; upstream: whisper.decoding's BeamSearchDecoder + MaximumLikelihoodRanker
         with DecodingOptions(without_timestamps=True), restated there — parity with the upstream binary is unpinned).  Arguments and
         result layout as greedy_decode, for the winning hypothesis of every audio; beam_size 1..8; the beams of an audio share its
-        cross keys / values and no self-attention key is ever copied.  return_all adds every audio's ranked hypotheses."""
+        cross keys / values and no self-attention key is ever copied.  return_all adds every audio's ranked hypotheses.
+        timestamp_begin / no_timestamps / max_initial_timestamp_index: as greedy_decode, applied inside the top-k kernel."""
         return _decode.beam_decode(self, mel, prompt, prompt_len, beam_size=beam_size, patience=patience, length_penalty=length_penalty,
                                    eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first, sync_every=sync_every,
-                                   step=step, return_all=return_all, _capture=_capture, _stream_gemm=_stream_gemm)
+                                   step=step, return_all=return_all, timestamp_begin=timestamp_begin, no_timestamps=no_timestamps,
+                                   max_initial_timestamp_index=max_initial_timestamp_index, _capture=_capture, _stream_gemm=_stream_gemm)
 
     def forward(self, mel: Tensor, tokens: Tensor, targets: Optional[Tensor] = None, label_smoothing: float = 0.0) -> Tensor:
         """logits f32 [B, S, V] — or, when `targets` is given (engine extension used by train_step, also

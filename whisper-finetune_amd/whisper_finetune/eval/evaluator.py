@@ -40,7 +40,7 @@ def _batch_token_stats(model, x, y_in, y_out):
     return None
 
 
-def _greedy_predictions(model, tokenizer, x, y_in, step: str = "eager", beam: dict = None) -> List[List[int]]:
+def _greedy_predictions(model, tokenizer, x, y_in, step: str = "eager", beam: dict = None, timestamps: bool = False) -> List[List[int]]:
     """t_config["wft_eval_decode"] = "greedy": every utterance's predicted ids from KV-cached greedy decoding
     (Whisper.greedy_decode) instead of the teacher-forced argmax.  The decoding prefix of a row is its y_in up to and including
     the start-of-transcript sequence; every special token but eot is suppressed (upstream's notimestamps decoding plus its
@@ -48,14 +48,18 @@ def _greedy_predictions(model, tokenizer, x, y_in, step: str = "eager", beam: di
     row's first token (upstream's SuppressBlank); at most n_text_ctx // 2 new tokens (upstream's sample_len).
     `step` is t_config["wft_eval_decode_step"]: "graph" = the captured step on the weight-streaming GEMMs (engine/decode.py).
     `beam` = {"beam_size", "patience"} (t_config["wft_eval_decode"] = "beam_search"): the same prefix, suppression and length rules
-    through Whisper.beam_decode, the winning hypothesis of every utterance."""
+    through Whisper.beam_decode, the winning hypothesis of every utterance.
+    `timestamps` (t_config["wft_eval_decode_timestamps"]): decode under upstream's timestamp rules, its command line's default mode —
+    the prefix stops behind the task token (a `<|notimestamps|>` in y_in is not copied), the timestamp ids stay out of the
+    suppress list and `timestamp_begin` / `no_timestamps` come from the tokenizer (max_initial_timestamp_index: the decoder's
+    default, upstream's 1 s).  The returned ids still hold the timestamps; the caller strips them before WER / CER."""
     if beam is not None and not hasattr(model, "beam_decode"):
         raise RuntimeError('wft_eval_decode: "beam_search" needs a model with beam_decode (the engine\'s Whisper)')
     if beam is None and not hasattr(model, "greedy_decode"):
         raise RuntimeError('wft_eval_decode: "greedy" needs a model with greedy_decode (the engine\'s Whisper)')
     eot = int(tokenizer.eot)
     rows = y_in.cpu().tolist()
-    plen = [decode_prefix_len(r, int(tokenizer.sot), int(tokenizer.no_timestamps)) for r in rows]
+    plen = [decode_prefix_len(r, int(tokenizer.sot), int(tokenizer.no_timestamps), with_timestamps=timestamps) for r in rows]
     width = max(plen)
     prompt = torch.full((len(rows), width), eot, dtype=torch.int64)
     for i, (r, n) in enumerate(zip(rows, plen)):
@@ -65,6 +69,10 @@ def _greedy_predictions(model, tokenizer, x, y_in, step: str = "eager", beam: di
     n_ctx = getattr(getattr(model, "dims", None), "n_text_ctx", 448)
     kw = dict(eot=eot, max_len=min(n_ctx, width + n_ctx // 2), suppress=suppress, suppress_first=[eot] + blank,
               **({} if step == "eager" else {"step": step}))
+    if timestamps:
+        ts_begin = int(tokenizer.timestamp_begin)
+        kw["suppress"] = [t for t in suppress if t < ts_begin]
+        kw.update(timestamp_begin=ts_begin, no_timestamps=int(tokenizer.no_timestamps))
     if beam is None:
         tokens, lengths, _ = model.greedy_decode(x, prompt.to(x.device), torch.tensor(plen), **kw)
     else:
@@ -111,6 +119,13 @@ def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict
     if decode_step not in (None, "eager", "graph"):
         raise ValueError(f'wft_eval_decode_step: "eager" (the default) or "graph", got {decode_step!r}')
     decode_step = decode_step or "eager"
+    decode_ts = t_config.get("wft_eval_decode_timestamps", False)
+    if not isinstance(decode_ts, bool):
+        raise ValueError(f"wft_eval_decode_timestamps: true or false, got {decode_ts!r}")
+    if decode_ts and decode_mode is None:
+        raise ValueError('wft_eval_decode_timestamps: true needs wft_eval_decode: "greedy" or "beam_search" (the teacher-forced argmax has no timestamp rules)')
+    if decode_ts:
+        ts_begin = int(tokenizer.timestamp_begin)
 
     for x, y_in, y_out in dataloader:
         x = x.to(device, non_blocking=True)
@@ -124,7 +139,11 @@ def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict
         y_host = y_out.cpu().numpy()
         pred_host = fused[0] if fused is not None else pred.cpu().numpy()
         # prediction TEXT from autoregressive decoding when asked for; NLL / entropy / ECE below stay teacher-forced
-        decoded = _greedy_predictions(model, tokenizer, x, y_in, decode_step, beam) if decode_mode is not None else None
+        decoded = None
+        if decode_mode is not None:
+            decoded = _greedy_predictions(model, tokenizer, x, y_in, decode_step, beam, **({"timestamps": True} if decode_ts else {}))
+            if decode_ts:  # the timestamps go the way of the other specials before WER / CER
+                decoded = [[t for t in row if t < ts_begin] for row in decoded]
         for i in range(y_host.shape[0]):
             pred_ids = pred_host[i].tolist() if decoded is None else decoded[i]
             pred_tokens = [t for t in pred_ids if t not in specials and t != -100]

@@ -37,16 +37,18 @@ def normalize_text(text: str, char_vocab: Set[str], char_lookup: Dict[str, str],
     return _SPACES.sub(" ", text).strip()
 
 
-def decode_prefix_len(y_in: Sequence[int], sot: int, no_timestamps: int) -> int:
+def decode_prefix_len(y_in: Sequence[int], sot: int, no_timestamps: int, with_timestamps: bool = False) -> int:
     """Length of the decoding prefix of one teacher-forcing input row: everything up to and including its start-of-transcript
     sequence — an optional prompt, then `sot`, language, task, and `no_timestamps` when it follows (a `no_speech` marker is not
-    part of it).  The writer it agrees with: data/data_loader.py AudioDataset._get_special_tokens (prompt + specials + text)."""
+    part of it).  The writer it agrees with: data/data_loader.py AudioDataset._get_special_tokens (prompt + specials + text).
+    with_timestamps (decoding under the timestamp rules): the prefix stops behind the task token, a `no_timestamps` that follows
+    is not part of it."""
     y = [int(t) for t in y_in]
     if sot not in y:
         raise ValueError("no start-of-transcript token in the decoder input")
     n = y.index(sot) + 3  # sot, <|language|>, <|task|>: a prompt holds text and sot_prev only, so the first sot is THE sot
     if n > len(y):
         raise ValueError("the decoder input ends inside its start-of-transcript sequence")
-    if n < len(y) and y[n] == no_timestamps:
+    if not with_timestamps and n < len(y) and y[n] == no_timestamps:
         n += 1
     return n
