@@ -269,22 +269,28 @@ typedef struct {
   int launch_mode; int variant;
 } wft_gemm_args;
 int wft_gemm_nt_bf16(const wft_gemm_args* args, void* stream);
-/* Which kernel wft_gemm_nt_bf16 dispatches these arguments to: 4 (gemm_nt4w_kernel: 256x256 tiles, four waves with 128x128
- * accumulators each), 256 (gemm_nt256_kernel, the 8-wave ping-pong 256x256 kernel) or 128 (gemm_nt_kernel).  Pure host
- * function (used by bench.py to attribute HIP-event timings to the kernel names rocprofv3 reports).        */
+/* The queries below and wft_gemm_nt_bf16 itself read ONE plan of the call (csrc/gemm.hip nt_plan: kernel, grid, K splits,
+ * workspace), so a query answers what the launcher will do with the same arguments; wft_gemm_tn_* likewise (tn_plan).  All pure
+ * host functions: no device call, nothing launched.
+ * Which kernel wft_gemm_nt_bf16 dispatches these arguments to: 4 (gemm_nt4w_kernel: 256x256 tiles, four waves with 128x128
+ * accumulators each), 256 (gemm_nt256_kernel, the 8-wave ping-pong 256x256 kernel) or 128 (gemm_nt_kernel and its rank-r form;
+ * used by bench.py to attribute HIP-event timings to the kernel names rocprofv3 reports).        */
 int wft_gemm_nt_variant(const wft_gemm_args* args);
-/* 1 if wft_gemm_tn_bf16 takes these arguments' tn_seg_* fields (a 256x256 weight-gradient path, f32 C, no rank-r forms, a
- * well-formed segment list), 0 if the caller has to use C and copy.  Pure host function.                                    */
+/* 1 if wft_gemm_tn_bf16 takes these arguments' tn_seg_* fields (the plan puts the call on a 256x256 kernel, and the segment
+ * list is well formed), 0 if the caller has to use C and copy.                                                              */
 int wft_gemm_tn_segments_ok(const wft_gemm_args* args);
+/* Bytes of `workspace` with which the plan forms `colsum` in the GEMM's epilogue (wft_gemm_args.colsum above); 0: it runs
+ * wft_colsum_bf16 over C after the GEMM whatever is granted.                                                                */
 int64_t wft_gemm_nt_colsum_workspace_bytes(const wft_gemm_args* args);
 /* Split-K form of the 128-tile kernel (round 6): bytes of fp32 partial tiles [nsplit][M][N] if a PLAIN bf16 product (batch 1, no bias /
  * residual / epilogue / colsum) has so few output tiles and so deep a K that the library would split K over the idle CUs when given
  * `workspace` of at least this size (the tied-embedding backward-data product of a short decoder batch, dX[B*S, d] = dlogits[B*S, V] E[V, d],
  * whisper.model.TextDecoder.forward's logits matmul reached from model_utils.py:83-84: 1 024 x 512 x 51 968 runs on 32 of 256 CUs
- * unsplit).  0: the call is not split.  Partials are summed in split order: bitwise reproducible.  Pure host function.          */
+ * unsplit).  0: the plan does not split the call.  Partials are summed in split order: bitwise reproducible.                    */
 int64_t wft_gemm_nt_splitk_workspace_bytes(const wft_gemm_args* args);
 /* Size of the one-byte gelu' buffer of WFT_EPI_GELU_GRAD8 / WFT_EPI_MUL_AUX8 for these arguments, or 0 if the call would not be
- * served in that form (not a gemm_nt4w_kernel problem).  Pure host function.                                                */
+ * served in that form (the plan does not put it on gemm_nt4w_kernel; MUL_AUX8 takes no bias): wft_gemm_nt_bf16 then refuses
+ * it with WFT_ERR_UNSUPPORTED before any device call.                                                                       */
 int64_t wft_gemm_nt_aux8_bytes(const wft_gemm_args* args);
 /* Weight-streaming form of the same product for the projections of a KV-cached decoding step (csrc/gemm_stream.hip; whisper.decoding's
  * per-token decoder forward, M = batch): K is split over the whole chip as a function of (N, K) and the CU count only — never of M, so row m
@@ -307,8 +313,8 @@ int64_t wft_gemm_nt_stream_workspace_bytes(const wft_gemm_args* args);
  *  batch > 1 sums over the batch as extra reduction (conv weight grads).     */
 int wft_gemm_tn_bf16(const wft_gemm_args* args, void* stream);
 /* Which kernel wft_gemm_tn_bf16 dispatches these arguments to: 4 (gemm_tn4w_kernel, one wave per SIMD), 256 (gemm_tn256_kernel, the
- * 8-wave ping-pong 256x256 kernel) or 128 (the 128-tile kernel and its rank-r form).  Pure host function from the launcher's own
- * predicates, workspace fields included (a split-K plan without its workspace runs on the 8-wave kernel); tests assert the dispatch. */
+ * 8-wave ping-pong 256x256 kernel) or 128 (the 128-tile kernel and its rank-r form).  Read from the launcher's plan, workspace
+ * fields included (a split-K plan without its workspace runs on the 8-wave kernel); tests assert the dispatch.               */
 int wft_gemm_tn_variant(const wft_gemm_args* args);
 /* Two independent rank-r products (p_valid > 0) in ONE launch of the load-stream kernels — the backward of an adapted Linear
  * group in the reference's parametrization (src/whisper_finetune/model/lora.py:30-71 via minLoRA; loss.backward() at
@@ -318,6 +324,7 @@ int wft_gemm_tn_variant(const wft_gemm_args* args);
  * (wft_gemm_tn_workspace_bytes each); its two split-K reduces (column scale / block layout included) are one launch too.   */
 int wft_gemm_nt_rank_pair_bf16(const wft_gemm_args* args0, const wft_gemm_args* args1, void* stream);
 int wft_gemm_tn_rank_pair_bf16(const wft_gemm_args* args0, const wft_gemm_args* args1, void* stream);
+/* Bytes of `workspace` the plan of wft_gemm_tn_bf16 wants for these arguments (split-K partial tiles; 0: none).              */
 int64_t wft_gemm_tn_workspace_bytes(const wft_gemm_args* args);
 
 /* -------------------------------------------------------------- Attention */

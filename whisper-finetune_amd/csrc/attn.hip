@@ -2323,29 +2323,42 @@ extern "C" int64_t wft_attn_bwd_colsum_workspace_bytes(const wft_attn_args* a) {
   return ((int64_t)a->B * ((a->Tq + 31) / 32) + (int64_t)a->B * ((a->Tk + 31) / 32) + 2 * ATT_CS_CHUNKS) * a->H * 64 * (int64_t)sizeof(float);
 }
 
-// Which dK/dV kernel: 0 (default) the one-wave-per-SIMD kernel where it applies, 1 always the 8-wave kernel.  WFT_DKDV_VARIANT=8w|4w
-// sets the start value; returns the previous one (a negative argument only reads).
-// persistent dK/dV launches (one workgroup per CU) or one item per workgroup: WFT_ATTN_PERSISTENT=0 at load time (engine/lib.py sets it
-// in a multi-GPU job), wft_attn_set_persistent() inside a process (bench.py's ddp_mode_1gpu block)
+// Which dK/dV kernel: 0 (default) the one-wave-per-SIMD kernel where it applies, 1 always the 8-wave kernel: WFT_DKDV_VARIANT=8w|4w at
+// load time (timing builds); per call: wft_attn_args.variant bit 4.
+// persistent launches (one workgroup per CU) or one item per workgroup: WFT_ATTN_PERSISTENT=0 at load time (engine/lib.py sets it
+// in a multi-GPU job); per call: wft_attn_args.launch_mode = 1 (bench.py's ddp_mode_1gpu block)
 static int g_attn_persistent = [] { const char* e = getenv("WFT_ATTN_PERSISTENT"); return (e && e[0] == '0') ? 0 : 1; }();
 static int g_dkdv_variant = [] { const char* e = wft_dev_getenv("WFT_DKDV_VARIANT"); return (e && !strcmp(e, "8w")) ? 1 : 0; }();
-// the same for the dQ kernel (attn_bwd_dq4w_kernel): WFT_DQ_VARIANT=8w|4w
+// the same for the dQ kernel (attn_bwd_dq4w_kernel): WFT_DQ_VARIANT=8w|4w, wft_attn_args.variant bit 2
 static int g_dq_variant = [] { const char* e = wft_dev_getenv("WFT_DQ_VARIANT"); return (e && !strcmp(e, "8w")) ? 1 : 0; }();
-// non-causal calls with enough queries to fill 256-query workgroups; byte offsets must fit the asm block's 32-bit buffer addressing
-static bool wft_dq4w_eligible(const wft_attn_args* a) {
-  static const int min_tq = [] { const char* e = wft_dev_getenv("WFT_DQ4W_MIN_TQ"); return e ? atoi(e) : 512; }();
-  if (g_dq_variant != 0 || (a->variant & 2) || a->causal || a->Tq < min_tq) return false;
+// byte offsets fit the 32-bit buffer addressing of the one-wave-per-SIMD kernels' asm blocks
+// (+ 256: the last workgroup's lanes address rows up to 255 past the end; the descriptors return zeros for them)
+static bool attn_offsets_fit32(const wft_attn_args* a) {
   const long lim = 0x7fffffffL;
   return (long)(a->Tq + 256) * a->ldq * 2 < lim && (long)(a->Tq + 256) * a->lddo * 2 < lim && (long)(a->Tk + 256) * a->ldk * 2 < lim &&
          (long)(a->Tk + 256) * a->ldv * 2 < lim;
 }
-// non-causal sweeps over at least two 64-query tiles whose byte offsets fit the 32-bit buffer addressing of the asm block
+// non-causal calls with enough queries to fill 256-query workgroups
+static bool wft_dq4w_eligible(const wft_attn_args* a) {
+  static const int min_tq = [] { const char* e = wft_dev_getenv("WFT_DQ4W_MIN_TQ"); return e ? atoi(e) : 512; }();
+  return g_dq_variant == 0 && !(a->variant & 2) && !a->causal && a->Tq >= min_tq && attn_offsets_fit32(a);
+}
+// non-causal sweeps over at least two 64-query tiles
 static bool wft_dkdv4w_eligible(const wft_attn_args* a) {
-  if (g_dkdv_variant != 0 || (a->variant & 4) || a->causal || a->Tq < 128) return false;
-  const long lim = 0x7fffffffL;
-  // (+ 256: the last workgroup's lanes address rows up to 255 past the end; the descriptors return zeros for them)
-  return (long)(a->Tq + 256) * a->ldq * 2 < lim && (long)(a->Tq + 256) * a->lddo * 2 < lim && (long)(a->Tk + 256) * a->ldk * 2 < lim &&
-         (long)(a->Tk + 256) * a->ldv * 2 < lim;
+  return g_dkdv_variant == 0 && !(a->variant & 4) && !a->causal && a->Tq >= 128 && attn_offsets_fit32(a);
+}
+// grid of a persistent backward kernel: one workgroup per CU walks the (batch, head, 256-row block) items (wgs_env > 0 overrides:
+// A/B runs; >= the number of items = one item per workgroup).
+// WFT_ATTN_PERSISTENT=0 (set by engine/lib.py in a multi-GPU job, like WFT_NT256_PERSISTENT) or launch_mode = 1: one item per
+// workgroup — RCCL's collective kernels hold CUs during the backward pass, and a static walk would leave those CUs' share of the
+// items for a second round; the hardware dispatcher balances single-item workgroups (measured equal on one GPU: 732 vs 735 us)
+static dim3 attn_persistent_grid(const wft_attn_args* a, int rows, int wgs_env) {
+  const bool persistent = g_attn_persistent != 0 && a->launch_mode != 1;
+  const long items = (long)((rows + 255) / 256) * a->H * a->B;
+  long wgs = wgs_env > 0 ? wgs_env : (persistent ? wft_num_cus() : items);
+  if (wgs > items) wgs = items;
+  if (((long)a->H * a->B) % 8 == 0 && wgs >= 8) wgs -= wgs % 8;  // XCD mode needs the same number of workgroups on every XCD
+  return dim3((unsigned)wgs);
 }
 
 // Which kernel serves these arguments (pure host function; bench.py / tests attribute timings and assert the dispatch):
@@ -2379,71 +2392,24 @@ extern "C" int wft_attn_bwd_bf16(const wft_attn_args* a, void* stream) {
     p.cs_v = a->colsum_ws + (long)a->B * ((a->Tq + 31) / 32) * a->H * 64;
   }
   hipStream_t s = (hipStream_t)stream;
+  const dim3 block(256);
+  int rc = WFT_OK;
   if (wft_dq4w_eligible(a)) {
-    static bool ldsq_set[64] = {false};
-    int devq = 0;
-    if (hipGetDevice(&devq) != hipSuccess || devq < 0 || devq >= 64) devq = 0;
-    if (!ldsq_set[devq]) {
-      hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_dq4w_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, Q4_LDS);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_dq4w_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, Q4_LDS);
-      if (e != hipSuccess) {
-        wft_set_error("wft_attn_bwd_bf16: the dQ kernel needs %d bytes of dynamic LDS, hipFuncSetAttribute: %s", Q4_LDS, hipGetErrorString(e));
-        return WFT_ERR_LAUNCH;
-      }
-      ldsq_set[devq] = true;
-    }
-    // persistent like the dK/dV kernel below: one workgroup per CU walks the (batch, head, 256-query block) items; launch_mode = 1
-    // (or WFT_ATTN_PERSISTENT=0): one item per workgroup
-    const long qitems = (long)((a->Tq + 255) / 256) * a->H * a->B;
-    long qwgs = (g_attn_persistent != 0 && a->launch_mode != 1) ? wft_num_cus() : qitems;
-    if (qwgs > qitems) qwgs = qitems;
-    if (((long)a->H * a->B) % 8 == 0 && qwgs >= 8) qwgs -= qwgs % 8;  // XCD mode needs the same number of workgroups on every XCD
-    const dim3 gq((unsigned)qwgs);
-    if (p.qpre) hipLaunchKernelGGL(attn_bwd_dq4w_kernel<true>, gq, dim3(256), Q4_LDS, s, p);
-    else hipLaunchKernelGGL(attn_bwd_dq4w_kernel<false>, gq, dim3(256), Q4_LDS, s, p);
+    const dim3 gq = attn_persistent_grid(a, a->Tq, 0);
+    rc = !p.qpre ? wft_launch_lds<attn_bwd_dq4w_kernel<false>>(gq, block, Q4_LDS, s, p) : wft_launch_lds<attn_bwd_dq4w_kernel<true>>(gq, block, Q4_LDS, s, p);
   } else {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3((unsigned)(((a->Tq + 127) / 128) * a->H * a->B)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3((unsigned)(((a->Tq + 127) / 128) * a->H * a->B)), block, 0, s, p);
   }
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  {
-    static bool lds_set[64] = {false};  // hipFuncSetAttribute is per device
-    if (!lds_set[dev]) {
-      const hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_dkdv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * DKDV_BUF);
-      if (e != hipSuccess) {  // (not remembered: the next call tries again)
-        wft_set_error("wft_attn_bwd_bf16: the dK/dV kernel needs %d bytes of dynamic LDS (160 KiB per CU: gfx950), hipFuncSetAttribute: %s",
-                      2 * DKDV_BUF, hipGetErrorString(e));
-        return WFT_ERR_LAUNCH;
-      }
-      lds_set[dev] = true;
-    }
-  }
+  if (rc != WFT_OK) return rc;
   if (wft_dkdv4w_eligible(a)) {
-    static bool lds4_set[64] = {false};
-    if (!lds4_set[dev]) {
-      hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_dkdv4w_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, D4_LDS);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_dkdv4w_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, D4_LDS);
-      if (e != hipSuccess) {
-        wft_set_error("wft_attn_bwd_bf16: the dK/dV kernel needs %d bytes of dynamic LDS, hipFuncSetAttribute: %s", D4_LDS, hipGetErrorString(e));
-        return WFT_ERR_LAUNCH;
-      }
-      lds4_set[dev] = true;
-    }
-    // persistent: one workgroup per CU (WFT_DKDV_WGS overrides: A/B runs; >= the number of items = one item per workgroup).
-    // WFT_ATTN_PERSISTENT=0 (set by engine/lib.py in a multi-GPU job, like WFT_NT256_PERSISTENT): one item per workgroup — RCCL's
-    // collective kernels hold CUs during the backward pass, and a static walk would leave those CUs' share of the items for a
-    // second round; the hardware dispatcher balances single-item workgroups (measured equal on one GPU: 732 vs 735 us)
     static const int wgs_env = [] { const char* e = wft_dev_getenv("WFT_DKDV_WGS"); return e ? atoi(e) : 0; }();
-    const bool persistent = g_attn_persistent != 0 && a->launch_mode != 1;
-    const long items = (long)((a->Tk + 255) / 256) * a->H * a->B;
-    long wgs = wgs_env > 0 ? wgs_env : (persistent ? wft_num_cus() : items);
-    if (wgs > items) wgs = items;
-    if (((long)a->H * a->B) % 8 == 0 && wgs >= 8) wgs -= wgs % 8;  // XCD mode needs the same number of workgroups on every XCD
-    if (p.qpre) hipLaunchKernelGGL(attn_bwd_dkdv4w_kernel<true>, dim3((unsigned)wgs), dim3(256), D4_LDS, s, p);
-    else hipLaunchKernelGGL(attn_bwd_dkdv4w_kernel<false>, dim3((unsigned)wgs), dim3(256), D4_LDS, s, p);
+    const dim3 gk = attn_persistent_grid(a, a->Tk, wgs_env);
+    rc = !p.qpre ? wft_launch_lds<attn_bwd_dkdv4w_kernel<false>>(gk, block, D4_LDS, s, p) : wft_launch_lds<attn_bwd_dkdv4w_kernel<true>>(gk, block, D4_LDS, s, p);
   } else {
-    hipLaunchKernelGGL(attn_bwd_dkdv_kernel, dim3((unsigned)(((a->Tk + 127) / 128) * a->H * a->B)), dim3(256), 2 * DKDV_BUF, s, p);
+    // (160 KiB of LDS per CU: gfx950)
+    rc = wft_launch_lds<attn_bwd_dkdv_kernel>(dim3((unsigned)(((a->Tk + 127) / 128) * a->H * a->B)), block, 2 * DKDV_BUF, s, p);
   }
+  if (rc != WFT_OK) return rc;
   if (p.cs_q) {
     const int n = a->H * 64;
     const long rq = (long)a->B * ((a->Tq + 31) / 32), rk = (long)a->B * ((a->Tk + 31) / 32);

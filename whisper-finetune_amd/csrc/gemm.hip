@@ -1631,31 +1631,53 @@ __global__ __launch_bounds__(256) void tn_splitk_reduce_pair_kernel(TnReduceP r0
 }
 
 // ---------------------------------------------------------------------------------- host
+// Which kernel serves a call, on which grid, with how many K splits and how much workspace is decided ONCE per family, by
+// nt_plan / tn_plan below: the dispatch and workspace queries, the launchers and the paired entry points all read that plan, and
+// nt_check / tn_check are each family's one argument check.
 static int g_diag = 0;
 // dispatch thresholds, measured at M = R = 4096 and 8704 (decoder-sized problems; tests/dev_small_gemm.py): the 256x256 kernels win once
 // they can occupy half of the CUs (NT: >= 128 tiles) / have >= 50 output tiles to split (TN).  Tunable: WFT_NT256_MIN_TILES, WFT_TN256_MIN_STEPS.
 static int g_nt256_min_tiles = 128, g_tn256_min_steps = 64, g_tn256_min_out_tiles = 50;
-static bool g_nt256_persistent = true;
+static int g_nt256_persistent = 1;
 static int g_nt256_band = 5;
 // which 256x256 NT kernel: 0 = the one-wave-per-SIMD kernel where it applies (gemm_nt4w.hip), 1 = always the ping-pong kernel.
 // WFT_NT_VARIANT=pp|4w at load time (timing builds); per call: wft_gemm_args.variant.
 static int g_nt_variant = 0;
-bool wft_nt4w_eligible(const wft_gemm_args* a);
 // the one-wave-per-SIMD weight-gradient kernel (gemm_tn4w.hip): WFT_TN_VARIANT=pp keeps gemm_tn256_kernel
 static int g_tn_variant = 0;
+static int g_force_128 = 0;  // debugging / A-B switch: WFT_GEMM_FORCE_128=1
+
+// the per-kernel facts of the one-wave-per-SIMD kernels, kept beside them (gemm_nt4w.hip, gemm_tn4w.hip)
+bool wft_nt4w_eligible(const wft_gemm_args* a);
+int wft_nt4w_launch(const wft_gemm_args* a, const GemmP& p, unsigned grid, void* stream);
 bool wft_tn4w_eligible(const wft_gemm_args* a);
 void wft_tn4w_plan(const wft_gemm_args* a, int* nsplit_out, int* per_out);
-int wft_tn4w_launch(const wft_gemm_args* a, GemmP p, int nsplit, int per, void* stream);
+int wft_tn4w_launch(const GemmP& p, unsigned grid, void* stream);
 
-int wft_nt4w_launch(const wft_gemm_args* a, const GemmP& p, bool persistent, void* stream);
+// environment at load time: a variable that is not set leaves its target alone
+static int env_int(const char* e, int) { return atoi(e); }
+static int env_positive_int(const char* e, int old) { return atoi(e) > 0 ? atoi(e) : old; }
+static int env_is_1(const char* e, int) { return e[0] == '1'; }
+static int env_not_0(const char* e, int) { return e[0] != '0'; }
+static int env_starts_with_p(const char* e, int) { return e[0] == 'p'; }
+static void env_read(const char* e, int& target, int (*parse)(const char*, int)) {
+  if (e) target = parse(e, target);
+}
+static struct EnvInit {
+  EnvInit() {
+    env_read(wft_dev_getenv("WFT_GEMM_FORCE_128"), g_force_128, env_is_1);
+    env_read(wft_dev_getenv("WFT_GEMM_DIAG"), g_diag, env_int);
+    env_read(wft_dev_getenv("WFT_NT256_MIN_TILES"), g_nt256_min_tiles, env_int);
+    env_read(wft_dev_getenv("WFT_TN256_MIN_STEPS"), g_tn256_min_steps, env_int);
+    env_read(wft_dev_getenv("WFT_TN256_MIN_OUT_TILES"), g_tn256_min_out_tiles, env_int);
+    env_read(getenv("WFT_NT256_PERSISTENT"), g_nt256_persistent, env_not_0);
+    env_read(wft_dev_getenv("WFT_NT256_BAND"), g_nt256_band, env_positive_int);
+    env_read(wft_dev_getenv("WFT_NT_VARIANT"), g_nt_variant, env_starts_with_p);
+    env_read(wft_dev_getenv("WFT_TN_VARIANT"), g_tn_variant, env_starts_with_p);
+  }
+} g_env_init;
 
-
-static bool g_force_128 = false;  // debugging / A-B switch: WFT_GEMM_FORCE_128=1
-static struct EnvInit { EnvInit() { const char* e = wft_dev_getenv("WFT_GEMM_FORCE_128"); g_force_128 = e && e[0] == '1'; const char* d = wft_dev_getenv("WFT_GEMM_DIAG"); g_diag = d ? atoi(d) : 0; const char* t1 = wft_dev_getenv("WFT_NT256_MIN_TILES"); if (t1) g_nt256_min_tiles = atoi(t1); const char* t2 = wft_dev_getenv("WFT_TN256_MIN_STEPS"); if (t2) g_tn256_min_steps = atoi(t2); const char* t3 = wft_dev_getenv("WFT_TN256_MIN_OUT_TILES"); if (t3) g_tn256_min_out_tiles = atoi(t3); const char* pe = getenv("WFT_NT256_PERSISTENT"); if (pe) g_nt256_persistent = pe[0] != '0'; const char* bw = wft_dev_getenv("WFT_NT256_BAND"); if (bw && atoi(bw) > 0) g_nt256_band = atoi(bw); const char* nv = wft_dev_getenv("WFT_NT_VARIANT"); if (nv) g_nt_variant = (nv[0] == 'p') ? 1 : 0; const char* tv = wft_dev_getenv("WFT_TN_VARIANT"); if (tv) g_tn_variant = (tv[0] == 'p') ? 1 : 0; } } g_env_init;
-
-
-
-static int fill_params(const wft_gemm_args* a, GemmP& p) {
+static void fill_params(const wft_gemm_args* a, GemmP& p) {
   p.A = a->A; p.lda = a->lda; p.sA = a->strideA;
   p.B = a->B; p.ldb = a->ldb; p.sB = a->strideB;
   p.C = a->C; p.ldc = a->ldc; p.sC = a->strideC;
@@ -1673,9 +1695,43 @@ static int fill_params(const wft_gemm_args* a, GemmP& p) {
   p.ws = nullptr;
   p.cs_part = nullptr;
   p.nsplit = 1;
-  return 0;
 }
 
+// the caller granted at least `bytes` of 16-byte aligned workspace
+static bool ws_granted(const wft_gemm_args* a, int64_t bytes) {
+  return a->workspace && a->workspace_bytes >= bytes && (((uintptr_t)a->workspace) & 15) == 0;
+}
+
+// what both families check alike
+static int gemm_check_common(const wft_gemm_args* a, const char* who) {
+  WFT_CHECK_ARG_AS(who, a->lda % 8 == 0 && a->ldb % 8 == 0 && a->ldc % 4 == 0, "ld alignment");
+  WFT_CHECK_ARG_AS(who, ((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->B & 15) == 0 && ((uintptr_t)a->C & 15) == 0,
+                   "base pointers must be 16-byte aligned");
+  WFT_CHECK_ARG_AS(who, !(a->accumulate && !a->c_is_f32), "accumulate needs an f32 C");
+  return WFT_OK;
+}
+
+// the load-stream kernels for rank-r operands take TWO products per launch (workgroups >= n0 work on p1): the paired entry points
+// pass both, a single product is (p, p, its grid, 0)
+template <bool TN, int PB>
+static int launch_rank_pb(const GemmP& p0, const GemmP& p1, int n0, int n1, hipStream_t s) {
+  constexpr int nst = PB <= 2 ? 4 : 3;
+  constexpr int bytes = nst * (16384 + 2048 * PB);
+  const dim3 grid((unsigned)(n0 + n1)), block(256);
+  if constexpr (TN) return wft_launch_lds<gemm_tn_rank_kernel<PB>>(grid, block, bytes, s, p0, p1, n0);
+  else return wft_launch_lds<gemm_nt_rank_kernel<PB>>(grid, block, bytes, s, p0, p1, n0);
+}
+template <bool TN>
+static int launch_rank(int pb, const GemmP& p0, const GemmP& p1, int n0, int n1, hipStream_t s) {
+  switch (pb) {
+    case 1: return launch_rank_pb<TN, 1>(p0, p1, n0, n1, s);
+    case 2: return launch_rank_pb<TN, 2>(p0, p1, n0, n1, s);
+    case 3: return launch_rank_pb<TN, 3>(p0, p1, n0, n1, s);
+    default: return launch_rank_pb<TN, 4>(p0, p1, n0, n1, s);
+  }
+}
+
+// ---------------------------------------------------------------------------------- NT host
 // out[col] = sum over `nrows` partial rows (fixed order): finishes the fused bias-gradient column sums of gemm_nt256_kernel
 __global__ __launch_bounds__(256) void nt_colsum_reduce_kernel(const float* partial, int nrows, int n, float* out) {
   // 64 columns per workgroup as 16 groups of four (16-byte loads: a wave instruction covers four whole 256-byte row segments),
@@ -1696,7 +1752,6 @@ __global__ __launch_bounds__(256) void nt_colsum_reduce_kernel(const float* part
   }
 }
 
-static bool nt_uses_256(const wft_gemm_args* a);
 // C[m][n] = bf16(sum over splits, in split order, of ws[split][m][n]): finishes the split-K form of the 128-tile NT kernel
 __global__ __launch_bounds__(256) void nt_splitk_reduce_kernel(const float* ws, int nsplit, int M, int N, unsigned short* C, long ldc) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;  // one thread per 4 consecutive columns
@@ -1719,19 +1774,14 @@ static int nt_splitk_plan(const wft_gemm_args* a, int* per_out) {
     return 1;
   const long tiles = ((a->M + 127) / 128) * (a->N / 128), nk = a->K / 64;
   const int ncu = wft_num_cus();
-  if (tiles * 2 > ncu || nk < 64) return 1;  // (at least two splits' worth of idle CUs)
+  if (tiles < 1 || tiles * 2 > ncu || nk < 64) return 1;  // (at least two splits' worth of idle CUs)
   long nsplit = ncu / tiles;
   if (nsplit > nk / 16) nsplit = nk / 16;
   const long per = (nk + nsplit - 1) / nsplit;
   *per_out = (int)per;
   return (int)((nk + per - 1) / per);  // (no empty split)
 }
-extern "C" int64_t wft_gemm_nt_splitk_workspace_bytes(const wft_gemm_args* a) {
-  if (!a || nt_uses_256(a)) return 0;
-  int per = 0;
-  const int ns = nt_splitk_plan(a, &per);
-  return ns > 1 ? (int64_t)ns * a->M * a->N * 4 : 0;
-}
+// big, 256-aligned-N problems go to the 256x256 kernels (one workgroup per CU, 128 KiB LDS and more)
 static bool nt_uses_256(const wft_gemm_args* a) {
   const bool wide_ok = a->c_is_f32 || (a->ldc % 8 == 0 && (!a->residual || (a->ldr % 8 == 0 && ((uintptr_t)a->residual & 15) == 0)) &&
                                        (!a->aux || (a->ldaux % 8 == 0 && ((uintptr_t)a->aux & 15) == 0)) &&
@@ -1739,184 +1789,166 @@ static bool nt_uses_256(const wft_gemm_args* a) {
   return !g_force_128 && wide_ok && a->N % 256 == 0 && a->M >= 1024 &&
          ((a->M + 255) / 256) * (a->N / 256) * a->batch >= g_nt256_min_tiles;
 }
-extern "C" int wft_gemm_nt_variant(const wft_gemm_args* a) {
-  if (!a || !nt_uses_256(a)) return 128;
-  return (g_nt_variant != 1 && a->variant == 0 && wft_nt4w_eligible(a)) ? 4 : 256;
+// p_valid: B is a rank-r operand in the first rows of a 128-row zero-padded buffer (u = x (sA*mask)^T, du = dy (sB)): the
+// load-stream kernel, which writes only the data columns of C (WFT_GEMM_DIAG=9: the 128-tile kernel, A/B runs).
+// -> number of 16-row blocks of B that hold data (0: not that form)
+static int nt_rank_pb(const wft_gemm_args* a) {
+  return (!a->c_is_f32 && a->N == 128 && a->batch == 1 && a->p_valid > 0 && a->p_valid <= 64 && a->epilogue == WFT_EPI_NONE &&
+          !a->bias && !a->residual && !a->aux && !a->colsum && a->valid_rows_period == 0 && g_diag != 9)
+             ? (a->p_valid + 15) / 16 : 0;
 }
+static bool epi_is_aux8(int e) { return e == WFT_EPI_GELU_GRAD8 || e == WFT_EPI_MUL_AUX8; }
 
-// bytes of the fragment-ordered one-byte gelu' buffer (WFT_EPI_GELU_GRAD8 writes, WFT_EPI_MUL_AUX8 reads) if these arguments are
-// served — only gemm_nt4w_kernel carries the two epilogues — else 0: 16 KiB per (256x256 tile, wave) = one byte per tile element
-extern "C" int64_t wft_gemm_nt_aux8_bytes(const wft_gemm_args* a) {
-  if (!a || (a->epilogue != WFT_EPI_GELU_GRAD8 && a->epilogue != WFT_EPI_MUL_AUX8)) return 0;
-  if (!nt_uses_256(a) || g_nt_variant == 1 || a->variant != 0 || !wft_nt4w_eligible(a)) return 0;
-  return (int64_t)((a->M + 255) / 256) * (a->N / 256) * 65536;
-}
-
-extern "C" int64_t wft_gemm_nt_colsum_workspace_bytes(const wft_gemm_args* a) {
-  if (!a || !a->colsum || a->c_is_f32 || a->batch != 1 || !nt_uses_256(a)) return 0;
-  return (int64_t)2 * ((a->M + 255) / 256) * a->N * (int64_t)sizeof(float);
-}
-
-extern "C" int wft_gemm_nt_bf16(const wft_gemm_args* a, void* stream) {
-  WFT_CHECK_ARG(a && a->A && a->B && a->C, "null pointer");
-  WFT_CHECK_ARG(a->M >= 1 && a->N >= 128 && a->K >= 64 && a->batch >= 1, "bad shape");
-  WFT_CHECK_ARG(a->N % 128 == 0, "N must be a multiple of 128");
-  WFT_CHECK_ARG(a->K % 64 == 0, "K must be a multiple of 64");
-  WFT_CHECK_ARG(a->lda % 8 == 0 && a->ldb % 8 == 0 && a->ldc % 4 == 0, "ld alignment");
-  WFT_CHECK_ARG(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->B & 15) == 0 && ((uintptr_t)a->C & 15) == 0,
-                "base pointers must be 16-byte aligned");
-  WFT_CHECK_ARG(!(a->accumulate && !a->c_is_f32), "accumulate needs an f32 C");
-  const bool aux8 = a->epilogue == WFT_EPI_GELU_GRAD8 || a->epilogue == WFT_EPI_MUL_AUX8;
-  WFT_CHECK_ARG((a->epilogue != WFT_EPI_DGELU && a->epilogue != WFT_EPI_GELU_GRAD && a->epilogue != WFT_EPI_MUL_AUX && !aux8) || a->aux,
-                "DGELU / GELU_GRAD / MUL_AUX epilogues need aux");
-  WFT_CHECK_ARG((a->epilogue != WFT_EPI_GELU_GRAD && a->epilogue != WFT_EPI_MUL_AUX && !aux8) || !a->c_is_f32,
-                "GELU_GRAD / MUL_AUX epilogues write a bf16 C");
-  if (aux8 && wft_gemm_nt_aux8_bytes(a) == 0) {
-    wft_set_error("wft_gemm_nt_bf16: the one-byte gelu' epilogues exist on gemm_nt4w_kernel only (ask wft_gemm_nt_aux8_bytes first)");
-    return WFT_ERR_UNSUPPORTED;
-  }
-  WFT_CHECK_ARG(a->M < (1ll << 31) && a->N < (1ll << 31) && a->K < (1ll << 31), "dims exceed int32");
-  GemmP p;
-  fill_params(a, p);
-  hipStream_t s = (hipStream_t)stream;
-  // big, 256-aligned-N problems go to the 256x256 kernel (one workgroup per CU, 128 KiB LDS)
-  const bool big = nt_uses_256(a);
-  const bool cs_fused = a->colsum && big && !a->c_is_f32 && a->batch == 1 && a->workspace &&
-                        a->workspace_bytes >= wft_gemm_nt_colsum_workspace_bytes(a) &&
-                        ((((uintptr_t)a->workspace) | ((uintptr_t)a->colsum)) & 15) == 0;  // (16-byte accesses in the reduce kernel)
-  if (a->colsum) {
-    WFT_CHECK_ARG(!a->c_is_f32 && a->batch == 1, "colsum needs a bf16 C and batch == 1");
-    if (cs_fused) p.cs_part = (float*)a->workspace;
-  }
-  // launch state is per call (wft_gemm_args.launch_mode / variant); the process-wide start values come from the environment at load
-  // time only (WFT_NT256_PERSISTENT; the variant variables in timing builds) and never change afterwards
-  const bool persistent = g_nt256_persistent && a->launch_mode != 1;
-  if (big && g_nt_variant != 1 && a->variant == 0 && wft_nt4w_eligible(a)) {
-    const int rc = wft_nt4w_launch(a, p, persistent, stream);
-    if (rc != WFT_OK) return rc;
-    if (cs_fused)
-      hipLaunchKernelGGL(nt_colsum_reduce_kernel, dim3((unsigned)((a->N + 63) / 64)), dim3(256), 0, s, (const float*)a->workspace,
-                         (int)(2 * ((a->M + 255) / 256)), (int)a->N, a->colsum);
-    WFT_CHECK_LAUNCH();
-    if (a->colsum && !cs_fused) return wft_colsum_bf16((const wft_bf16*)a->C, a->M, a->N, a->ldc, a->colsum, 0, stream);
-    return WFT_OK;
-  }
-  if (big) {
-    const long t256 = ((a->M + 255) / 256) * (a->N / 256) * a->batch;
-    const int ncu = wft_num_cus();
+enum NtKind { NT_4W, NT_256, NT_RANK, NT_128_SPLITK, NT_128_RING, NT_128_2BUF };
+struct NtPlan {
+  NtKind kind = NT_128_2BUF;
+  unsigned grid_x = 0, grid_z = 1;
+  int pb = 0;                // NT_RANK: nt_rank_pb
+  int nsplit = 1, per = 0;   // NT_128_SPLITK: K splits, k-steps per split
+  // what the three size queries answer (0: not served in that form); colsum_bytes and splitk_bytes are workspace to grant
+  int64_t aux8_bytes = 0, colsum_bytes = 0, splitk_bytes = 0;
+  bool cs_fused = false;     // the column sums come out of the GEMM's epilogue (their workspace was granted)
+};
+static NtPlan nt_plan(const wft_gemm_args* a) {
+  NtPlan pl;
+  if (!a) return pl;
+  const int ncu = wft_num_cus();
+  if (nt_uses_256(a)) {
+    const long tm = (a->M + 255) / 256, tn = a->N / 256, t256 = tm * tn * a->batch;
+    pl.kind = (g_nt_variant != 1 && a->variant == 0 && wft_nt4w_eligible(a)) ? NT_4W : NT_256;
+    // launch state is per call (wft_gemm_args.launch_mode / variant); the process-wide start values come from the environment at load
+    // time only (WFT_NT256_PERSISTENT; the variant variables in timing builds) and never change afterwards.
     // persistent (one workgroup per CU walks the tiles, prefetching across tile seams) unless WFT_NT256_PERSISTENT=0: with
     // collectives running beside the GEMMs (DDP over RCCL) some CUs are busy when the kernel starts, and a static tile
     // walk would leave their share for the end; one workgroup per tile lets the hardware dispatcher balance instead
-    dim3 grid((unsigned)((t256 < ncu || !persistent) ? t256 : ncu)), block(512);
-#define LAUNCH_256(E, F)                                                                                   \
-  do {                                                                                                    \
-    auto kfn = gemm_nt256_kernel<E, F>;                                                                   \
-    static DynLdsOnce once;                                                                               \
-    if (!once.set(kfn, 163840)) return WFT_ERR_LAUNCH;                                                                                \
-    hipLaunchKernelGGL(kfn, grid, block, 163840, s, p);                                                   \
-  } while (0)
-    switch (a->epilogue) {
-      case WFT_EPI_NONE: if (a->c_is_f32) LAUNCH_256(WFT_EPI_NONE, true); else LAUNCH_256(WFT_EPI_NONE, false); break;
-      case WFT_EPI_GELU: if (a->c_is_f32) LAUNCH_256(WFT_EPI_GELU, true); else LAUNCH_256(WFT_EPI_GELU, false); break;
-      case WFT_EPI_DGELU: if (a->c_is_f32) LAUNCH_256(WFT_EPI_DGELU, true); else LAUNCH_256(WFT_EPI_DGELU, false); break;
-      case WFT_EPI_GELU_GRAD: LAUNCH_256(WFT_EPI_GELU_GRAD, false); break;
-      case WFT_EPI_MUL_AUX: LAUNCH_256(WFT_EPI_MUL_AUX, false); break;
-      default: wft_set_error("wft_gemm_nt_bf16: unknown epilogue %d", a->epilogue); return WFT_ERR_ARG;
+    const bool persistent = g_nt256_persistent && a->launch_mode != 1;
+    pl.grid_x = (unsigned)((t256 < ncu || !persistent) ? t256 : ncu);
+    // 16 KiB of one-byte gelu' per (256x256 tile, wave) = one byte per tile element: only gemm_nt4w_kernel carries the two epilogues
+    if (pl.kind == NT_4W && epi_is_aux8(a->epilogue)) pl.aux8_bytes = tm * tn * 65536;
+    if (a->colsum && !a->c_is_f32 && a->batch == 1) {
+      pl.colsum_bytes = 2 * tm * a->N * (int64_t)sizeof(float);
+      pl.cs_fused = ws_granted(a, pl.colsum_bytes) && ((uintptr_t)a->colsum & 15) == 0;  // (16-byte accesses in the reduce kernel)
     }
-#undef LAUNCH_256
-    if (cs_fused)
-      hipLaunchKernelGGL(nt_colsum_reduce_kernel, dim3((unsigned)((a->N + 63) / 64)), dim3(256), 0, s, (const float*)a->workspace,
-                         (int)(2 * ((a->M + 255) / 256)), (int)a->N, a->colsum);
-    WFT_CHECK_LAUNCH();
-    if (a->colsum && !cs_fused) return wft_colsum_bf16((const wft_bf16*)a->C, a->M, a->N, a->ldc, a->colsum, 0, stream);
-    return WFT_OK;
+    return pl;
   }
-  // p_valid: B is a rank-r operand in the first rows of a 128-row zero-padded buffer (u = x (sA*mask)^T, du = dy (sB)): the
-  // load-stream kernel, which writes only the data columns of C (WFT_GEMM_DIAG=9: the 128-tile kernel, A/B runs)
-  const int npb = (!a->c_is_f32 && a->N == 128 && a->batch == 1 && a->p_valid > 0 && a->p_valid <= 64 && a->epilogue == WFT_EPI_NONE &&
-                   !a->bias && !a->residual && !a->aux && !a->colsum && a->valid_rows_period == 0 && g_diag != 9)
-                      ? (a->p_valid + 15) / 16 : 0;
-  if (npb) {
-    const dim3 g1((unsigned)((a->M + 127) / 128));
-#define WFT_NT_RANK_LAUNCH(PBV)                                                                   \
-  {                                                                                               \
-    constexpr int nst = (PBV) <= 2 ? 4 : 3;                                                       \
-    constexpr int bytes = nst * (16384 + 2048 * (PBV));                                           \
-    static DynLdsOnce once;                                                                       \
-    auto kfn = gemm_nt_rank_kernel<PBV>;                                                          \
-    if (!once.set(kfn, bytes)) return WFT_ERR_LAUNCH;                                                                         \
-    hipLaunchKernelGGL(kfn, g1, dim3(256), bytes, s, p, p, (int)g1.x);                            \
-  }
-    if (npb == 1) WFT_NT_RANK_LAUNCH(1)
-    else if (npb == 2) WFT_NT_RANK_LAUNCH(2)
-    else if (npb == 3) WFT_NT_RANK_LAUNCH(3)
-    else WFT_NT_RANK_LAUNCH(4)
-#undef WFT_NT_RANK_LAUNCH
-    WFT_CHECK_LAUNCH();
-    return WFT_OK;
+  pl.pb = nt_rank_pb(a);
+  if (pl.pb) {
+    pl.kind = NT_RANK;
+    pl.grid_x = (unsigned)((a->M + 127) / 128);
+    return pl;
   }
   const long tiles = ((a->M + 127) / 128) * (a->N / 128);
-  dim3 grid((unsigned)tiles, 1, (unsigned)a->batch), block(256);
+  pl.grid_x = (unsigned)tiles;
+  pl.grid_z = (unsigned)a->batch;
   // a grid of at most one workgroup per CU: the four-buffer ring form (one exposed load latency per CALL instead of one per
   // k-step; WFT_GEMM_DIAG=11 keeps the two-buffer form for A/B runs)
-  const bool ring = tiles * a->batch <= wft_num_cus() && g_diag != 11;
-#define LAUNCH_NT_RING(E, F)                                                       \
-  do {                                                                             \
-    auto kfn = gemm_nt_kernel<E, F, 4>;                                            \
-    static DynLdsOnce once;                                                        \
-    if (!once.set(kfn, 131072)) return WFT_ERR_LAUNCH;                             \
-    hipLaunchKernelGGL(kfn, grid, block, 131072, s, p);                            \
-  } while (0)
-  if (ring) {
-    int per = 0;
-    const int ns = nt_splitk_plan(a, &per);
-    if (ns > 1 && a->workspace && a->workspace_bytes >= (int64_t)ns * a->M * a->N * 4 && (((uintptr_t)a->workspace) & 15) == 0) {
-      GemmP ps = p;  // fp32 partial tiles [split][M][N]; alpha is applied to every partial (linear)
-      ps.C = a->workspace; ps.ldc = a->N; ps.accumulate = 0; ps.nsplit = ns; ps.band = per;
-      grid.z = (unsigned)ns;
-      {
-        auto kfn = gemm_nt_kernel<WFT_EPI_NONE, true, 4>;
-        static DynLdsOnce once;
-        if (!once.set(kfn, 131072)) return WFT_ERR_LAUNCH;
-        hipLaunchKernelGGL(kfn, grid, block, 131072, s, ps);
-      }
-      hipLaunchKernelGGL(nt_splitk_reduce_kernel, dim3((unsigned)((a->M * (a->N / 4) + 255) / 256)), dim3(256), 0, s,
-                         (const float*)a->workspace, ns, (int)a->M, (int)a->N, (unsigned short*)a->C, (long)a->ldc);
-      WFT_CHECK_LAUNCH();
-      return WFT_OK;
+  pl.kind = (tiles * a->batch <= ncu && g_diag != 11) ? NT_128_RING : NT_128_2BUF;
+  pl.nsplit = nt_splitk_plan(a, &pl.per);
+  if (pl.nsplit > 1) {  // (which implies the ring form: at most half a workgroup per CU)
+    pl.splitk_bytes = (int64_t)pl.nsplit * a->M * a->N * 4;
+    if (ws_granted(a, pl.splitk_bytes)) {
+      pl.kind = NT_128_SPLITK;
+      pl.grid_z = (unsigned)pl.nsplit;
     }
-    switch (a->epilogue) {
-      case WFT_EPI_NONE: if (a->c_is_f32) LAUNCH_NT_RING(WFT_EPI_NONE, true); else LAUNCH_NT_RING(WFT_EPI_NONE, false); break;
-      case WFT_EPI_GELU: if (a->c_is_f32) LAUNCH_NT_RING(WFT_EPI_GELU, true); else LAUNCH_NT_RING(WFT_EPI_GELU, false); break;
-      case WFT_EPI_DGELU: if (a->c_is_f32) LAUNCH_NT_RING(WFT_EPI_DGELU, true); else LAUNCH_NT_RING(WFT_EPI_DGELU, false); break;
-      case WFT_EPI_GELU_GRAD: LAUNCH_NT_RING(WFT_EPI_GELU_GRAD, false); break;
-      case WFT_EPI_MUL_AUX: LAUNCH_NT_RING(WFT_EPI_MUL_AUX, false); break;
-      default: wft_set_error("wft_gemm_nt_bf16: unknown epilogue %d", a->epilogue); return WFT_ERR_ARG;
-    }
-    WFT_CHECK_LAUNCH();
-    if (a->colsum) return wft_colsum_bf16((const wft_bf16*)a->C, a->M, a->N, a->ldc, a->colsum, 0, stream);
-    return WFT_OK;
   }
-#undef LAUNCH_NT_RING
-#define LAUNCH_NT(E)                                                               \
-  do {                                                                             \
-    if (a->c_is_f32) hipLaunchKernelGGL((gemm_nt_kernel<E, true>), grid, block, 0, s, p);  \
-    else hipLaunchKernelGGL((gemm_nt_kernel<E, false>), grid, block, 0, s, p);     \
-  } while (0)
-  switch (a->epilogue) {
-    case WFT_EPI_NONE: LAUNCH_NT(WFT_EPI_NONE); break;
-    case WFT_EPI_GELU: LAUNCH_NT(WFT_EPI_GELU); break;
-    case WFT_EPI_DGELU: LAUNCH_NT(WFT_EPI_DGELU); break;
-    case WFT_EPI_GELU_GRAD: hipLaunchKernelGGL((gemm_nt_kernel<WFT_EPI_GELU_GRAD, false>), grid, block, 0, s, p); break;
-    case WFT_EPI_MUL_AUX: hipLaunchKernelGGL((gemm_nt_kernel<WFT_EPI_MUL_AUX, false>), grid, block, 0, s, p); break;
-    default: wft_set_error("wft_gemm_nt_bf16: unknown epilogue %d", a->epilogue); return WFT_ERR_ARG;
+  return pl;
+}
+
+static int nt_check(const wft_gemm_args* a, const NtPlan& pl, const char* who) {
+  WFT_CHECK_ARG_AS(who, a && a->A && a->B && a->C, "null pointer");
+  WFT_CHECK_ARG_AS(who, a->M >= 1 && a->N >= 128 && a->K >= 64 && a->batch >= 1, "bad shape");
+  WFT_CHECK_ARG_AS(who, a->N % 128 == 0, "N must be a multiple of 128");
+  WFT_CHECK_ARG_AS(who, a->K % 64 == 0, "K must be a multiple of 64");
+  const int rc = gemm_check_common(a, who);
+  if (rc != WFT_OK) return rc;
+  const bool aux8 = epi_is_aux8(a->epilogue);
+  WFT_CHECK_ARG_AS(who, (a->epilogue != WFT_EPI_DGELU && a->epilogue != WFT_EPI_GELU_GRAD && a->epilogue != WFT_EPI_MUL_AUX && !aux8) || a->aux,
+                   "DGELU / GELU_GRAD / MUL_AUX epilogues need aux");
+  WFT_CHECK_ARG_AS(who, (a->epilogue != WFT_EPI_GELU_GRAD && a->epilogue != WFT_EPI_MUL_AUX && !aux8) || !a->c_is_f32,
+                   "GELU_GRAD / MUL_AUX epilogues write a bf16 C");
+  if (aux8 && pl.aux8_bytes == 0) {
+    wft_set_error("%s: the one-byte gelu' epilogues exist on gemm_nt4w_kernel only (ask wft_gemm_nt_aux8_bytes first)", who);
+    return WFT_ERR_UNSUPPORTED;
   }
-#undef LAUNCH_NT
-  WFT_CHECK_LAUNCH();
-  if (a->colsum) return wft_colsum_bf16((const wft_bf16*)a->C, a->M, a->N, a->ldc, a->colsum, 0, stream);
+  WFT_CHECK_ARG_AS(who, a->M < (1ll << 31) && a->N < (1ll << 31) && a->K < (1ll << 31), "dims exceed int32");
+  if (a->colsum) WFT_CHECK_ARG_AS(who, !a->c_is_f32 && a->batch == 1, "colsum needs a bf16 C and batch == 1");
   return WFT_OK;
 }
 
+extern "C" int wft_gemm_nt_variant(const wft_gemm_args* a) {
+  const NtKind k = nt_plan(a).kind;
+  return k == NT_4W ? 4 : k == NT_256 ? 256 : 128;
+}
+extern "C" int64_t wft_gemm_nt_aux8_bytes(const wft_gemm_args* a) { return nt_plan(a).aux8_bytes; }
+extern "C" int64_t wft_gemm_nt_colsum_workspace_bytes(const wft_gemm_args* a) { return nt_plan(a).colsum_bytes; }
+extern "C" int64_t wft_gemm_nt_splitk_workspace_bytes(const wft_gemm_args* a) { return nt_plan(a).splitk_bytes; }
+
+// f(epilogue, C is fp32) with both as compile-time constants, for the (epilogue, C type) pairs the 128-tile and the ping-pong
+// kernels are instantiated with: GELU_GRAD and MUL_AUX write a bf16 C only
+template <int E>
+using EpiC = std::integral_constant<int, E>;
+template <class F>
+static int nt_with_epilogue(const wft_gemm_args* a, F&& f) {
+  const auto either = [&](auto e) { return a->c_is_f32 ? f(e, std::true_type{}) : f(e, std::false_type{}); };
+  switch (a->epilogue) {
+    case WFT_EPI_NONE: return either(EpiC<WFT_EPI_NONE>{});
+    case WFT_EPI_GELU: return either(EpiC<WFT_EPI_GELU>{});
+    case WFT_EPI_DGELU: return either(EpiC<WFT_EPI_DGELU>{});
+    case WFT_EPI_GELU_GRAD: return f(EpiC<WFT_EPI_GELU_GRAD>{}, std::false_type{});
+    case WFT_EPI_MUL_AUX: return f(EpiC<WFT_EPI_MUL_AUX>{}, std::false_type{});
+    default: wft_set_error("wft_gemm_nt_bf16: unknown epilogue %d", a->epilogue); return WFT_ERR_ARG;
+  }
+}
+
+extern "C" int wft_gemm_nt_bf16(const wft_gemm_args* a, void* stream) {
+  const NtPlan pl = nt_plan(a);
+  int rc = nt_check(a, pl, __func__);
+  if (rc != WFT_OK) return rc;
+  GemmP p;
+  fill_params(a, p);
+  if (pl.cs_fused) p.cs_part = (float*)a->workspace;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(pl.grid_x, 1, pl.grid_z), block(256);
+  switch (pl.kind) {
+    case NT_4W: rc = wft_nt4w_launch(a, p, pl.grid_x, stream); break;
+    case NT_256:
+      rc = nt_with_epilogue(a, [&](auto e, auto f32) {
+        return wft_launch_lds<gemm_nt256_kernel<decltype(e)::value, decltype(f32)::value>>(grid, dim3(512), 163840, s, p);
+      });
+      break;
+    case NT_RANK: rc = launch_rank<false>(pl.pb, p, p, (int)pl.grid_x, 0, s); break;
+    case NT_128_SPLITK: {
+      GemmP ps = p;  // fp32 partial tiles [split][M][N]; alpha is applied to every partial (linear)
+      ps.C = a->workspace; ps.ldc = a->N; ps.accumulate = 0; ps.nsplit = pl.nsplit; ps.band = pl.per;
+      rc = wft_launch_lds<gemm_nt_kernel<WFT_EPI_NONE, true, 4>>(grid, block, 131072, s, ps);
+      if (rc == WFT_OK)
+        hipLaunchKernelGGL(nt_splitk_reduce_kernel, dim3((unsigned)((a->M * (a->N / 4) + 255) / 256)), dim3(256), 0, s,
+                           (const float*)a->workspace, pl.nsplit, (int)a->M, (int)a->N, (unsigned short*)a->C, (long)a->ldc);
+      break;
+    }
+    case NT_128_RING:
+      rc = nt_with_epilogue(a, [&](auto e, auto f32) {
+        return wft_launch_lds<gemm_nt_kernel<decltype(e)::value, decltype(f32)::value, 4>>(grid, block, 131072, s, p);
+      });
+      break;
+    case NT_128_2BUF:
+      rc = nt_with_epilogue(a, [&](auto e, auto f32) {
+        hipLaunchKernelGGL((gemm_nt_kernel<decltype(e)::value, decltype(f32)::value>), grid, block, 0, s, p);
+        return (int)WFT_OK;
+      });
+      break;
+  }
+  if (rc != WFT_OK) return rc;
+  // column sums of C: finished from the epilogue's partial rows, or (not fused) a second pass over C
+  if (pl.cs_fused)
+    hipLaunchKernelGGL(nt_colsum_reduce_kernel, dim3((unsigned)((a->N + 63) / 64)), dim3(256), 0, s, (const float*)a->workspace,
+                       (int)(2 * ((a->M + 255) / 256)), (int)a->N, a->colsum);
+  WFT_CHECK_LAUNCH();
+  if (a->colsum && !pl.cs_fused) return wft_colsum_bf16((const wft_bf16*)a->C, a->M, a->N, a->ldc, a->colsum, 0, stream);
+  return WFT_OK;
+}
+
+// ---------------------------------------------------------------------------------- TN host
 static bool tn_uses_256(const wft_gemm_args* a) {
   const long nsteps = ((a->K + 63) / 64) * a->batch;
   // (round 5: 25 output tiles — a decoder block's 1280 x 1280 gradients — take the 256 x 256 kernel from 8 192 reduction rows on:
@@ -1925,6 +1957,7 @@ static bool tn_uses_256(const wft_gemm_args* a) {
   return !g_force_128 && a->c_is_f32 && a->M % 256 == 0 && a->N % 256 == 0 && nsteps >= g_tn256_min_steps &&
          (nsteps >= 256 || t256 >= g_tn256_min_out_tiles || (t256 >= g_tn256_min_out_tiles / 2 && nsteps >= 128));
 }
+// 256x256 tiles, one workgroup per CU: the split-K factor that fills 256 slots in whole waves
 static int tn256_nsplit(const wft_gemm_args* a) {
   const long t256 = (a->M / 256) * (a->N / 256);
   const long nslabs = ((a->K + 31) / 32) * a->batch;
@@ -1942,7 +1975,6 @@ static int tn256_nsplit(const wft_gemm_args* a) {
   const long per = (nslabs + nsplit - 1) / nsplit;
   return (int)((nslabs + per - 1) / per);
 }
-// 128x128 path: split-K factor that fills the 512 resident-block slots (256 CUs x 2) in whole waves
 // the ring form of gemm_tn_kernel (one workgroup per CU): the general fp32 product on a grid that fits the chip once
 static bool tn128_ring(const wft_gemm_args* a) {
   // (P = 128 is the rank-r operand's buffer width: that product stays bit-identical to its p_valid form, gemm_tn_rank_kernel)
@@ -1952,11 +1984,11 @@ static bool tn128_ring(const wft_gemm_args* a) {
   return a->c_is_f32 && a->M != 128 && a->tn_col_scale == nullptr && a->tn_block_n == 0 && tiles <= wft_num_cus() &&
          (tiles <= 32 || nsteps <= 32) && g_diag != 13;
 }
-static int tn128_nsplit(const wft_gemm_args* a) {
-  if (!a->c_is_f32) return 1;
+static int tn128_nsplit(const wft_gemm_args* a, bool ring) {
   const long tiles = (a->M / 128) * (a->N / 128);
   const long nsteps = ((a->K + 63) / 64) * a->batch;
-  if (tn128_ring(a)) {
+  if (!a->c_is_f32 || tiles < 1 || nsteps < 1) return 1;  // (the plan is made before the arguments are checked)
+  if (ring) {
     // as many splits as fill the chip once, four reduction steps each at least (the ring's depth)
     long sp = wft_num_cus() / tiles;
     if (sp > nsteps / 4) sp = nsteps / 4;
@@ -1966,6 +1998,7 @@ static int tn128_nsplit(const wft_gemm_args* a) {
   }
   int nsplit = 1;
   double best = 0.0;
+  // the two-buffer form: the split-K factor that fills the 512 resident-block slots (256 CUs x 2) in whole waves;
   // up to 64 splits: rank-r LoRA gradients are ONE 128-wide tile row (10-40 tiles) over a 48 000+ row reduction
   for (int sp = 1; sp <= 64; ++sp) {
     if (sp > 1 && nsteps / sp < (sp <= 8 ? 16 : 12)) break;
@@ -1980,16 +2013,67 @@ static int tn128_nsplit(const wft_gemm_args* a) {
 static int tn128_pb(const wft_gemm_args* a) {
   return (a->c_is_f32 && a->M == 128 && a->p_valid > 0 && a->p_valid <= 64) ? (a->p_valid + 15) / 16 : 0;
 }
-// rows of a split's partial tile kept in the workspace
-static int64_t tn_ws_rows(const wft_gemm_args* a) {
-  if (tn_uses_256(a)) return a->M;
-  const int pb = tn128_pb(a);
-  return pb ? 16 * pb : a->M;
-}
 // the adapter-gradient forms (column scale / block-transposed output) are applied by the reduce kernel: always through the workspace
 static bool tn_needs_reduce(const wft_gemm_args* a) { return a->tn_col_scale != nullptr || a->tn_block_n > 0; }
+
+enum TnKind { TN_4W, TN_256, TN_RANK, TN_128_PB, TN_128_RING, TN_128_2BUF, TN_128_BF16C };
+struct TnPlan {
+  TnKind kind = TN_128_2BUF;
+  long tiles = 0;            // output tiles of the kernel's tile size (256 x 256: TN_4W, TN_256; else 128 x 128)
+  int nsplit = 1, per = 0;   // K splits; TN_4W: reduction steps per split
+  int pb = 0;                // tn128_pb (TN_RANK, TN_128_PB)
+  int64_t ws_rows = 0;       // rows of a split's partial tile kept in the workspace
+  int64_t part_bytes = 0;    // the partial tiles [nsplit][ws_rows][Q] of the kernel chosen
+  int64_t ws_bytes = 0;      // what wft_gemm_tn_workspace_bytes answers: the workspace to grant (0: none wanted)
+  bool use_ws = false;       // the partial tiles go to the granted workspace and the reduce kernel finishes C
+};
+static TnPlan tn_plan(const wft_gemm_args* a) {
+  TnPlan pl;
+  if (!a) return pl;
+  const bool seg = a->tn_seg_count > 0;  // segmented output: always through the workspace, even unsplit
+  const auto part = [&](int nsplit) { return (int64_t)nsplit * pl.ws_rows * a->N * 4; };
+  if (tn_uses_256(a)) {
+    pl.tiles = (a->M / 256) * (a->N / 256);
+    pl.ws_rows = a->M;
+    const int ns256 = tn256_nsplit(a);
+    int ns4 = 0, per4 = 0;
+    const bool elig4 = wft_tn4w_eligible(a);
+    if (elig4) wft_tn4w_plan(a, &ns4, &per4);
+    // (the larger of the two kernels' plans: with it granted, the call is served whichever of them the variant switch selects)
+    const int nsq = ns4 > ns256 ? ns4 : ns256;
+    pl.ws_bytes = (nsq > 1 || seg || tn_needs_reduce(a)) ? part(nsq) : 0;
+    if (elig4 && g_tn_variant != 1 && a->variant == 0) {
+      const bool use4 = (ns4 > 1 || seg) && ws_granted(a, part(ns4));
+      if (ns4 == 1 || use4) {  // (split without a workspace: the ping-pong kernel's atomic path)
+        pl.kind = TN_4W; pl.nsplit = ns4; pl.per = per4; pl.use_ws = use4; pl.part_bytes = part(ns4);
+        return pl;
+      }
+    }
+    pl.kind = TN_256; pl.nsplit = ns256; pl.part_bytes = part(ns256);
+    pl.use_ws = (ns256 > 1 || seg) && ws_granted(a, pl.part_bytes);
+    return pl;
+  }
+  pl.tiles = (a->M / 128) * (a->N / 128);
+  const bool ring = tn128_ring(a);
+  pl.nsplit = tn128_nsplit(a, ring);
+  pl.pb = tn128_pb(a);
+  pl.ws_rows = pl.pb ? 16 * pl.pb : a->M;
+  pl.part_bytes = part(pl.nsplit);
+  const bool want_ws = pl.nsplit > 1 || tn_needs_reduce(a);
+  pl.ws_bytes = (want_ws || seg) ? pl.part_bytes : 0;
+  pl.use_ws = want_ws && ws_granted(a, pl.part_bytes);
+  // p_valid: A is a rank-r operand in a 128-wide zero-padded buffer — its own load-stream kernel (gemm_tn_rank_kernel); the
+  // 128-tile kernel only when a split-K run was given no workspace (WFT_GEMM_DIAG=9 forces it: A/B runs)
+  if (pl.pb > 0 && (pl.nsplit == 1 || pl.use_ws) && g_diag != 9) pl.kind = TN_RANK;
+  else if (!a->c_is_f32) pl.kind = TN_128_BF16C;
+  else if (pl.pb > 0) pl.kind = TN_128_PB;
+  else pl.kind = ring ? TN_128_RING : TN_128_2BUF;
+  return pl;
+}
+
 extern "C" int wft_gemm_tn_segments_ok(const wft_gemm_args* a) {
-  if (!a || a->tn_seg_count < 1 || a->tn_seg_count > 4 || !tn_uses_256(a) || tn_needs_reduce(a) || a->p_valid != 0 || a->batch != 1) return 0;
+  const TnKind k = tn_plan(a).kind;
+  if ((k != TN_4W && k != TN_256) || a->tn_seg_count < 1 || a->tn_seg_count > 4 || tn_needs_reduce(a) || a->p_valid != 0 || a->batch != 1) return 0;
   int prev = 0;
   for (int i = 0; i < a->tn_seg_count; ++i) {
     if (a->tn_seg_end[i] <= prev || !a->tn_seg_ptr[i] || (((uintptr_t)a->tn_seg_ptr[i]) & 15) != 0) return 0;
@@ -1997,6 +2081,34 @@ extern "C" int wft_gemm_tn_segments_ok(const wft_gemm_args* a) {
   }
   return prev == a->M ? 1 : 0;
 }
+extern "C" int64_t wft_gemm_tn_workspace_bytes(const wft_gemm_args* a) { return tn_plan(a).ws_bytes; }
+// 4 gemm_tn4w_kernel, 256 gemm_tn256_kernel, 128 the 128-tile kernel and its rank-r load-stream form
+extern "C" int wft_gemm_tn_variant(const wft_gemm_args* a) {
+  const TnKind k = tn_plan(a).kind;
+  return k == TN_4W ? 4 : k == TN_256 ? 256 : 128;
+}
+
+static int tn_check(const wft_gemm_args* a, const TnPlan& pl, const char* who) {
+  WFT_CHECK_ARG_AS(who, a && a->A && a->B && a->C, "null pointer");
+  WFT_CHECK_ARG_AS(who, a->M >= 128 && a->N >= 128 && a->K >= 1 && a->batch >= 1, "bad shape");
+  WFT_CHECK_ARG_AS(who, a->M % 128 == 0 && a->N % 128 == 0, "P and Q must be multiples of 128");
+  const int rc = gemm_check_common(a, who);
+  if (rc != WFT_OK) return rc;
+  WFT_CHECK_ARG_AS(who, a->M < (1ll << 31) && a->N < (1ll << 31) && a->K < (1ll << 31), "dims exceed int32");
+  if (tn_needs_reduce(a)) {
+    WFT_CHECK_ARG_AS(who, pl.pb > 0, "tn_col_scale / tn_block_n need a rank-r operand (P = 128, 0 < p_valid <= 64)");
+    WFT_CHECK_ARG_AS(who, ws_granted(a, pl.ws_bytes), "tn_col_scale / tn_block_n need the workspace of wft_gemm_tn_workspace_bytes");
+    WFT_CHECK_ARG_AS(who, a->tn_scale_rows >= 0 && (((uintptr_t)a->tn_col_scale) & 15) == 0, "tn_col_scale: 16-byte aligned f32 [S][Q]");
+    if (a->tn_block_n > 0)
+      WFT_CHECK_ARG_AS(who, a->tn_block_n % 4 == 0 && a->N % a->tn_block_n == 0 && a->tn_block_r >= 1 &&
+                       (a->N / a->tn_block_n) * (int64_t)a->tn_block_r <= 16 * pl.pb, "tn_block_n / tn_block_r do not tile the product");
+  }
+  if (a->tn_seg_count > 0)
+    WFT_CHECK_ARG_AS(who, wft_gemm_tn_segments_ok(a) && ws_granted(a, pl.ws_bytes),
+                     "tn_seg_*: not a segmentable call (wft_gemm_tn_segments_ok) or no workspace");
+  return WFT_OK;
+}
+
 static TnSegs tn_segs_of(const wft_gemm_args* a) {
   TnSegs sg;
   for (int i = 0; i < 4; ++i) {
@@ -2006,267 +2118,117 @@ static TnSegs tn_segs_of(const wft_gemm_args* a) {
   }
   return sg;
 }
-extern "C" int64_t wft_gemm_tn_workspace_bytes(const wft_gemm_args* a) {
-  if (!a) return 0;
-  int nsplit = tn_uses_256(a) ? tn256_nsplit(a) : tn128_nsplit(a);
-  if (a->tn_seg_count > 0) {  // segmented output: always through the workspace, even unsplit
-    if (tn_uses_256(a) && wft_tn4w_eligible(a)) {
-      int ns4, per4;
-      wft_tn4w_plan(a, &ns4, &per4);
-      if (ns4 > nsplit) nsplit = ns4;
-    }
-    return (int64_t)nsplit * a->M * a->N * 4;
-  }
-  if (tn_uses_256(a) && wft_tn4w_eligible(a)) {  // (the larger of the two plans: the variant switch may change between this call and the launch)
-    int ns4, per4;
-    wft_tn4w_plan(a, &ns4, &per4);
-    if (ns4 > nsplit) nsplit = ns4;
-  }
-  return (nsplit > 1 || tn_needs_reduce(a)) ? (int64_t)nsplit * tn_ws_rows(a) * a->N * 4 : 0;
+// the kernel that sums the split-K partial tiles of the workspace into C (and applies the adapter-gradient forms)
+static unsigned tn_reduce_grid(const wft_gemm_args* a) {
+  const long g = (a->M * (a->N / 4) + 255) / 256;
+  return (unsigned)(g > 2048 ? 2048 : g);
 }
-
-// Which kernel wft_gemm_tn_bf16 below serves these arguments with (pure host function, like wft_gemm_nt_variant: the launcher's own
-// predicates in the launcher's order, nothing launched): 4 gemm_tn4w_kernel, 256 gemm_tn256_kernel, 128 the 128-tile kernel and its
-// rank-r load-stream form
-extern "C" int wft_gemm_tn_variant(const wft_gemm_args* a) {
-  if (!a || !tn_uses_256(a)) return 128;
-  if (g_tn_variant != 1 && a->variant == 0 && wft_tn4w_eligible(a)) {
-    int nsplit, per;
-    wft_tn4w_plan(a, &nsplit, &per);
-    const bool use_ws = (nsplit > 1 || a->tn_seg_count > 0) && a->workspace && a->workspace_bytes >= (int64_t)nsplit * a->M * a->N * 4 &&
-                        (((uintptr_t)a->workspace) & 15) == 0;
-    if (nsplit == 1 || use_ws) return 4;  // (split without a workspace: the ping-pong kernel's atomic path)
+static TnReduceP tn_reduce_params(const wft_gemm_args* a, const TnPlan& pl) {
+  return TnReduceP{(const float*)a->workspace, (float*)a->C, (long)a->ldc, (int)pl.ws_rows, (int)a->N, pl.nsplit, a->accumulate, (int)a->M,
+                   a->tn_col_scale, a->tn_scale_rows, a->tn_block_n, a->tn_block_r, pl.pb > 0 ? a->p_valid : (int)a->M};
+}
+static void launch_tn_reduce(const wft_gemm_args* a, const TnPlan& pl, hipStream_t s) {
+  const dim3 grid(tn_reduce_grid(a)), block(256);
+  if (a->tn_seg_count > 0) {
+    hipLaunchKernelGGL(tn_splitk_reduce_seg_kernel, grid, block, 0, s, (const float*)a->workspace, tn_segs_of(a), (int)a->M, (int)a->N,
+                       pl.nsplit, a->accumulate);
+    return;
   }
-  return 256;
+  const TnReduceP r = tn_reduce_params(a, pl);
+  hipLaunchKernelGGL(tn_splitk_reduce_kernel, grid, block, 0, s, r.ws, r.C, r.ldc, r.P, r.Q, r.nsplit, r.accumulate, r.Pz, r.col_scale,
+                     r.scale_rows, r.blk_n, r.blk_r, r.Pv);
 }
 
 extern "C" int wft_gemm_tn_bf16(const wft_gemm_args* a, void* stream) {
-  WFT_CHECK_ARG(a && a->A && a->B && a->C, "null pointer");
-  WFT_CHECK_ARG(a->M >= 128 && a->N >= 128 && a->K >= 1 && a->batch >= 1, "bad shape");
-  WFT_CHECK_ARG(a->M % 128 == 0 && a->N % 128 == 0, "P and Q must be multiples of 128");
-  WFT_CHECK_ARG(a->lda % 8 == 0 && a->ldb % 8 == 0 && a->ldc % 4 == 0, "ld alignment");
-  WFT_CHECK_ARG(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->B & 15) == 0 && ((uintptr_t)a->C & 15) == 0,
-                "base pointers must be 16-byte aligned");
-  WFT_CHECK_ARG(!(a->accumulate && !a->c_is_f32), "accumulate needs an f32 C");
-  WFT_CHECK_ARG(a->M < (1ll << 31) && a->N < (1ll << 31) && a->K < (1ll << 31), "dims exceed int32");
-  if (tn_needs_reduce(a)) {
-    WFT_CHECK_ARG(tn128_pb(a) > 0 && !tn_uses_256(a), "tn_col_scale / tn_block_n need a rank-r operand (P = 128, 0 < p_valid <= 64)");
-    WFT_CHECK_ARG(a->workspace && a->workspace_bytes >= wft_gemm_tn_workspace_bytes(a) && (((uintptr_t)a->workspace) & 15) == 0,
-                  "tn_col_scale / tn_block_n need the workspace of wft_gemm_tn_workspace_bytes");
-    WFT_CHECK_ARG(a->tn_scale_rows >= 0 && (((uintptr_t)a->tn_col_scale) & 15) == 0, "tn_col_scale: 16-byte aligned f32 [S][Q]");
-    if (a->tn_block_n > 0)
-      WFT_CHECK_ARG(a->tn_block_n % 4 == 0 && a->N % a->tn_block_n == 0 && a->tn_block_r >= 1 &&
-                    (a->N / a->tn_block_n) * (int64_t)a->tn_block_r <= 16 * tn128_pb(a), "tn_block_n / tn_block_r do not tile the product");
-  }
-  const bool seg = a->tn_seg_count > 0;
-  if (seg)
-    WFT_CHECK_ARG(wft_gemm_tn_segments_ok(a) && a->workspace && a->workspace_bytes >= wft_gemm_tn_workspace_bytes(a) &&
-                  (((uintptr_t)a->workspace) & 15) == 0, "tn_seg_*: not a segmentable call (wft_gemm_tn_segments_ok) or no workspace");
+  const TnPlan pl = tn_plan(a);
+  int rc = tn_check(a, pl, __func__);
+  if (rc != WFT_OK) return rc;
   GemmP p;
   fill_params(a, p);
   hipStream_t s = (hipStream_t)stream;
-  const long nsteps = ((a->K + 63) / 64) * a->batch;
-  if (tn_uses_256(a) && g_tn_variant != 1 && a->variant == 0 && wft_tn4w_eligible(a)) {
-    int nsplit, per;
-    wft_tn4w_plan(a, &nsplit, &per);
-    const bool use_ws = (nsplit > 1 || seg) && a->workspace && a->workspace_bytes >= (int64_t)nsplit * a->M * a->N * 4 &&
-                        (((uintptr_t)a->workspace) & 15) == 0;
-    if (nsplit == 1 || use_ws) {  // (split without a workspace: the ping-pong kernel's atomic path below)
-      if (use_ws) p.ws = (float*)a->workspace;
-      const int rc4 = wft_tn4w_launch(a, p, nsplit, per, stream);
-      if (rc4 != WFT_OK) return rc4;
-      if (use_ws && seg) {
-        const long total = a->M * (a->N / 4);
-        long g = (total + 255) / 256;
-        if (g > 2048) g = 2048;
-        hipLaunchKernelGGL(tn_splitk_reduce_seg_kernel, dim3((unsigned)g), dim3(256), 0, s, (const float*)a->workspace, tn_segs_of(a),
-                           (int)a->M, (int)a->N, nsplit, a->accumulate);
-      } else if (use_ws) {
-        const long total = a->M * (a->N / 4);
-        long g = (total + 255) / 256;
-        if (g > 2048) g = 2048;
-        hipLaunchKernelGGL(tn_splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, s, (const float*)a->workspace, (float*)a->C,
-                           (long)a->ldc, (int)a->M, (int)a->N, nsplit, a->accumulate, (int)a->M, (const float*)nullptr, 0, 0, 0, (int)a->M);
-      }
-      WFT_CHECK_LAUNCH();
-      return WFT_OK;
-    }
-  }
-  if (tn_uses_256(a)) {
-    // 256x256 tiles, one workgroup per CU: pick the split-K factor that fills 256 slots in whole waves
-    const long t256 = (a->M / 256) * (a->N / 256);
-    const int nsplit = tn256_nsplit(a);
-    const bool use_ws = (nsplit > 1 || seg) && a->workspace && a->workspace_bytes >= (int64_t)nsplit * a->M * a->N * 4 &&
-                        (((uintptr_t)a->workspace) & 15) == 0;
-    if (use_ws) p.ws = (float*)a->workspace;
-    if (nsplit > 1 && !use_ws && !a->accumulate)
-      (void)hipMemset2DAsync(a->C, (size_t)a->ldc * 4, 0, (size_t)a->N * 4, (size_t)a->M, s);
-    static DynLdsOnce once;
-    auto kfn = gemm_tn256_kernel<true>;
-    if (!once.set(kfn, WFT_TN_RING * 32768)) return WFT_ERR_LAUNCH;
-    p.nsplit = g_diag == 20 ? -nsplit : nsplit;  // (WFT_GEMM_DIAG=20: round 2's tile-major placement, A/B runs)
-    hipLaunchKernelGGL(kfn, dim3((unsigned)(t256 * nsplit)), dim3(512), WFT_TN_RING * 32768, s, p);
-    if (use_ws && seg) {
-      const long total = a->M * (a->N / 4);
-      long g = (total + 255) / 256;
-      if (g > 2048) g = 2048;
-      hipLaunchKernelGGL(tn_splitk_reduce_seg_kernel, dim3((unsigned)g), dim3(256), 0, s, (const float*)a->workspace, tn_segs_of(a),
-                         (int)a->M, (int)a->N, nsplit, a->accumulate);
-    } else if (use_ws) {
-      const long total = a->M * (a->N / 4);
-      long g = (total + 255) / 256;
-      if (g > 2048) g = 2048;
-      hipLaunchKernelGGL(tn_splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, s, (const float*)a->workspace, (float*)a->C,
-                         (long)a->ldc, (int)a->M, (int)a->N, nsplit, a->accumulate, (int)a->M, (const float*)nullptr, 0, 0, 0, (int)a->M);
-    }
-    WFT_CHECK_LAUNCH();
-    return WFT_OK;
-  }
-  const long tiles = (a->M / 128) * (a->N / 128);
-  const int nsplit = tn128_nsplit(a);
-  const bool use_ws = (nsplit > 1 || tn_needs_reduce(a)) && a->workspace &&
-                      a->workspace_bytes >= (int64_t)nsplit * tn_ws_rows(a) * a->N * 4 && (((uintptr_t)a->workspace) & 15) == 0;
-  if (use_ws) p.ws = (float*)a->workspace;
-  if (nsplit > 1 && !use_ws && !a->accumulate)
+  if (pl.use_ws) p.ws = (float*)a->workspace;
+  else if (pl.nsplit > 1 && !a->accumulate)  // (the splits add to C atomically)
     (void)hipMemset2DAsync(a->C, (size_t)a->ldc * 4, 0, (size_t)a->N * 4, (size_t)a->M, s);
-  dim3 grid((unsigned)tiles, (unsigned)nsplit), block(256);
-  // p_valid: A is a rank-r operand in a 128-wide zero-padded buffer — its own load-stream kernel (gemm_tn_rank_kernel); the
-  // 128-tile kernel below only when a split-K run was given no workspace (WFT_GEMM_DIAG=9 forces it: A/B runs)
-  const int pb = tn128_pb(a);
-  if (pb > 0 && (nsplit == 1 || use_ws) && g_diag != 9) {
-    p.nsplit = nsplit;
-    const dim3 g1((unsigned)(tiles * nsplit));
-#define WFT_RANK_LAUNCH(PBV)                                                                      \
-  {                                                                                               \
-    constexpr int nst = (PBV) <= 2 ? 4 : 3;                                                       \
-    constexpr int bytes = nst * (16384 + 2048 * (PBV));                                           \
-    static DynLdsOnce once;                                                                       \
-    auto kfn = gemm_tn_rank_kernel<PBV>;                                                          \
-    if (!once.set(kfn, bytes)) return WFT_ERR_LAUNCH;                                                                         \
-    hipLaunchKernelGGL(kfn, g1, block, bytes, s, p, p, (int)g1.x);                                \
+  const dim3 grid((unsigned)pl.tiles, (unsigned)pl.nsplit), block(256);
+  switch (pl.kind) {
+    case TN_4W:
+      p.nsplit = pl.nsplit;
+      p.band = pl.per;  // (reused field: reduction steps per split)
+      rc = wft_tn4w_launch(p, (unsigned)(pl.tiles * pl.nsplit), stream);
+      break;
+    case TN_256:
+      p.nsplit = g_diag == 20 ? -pl.nsplit : pl.nsplit;  // (WFT_GEMM_DIAG=20: round 2's tile-major placement, A/B runs)
+      rc = wft_launch_lds<gemm_tn256_kernel<true>>(dim3((unsigned)(pl.tiles * pl.nsplit)), dim3(512), WFT_TN_RING * 32768, s, p);
+      break;
+    case TN_RANK:
+      p.nsplit = pl.nsplit;  // (its grid is 1-D)
+      rc = launch_rank<true>(pl.pb, p, p, (int)(pl.tiles * pl.nsplit), 0, s);
+      break;
+    case TN_128_BF16C: hipLaunchKernelGGL((gemm_tn_kernel<false>), grid, block, 0, s, p); break;
+    case TN_128_PB:
+      if (pl.pb == 1) hipLaunchKernelGGL((gemm_tn_kernel<true, 1>), grid, block, 0, s, p);
+      else if (pl.pb == 2) hipLaunchKernelGGL((gemm_tn_kernel<true, 2>), grid, block, 0, s, p);
+      else if (pl.pb == 3) hipLaunchKernelGGL((gemm_tn_kernel<true, 3>), grid, block, 0, s, p);
+      else hipLaunchKernelGGL((gemm_tn_kernel<true, 4>), grid, block, 0, s, p);
+      break;
+    case TN_128_RING: rc = wft_launch_lds<gemm_tn_kernel<true, 0, 4>>(grid, block, 131072, s, p); break;
+    case TN_128_2BUF: hipLaunchKernelGGL((gemm_tn_kernel<true>), grid, block, 0, s, p); break;
   }
-    if (pb == 1) WFT_RANK_LAUNCH(1)
-    else if (pb == 2) WFT_RANK_LAUNCH(2)
-    else if (pb == 3) WFT_RANK_LAUNCH(3)
-    else WFT_RANK_LAUNCH(4)
-#undef WFT_RANK_LAUNCH
-  } else if (!a->c_is_f32) hipLaunchKernelGGL((gemm_tn_kernel<false>), grid, block, 0, s, p);
-  else if (pb == 1) hipLaunchKernelGGL((gemm_tn_kernel<true, 1>), grid, block, 0, s, p);
-  else if (pb == 2) hipLaunchKernelGGL((gemm_tn_kernel<true, 2>), grid, block, 0, s, p);
-  else if (pb == 3) hipLaunchKernelGGL((gemm_tn_kernel<true, 3>), grid, block, 0, s, p);
-  else if (pb == 4) hipLaunchKernelGGL((gemm_tn_kernel<true, 4>), grid, block, 0, s, p);
-  else if (tn128_ring(a)) {
-    static DynLdsOnce once;
-    auto kfn = gemm_tn_kernel<true, 0, 4>;
-    if (!once.set(kfn, 131072)) return WFT_ERR_LAUNCH;
-    hipLaunchKernelGGL(kfn, grid, block, 131072, s, p);
-  } else hipLaunchKernelGGL((gemm_tn_kernel<true>), grid, block, 0, s, p);
-  if (use_ws) {
-    const long total = a->M * (a->N / 4);
-    long g = (total + 255) / 256;
-    if (g > 2048) g = 2048;
-    hipLaunchKernelGGL(tn_splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, s, (const float*)a->workspace, (float*)a->C,
-                       (long)a->ldc, (int)tn_ws_rows(a), (int)a->N, nsplit, a->accumulate, (int)a->M, a->tn_col_scale,
-                       a->tn_scale_rows, a->tn_block_n, a->tn_block_r, pb > 0 ? a->p_valid : (int)a->M);
-  }
+  if (rc != WFT_OK) return rc;
+  if (pl.use_ws) launch_tn_reduce(a, pl, s);
   WFT_CHECK_LAUNCH();
   return WFT_OK;
 }
-
 
 // ---------------------------------------------------------------------------------- paired rank-r launches (round 3)
 // The four rank-r products of one adapted Linear group's backward are two independent pairs: {u = x (sA*m)^T, du = dy (sB)} and
 // {dA = du^T x, dB^T = u^T dy}.  Each pair goes out as ONE launch of the load-stream kernel (and the two split-K reduces of the
 // second pair as one): half the launches, and a grid that fills the chip (an NT rank product alone is 1.46 rounds of 256 CUs at
 // 32 clips).  Same arithmetic per product as the single entry points: bit-identical results.  Anything the load-stream kernels do
-// not take falls back to two calls of the single entry point.
-static int nt_rank_pb(const wft_gemm_args* a) {
-  return (!a->c_is_f32 && a->N == 128 && a->batch == 1 && a->p_valid > 0 && a->p_valid <= 64 && a->epilogue == WFT_EPI_NONE &&
-          !a->bias && !a->residual && !a->aux && !a->colsum && a->valid_rows_period == 0 && g_diag != 9 && a->M >= 1 && a->K >= 64 &&
-          a->K % 64 == 0 && a->lda % 8 == 0 && a->ldb % 8 == 0 && a->ldc % 4 == 0 && a->A && a->B && a->C &&
-          (((uintptr_t)a->A | (uintptr_t)a->B | (uintptr_t)a->C) & 15) == 0 && a->M < (1ll << 31) && a->K < (1ll << 31))
-             ? (a->p_valid + 15) / 16 : 0;
-}
+// not take falls back to two calls of the single entry point, which reports what is wrong with it.
 extern "C" int wft_gemm_nt_rank_pair_bf16(const wft_gemm_args* a0, const wft_gemm_args* a1, void* stream) {
   WFT_CHECK_ARG(a0 && a1, "null pointer");
-  const int pb0 = nt_rank_pb(a0), pb1 = nt_rank_pb(a1);
-  if (pb0 == 0 || pb0 != pb1 || g_diag == 21) {  // (WFT_GEMM_DIAG=21: always two launches, A/B runs)
+  const NtPlan pl0 = nt_plan(a0), pl1 = nt_plan(a1);
+  if (pl0.kind != NT_RANK || pl1.kind != NT_RANK || pl0.pb != pl1.pb || g_diag == 21 ||  // (WFT_GEMM_DIAG=21: always two launches, A/B runs)
+      nt_check(a0, pl0, __func__) != WFT_OK || nt_check(a1, pl1, __func__) != WFT_OK) {
     const int rc = wft_gemm_nt_bf16(a0, stream);
     return rc != WFT_OK ? rc : wft_gemm_nt_bf16(a1, stream);
   }
   GemmP p0, p1;
   fill_params(a0, p0);
   fill_params(a1, p1);
-  const int n0 = (int)((a0->M + 127) / 128), n1 = (int)((a1->M + 127) / 128);
-  hipStream_t s = (hipStream_t)stream;
-#define WFT_NT_RANK_PAIR(PBV)                                                                     \
-  {                                                                                               \
-    constexpr int nst = (PBV) <= 2 ? 4 : 3;                                                       \
-    constexpr int bytes = nst * (16384 + 2048 * (PBV));                                           \
-    static DynLdsOnce once;                                                                       \
-    auto kfn = gemm_nt_rank_kernel<PBV>;                                                          \
-    if (!once.set(kfn, bytes)) return WFT_ERR_LAUNCH;                                                                         \
-    hipLaunchKernelGGL(kfn, dim3((unsigned)(n0 + n1)), dim3(256), bytes, s, p0, p1, n0);          \
-  }
-  if (pb0 == 1) WFT_NT_RANK_PAIR(1)
-  else if (pb0 == 2) WFT_NT_RANK_PAIR(2)
-  else if (pb0 == 3) WFT_NT_RANK_PAIR(3)
-  else WFT_NT_RANK_PAIR(4)
-#undef WFT_NT_RANK_PAIR
+  const int rc = launch_rank<false>(pl0.pb, p0, p1, (int)pl0.grid_x, (int)pl1.grid_x, (hipStream_t)stream);
+  if (rc != WFT_OK) return rc;
   WFT_CHECK_LAUNCH();
   return WFT_OK;
 }
 
 // both through the workspace + reduce (what the adapter-gradient forms tn_col_scale / tn_block_n always do)
-static bool tn_rank_pair_ok(const wft_gemm_args* a) {
-  return a->A && a->B && a->C && a->c_is_f32 && tn128_pb(a) > 0 && !tn_uses_256(a) && a->N >= 128 && a->N % 128 == 0 && a->K >= 1 &&
-         a->batch >= 1 && a->lda % 8 == 0 && a->ldb % 8 == 0 && a->ldc % 4 == 0 &&
-         (((uintptr_t)a->A | (uintptr_t)a->B | (uintptr_t)a->C | (uintptr_t)a->workspace | (uintptr_t)a->tn_col_scale) & 15) == 0 &&
-         a->workspace && a->workspace_bytes >= (int64_t)tn128_nsplit(a) * tn_ws_rows(a) * a->N * 4 && a->tn_scale_rows >= 0 &&
-         (a->tn_block_n == 0 || (a->tn_block_n % 4 == 0 && a->N % a->tn_block_n == 0 && a->tn_block_r >= 1 &&
-                                 (a->N / a->tn_block_n) * (int64_t)a->tn_block_r <= 16 * tn128_pb(a))) &&
-         a->N < (1ll << 31) && a->K < (1ll << 31) && g_diag != 9 && g_diag != 21;
-}
 extern "C" int wft_gemm_tn_rank_pair_bf16(const wft_gemm_args* a0, const wft_gemm_args* a1, void* stream) {
   WFT_CHECK_ARG(a0 && a1, "null pointer");
-  if (!tn_rank_pair_ok(a0) || !tn_rank_pair_ok(a1) || tn128_pb(a0) != tn128_pb(a1)) {
+  const wft_gemm_args* as[2] = {a0, a1};
+  const TnPlan pl[2] = {tn_plan(a0), tn_plan(a1)};
+  bool paired = pl[0].pb == pl[1].pb && g_diag != 21;
+  for (int i = 0; i < 2 && paired; ++i)
+    paired = pl[i].kind == TN_RANK && ws_granted(as[i], pl[i].part_bytes) && tn_check(as[i], pl[i], __func__) == WFT_OK;
+  if (!paired) {
     const int rc = wft_gemm_tn_bf16(a0, stream);
     return rc != WFT_OK ? rc : wft_gemm_tn_bf16(a1, stream);
   }
   hipStream_t s = (hipStream_t)stream;
-  const wft_gemm_args* as[2] = {a0, a1};
   GemmP p[2];
   TnReduceP r[2];
   int nb[2], gr[2];
   for (int i = 0; i < 2; ++i) {
-    const wft_gemm_args* a = as[i];
-    fill_params(a, p[i]);
-    const int nsplit = tn128_nsplit(a);
-    p[i].ws = (float*)a->workspace;
-    p[i].nsplit = nsplit;
-    nb[i] = (int)((a->N / 128) * nsplit);
-    const long total = a->M * (a->N / 4);
-    long g = (total + 255) / 256;
-    if (g > 2048) g = 2048;
-    gr[i] = (int)g;
-    r[i] = TnReduceP{(const float*)a->workspace, (float*)a->C, (long)a->ldc, (int)tn_ws_rows(a), (int)a->N, nsplit, a->accumulate,
-                     (int)a->M, a->tn_col_scale, a->tn_scale_rows, a->tn_block_n, a->tn_block_r, a->p_valid};
+    fill_params(as[i], p[i]);
+    p[i].ws = (float*)as[i]->workspace;
+    p[i].nsplit = pl[i].nsplit;
+    nb[i] = (int)(pl[i].tiles * pl[i].nsplit);
+    gr[i] = (int)tn_reduce_grid(as[i]);
+    r[i] = tn_reduce_params(as[i], pl[i]);
   }
-  const int pb = tn128_pb(a0);
-#define WFT_TN_RANK_PAIR(PBV)                                                                     \
-  {                                                                                               \
-    constexpr int nst = (PBV) <= 2 ? 4 : 3;                                                       \
-    constexpr int bytes = nst * (16384 + 2048 * (PBV));                                           \
-    static DynLdsOnce once;                                                                       \
-    auto kfn = gemm_tn_rank_kernel<PBV>;                                                          \
-    if (!once.set(kfn, bytes)) return WFT_ERR_LAUNCH;                                                                         \
-    hipLaunchKernelGGL(kfn, dim3((unsigned)(nb[0] + nb[1])), dim3(256), bytes, s, p[0], p[1], nb[0]); \
-  }
-  if (pb == 1) WFT_TN_RANK_PAIR(1)
-  else if (pb == 2) WFT_TN_RANK_PAIR(2)
-  else if (pb == 3) WFT_TN_RANK_PAIR(3)
-  else WFT_TN_RANK_PAIR(4)
-#undef WFT_TN_RANK_PAIR
+  const int rc = launch_rank<true>(pl[0].pb, p[0], p[1], nb[0], nb[1], s);
+  if (rc != WFT_OK) return rc;
   hipLaunchKernelGGL(tn_splitk_reduce_pair_kernel, dim3((unsigned)(gr[0] + gr[1])), dim3(256), 0, s, r[0], r[1], gr[0]);
   WFT_CHECK_LAUNCH();
   return WFT_OK;

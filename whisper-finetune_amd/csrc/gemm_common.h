@@ -77,3 +77,11 @@ struct DynLdsOnce {
     return true;
   }
 };
+// launch of a kernel whose dynamic LDS exceeds the 64 KiB default: one DynLdsOnce per kernel, however many call sites launch it
+template <auto KFN, class... Args>
+static inline int wft_launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t s, const Args&... args) {
+  static DynLdsOnce once;
+  if (!once.set(KFN, lds_bytes)) return WFT_ERR_LAUNCH;
+  hipLaunchKernelGGL(KFN, grid, block, lds_bytes, s, args...);
+  return WFT_OK;
+}

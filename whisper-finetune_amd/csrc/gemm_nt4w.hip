@@ -673,32 +673,28 @@ bool wft_nt4w_eligible(const wft_gemm_args* a) {
   const bool epi_ok = a->epilogue == WFT_EPI_NONE || ((a->epilogue == WFT_EPI_GELU_GRAD || a->epilogue == WFT_EPI_MUL_AUX || aux8) && !a->residual);
   if (a->colsum && a->epilogue != WFT_EPI_MUL_AUX && a->epilogue != WFT_EPI_MUL_AUX8) return false;  // (fused column sums exist for the fc2 backward-data product only)
   if (aux8 && (a->batch != 1 || a->alpha != 1.f)) return false;
+  if (a->epilogue == WFT_EPI_MUL_AUX8 && a->bias) return false;  // (the epilogue that reads the one-byte buffer adds no bias)
   return epi_ok && !a->c_is_f32 && !a->accumulate && a->K % 128 == 0 && a->K >= 256 && a->N % 256 == 0 && a->lda >= a->K &&
          a->valid_rows_period == 0 && !a->residual_first && 256 * a->lda * 2 < (1ll << 31) && 256 * a->ldb * 2 < (1ll << 31) &&
          256 * a->ldc * 2 < (1ll << 31) && 256 * a->ldr * 2 < (1ll << 31) && (aux8 || 256 * a->ldaux * 2 < (1ll << 31));
 }
 
-int wft_nt4w_launch(const wft_gemm_args* a, const GemmP& p, bool persistent, void* stream) {
-  const long t256 = ((a->M + 255) / 256) * (a->N / 256) * a->batch;
-  const int ncu = wft_num_cus();
-  dim3 grid((unsigned)((t256 < ncu || !persistent) ? t256 : ncu)), block(256);
-  hipStream_t s = (hipStream_t)stream;
-#define LAUNCH_4W(E, R, CSF)                                              \
-  do {                                                                    \
-    auto kfn = gemm_nt4w_kernel<E, R, CSF>;                               \
-    static DynLdsOnce once;                                               \
-    if (!once.set(kfn, NT4W_LDS)) return WFT_ERR_LAUNCH;                                              \
-    hipLaunchKernelGGL(kfn, grid, block, NT4W_LDS, s, p);                 \
-  } while (0)
-  const bool res = a->residual != nullptr, csf = p.cs_part != nullptr;
+// f(epilogue, residual, fused column sums) as compile-time constants, for the combinations gemm_nt4w_kernel is instantiated with
+template <int E>
+using Nt4wEpi = std::integral_constant<int, E>;
+int wft_nt4w_launch(const wft_gemm_args* a, const GemmP& p, unsigned grid, void* stream) {
+  const auto f = [&](auto e, auto res, auto csf) {
+    return wft_launch_lds<gemm_nt4w_kernel<decltype(e)::value, decltype(res)::value, decltype(csf)::value>>(
+        dim3(grid), dim3(256), NT4W_LDS, (hipStream_t)stream, p);
+  };
+  const auto with_cs = [&](auto e) { return p.cs_part ? f(e, std::false_type{}, std::true_type{}) : f(e, std::false_type{}, std::false_type{}); };
   switch (a->epilogue) {
-    case WFT_EPI_NONE: if (res) LAUNCH_4W(WFT_EPI_NONE, true, false); else LAUNCH_4W(WFT_EPI_NONE, false, false); break;
-    case WFT_EPI_GELU_GRAD: LAUNCH_4W(WFT_EPI_GELU_GRAD, false, false); break;
-    case WFT_EPI_MUL_AUX: if (csf) LAUNCH_4W(WFT_EPI_MUL_AUX, false, true); else LAUNCH_4W(WFT_EPI_MUL_AUX, false, false); break;
-    case WFT_EPI_GELU_GRAD8: LAUNCH_4W(WFT_EPI_GELU_GRAD8, false, false); break;
-    case WFT_EPI_MUL_AUX8: if (csf) LAUNCH_4W(WFT_EPI_MUL_AUX8, false, true); else LAUNCH_4W(WFT_EPI_MUL_AUX8, false, false); break;
+    case WFT_EPI_NONE: return a->residual ? f(Nt4wEpi<WFT_EPI_NONE>{}, std::true_type{}, std::false_type{})
+                                          : f(Nt4wEpi<WFT_EPI_NONE>{}, std::false_type{}, std::false_type{});
+    case WFT_EPI_GELU_GRAD: return f(Nt4wEpi<WFT_EPI_GELU_GRAD>{}, std::false_type{}, std::false_type{});
+    case WFT_EPI_MUL_AUX: return with_cs(Nt4wEpi<WFT_EPI_MUL_AUX>{});
+    case WFT_EPI_GELU_GRAD8: return f(Nt4wEpi<WFT_EPI_GELU_GRAD8>{}, std::false_type{}, std::false_type{});
+    case WFT_EPI_MUL_AUX8: return with_cs(Nt4wEpi<WFT_EPI_MUL_AUX8>{});
     default: wft_set_error("wft_gemm_nt_bf16: unknown epilogue %d", a->epilogue); return WFT_ERR_ARG;
   }
-#undef LAUNCH_4W
-  return WFT_OK;
 }

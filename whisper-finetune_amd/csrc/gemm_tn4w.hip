@@ -389,13 +389,7 @@ void wft_tn4w_plan(const wft_gemm_args* a, int* nsplit_out, int* per_out) {
   *per_out = (int)per;
   *nsplit_out = (int)ns;
 }
-int wft_tn4w_launch(const wft_gemm_args* a, GemmP p, int nsplit, int per, void* stream) {
-  const long t256 = (a->M / 256) * (a->N / 256);
-  p.nsplit = nsplit;
-  p.band = per;  // (reused field: reduction steps per split)
-  static DynLdsOnce once;
-  auto kfn = gemm_tn4w_kernel;
-  if (!once.set(kfn, TN4W_LDS)) return WFT_ERR_LAUNCH;
-  hipLaunchKernelGGL(kfn, dim3((unsigned)(t256 * nsplit)), dim3(256), TN4W_LDS, (hipStream_t)stream, p);
-  return WFT_OK;
+// p.nsplit / p.band (reused field: reduction steps per split) carry the plan; grid = output tiles x splits
+int wft_tn4w_launch(const GemmP& p, unsigned grid, void* stream) {
+  return wft_launch_lds<gemm_tn4w_kernel>(dim3(grid), dim3(256), TN4W_LDS, (hipStream_t)stream, p);
 }

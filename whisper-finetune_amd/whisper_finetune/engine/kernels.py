@@ -344,16 +344,10 @@ def gemm_nt(a, b, *, M=None, N=None, K=None, lda=None, ldb=None, out=None, out_f
     if colsum is not None:  # f32 [N]: column sums of C (bias gradient of C's consumer), fused into the epilogue when possible
         _chk(colsum, F32, "colsum")
         args.colsum = colsum.data_ptr()
-        need = L.load().wft_gemm_nt_colsum_workspace_bytes(C.byref(args))
-        if need > 0:
-            ws = _tn_workspace(a.device, need, slot="nt_colsum")
-            args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+        _grant_workspace(args, "wft_gemm_nt_colsum_workspace_bytes", a.device, "nt_colsum")
     elif not out_f32 and batch == 1 and epilogue == L.EPI_NONE and K >= 4096 and N * M <= (1 << 21):
         # few output tiles over a deep K (the tied-embedding backward-data product of a short decoder batch): split-K partials
-        need = L.load().wft_gemm_nt_splitk_workspace_bytes(C.byref(args))
-        if need > 0:
-            ws = _tn_workspace(a.device, need, slot="nt_splitk")
-            args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+        _grant_workspace(args, "wft_gemm_nt_splitk_workspace_bytes", a.device, "nt_splitk")
     if _args_only:  # (paired launches: gemm_nt_rank_pair)
         return args, out
     if epilogue in (L.EPI_GELU_GRAD8, L.EPI_MUL_AUX8):
@@ -402,18 +396,14 @@ def gemm_nt_stream(a, b, *, M=None, N=None, K=None, lda=None, ldb=None, out=None
         args.C, args.ldc = out.data_ptr(), out.stride(-2) if ldc is None else ldc
     else:
         args.C, args.ldc = 1 << 20, N  # (a placeholder with the alignment a fresh tensor has: nothing is allocated for a refused call)
-    lib = L.load()
-    need = lib.wft_gemm_nt_stream_workspace_bytes(C.byref(args))
-    if need <= 0:
+    if _grant_workspace(args, "wft_gemm_nt_stream_workspace_bytes", a.device, "nt_stream") <= 0:
         return None
     if out is None:
         out = torch.empty((M, N), dtype=BF16, device=a.device)
         args.C, args.ldc = out.data_ptr(), out.stride(-2)
-    ws = _tn_workspace(a.device, need, slot="nt_stream")
-    args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
     if _args_only:
         return args, out
-    L.check(lib.wft_gemm_nt_stream_bf16(C.byref(args), L.stream_ptr()), "wft_gemm_nt_stream_bf16")
+    L.check(L.load().wft_gemm_nt_stream_bf16(C.byref(args), L.stream_ptr()), "wft_gemm_nt_stream_bf16")
     return out
 
 
@@ -491,10 +481,7 @@ def gemm_tn(a, b, *, P=None, Q=None, R=None, lda=None, ldb=None, out=None, out_f
             args.tn_seg_end[i], args.tn_seg_ptr[i] = end, t.data_ptr()
         if not lib.wft_gemm_tn_segments_ok(C.byref(args)):
             return None
-    need = lib.wft_gemm_tn_workspace_bytes(C.byref(args))
-    if need > 0:
-        ws = _tn_workspace(a.device, need, slot=_ws_slot)
-        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    _grant_workspace(args, "wft_gemm_tn_workspace_bytes", a.device, _ws_slot)
     if _args_only:  # (paired launches: gemm_tn_rank_pair)
         return args, out
     L.check(lib.wft_gemm_tn_bf16(C.byref(args), L.stream_ptr()), "wft_gemm_tn_bf16")
@@ -532,6 +519,16 @@ def _tn_workspace(device, nbytes: int, slot: str = "tn") -> torch.Tensor:
         ws = torch.empty(max(nbytes, 64 << 20), dtype=torch.uint8, device=device)
         _TN_WS[key] = ws
     return ws
+
+
+def _grant_workspace(args, query: str, device, slot: str) -> int:
+    """Ask the library's `query`(args) how much scratch the call wants and, if any, point args.workspace / workspace_bytes at the
+    device's `slot`.  -> the answer (<= 0: no workspace wanted, or the call is not served in that form)."""
+    need = getattr(L.load(), query)(C.byref(args))
+    if need > 0:
+        ws = _tn_workspace(device, need, slot=slot)
+        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    return need
 
 
 # --------------------------------------------------------------------------- attention
@@ -621,10 +618,7 @@ def _attn_decode_call(a, stem: str, q, cache, n_head: int, scale: float, new_kv,
             raise ValueError(f"{who}: k_new / v_new must be [rows, H*64] views with one row stride")
         a.k_new, a.v_new, a.ld_new, a.len = k.data_ptr(), v.data_ptr(), k.stride(0), lens.data_ptr()
     a.H, a.Tk, a.scale, a.q_prescaled = n_head, cache.shape[1], scale, int(bool(q_prescaled))
-    need = getattr(L.load(), stem + "_workspace_bytes")(C.byref(a))
-    if need > 0:
-        ws = _tn_workspace(q.device, need, slot=who)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    _grant_workspace(a, stem + "_workspace_bytes", q.device, who)
     if args_only:  # (timing tools replay one argument struct)
         return a, o
     L.check(getattr(L.load(), stem + "_bf16")(C.byref(a), L.stream_ptr()), stem + "_bf16")
