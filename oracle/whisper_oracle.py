@@ -335,7 +335,7 @@ class _RoundWeight(torch.autograd.Function):
 
 
 class _EmulatedAttention(torch.autograd.Function):
-    """The attention kernels' arithmetic (csrc/attn.hip) on [B, H, T, 64] fp32 tensors holding bf16 values:
+    """The attention kernels' arithmetic (csrc/attn_fwd.hip, attn_bwd.hip, attn_dq4w.hip, attn_dkdv4w.hip) on [B, H, T, 64] fp32 tensors holding bf16 values:
     forward  S = q k^T (fp32) -> P = exp(scale*S - max) -> l = sum P (fp32, unrounded P) -> O = (bf16(P) v) / l -> bf16;
     backward recompute P = exp(scale*S - lse), delta = sum_d dO*O, dP = dO v^T, dS = P (dP - delta),
              dV = bf16(P)^T dO, dQ = scale * bf16(dS) k, dK = scale * bf16(dS)^T q, each stored as bf16."""

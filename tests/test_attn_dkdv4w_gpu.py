@@ -1,4 +1,4 @@
-"""GPU tests of the one-wave-per-SIMD dK/dV kernel (csrc/attn.hip, attn_bwd_dkdv4w_kernel), called through the C ABI.
+"""GPU tests of the one-wave-per-SIMD dK/dV kernel (csrc/attn_dkdv4w.hip, attn_bwd_dkdv4w_kernel), called through the C ABI.
 
 The kernel serves the non-causal attention backward of the encoder blocks and of the decoder's cross attention (reference:
 whisper's MultiHeadAttention reached through src/whisper_finetune/model/model_utils.py:283-285, 320-325; its backward is autograd's).

@@ -1,4 +1,4 @@
-"""GPU tests of the one-wave-per-SIMD dQ kernel (csrc/attn.hip, attn_bwd_dq4w_kernel), called through the C ABI.
+"""GPU tests of the one-wave-per-SIMD dQ kernel (csrc/attn_dq4w.hip, attn_bwd_dq4w_kernel), called through the C ABI.
 
 The kernel serves the non-causal attention backward of the encoder blocks (reference: whisper's MultiHeadAttention reached through
 src/whisper_finetune/model/model_utils.py:283-285; its backward is autograd's).  It forms every dQ element from the same products

@@ -1,4 +1,4 @@
-"""GPU tests of the software-pipelined forward attention kernel (csrc/attn.hip, attn_fwd_pipe_kernel), called through the C ABI.
+"""GPU tests of the software-pipelined forward attention kernel (csrc/attn_fwd.hip, attn_fwd_pipe_kernel), called through the C ABI.
 
 The kernel serves the non-causal attention forward of the encoder blocks and the decoder's cross attention over long key ranges
 (reference: whisper's MultiHeadAttention.qkv_attention reached through src/whisper_finetune/model/model_utils.py:283-285,320-322).

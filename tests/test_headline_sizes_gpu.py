@@ -1,6 +1,6 @@
 """Correctness at the sizes bench.py TIMES (VERDICT r5 "weak" 1a): the headline is 96 clips of whisper-large-v3 — 144 000 activation rows,
 1.47 GB GEMM operands, byte offsets close to the 32-bit eligibility limits of the one-wave-per-SIMD kernels (gemm_nt4w.hip, gemm_tn4w.hip,
-attn.hip: the dispatch predicates) — and the turbo YAML's B = 64, S = 448 logits (28 672 x 51 866).  The row-count tests run at 96 clips
+attn_dq4w.hip, attn_dkdv4w.hip: the dispatch predicates) — and the turbo YAML's B = 64, S = 448 logits (28 672 x 51 866).  The row-count tests run at 96 clips
 (bench.py's --batch default, read from its source: test_headline_sizes_cover_the_benchmark_default_batch) AND at the 87 clips = 130 500
 rows of the earlier headline; each has edges the other lacks: 130 500 = 509 x 256 + 196 (ragged last row tile) = 2039 x 64 + 4 (ragged
 reduction tail), 144 000 = 562 x 256 + 128 (half a last row tile) = 2250 x 64 (no tail).  The CPU oracle cannot run these sizes:

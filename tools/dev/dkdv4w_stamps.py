@@ -1,5 +1,5 @@
-"""Developer script (GPU box): where a workgroup of attn_bwd_dkdv4w_kernel spends its clock ticks (build with -DD4_STAMPS, see
-csrc/attn.hip; WFT_LIB points at that build).   WFT_LIB=.../libwft_stamps.so python tools/dev/dkdv4w_stamps.py"""
+"""Developer script (GPU box): where a workgroup of attn_bwd_dkdv4w_kernel spends its clock ticks (csrc/attn_dkdv4w.hip; build:
+make -C whisper-finetune_amd/csrc ATTN_DEFS=-DD4_STAMPS OUT=../libwft_stamps.so).   WFT_LIB=.../libwft_stamps.so python tools/dev/dkdv4w_stamps.py"""
 import ctypes, os, sys, torch
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[2] / "whisper-finetune_amd"))

@@ -1,5 +1,5 @@
 """Developer script (GPU box): where a wave of attn_fwd_kernel spends its clock ticks per 64-key tile (encoder call: 20 heads, 1500 x 1500;
-build: tools/dev/fwd_stamps.sh -> libwft_fwdstamps.so, selected through WFT_LIB).  Ideal per tile and wave: 16 MFMA 32x32x16 = 512
+build: tools/dev/fwd_stamps.sh = make ATTN_DEFS=-DFWD_STAMPS OUT=../libwft_fwdstamps.so, selected through WFT_LIB).  Ideal per tile and wave: 16 MFMA 32x32x16 = 512
 matrix-pipe cycles; the vector stream is 32 v_exp_f32 (8 issue cycles each) + ~100 other vector instructions (4.5 each)."""
 import ctypes, os, sys, torch
 from pathlib import Path
