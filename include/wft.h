@@ -554,6 +554,35 @@ typedef struct {
 } wft_beam_update_args;
 int wft_beam_update(const wft_beam_update_args* args, void* stream);
 
+/* ------------------------------------------------------ Sampled decoding */
+/* wft_decode_pick / wft_decode_pick_ts with a temperature per state row (csrc/decode.hip): upstream's `GreedyDecoder.update` at
+ * temperature > 0 (`Categorical(logits / temperature).sample()`), restated with a counter-based generator on the device
+ * (openai-whisper is not a dependency: parity with the upstream binary and with torch's random stream is unpinned).
+ *  rows: args->B = R state rows; state row r reads logits row r / group (group >= 1, R % group == 0), so the prefill's one row per
+ *    audio feeds all `group` samples of that audio.  Everything else in `args` is per state row, as in wft_decode_pick.
+ *  temperature f32 [R], seed u64 [R]: DEVICE memory, read by the kernel; nothing of the launch depends on their values (one
+ *    captured graph serves every temperature and every seed).
+ *  live columns: exactly those of wft_decode_pick / wft_decode_pick_ts — the suppress / suppress_first masks, then the timestamp
+ *    rules; rule 5 is decided on the UNTEMPERED row (upstream's filters run before the division by the temperature).
+ *  t = temperature[r] <= 0: the row behaves as wft_decode_pick(_ts) does, bit for bit in pick, log-probability and state.
+ *  t > 0: key(col) = x[col] * (1.0f / t) + g(col) in fp32 over the live columns; pick = arg-max of the key, ties to the lower
+ *    column; a live column whose logit is -inf is never picked (the Gumbel-max rule: the pick is a draw from softmax(x / t)).
+ *  logprob: the pick's log-softmax over the live columns at temperature 1 (upstream sums F.log_softmax(logits) of the sampled
+ *    token, not the tempered one).
+ *  state update: that of wft_decode_pick word for word — a finished row is frozen; tokens / sum_logprob / len / finished /
+ *    max_len / unfinished[0] / pick_out / logprob_out as there; no live column: the pick is eot with log-probability 0.
+ *  noise: g(col) = -logf(-logf(v)) with the accurate logf; v from Philox4x32-10 (Salmon et al. 2011: multipliers 0xD2511F53 /
+ *    0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85) under key = (low, high 32 bits of seed[r]), counter = (col >> 2, L, 0, 0)
+ *    with L = len[r] before the update (the position the token is written to); output word col & 3; k = word >> 9;
+ *    v = (2k + 1) * 2^-24 — an odd 24-bit integer scaled: exact in fp32, inside (0, 1).  Known answers: counter 0, key 0 ->
+ *    6627e8d5 e169c58d bc57ac4c 9b00dbd8; all-ones counter and key -> 408f276d 41c83b0e a20bc7c6 6d5451fd.  The noise depends on
+ *    (seed, position, column) only — not on masks, batch, group or launch shape.  No atomics: reruns are bit-identical.
+ *  errors (returned without a launch): NULL temperature / seed; group < 1 or R % group != 0; whatever wft_decode_pick /
+ *    wft_decode_pick_ts reject.                                                                                                  */
+typedef struct { const float* temperature; const uint64_t* seed; int group; } wft_sample_rules;
+int wft_decode_sample(const wft_decode_pick_args* args, const wft_sample_rules* sample, void* stream);
+int wft_decode_sample_ts(const wft_decode_pick_args* args, const wft_sample_rules* sample, const wft_ts_rules* rules, void* stream);
+
 /* ------------------------------------------------- Log-mel + SpecAugment */
 /* whisper.audio.log_mel_spectrogram (data/data_loader.py:278; SURVEY.md App.
  * A.2): reflect-pad 200, Hann-400 STFT hop 160, |.|^2, mel filterbank,

@@ -23,7 +23,13 @@
          same rows, V = 51 866, --batches = rows: histories of 100 sampled tokens ending in text, so every rule-5 pass runs (the
          two arg-best pairs, the two sums, and for top-k the third scan).
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,beam,ts] [--batches 1,8,32] [--out FILE]
+  sample the sampled pick (wft_decode_sample, wft_decode_sample_ts at temperature 1) against the greedy pick (wft_decode_pick,
+         wft_decode_pick_ts) on the same rows, V = 51 866, R = 5 * B rows (--batches = audios, e.g. 1,4,6 for R = 5, 20, 30): what Philox
+         and two logf per column cost beside the 104 KB row read; then sample_decode(best_of = 5) over B audios against
+         beam_decode(W = 5) over B audios and greedy_decode at batch 5 * B, eager and graph: tokens/s, ms per step.
+         (profiles/decode_bench_sample.jsonl: --parts sample --batches 1,4,6 --out profiles/decode_bench_sample.jsonl)
+
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,beam,ts,sample] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -539,6 +545,87 @@ def bench_ts(batches):
         del logits
 
 
+def bench_sample(batches, N=5, new_tokens=64, runs=3):
+    """(i) the sampled pick against the greedy pick, plain and under the timestamp rules, at R = N * B rows: bench_ts's rows and
+    rotating logits buffers, issued through the Python wrappers (their host time is in every arm); (ii) sample_decode(best_of = N)
+    against beam_decode(W = N) over B audios and greedy_decode at batch N * B."""
+    from whisper_finetune.engine import decode as Dm
+
+    V, n_ctx, tsb, eot = 51866, CAP, 50365, 50257
+    ld = K.round_up(V, 128)
+    i32 = dict(dtype=torch.int32, device=DEV)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for B in batches:
+        R = B * N
+        logits = [(torch.randn(R, ld, device=DEV, generator=g) * 3).to(BF) for _ in range(LAYERS)]
+        tokens = torch.randint(0, eot, (R, n_ctx), device=DEV, generator=g)
+        tokens[:, 4] = tsb + 10  # the opening timestamp of every row; text behind it
+        sup = torch.zeros(V, dtype=torch.uint8, device=DEV); sup[eot + 1:tsb] = 1
+        first = torch.full((R,), 4, **i32)
+        st = dict(lens=torch.full((R,), 104, **i32), fin=torch.zeros(R, **i32), slp=torch.zeros(R, device=DEV), unf=torch.zeros(1, **i32))
+        temps = {0.0: torch.zeros(R, device=DEV), 1.0: torch.ones(R, device=DEV)}
+        seeds = torch.arange(R, dtype=torch.int64, device=DEV) + 1234
+        rules = (tsb, tsb - 1, 50)
+
+        def pick(ru):
+            st["fin"].zero_()
+            for lg in logits:
+                st["lens"].fill_(104)
+                K.decode_pick(lg, V, tokens, st["lens"], st["fin"], st["slp"], st["unf"], eot=eot, max_len=n_ctx, suppress=sup, first_len=first, ts_rules=ru)
+
+        def sample(ru, t):
+            st["fin"].zero_()
+            for lg in logits:
+                st["lens"].fill_(104)
+                K.decode_sample(lg, V, tokens, st["lens"], st["fin"], st["slp"], st["unf"], temps[t], seeds, eot=eot, max_len=n_ctx, suppress=sup,
+                                first_len=first, ts_rules=ru)
+
+        res = ab({"pick": lambda: pick(None), "sample_t0": lambda: sample(None, 0.0), "sample": lambda: sample(None, 1.0),
+                  "pick_ts": lambda: pick(rules), "sample_ts_t0": lambda: sample(rules, 0.0), "sample_ts": lambda: sample(rules, 1.0)}, iters=2)
+        rec = dict(part="sample", arm="pick", rows=R, V=V, sampled_tokens=100, logits_MB=round(R * V * 2 / 1e6, 2),
+                   note="us per call; every arm includes one fill_ of `len` per call; _t0: the sampled kernel at temperature 0 (its greedy path)")
+        for n, (med, mn, spread) in res.items():
+            rec[n + "_us"] = round(med * 1e3 / LAYERS, 2)
+            rec[n + "_min_us"] = round(mn * 1e3 / LAYERS, 2)
+            rec[n + "_spread"] = round(spread, 3)
+        rec["sample_vs_pick"] = round(res["sample"][0] / res["pick"][0], 2)
+        rec["sample_ts_vs_pick_ts"] = round(res["sample_ts"][0] / res["pick_ts"][0], 2)
+        emit(rec)
+        del logits
+
+    m, dims = _random_large_v3()
+    for B in batches:
+        R = B * N
+        gm = torch.Generator(device="cuda").manual_seed(B)
+        mel = torch.randn(R, dims.n_mels, 2 * dims.n_audio_ctx, device=DEV, generator=gm)
+        prompt = torch.tensor([[50258, 50261, 50360, 50364]], device=DEV).expand(R, 4).contiguous()
+        max_len = 4 + new_tokens
+        kw = dict(eot=eot, suppress=[eot])  # eot suppressed: every row generates exactly new_tokens tokens
+        arms = {}
+        for mode in ("eager", "graph"):
+            arms["sample_" + mode] = lambda n=1, mode=mode: m.sample_decode(mel[:B], prompt[:B], None, temperature=1.0, best_of=N, seed=7,
+                                                                            max_len=max_len if n else 5, step=mode, **kw)
+            arms["beam_" + mode] = lambda n=1, mode=mode: m.beam_decode(mel[:B], prompt[:B], None, beam_size=N, max_len=max_len if n else 5, step=mode, **kw)
+            arms["greedy_" + mode] = lambda n=1, mode=mode: m.greedy_decode(mel, prompt, None, max_len=max_len if n else 5, step=mode, **kw)
+        times, pre = {a: [] for a in arms}, {a: [] for a in arms}
+        for fn in arms.values():
+            fn()  # warm-up: shadows, workspaces, code objects, the capture
+        for rnd in range(runs):
+            for a, fn in arms.items():
+                torch.cuda.synchronize(); t0 = time.perf_counter(); fn(); torch.cuda.synchronize(); times[a].append(time.perf_counter() - t0)
+                torch.cuda.synchronize(); t0 = time.perf_counter(); fn(0); torch.cuda.synchronize(); pre[a].append(time.perf_counter() - t0)
+        for a in arms:
+            med, pre_s = statistics.median(times[a]), statistics.median(pre[a])
+            mode = a.split("_")[1]
+            emit(dict(part="sample", arm="e2e_" + a, B=B, N=N, rows=R, new_tokens=new_tokens, runs_s=[round(t, 4) for t in times[a]], median_s=round(med, 4),
+                      spread=round((max(times[a]) - min(times[a])) / med, 3), encoder_prefill_s=round(pre_s, 4),
+                      ms_per_step=round((med - pre_s) / (new_tokens - 1) * 1e3, 3),
+                      tok_s=round((R if a.startswith("greedy") else B) * new_tokens / med, 1), row_tok_s=round(R * new_tokens / med, 1),
+                      time_vs_beam=round(med / statistics.median(times["beam_" + mode]), 3),
+                      time_vs_greedy_at_R_rows=round(med / statistics.median(times["greedy_" + mode]), 3)))
+        Dm.release_graphs(m)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="attn,gemm,e2e")
@@ -551,7 +638,7 @@ def main():
     emit(dict(part="env", device=torch.cuda.get_device_name(0), lib=L.load().wft_version().decode(), torch=torch.__version__))
     for part in a.parts.split(","):
         {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": bench_gemm_stream, "e2e_step": bench_e2e_step,
-         "beam": bench_beam, "ts": bench_ts}[part](batches)
+         "beam": bench_beam, "ts": bench_ts, "sample": bench_sample}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

@@ -11,6 +11,7 @@
 //  decode_pick_kernel / decode_count_kernel        suppress, arg-max, log-probability, state update, unfinished-row count
 //  decode_topk_kernel / beam_update_kernel         the W + 1 best continuations per hypothesis; one beam-search step per audio
 //  decode_pick_kernel<true> / decode_topk_kernel<true>   the same two under upstream's timestamp rules (ts_row_rules, ts_decide)
+//  decode_sample_kernel<TS>                         the pick with a temperature per row: Gumbel-max over Philox noise (include/wft.h "Sampled decoding")
 #include "common.h"
 
 // ----------------------------------------------------------------------------- single-token attention
@@ -801,6 +802,195 @@ extern "C" int wft_decode_pick_ts(const wft_decode_pick_args* a, const wft_ts_ru
   if (int rc = ts_check(ru, a->eot, a->V, __func__)) return rc;
   WFT_CHECK_ARG(a->first_len, "the timestamp rules need first_len");
   hipLaunchKernelGGL(decode_pick_kernel<true>, dim3((unsigned)a->B), dim3(PICK_THREADS), 0, (hipStream_t)stream, *a, *ru);
+  hipLaunchKernelGGL(decode_count_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int*)a->finished, a->B, a->unfinished);
+  WFT_CHECK_LAUNCH();
+  return WFT_OK;
+}
+
+// ----------------------------------------------------------------------------- sampled pick (include/wft.h "Sampled decoding")
+// decode_pick_kernel with one more question per row: t = temperature[r] > 0 draws the token by the Gumbel-max rule — the arg-max of
+// key(col) = x[col] / t + g(col) over the live columns is a draw from softmax(x / t) — and t <= 0 is decode_pick_kernel's own code,
+// statement for statement (same scans, same reduction order: same bits).  The noise is a pure function of (seed[r], len[r], col):
+// Philox4x32-10 keyed by the seed, counter (col >> 2, len, 0, 0), output word col & 3; one block serves the 4 columns of a lane's
+// 16-byte read half, so a lane runs 2 blocks per 8 columns (kept in registers across the calls of pick_scan's f).
+struct philox4 {
+  unsigned w[4];
+};
+
+__host__ __device__ __forceinline__ unsigned philox_mulhi(unsigned a, unsigned b) { return (unsigned)(((unsigned long long)a * b) >> 32); }
+
+__host__ __device__ __forceinline__ philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned h0 = philox_mulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const unsigned h1 = philox_mulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0;
+    c1 = l1;
+    c2 = h0 ^ c3 ^ k1;
+    c3 = l0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return philox4{{c0, c1, c2, c3}};
+}
+
+// g = -log(-log(v)), v = (2k + 1) * 2^-24 with k the word's top 23 bits: an odd 24-bit integer scaled, exact in fp32 and inside
+// (0, 1).  The accurate logf: the winners are the columns with v near 1, where -log(v) ~ 1 - v is tiny and __logf's absolute error
+// would be a large relative one.
+__device__ __forceinline__ float gumbel_of(unsigned word) {
+  const float v = (float)(2u * (word >> 9) + 1u) * 5.9604644775390625e-08f;
+  return -logf(-logf(v));
+}
+
+// the per-row noise source: g(col), one Philox block per 4 columns, the last block kept
+struct gumbel_row {
+  unsigned k0, k1, pos;
+  int blk;
+  philox4 cur;
+  __device__ __forceinline__ float operator()(int col) {
+    if ((col >> 2) != blk) {
+      blk = col >> 2;
+      cur = philox4x32_10((unsigned)blk, pos, 0u, 0u, k0, k1);
+    }
+    const int j = col & 3;
+    const unsigned w = j == 0 ? cur.w[0] : (j == 1 ? cur.w[1] : (j == 2 ? cur.w[2] : cur.w[3]));
+    return gumbel_of(w);
+  }
+};
+
+// the logit of the workgroup's winning key column `bi` in every thread: the thread that brought (mine_i == bi) publishes the logit
+// it carried.  s_x: used by nothing else.
+__device__ __forceinline__ float sample_wg_logit(int bi, int mine_i, float mine_x, float* s_x) {
+  if (bi != PICK_NONE && mine_i == bi) *s_x = mine_x;
+  __syncthreads();
+  return bi != PICK_NONE ? *s_x : -INFINITY;
+}
+
+// Plain form: the key scan rides the max pass (one HBM read of the row), the sum pass is decode_pick_kernel's.  TS form: ts_decide's
+// two passes on the UNTEMPERED row (upstream filters before GreedyDecoder.update divides by the temperature), then — t > 0 only — one
+// more scan of the L2-resident row under the final predicate, as decode_topk_kernel<true> does; the log-probability reuses
+// ts_decide's maximum and sums.  Either way it is the pick's log-softmax at temperature 1 over the live columns.
+template <bool TS>
+__global__ __launch_bounds__(PICK_THREADS) void decode_sample_kernel(wft_decode_pick_args a, wft_ts_rules ru, const float* temperature,
+                                                                     const unsigned long long* seed, int group) {
+  __shared__ float s_v[PICK_WAVES];
+  __shared__ int s_i[PICK_WAVES];
+  __shared__ float s_sum[PICK_WAVES];
+  __shared__ float s_x;
+  const int b = blockIdx.x;
+  const unsigned short* row = a.logits + (long)(b / group) * a.ld;
+  const int V = (int)a.V;
+  const int L = a.len[b];
+  const unsigned char* m1 = a.suppress;
+  const unsigned char* m2 = (a.suppress_first && a.first_len && L == a.first_len[b]) ? a.suppress_first : nullptr;
+  const float temp = temperature[b];
+  const bool draw = temp > 0.f;
+  const float inv_t = draw ? 1.0f / temp : 0.f;
+  const unsigned long long sd = seed[b];
+  gumbel_row g = {(unsigned)sd, (unsigned)(sd >> 32), (unsigned)L, -1, {}};
+
+  float best = -INFINITY;
+  int bi = PICK_NONE;
+  float lp;
+  float kbest = -INFINITY, kx = -INFINITY;  // the best key of this thread's columns, its column and its logit
+  int ki = PICK_NONE;
+  auto key = [&](float x, int col) {
+    const float k = x * inv_t + g(col);
+    if (k > kbest) {  // (strict, ascending columns: a tie stays with the lower column; a -inf logit never enters)
+      kbest = k;
+      ki = col;
+      kx = x;
+    }
+  };
+  if constexpr (TS) {
+    __shared__ int s_ts[PICK_WAVES];
+    __shared__ float s_sum2[PICK_WAVES];
+    ts_row t = ts_row_rules(ru, a.tokens + (long)b * a.ld_tokens, a.ld_tokens, a.first_len[b], L, V, a.eot, s_ts);
+    const ts_pass p = ts_decide(row, V, m1, m2, t.ts_begin, [&](int col) { return ts_live(t, col); }, s_v, s_i, s_sum, s_sum2);
+    if (draw) {
+      if (p.wins) t.text_lo = t.ts_begin;
+      pick_scan(row, V, m1, m2, [&](int col) { return ts_live(t, col); }, key);
+      const int mine = ki;
+      __syncthreads();
+      pick_wg_best(kbest, ki, s_v, s_i);
+      bi = ki;
+      best = sample_wg_logit(bi, mine, kx, &s_x);
+      lp = (best - p.m) - __logf(p.wins ? p.ss : p.st + p.ss);
+    } else {
+      const bool ts = p.wins || pick_better(p.bs, p.is, p.bt, p.it);
+      best = ts ? p.bs : p.bt;
+      bi = ts ? p.is : p.it;
+      lp = p.wins ? (p.bs - p.m) - __logf(p.ss) : -__logf(p.st + p.ss);
+    }
+  } else {
+    if (draw) {
+      pick_scan(row, V, m1, m2, pick_all{}, [&](float x, int col) {
+        if (x > best) {
+          best = x;
+          bi = col;
+        }
+        key(x, col);
+      });
+    } else {
+      pick_scan(row, V, m1, m2, pick_all{}, [&](float x, int col) {
+        if (x > best) {
+          best = x;
+          bi = col;
+        }
+      });
+    }
+    pick_wg_best(best, bi, s_v, s_i);
+    if (draw) {
+      const int mine = ki;
+      __syncthreads();
+      pick_wg_best(kbest, ki, s_v, s_i);
+      const float x = sample_wg_logit(ki, mine, kx, &s_x);
+      const float sum = pick_wg_sumexp(row, V, m1, m2, best, bi != PICK_NONE, s_sum);
+      lp = (x - best) - __logf(sum);
+      bi = ki;
+    } else {
+      lp = -__logf(pick_wg_sumexp(row, V, m1, m2, best, bi != PICK_NONE, s_sum));
+    }
+  }
+  const bool any = bi != PICK_NONE;
+  if (threadIdx.x == 0) {
+    const long pick = any ? bi : a.eot;  // (every column suppressed: the row ends)
+    if (!any) lp = 0.f;
+    if (a.pick_out) a.pick_out[b] = pick;
+    if (a.logprob_out) a.logprob_out[b] = lp;
+    if (!a.finished[b]) {  // a finished row is frozen
+      if (L >= 0 && L < a.max_len) {
+        a.tokens[(long)b * a.ld_tokens + L] = pick;
+        a.sum_logprob[b] += lp;
+        a.len[b] = L + 1;
+      }
+      a.finished[b] = (pick == a.eot || L + 1 >= a.max_len) ? 1 : 0;
+    }
+  }
+}
+
+static int sample_check(const wft_decode_pick_args* a, const wft_sample_rules* s, const char* who) {
+  if (int rc = pick_check(a, who)) return rc;
+  WFT_CHECK_ARG_AS(who, s && s->temperature && s->seed, "null pointer (temperature / seed)");
+  WFT_CHECK_ARG_AS(who, s->group >= 1 && a->B % s->group == 0, "group must be >= 1 and divide the state rows");
+  return WFT_OK;
+}
+
+extern "C" int wft_decode_sample(const wft_decode_pick_args* a, const wft_sample_rules* s, void* stream) {
+  if (int rc = sample_check(a, s, __func__)) return rc;
+  hipLaunchKernelGGL(decode_sample_kernel<false>, dim3((unsigned)a->B), dim3(PICK_THREADS), 0, (hipStream_t)stream, *a, wft_ts_rules{},
+                     s->temperature, (const unsigned long long*)s->seed, s->group);
+  hipLaunchKernelGGL(decode_count_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int*)a->finished, a->B, a->unfinished);
+  WFT_CHECK_LAUNCH();
+  return WFT_OK;
+}
+
+extern "C" int wft_decode_sample_ts(const wft_decode_pick_args* a, const wft_sample_rules* s, const wft_ts_rules* ru, void* stream) {
+  if (int rc = sample_check(a, s, __func__)) return rc;
+  if (int rc = ts_check(ru, a->eot, a->V, __func__)) return rc;
+  WFT_CHECK_ARG(a->first_len, "the timestamp rules need first_len");
+  hipLaunchKernelGGL(decode_sample_kernel<true>, dim3((unsigned)a->B), dim3(PICK_THREADS), 0, (hipStream_t)stream, *a, *ru, s->temperature,
+                     (const unsigned long long*)s->seed, s->group);
   hipLaunchKernelGGL(decode_count_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int*)a->finished, a->B, a->unfinished);
   WFT_CHECK_LAUNCH();
   return WFT_OK;

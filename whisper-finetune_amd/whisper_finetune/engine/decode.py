@@ -4,7 +4,12 @@ The greedy path of upstream's `whisper.decoding` (`DecodingTask._main_loop` with
 `SuppressBlank`, `DecodingOptions(without_timestamps=True)`) and, in the second half of this file, its `BeamSearchDecoder` +
 `MaximumLikelihoodRanker` on a KV cache that the beams of an audio share (`BeamCache`, `beam_decode`); with `timestamp_begin=` both
 decode under upstream's `ApplyTimestampRules` (restated in include/wft.h "Timestamp rules"; the pick / top-k kernels apply them,
-`timestamp_segments` reads the result); no tokenizer, temperature fallback or language detection.
+`timestamp_segments` reads the result).  The third part is sampling: `sample_decode` draws `best_of` samples per audio at a
+temperature on the device (wft_decode_sample: Gumbel-max over Philox noise, include/wft.h "Sampled decoding") on a cache whose samples
+share the prompt keys and the cross keys / values (`SampleCache`), and `decode_with_fallback` is upstream's temperature ladder of
+`transcribe()` (`decode_with_fallback`, `needs_fallback`: average log-probability, compression ratio, no-speech probability).
+Upstream's behaviour is restated; parity with its binary and with torch's random stream is unpinned.  No tokenizer, language
+detection or long-audio `transcribe()` (INTEGRATION.md).
 
 Everything that changes from token to token lives in device memory (`KVCache`: len / tokens / finished / sum_logprob), so a
 step is a fixed sequence of launches whose arguments never change: LayerNorm and every projection through the existing
@@ -236,10 +241,11 @@ def _greedy_body(decoder, cache: KVCache) -> torch.Tensor:
 # ----------------------------------------------------------------------------- the captured step
 MAX_SESSIONS = 2  # graph sessions kept per model and kind of decoding; the oldest is evicted
 # model -> OrderedDict[key -> _GraphSession], one table per kind, so greedy and beam sessions are counted and evicted apart:
-# key = (batch, device), or (audios, beam, candidates, device) for beam search.  Kept OFF the module, like engine/graph.py's
+# key = (batch, device), (audios, beam, candidates, device) for beam search, (audios, best_of, device) for sampling.  Kept OFF the module, like engine/graph.py's
 # registry: CUDAGraph objects neither pickle nor deep-copy, and a dropped model drops its sessions.
 _SESSIONS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 _BEAM_SESSIONS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
+_SAMPLE_SESSIONS: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 
 
 def _groups(decoder):
@@ -374,10 +380,15 @@ def beam_sessions(model) -> dict:
     return dict(_BEAM_SESSIONS.get(model) or {})
 
 
+def sample_sessions(model) -> dict:
+    """{(audios, best_of, device): session} of `model`: the captured sampling steps (a third table, counted and evicted apart)."""
+    return dict(_SAMPLE_SESSIONS.get(model) or {})
+
+
 def release_graphs(model) -> None:
     """Drop every captured decoding step of `model` with the static buffers it pins (self-attention cache, cross keys / values,
     the graph's private pool).  The evaluator calls it when a dataset is done, so nothing stays pinned during training."""
-    for table in (_SESSIONS, _BEAM_SESSIONS):
+    for table in (_SESSIONS, _BEAM_SESSIONS, _SAMPLE_SESSIONS):
         reg = table.pop(model, None)
         if reg:
             reg.clear()
@@ -397,11 +408,12 @@ def _check_mode(model, who: str, step: str, sync_every: int) -> None:
 
 
 def _decode(model, mel: torch.Tensor, start: dict, *, who: str, table, key: tuple, make_cache, prefill, first, body, readout, extra=(),
-            graph: bool, stream: bool, sync_every: int):
+            graph: bool, stream: bool, sync_every: int, xa: Optional[torch.Tensor] = None):
     """The loop of greedy_decode and beam_decode -> readout(cache) after the last step (read while the model is still in eval mode).  make_cache(decoder) builds the cache (kept in a
     graph session of `table` under key + (device,) when `graph`), start: the arguments of its start(); prefill(decoder, cache, xa)
     -> logits, first(decoder, cache, logits): the update they feed, body(decoder, cache): one cached step with its update.
-    Host reads: the fingerprint check once after the prefill, the `unfinished` counter every `sync_every` steps."""
+    Host reads: the fingerprint check once after the prefill, the `unfinished` counter every `sync_every` steps.
+    xa: the encoder output of `mel` when the caller already has it (decode_with_fallback runs the encoder once for all rungs)."""
     was_training = model.training
     model.eval()
     try:
@@ -415,7 +427,7 @@ def _decode(model, mel: torch.Tensor, start: dict, *, who: str, table, key: tupl
         # updates until the shortest prompt reaches max_len (start() has just set len to the prompt lengths; nothing ran since)
         most = cache.max_len - int(cache.len.min())
         if most > 0:
-            logits = prefill(dec, cache, model.encoder(mel))
+            logits = prefill(dec, cache, model.encoder(mel) if xa is None else xa)
             if graph:
                 sess.adopt_prefill()
             first(dec, cache, logits)
@@ -442,7 +454,7 @@ def _decode(model, mel: torch.Tensor, start: dict, *, who: str, table, key: tupl
 def greedy_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None, *, eot: int, max_len: Optional[int] = None,
                   suppress: Sequence[int] = (), suppress_first: Sequence[int] = (), sync_every: int = 8, step: str = "eager",
                   timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
-                  max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True, _stream_gemm: bool = True):
+                  max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True, _stream_gemm: bool = True, _xa=None):
     """-> (tokens i64 [B, L] — prompt included, padded with `eot` behind each row's end —, lengths i64 [B], sum_logprob f32 [B]).
 
     timestamp_begin (default None: no rules, today's path exactly): the first timestamp id; every pick then runs under upstream's
@@ -457,7 +469,7 @@ def greedy_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=Non
     (`stream_gemm`) and are replayed from ONE captured HIP graph per (batch, device) session — the first step of a decode that
     has no valid graph runs eagerly, the second is captured; at most MAX_SESSIONS sessions per model, `release_graphs(model)` frees
     them.  The prefill and the encoder keep their kernels in both modes.  `_capture=False` / `_stream_gemm=False` switch off one
-    half each (tests and the A/B bench only)."""
+    half each (tests and the A/B bench only); `_xa`: the encoder output of `mel`, when decode_with_fallback has it already."""
     _check_mode(model, "greedy_decode", step, sync_every)
     rules = check_ts_rules(model.dims.n_vocab, eot, suppress, suppress_first, timestamp_begin, no_timestamps, max_initial_timestamp_index)
     ts_kw = dict(timestamp_begin=timestamp_begin, no_timestamps=no_timestamps, max_initial_timestamp_index=max_initial_timestamp_index)
@@ -473,7 +485,7 @@ def greedy_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=Non
     return _decode(model, mel, dict(prompt=prompt, prompt_len=prompt_len, eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first, **ts_kw),
                    who="greedy_decode", table=_SESSIONS, key=(int(B),), make_cache=lambda dec: KVCache(dec, B, device=mel.device),
                    prefill=prefill, first=pick, body=_greedy_body, readout=readout, extra=ts_extra(rules), graph=step == "graph" and _capture,
-                   stream=step == "graph" and _stream_gemm, sync_every=sync_every)
+                   stream=step == "graph" and _stream_gemm, sync_every=sync_every, xa=_xa)
 
 
 # ============================================================================= beam search
@@ -663,7 +675,7 @@ def beam_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None,
                 length_penalty: Optional[float] = None, eot: int, max_len: Optional[int] = None, suppress: Sequence[int] = (),
                 suppress_first: Sequence[int] = (), sync_every: int = 8, step: str = "eager", return_all: bool = False,
                 timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
-                max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True, _stream_gemm: bool = True):
+                max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True, _stream_gemm: bool = True, _xa=None):
     """Beam search -> (tokens i64 [B, L], lengths i64 [B], sum_logprob f32 [B]) of the winning hypothesis per audio, in greedy_decode's
     layout: prompt included, the `eot` that ended the hypothesis included (one that ran into `max_len` has none), padded with `eot`.
     return_all: a fourth value, per audio the list of (tokens, sum_logprob, score) of all its entries, best score first (stable).
@@ -672,7 +684,7 @@ def beam_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None,
     sum_logprob / n over the generated tokens (n without the final eot), or sum_logprob / ((5 + n) / 6) ** length_penalty.
     timestamp_begin / no_timestamps / max_initial_timestamp_index: as greedy_decode (default: no rules), every hypothesis under
     its own history; beam search needs max_initial_timestamp_index >= beam_size - 1 or None (check_ts_rules says why).
-    Argument errors are raised before any device work.  `step`, `sync_every`, `_capture`, `_stream_gemm`: as greedy_decode; the
+    Argument errors are raised before any device work.  `step`, `sync_every`, `_capture`, `_stream_gemm`, `_xa`: as greedy_decode; the
     captured beam steps live in their own sessions (`beam_sessions`), freed by `release_graphs` too."""
     C = beam_candidates(beam_size, patience)
     if length_penalty is not None and (isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float))):
@@ -702,7 +714,326 @@ def beam_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None,
                    who="beam_decode", table=_BEAM_SESSIONS, key=(int(B), int(beam_size), int(C)),
                    make_cache=lambda dec: BeamCache(dec, B, beam_size, C, device=mel.device), prefill=beam_prefill, first=_beam_first,
                    body=_beam_body, readout=readout, extra=(("beam", beam_size, C),) + ts_extra(rules), graph=step == "graph" and _capture,
-                   stream=step == "graph" and _stream_gemm, sync_every=sync_every)
+                   stream=step == "graph" and _stream_gemm, sync_every=sync_every, xa=_xa)
+
+
+# ============================================================================= sampling and the temperature ladder
+# Upstream's `GreedyDecoder` at temperature > 0 with `best_of` samples, its `MaximumLikelihoodRanker`, and the fallback loop of
+# `transcribe()` (`decode_with_fallback`), restated (none of it is in the reference tree and openai-whisper is not a dependency:
+# parity with the upstream binary and with torch's random stream is unpinned).  N = best_of; audio a owns the state rows
+# r = a*N + j.  The N samples of an audio are what the beam kernels were built for (DESIGN.md §3 "Sampling layouts"): one copy of the
+# cross keys / values per audio read once per step for all N rows (the group = N form), and the prompt keys shared through the
+# ancestry table — which for samples is STATIC: position t of row r lives in slot a*N while t is a prompt position and in slot r
+# from there on.  The pick is wft_decode_sample: temperature and seed per row are device memory, so one captured step serves every
+# rung of the ladder and every seed.
+class SampleCache(_Cache):
+    """Keys / values plus the state of `audios` audios x `best_of` samples (R = audios * best_of slot rows), handed to the decoder
+    as `kv_cache=` like a BeamCache: the prefill carries ONE row per audio (k / v into slot row a*N), a step all R rows.
+      self_kv[attn]  bf16 [R, n_text_ctx, 2d];  anc i32 [R, n_text_ctx]: a*N below the prompt length of audio a, r from there on
+      cross_kv[attn] bf16 [audios, n_audio_ctx, 2d]   one copy per audio, shared by its samples
+      tokens i64 [R, n_ctx], len / first_len / finished i32 [R], sum_logprob f32 [R], unfinished i32 [1] (counts ROWS)
+      temperature f32 [R], seed i64 [R] (the bits of the u64 the kernel reads)"""
+
+    def __init__(self, decoder, audios: int, best_of: int, device=None):
+        N = int(best_of)
+        if not 1 <= N <= MAX_BEAM:
+            raise ValueError(f"best_of must lie in [1, {MAX_BEAM}] (the group limit of the cross-attention form)")
+        self.audios, self.beam = int(audios), N  # (`beam`: the rows per audio, under the name beam_prefill and the step methods read)
+        R = self.audios * N
+        super().__init__(decoder, R, R, device)
+        device = self.tokens.device
+        self.anc = torch.zeros((R, self.n_ctx), dtype=torch.int32, device=device)
+        self.first_len = torch.ones(R, dtype=torch.int32, device=device)
+        self.finished = torch.zeros(R, dtype=torch.int32, device=device)
+        self.temperature = torch.zeros(R, dtype=torch.float32, device=device)
+        self.seed = torch.zeros(R, dtype=torch.int64, device=device)
+
+    def start(self, prompt: torch.Tensor, prompt_len: Optional[torch.Tensor], *, temperature, seeds: Sequence[int], eot: int,
+              max_len: Optional[int] = None, suppress: Sequence[int] = (), suppress_first: Sequence[int] = (), n_vocab: int,
+              timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None, max_initial_timestamp_index: Optional[int] = 50) -> None:
+        """Load the prompts (i64 [audios, T], right-padded; prompt_len [audios] or None) into all N rows of every audio, write the
+        static ancestry table and reset the state.  temperature: one number or R of them; seeds: R integers (taken mod 2^64)."""
+        B, N, R = self.audios, self.beam, self.batch
+        rules = check_ts_rules(n_vocab, eot, suppress, suppress_first, timestamp_begin, no_timestamps, max_initial_timestamp_index)
+        seeds = [int(s) % (1 << 64) for s in seeds]
+        if len(seeds) != R:
+            raise ValueError(f"seeds: {R} integers expected, got {len(seeds)}")
+        T, pl = self._start(B, prompt, prompt_len, eot, max_len, suppress, suppress_first, n_vocab, rules)
+        dev = self.tokens.device
+        self.tokens.view(B, N, self.n_ctx)[:, :, :T].copy_(prompt.to(dev)[:, None, :])
+        plr = pl.repeat_interleave(N)
+        self.len.copy_(plr)
+        self.first_len.copy_(self.len)
+        own = torch.arange(R, dtype=torch.int32)
+        shared = (torch.arange(B, dtype=torch.int32) * N).repeat_interleave(N)
+        self.anc.copy_(torch.where(torch.arange(self.n_ctx)[None, :] < plr[:, None], shared[:, None], own[:, None]))
+        self.finished.copy_((plr >= self.max_len).to(torch.int32))
+        self.unfinished.copy_((self.finished == 0).sum().to(torch.int32).reshape(1))
+        t = torch.as_tensor(temperature, dtype=torch.float32).reshape(-1)
+        self.temperature.copy_(t.expand(R) if t.numel() == 1 else t.reshape(R))
+        self.seed.copy_(torch.tensor([s - (1 << 64) if s >= (1 << 63) else s for s in seeds], dtype=torch.int64))
+
+    # the layout is BeamCache's (slot rows behind an ancestry table, one cross copy per audio), and so is the code that reads it
+    store_prefill = BeamCache.store_prefill
+    self_step = BeamCache.self_step
+    cross_step = BeamCache.cross_step
+
+
+def sample_pick(decoder, cache: SampleCache, logits: torch.Tensor, want_pick: bool = False):
+    """Sampled pick and state update of every unfinished row (wft_decode_sample; _ts under timestamp rules).  logits: one row per
+    state row, or — the prefill's — one per audio, which then feeds all of its N samples (group = N)."""
+    V = decoder.token_embedding.weight.shape[0]
+    return K.decode_sample(logits, V, cache.tokens, cache.len, cache.finished, cache.sum_logprob, cache.unfinished, cache.temperature, cache.seed,
+                           group=cache.batch // logits.shape[0], eot=cache.eot, max_len=cache.max_len, suppress=cache.suppress,
+                           suppress_first=cache.suppress_first, first_len=cache.first_len, want_pick=want_pick, ts_rules=cache.ts_rules)
+
+
+def _sample_body(decoder, cache: SampleCache) -> torch.Tensor:
+    logits = step(decoder, cache)
+    sample_pick(decoder, cache, logits)
+    return logits
+
+
+def sample_seeds(seed, audios: int, best_of: int) -> list:
+    """The per-row seeds of sample_decode: `seed` an int (audio a draws with seed + a) or one int per audio; sample j of an audio
+    with seed s draws with (8*s + j) mod 2^64."""
+    if isinstance(seed, bool):
+        raise ValueError(f"seed must be an integer or one per audio, got {seed!r}")
+    if isinstance(seed, int):
+        per_audio = [seed + a for a in range(audios)]
+    else:
+        per_audio = [int(s) for s in (seed.tolist() if hasattr(seed, "tolist") else seed)]
+        if len(per_audio) != audios:
+            raise ValueError(f"seed: one integer or {audios} of them (one per audio), got {len(per_audio)}")
+    return [(8 * s + j) % (1 << 64) for s in per_audio for j in range(best_of)]
+
+
+def _check_sampling(temperature, best_of, length_penalty=None) -> None:
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not 0 <= temperature < float("inf"):
+        raise ValueError(f"temperature must be a finite number >= 0, got {temperature!r}")
+    if isinstance(best_of, bool) or not isinstance(best_of, int) or not 1 <= best_of <= MAX_BEAM:
+        raise ValueError(f"best_of must be an integer in [1, {MAX_BEAM}], got {best_of!r}")
+    if length_penalty is not None and (isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float))):
+        raise ValueError(f"length_penalty must be None or a number, got {length_penalty!r}")
+
+
+@torch.no_grad()
+def sample_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None, *, temperature: float, best_of: int = 1, seed=0,
+                  length_penalty: Optional[float] = None, return_all: bool = False, eot: int, max_len: Optional[int] = None,
+                  suppress: Sequence[int] = (), suppress_first: Sequence[int] = (), sync_every: int = 8, step: str = "eager",
+                  timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
+                  max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True, _stream_gemm: bool = True, _xa=None):
+    """`best_of` samples per audio at `temperature`, the best of them -> (tokens i64 [B, L], lengths i64 [B], sum_logprob f32 [B]) in
+    greedy_decode's layout.  return_all: a fourth value, per audio the list of (tokens, sum_logprob, score) of its samples, best
+    score first (stable).
+
+    Every token is a draw from softmax(logits / temperature) over the live columns — the suppress masks and, with timestamp_begin,
+    the timestamp rules, as in greedy_decode — made on the device (wft_decode_sample); `sum_logprob` sums the tokens'
+    log-probabilities at temperature 1, as upstream does.  The winner maximises sum_logprob / n (n generated tokens without the
+    final eot), or sum_logprob / ((5 + n) / 6) ** length_penalty (`beam_rank`: upstream's MaximumLikelihoodRanker); ties go to the
+    lower sample.  temperature = 0 returns greedy_decode's result (upstream drops best_of at 0).
+    seed: an int — audio a then draws with seed + a — or one int per audio; sample j of an audio with seed s draws with
+    (8*s + j) mod 2^64.  The noise depends on (that seed, position, column) only, so a result does not depend on the batch an audio
+    is decoded in.  Errors (temperature < 0, best_of outside 1..8, ...) are raised before any device work.
+    `step`, `sync_every`, `_capture`, `_stream_gemm`, `_xa`: as greedy_decode.  The captured steps live in a third table
+    (`sample_sessions`, keyed (audios, best_of, device)); temperature and seeds are device memory, so a second call with other
+    values replays the same graph."""
+    _check_sampling(temperature, best_of, length_penalty)
+    B, N = int(prompt.shape[0]), int(best_of)
+    seeds = sample_seeds(seed, B, N)
+    _check_mode(model, "sample_decode", step, sync_every)
+    rules = check_ts_rules(model.dims.n_vocab, eot, suppress, suppress_first, timestamp_begin, no_timestamps, max_initial_timestamp_index)
+    ts_kw = dict(timestamp_begin=timestamp_begin, no_timestamps=no_timestamps, max_initial_timestamp_index=max_initial_timestamp_index)
+    if temperature == 0:
+        res = greedy_decode(model, mel, prompt, prompt_len, eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first,
+                            sync_every=sync_every, step=step, _capture=_capture, _stream_gemm=_stream_gemm, _xa=_xa, **ts_kw)
+        if return_all:
+            toks, lens, slp = res[0].cpu().tolist(), res[1].cpu().tolist(), res[2].cpu().tolist()
+            first = [int(prompt.shape[1])] * B if prompt_len is None else torch.as_tensor(prompt_len).reshape(B).tolist()
+            res += ([[(toks[a][:lens[a]], slp[a], beam_score(_generated_n(toks[a], first[a], lens[a], eot), slp[a], length_penalty))] for a in range(B)],)
+        return res
+
+    def readout(cache):
+        tokens, lens, first, slp = cache.tokens.cpu().tolist(), cache.len.cpu().tolist(), cache.first_len.cpu().tolist(), cache.sum_logprob.cpu().tolist()
+        ranked, wins = [], []
+        for a in range(B):
+            rows = range(a * N, (a + 1) * N)
+            ns = [_generated_n(tokens[r], first[r], lens[r], cache.eot) for r in rows]
+            entries = [(tokens[r][:lens[r]], slp[r], beam_score(n, slp[r], length_penalty)) for r, n in zip(rows, ns)]
+            wins.append(entries[beam_rank([(n, slp[r]) for r, n in zip(rows, ns)], length_penalty)])
+            ranked.append(sorted(entries, key=lambda e: -e[2]))
+        L = max(len(t) for t, _, _ in wins)
+        out = torch.full((B, L), cache.eot, dtype=torch.int64)
+        for a, (t, _, _) in enumerate(wins):
+            out[a, :len(t)] = torch.tensor(t, dtype=torch.int64)
+        dev = cache.tokens.device
+        res = (out.to(dev), torch.tensor([len(t) for t, _, _ in wins], dtype=torch.int64, device=dev),
+               torch.tensor([s for _, s, _ in wins], dtype=torch.float32, device=dev))
+        return res + ((ranked,) if return_all else ())
+
+    return _decode(model, mel, dict(prompt=prompt, prompt_len=prompt_len, temperature=float(temperature), seeds=seeds, eot=eot, max_len=max_len,
+                                    suppress=suppress, suppress_first=suppress_first, **ts_kw),
+                   who="sample_decode", table=_SAMPLE_SESSIONS, key=(B, N), make_cache=lambda dec: SampleCache(dec, B, N, device=mel.device),
+                   prefill=beam_prefill, first=sample_pick, body=_sample_body, readout=readout, extra=ts_extra(rules),
+                   graph=step == "graph" and _capture, stream=step == "graph" and _stream_gemm, sync_every=sync_every, xa=_xa)
+
+
+def _generated_n(row, first: int, length: int, eot: int) -> int:
+    """Generated tokens of a decoded row without the eot that ended it (a row cut at max_len has none and counts them all)."""
+    n = int(length) - int(first)
+    return n - 1 if n > 0 and int(row[int(length) - 1]) == int(eot) else n
+
+
+@torch.no_grad()
+def no_speech_prob(model, xa: torch.Tensor, prompt: torch.Tensor, sot_index, no_speech: int) -> torch.Tensor:
+    """Upstream's `probs_at_sot[:, no_speech]` -> f32 [B]: the probability of the `no_speech` id under the softmax of the logits at
+    the start-of-transcript position `sot_index` (an int, or one per row) of the prompt block.  One teacher-forced pass over the
+    prompts (right padding lies behind sot: causal attention never sees it), the row at sot_index through the tied logits product,
+    exp(x_target - logsumexp) from wft_token_stats.  Call it in eval mode."""
+    B, T = prompt.shape
+    V = model.dims.n_vocab
+    idx = torch.as_tensor(sot_index, dtype=torch.int64).reshape(-1).cpu()
+    if idx.numel() == 1:
+        idx = idx.expand(B)
+    if idx.numel() != B or int(idx.min()) < 0 or int(idx.max()) >= T:
+        raise ValueError(f"sot_index must be an int or one per row, inside the prompt width {T}")
+    if not 0 <= int(no_speech) < V:
+        raise ValueError(f"no_speech={no_speech} is outside the vocabulary")
+    dec = model.decoder
+    h = dec.hidden(prompt.to(xa.device), xa)  # [B, T, d], final LayerNorm applied
+    rows = torch.arange(B, device=h.device) * T + idx.to(h.device)
+    logits = dec.padded_logits(h.reshape(B * T, -1).index_select(0, rows).view(B, 1, -1))
+    stats, _ = K.token_stats(logits, torch.full((B,), int(no_speech), dtype=torch.int64, device=h.device), V)
+    return torch.exp(stats[:, 3] - stats[:, 0])
+
+
+UPSTREAM_TEMPERATURES = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0)
+
+
+def needs_fallback(avg_logprob: float, no_speech_prob: Optional[float], compression_ratio: Optional[float], *, thresholds: dict) -> bool:
+    """Upstream's three tests of a decoded window, in its order -> True: decode again at the next temperature.  thresholds: a dict
+    with "compression_ratio", "logprob" and "no_speech" (a missing key or None switches that test off).
+      1. the compression ratio above its threshold -> retry (the text repeats itself);
+      2. the average log-probability below its threshold -> retry;
+      3. but a no-speech probability above its threshold together with an average log-probability below the log-probability
+         threshold -> accept: the window is silence, another temperature will not help."""
+    cr, lp, ns = thresholds.get("compression_ratio"), thresholds.get("logprob"), thresholds.get("no_speech")
+    retry = False
+    if cr is not None and compression_ratio is not None and compression_ratio > cr:
+        retry = True
+    if lp is not None and avg_logprob < lp:
+        retry = True
+    if ns is not None and no_speech_prob is not None and no_speech_prob > ns and lp is not None and avg_logprob < lp:
+        retry = False
+    return retry
+
+
+def avg_logprob(sum_logprob: float, n: int) -> float:
+    """Upstream's `sum_logprob / (len(tokens) + 1)`, n = the generated tokens before the eot."""
+    return float(sum_logprob) / (int(n) + 1)
+
+
+def compression_ratio(text: str) -> float:
+    """len(utf-8 bytes) / len(zlib.compress(them)): upstream's measure of a text that repeats itself."""
+    import zlib
+
+    b = text.encode("utf-8")
+    return len(b) / len(zlib.compress(b))
+
+
+def generated_ids(row, first: int, length: int, eot: int, timestamp_begin: Optional[int] = None) -> tuple:
+    """(ids of row[first:length] up to the first eot, the same without timestamp ids)."""
+    ids = [int(t) for t in row[int(first):int(length)]]
+    if int(eot) in ids:
+        ids = ids[:ids.index(int(eot))]
+    return ids, (ids if timestamp_begin is None else [t for t in ids if t < int(timestamp_begin)])
+
+
+@torch.no_grad()
+def decode_with_fallback(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None, *, temperatures=UPSTREAM_TEMPERATURES,
+                         best_of: int = 5, beam_size: Optional[int] = None, patience: float = 1.0, length_penalty: Optional[float] = None,
+                         logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
+                         compression_ratio_threshold: Optional[float] = None, text_of=None, no_speech: Optional[int] = None, sot_index=None,
+                         seed: int = 0, **decode_kw):
+    """Upstream's temperature ladder (`transcribe()`'s decode_with_fallback) -> (tokens i64 [B, L], lengths i64 [B], sum_logprob f32
+    [B], info) in greedy_decode's layout, rows from different rungs padded with `eot` to one width.
+
+    The encoder runs once.  Rung i decodes the audios still pending at temperatures[i]: at 0 with beam_decode (beam_size, patience)
+    if beam_size is given, else greedy_decode; above 0 with sample_decode(best_of), the audio with original index a drawing with
+    seed + i*B + a.  An audio leaves the ladder when `needs_fallback` accepts its result; the last rung's result stands for audios
+    that never pass.  Per result: avg_logprob = sum_logprob / (n + 1) over the n generated tokens before the eot (a row cut at
+    max_len counts all of them); compression ratio = `compression_ratio(text_of(ids))` over the generated ids without eot and
+    timestamp ids (a ratio threshold needs `text_of`, e.g. a tokenizer's decode: ValueError otherwise); the no-speech probability
+    comes from `no_speech_prob` at `sot_index` (default 0: the prompt starts with sot) when the `no_speech` id is given.  A None
+    threshold switches its test off.
+    info: {"temperature": [B] the rung that produced each result, "avg_logprob": [B], "no_speech_prob": [B] (None without
+    `no_speech`), "compression_ratio": [B] (None without `text_of`), "rungs": per rung the original indices decoded there}.
+    decode_kw: what all three decoders share (eot — required —, max_len, suppress, suppress_first, sync_every, step and the
+    timestamp keywords).  Under step="graph" a rung with a new number of pending audios is a new graph session (sessions are keyed
+    by batch size): accepted, not optimised — at most MAX_SESSIONS of a kind are kept, so a long ladder recaptures."""
+    temps = list(temperatures)
+    if not temps:
+        raise ValueError("temperatures must not be empty")
+    for t in temps:
+        _check_sampling(t, best_of, length_penalty)
+    if beam_size is not None:
+        beam_candidates(beam_size, patience)
+    if compression_ratio_threshold is not None and text_of is None:
+        raise ValueError("compression_ratio_threshold needs text_of (ids -> str): the ratio is taken over the decoded text")
+    if "eot" not in decode_kw:
+        raise TypeError("decode_with_fallback needs eot=")
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"seed must be an integer, got {seed!r}")
+    _check_mode(model, "decode_with_fallback", decode_kw.get("step", "eager"), decode_kw.get("sync_every", 8))
+    eot, ts_begin = int(decode_kw["eot"]), decode_kw.get("timestamp_begin")
+    thresholds = {"compression_ratio": compression_ratio_threshold, "logprob": logprob_threshold, "no_speech": no_speech_threshold}
+    B = int(prompt.shape[0])
+    first = [int(prompt.shape[1])] * B if prompt_len is None else [int(n) for n in torch.as_tensor(prompt_len).reshape(B).tolist()]
+
+    was_training = model.training
+    model.eval()
+    try:
+        xa = model.encoder(mel)
+        nsp = [None] * B
+        if no_speech is not None:
+            nsp = no_speech_prob(model, xa, prompt, 0 if sot_index is None else sot_index, no_speech).cpu().tolist()
+        result = [None] * B  # per audio (tokens, sum_logprob)
+        info = {"temperature": [None] * B, "avg_logprob": [None] * B, "no_speech_prob": nsp, "compression_ratio": [None] * B, "rungs": []}
+        pending = list(range(B))
+        for i, t in enumerate(temps):
+            if not pending:
+                break
+            info["rungs"].append(list(pending))
+            sel = torch.tensor(pending, dtype=torch.int64)
+            sub = dict(prompt_len=torch.tensor([first[a] for a in pending]), _xa=xa[sel.to(xa.device)], **decode_kw)
+            sub_mel, sub_prompt = mel[sel.to(mel.device)], prompt[sel.to(prompt.device)]
+            if t > 0:
+                out = sample_decode(model, sub_mel, sub_prompt, temperature=t, best_of=best_of, seed=[seed + i * B + a for a in pending],
+                                    length_penalty=length_penalty, **sub)
+            elif beam_size is not None:
+                out = beam_decode(model, sub_mel, sub_prompt, beam_size=beam_size, patience=patience, length_penalty=length_penalty, **sub)
+            else:
+                out = greedy_decode(model, sub_mel, sub_prompt, **sub)
+            toks, lens, slp = out[0].cpu().tolist(), out[1].cpu().tolist(), out[2].cpu().tolist()
+            still = []
+            for j, a in enumerate(pending):
+                ids, text_ids = generated_ids(toks[j], first[a], lens[j], eot, ts_begin)
+                alp = avg_logprob(slp[j], len(ids))
+                ratio = compression_ratio(text_of(text_ids)) if text_of is not None else None
+                result[a] = (toks[j][:lens[j]], slp[j])
+                info["temperature"][a], info["avg_logprob"][a], info["compression_ratio"][a] = float(t), alp, ratio
+                if needs_fallback(alp, nsp[a], ratio, thresholds=thresholds):
+                    still.append(a)
+            pending = still
+    finally:
+        model.train(was_training)
+    width = max(len(t) for t, _ in result)
+    tokens = torch.full((B, width), eot, dtype=torch.int64)
+    for a, (t, _) in enumerate(result):
+        tokens[a, :len(t)] = torch.tensor(t, dtype=torch.int64)
+    dev = mel.device
+    return (tokens.to(dev), torch.tensor([len(t) for t, _ in result], dtype=torch.int64, device=dev),
+            torch.tensor([s for _, s in result], dtype=torch.float32, device=dev), info)
 
 
 # ============================================================================= timed segments

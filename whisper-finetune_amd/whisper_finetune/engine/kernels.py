@@ -673,14 +673,11 @@ def _ts_rules(ts_rules):
     return ru
 
 
-def decode_pick(logits, V: int, tokens, lens, finished, sum_logprob, unfinished, *, eot: int, max_len: int, suppress=None,
-                suppress_first=None, first_len=None, want_pick: bool = False, ts_rules=None):
-    """Greedy pick + state update (wft_decode_pick; include/wft.h).  logits bf16 [B, ld >= V]; suppress / suppress_first u8 [V] or None.
-    want_pick -> (pick i64 [B], logprob f32 [B]) as computed for EVERY row, finished or not.
-    ts_rules = (ts_begin, no_timestamps or None, max_initial or None): the pick under the timestamp rules (wft_decode_pick_ts)."""
+def _pick_args(logits, V: int, tokens, lens, finished, sum_logprob, unfinished, eot, max_len, suppress, suppress_first, first_len, want_pick, group=1):
+    """DecodePickArgs of decode_pick / decode_sample for the R = tokens.shape[0] state rows (logits: R // group rows) -> (args, pick, lp)."""
     _chk(logits, BF16, "logits"); _chk(tokens, torch.int64, "tokens"); _chk(sum_logprob, F32, "sum_logprob")
-    B = logits.shape[0]
-    assert logits.dim() == 2 and logits.stride(1) == 1 and tokens.dim() == 2 and tokens.stride(1) == 1 and tokens.shape[0] == B
+    B = tokens.shape[0]
+    assert logits.dim() == 2 and logits.stride(1) == 1 and tokens.dim() == 2 and tokens.stride(1) == 1 and logits.shape[0] * group == B
     _chk_flag(lens, B, "lens"); _chk_flag(finished, B, "finished"); _chk_flag(unfinished, 1, "unfinished")
     a = L.DecodePickArgs()
     a.logits, a.ld, a.V = logits.data_ptr(), logits.stride(0), V
@@ -696,11 +693,45 @@ def decode_pick(logits, V: int, tokens, lens, finished, sum_logprob, unfinished,
         lp = torch.empty(B, dtype=F32, device=logits.device)
         a.pick_out, a.logprob_out = pick.data_ptr(), lp.data_ptr()
     a.B, a.eot, a.max_len = B, int(eot), int(max_len)
+    return a, pick, lp
+
+
+def decode_pick(logits, V: int, tokens, lens, finished, sum_logprob, unfinished, *, eot: int, max_len: int, suppress=None,
+                suppress_first=None, first_len=None, want_pick: bool = False, ts_rules=None):
+    """Greedy pick + state update (wft_decode_pick; include/wft.h).  logits bf16 [B, ld >= V]; suppress / suppress_first u8 [V] or None.
+    want_pick -> (pick i64 [B], logprob f32 [B]) as computed for EVERY row, finished or not.
+    ts_rules = (ts_begin, no_timestamps or None, max_initial or None): the pick under the timestamp rules (wft_decode_pick_ts)."""
+    a, pick, lp = _pick_args(logits, V, tokens, lens, finished, sum_logprob, unfinished, eot, max_len, suppress, suppress_first, first_len, want_pick)
     if ts_rules is not None:
         ru = _ts_rules(ts_rules)
         L.check(L.load().wft_decode_pick_ts(C.byref(a), C.byref(ru), L.stream_ptr()), "wft_decode_pick_ts")
     else:
         L.check(L.load().wft_decode_pick(C.byref(a), L.stream_ptr()), "wft_decode_pick")
+    return pick, lp
+
+
+def decode_sample(logits, V: int, tokens, lens, finished, sum_logprob, unfinished, temperature, seed, *, group: int = 1, eot: int,
+                  max_len: int, suppress=None, suppress_first=None, first_len=None, want_pick: bool = False, ts_rules=None):
+    """Sampled pick + state update (wft_decode_sample; include/wft.h "Sampled decoding").  As decode_pick for the R = tokens.shape[0]
+    state rows; logits bf16 [R // group, ld >= V], state row r reads logits row r // group.  temperature f32 [R] and seed i64 [R]
+    (the bits of a u64) live on the device and are read by the kernel: rows with temperature <= 0 pick greedily, the others draw
+    from softmax(logits / temperature) over the live columns; the log-probability is the pick's at temperature 1.
+    ts_rules: as decode_pick (wft_decode_sample_ts)."""
+    group = int(group)
+    if group < 1 or tokens.shape[0] % group:
+        raise ValueError(f"decode_sample: group={group} must be >= 1 and divide the {tokens.shape[0]} state rows")
+    a, pick, lp = _pick_args(logits, V, tokens, lens, finished, sum_logprob, unfinished, eot, max_len, suppress, suppress_first, first_len, want_pick,
+                             group=group)
+    _chk(temperature, F32, "temperature"); _chk(seed, torch.int64, "seed")
+    if temperature.numel() != a.B or seed.numel() != a.B or not temperature.is_contiguous() or not seed.is_contiguous():
+        raise ValueError(f"decode_sample: temperature f32 / seed i64 must be contiguous [{a.B}]")
+    s = L.SampleRules()
+    s.temperature, s.seed, s.group = temperature.data_ptr(), seed.data_ptr(), group
+    if ts_rules is not None:
+        ru = _ts_rules(ts_rules)
+        L.check(L.load().wft_decode_sample_ts(C.byref(a), C.byref(s), C.byref(ru), L.stream_ptr()), "wft_decode_sample_ts")
+    else:
+        L.check(L.load().wft_decode_sample(C.byref(a), C.byref(s), L.stream_ptr()), "wft_decode_sample")
     return pick, lp
 
 

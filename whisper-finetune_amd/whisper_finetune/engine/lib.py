@@ -134,6 +134,12 @@ class TsRules(C.Structure):
     _fields_ = [("ts_begin", C.c_int), ("no_timestamps", C.c_int), ("max_initial", C.c_int)]
 
 
+class SampleRules(C.Structure):
+    """Mirror of wft_sample_rules (include/wft.h "Sampled decoding"): per-row temperature / seed in device memory, and the group."""
+
+    _fields_ = [("temperature", c_vp), ("seed", c_vp), ("group", C.c_int)]
+
+
 class BeamUpdateArgs(C.Structure):
     """Mirror of wft_beam_update_args (include/wft.h): one beam-search step per audio on the device-side state."""
 
@@ -205,6 +211,8 @@ SIGNATURES = {
     "wft_decode_pick_ts": [C.POINTER(DecodePickArgs), C.POINTER(TsRules), c_vp],
     "wft_decode_topk_ts": [C.POINTER(DecodeTopkArgs), C.POINTER(TsRules), c_vp, c_i64, C.c_int, c_vp],
     "wft_beam_update": [C.POINTER(BeamUpdateArgs), c_vp],
+    "wft_decode_sample": [C.POINTER(DecodePickArgs), C.POINTER(SampleRules), c_vp],
+    "wft_decode_sample_ts": [C.POINTER(DecodePickArgs), C.POINTER(SampleRules), C.POINTER(TsRules), c_vp],
     "wft_embed_fwd": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_int, c_i64, c_vp],
     "wft_embed_bwd": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_int, c_i64, c_vp],
     "wft_ce_fwd": [c_vp, c_i64, c_vp, c_i64, c_i64, C.c_float, c_vp, c_vp, c_vp, c_vp, c_vp],

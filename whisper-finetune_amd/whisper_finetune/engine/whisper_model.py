@@ -174,9 +174,9 @@ class MultiHeadAttention(nn.Module):
         => causal (the decoder's -inf upper-triangular buffer).  Returns (out, None) like upstream;
         `residual` (engine extension) is added inside the out-projection epilogue."""
         if kv_cache:
-            if not isinstance(kv_cache, (_decode.KVCache, _decode.BeamCache)):
-                raise NotImplementedError("kv_cache must be an engine.decode.KVCache or BeamCache (Whisper.greedy_decode / beam_decode "
-                                          "build one); upstream's hook-filled dict is not supported")
+            if not isinstance(kv_cache, (_decode.KVCache, _decode.BeamCache, _decode.SampleCache)):
+                raise NotImplementedError("kv_cache must be an engine.decode.KVCache, BeamCache or SampleCache (Whisper.greedy_decode / "
+                                          "beam_decode / sample_decode build one); upstream's hook-filled dict is not supported")
             return self._forward_cached(x, xa, kv_cache, residual)
         B, T, d = x.shape
         if self.wft_fp32:  # fp32 mode: separate projections, strided per-head GEMMs, materialised probabilities
@@ -491,6 +491,29 @@ class Whisper(nn.Module):
                                    eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first, sync_every=sync_every,
                                    step=step, return_all=return_all, timestamp_begin=timestamp_begin, no_timestamps=no_timestamps,
                                    max_initial_timestamp_index=max_initial_timestamp_index, _capture=_capture, _stream_gemm=_stream_gemm)
+
+    def sample_decode(self, mel: Tensor, prompt: Tensor, prompt_len=None, *, temperature: float, best_of: int = 1, seed=0,
+                      length_penalty=None, return_all: bool = False, eot: int, max_len: Optional[int] = None, suppress=(), suppress_first=(),
+                      sync_every: int = 8, step: str = "eager", timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
+                      max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True, _stream_gemm: bool = True):
+        """KV-cached sampling (engine/decode.py sample_decode; upstream: GreedyDecoder at temperature > 0 with best_of samples and the
+        MaximumLikelihoodRanker, restated there — parity with the upstream binary and with torch's random stream is unpinned).
+        Arguments and result layout as greedy_decode, for the best of the `best_of` (1..8) samples of every audio; every token is
+        drawn on the device from softmax(logits / temperature) (include/wft.h "Sampled decoding"), reproducibly from `seed` (an int,
+        or one per audio); temperature 0 is greedy_decode.  The samples of an audio share its prompt keys and its cross keys /
+        values.  return_all adds every audio's ranked samples.  The fp32 compute mode raises, as for the other decoders."""
+        return _decode.sample_decode(self, mel, prompt, prompt_len, temperature=temperature, best_of=best_of, seed=seed,
+                                     length_penalty=length_penalty, return_all=return_all, eot=eot, max_len=max_len, suppress=suppress,
+                                     suppress_first=suppress_first, sync_every=sync_every, step=step, timestamp_begin=timestamp_begin,
+                                     no_timestamps=no_timestamps, max_initial_timestamp_index=max_initial_timestamp_index,
+                                     _capture=_capture, _stream_gemm=_stream_gemm)
+
+    def decode_with_fallback(self, mel: Tensor, prompt: Tensor, prompt_len=None, **kw):
+        """Upstream's temperature ladder (`transcribe()`'s decode_with_fallback; engine/decode.py decode_with_fallback has the
+        keywords): greedy_decode / beam_decode at temperature 0, sample_decode(best_of) at each higher temperature for the audios
+        whose result fails the average log-probability / compression ratio / no-speech tests (`decode.needs_fallback`)
+        -> (tokens, lengths, sum_logprob, info).  The encoder runs once.  The fp32 compute mode raises."""
+        return _decode.decode_with_fallback(self, mel, prompt, prompt_len, **kw)
 
     def forward(self, mel: Tensor, tokens: Tensor, targets: Optional[Tensor] = None, label_smoothing: float = 0.0) -> Tensor:
         """logits f32 [B, S, V] — or, when `targets` is given (engine extension used by train_step, also

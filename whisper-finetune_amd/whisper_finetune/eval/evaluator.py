@@ -40,7 +40,8 @@ def _batch_token_stats(model, x, y_in, y_out):
     return None
 
 
-def _greedy_predictions(model, tokenizer, x, y_in, step: str = "eager", beam: dict = None, timestamps: bool = False) -> List[List[int]]:
+def _greedy_predictions(model, tokenizer, x, y_in, step: str = "eager", beam: dict = None, timestamps: bool = False,
+                        fallback: dict = None) -> List[List[int]]:
     """t_config["wft_eval_decode"] = "greedy": every utterance's predicted ids from KV-cached greedy decoding
     (Whisper.greedy_decode) instead of the teacher-forced argmax.  The decoding prefix of a row is its y_in up to and including
     the start-of-transcript sequence; every special token but eot is suppressed (upstream's notimestamps decoding plus its
@@ -52,10 +53,16 @@ def _greedy_predictions(model, tokenizer, x, y_in, step: str = "eager", beam: di
     `timestamps` (t_config["wft_eval_decode_timestamps"]): decode under upstream's timestamp rules, its command line's default mode —
     the prefix stops behind the task token (a `<|notimestamps|>` in y_in is not copied), the timestamp ids stay out of the
     suppress list and `timestamp_begin` / `no_timestamps` come from the tokenizer (max_initial_timestamp_index: the decoder's
-    default, upstream's 1 s).  The returned ids still hold the timestamps; the caller strips them before WER / CER."""
-    if beam is not None and not hasattr(model, "beam_decode"):
+    default, upstream's 1 s).  The returned ids still hold the timestamps; the caller strips them before WER / CER.
+    `fallback` (t_config["wft_eval_decode"] = "fallback"): the keywords of Whisper.decode_with_fallback — upstream's temperature
+    ladder, the decoding `transcribe()` runs — under the same prefix, suppression and length rules; `beam` then chooses the rung at
+    temperature 0.  The compression ratio is taken over tokenizer.decode; a tokenizer with `no_speech` also supplies the no-speech
+    probability (read at each row's start-of-transcript position)."""
+    if fallback is not None and not hasattr(model, "decode_with_fallback"):
+        raise RuntimeError('wft_eval_decode: "fallback" needs a model with decode_with_fallback (the engine\'s Whisper)')
+    if fallback is None and beam is not None and not hasattr(model, "beam_decode"):
         raise RuntimeError('wft_eval_decode: "beam_search" needs a model with beam_decode (the engine\'s Whisper)')
-    if beam is None and not hasattr(model, "greedy_decode"):
+    if fallback is None and beam is None and not hasattr(model, "greedy_decode"):
         raise RuntimeError('wft_eval_decode: "greedy" needs a model with greedy_decode (the engine\'s Whisper)')
     eot = int(tokenizer.eot)
     rows = y_in.cpu().tolist()
@@ -73,13 +80,42 @@ def _greedy_predictions(model, tokenizer, x, y_in, step: str = "eager", beam: di
         ts_begin = int(tokenizer.timestamp_begin)
         kw["suppress"] = [t for t in suppress if t < ts_begin]
         kw.update(timestamp_begin=ts_begin, no_timestamps=int(tokenizer.no_timestamps))
-    if beam is None:
+    if fallback is not None:
+        fb = dict(fallback, text_of=tokenizer.decode, **({} if beam is None else beam))
+        if hasattr(tokenizer, "no_speech"):
+            sot = int(tokenizer.sot)
+            fb.update(no_speech=int(tokenizer.no_speech), sot_index=[r[:n].index(sot) if sot in r[:n] else 0 for r, n in zip(rows, plen)])
+        tokens, lengths, _, _ = model.decode_with_fallback(x, prompt.to(x.device), torch.tensor(plen), **fb, **kw)
+    elif beam is None:
         tokens, lengths, _ = model.greedy_decode(x, prompt.to(x.device), torch.tensor(plen), **kw)
     else:
         tokens, lengths, _ = model.beam_decode(x, prompt.to(x.device), torch.tensor(plen), beam_size=beam["beam_size"],
                                                patience=beam["patience"], **kw)
     tokens, lengths = tokens.cpu().tolist(), lengths.cpu().tolist()
     return [tokens[i][plen[i]:lengths[i]] for i in range(len(rows))]
+
+
+def _fallback_config(t_config: dict) -> dict:
+    """The wft_eval_decode_* keys of the "fallback" mode -> keywords of Whisper.decode_with_fallback, validated before the loop.
+    Defaults: upstream's six temperatures, best_of 5, thresholds -1.0 / 0.6 / 2.4 (null switches a test off), seed 0."""
+    num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and v == v
+    temps = t_config.get("wft_eval_decode_temperatures", [0.0, 0.2, 0.4, 0.6, 0.8, 1.0])
+    if not isinstance(temps, (list, tuple)) or not temps or not all(num(t) and 0 <= t < float("inf") for t in temps):
+        raise ValueError(f"wft_eval_decode_temperatures: a non-empty list of numbers >= 0, got {temps!r}")
+    best_of = t_config.get("wft_eval_decode_best_of", 5)
+    if isinstance(best_of, bool) or not isinstance(best_of, int) or not 1 <= best_of <= 8:
+        raise ValueError(f"wft_eval_decode_best_of: an integer in [1, 8], got {best_of!r}")
+    out = {"temperatures": tuple(float(t) for t in temps), "best_of": best_of}
+    for key, default in (("logprob_threshold", -1.0), ("no_speech_threshold", 0.6), ("compression_ratio_threshold", 2.4)):
+        v = t_config.get("wft_eval_decode_" + key, default)
+        if v is not None and not num(v):
+            raise ValueError(f"wft_eval_decode_{key}: a number or null, got {v!r}")
+        out[key] = v
+    seed = t_config.get("wft_eval_decode_seed", 0)
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"wft_eval_decode_seed: an integer, got {seed!r}")
+    out["seed"] = seed
+    return out
 
 
 @torch.no_grad()
@@ -105,16 +141,17 @@ def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict
     spec = VOCAB_SPECS["v0"]
     per_utt: List[PerUtteranceMetrics] = []
     decode_mode = t_config.get("wft_eval_decode")
-    if decode_mode not in (None, "greedy", "beam_search"):
-        raise ValueError(f'wft_eval_decode: "greedy" or "beam_search" (absent = the teacher-forced argmax), got {decode_mode!r}')
+    if decode_mode not in (None, "greedy", "beam_search", "fallback"):
+        raise ValueError(f'wft_eval_decode: "greedy", "beam_search" or "fallback" (absent = the teacher-forced argmax), got {decode_mode!r}')
     beam = None
-    if decode_mode == "beam_search":
+    if decode_mode == "beam_search" or (decode_mode == "fallback" and ("wft_eval_decode_beam_size" in t_config or "wft_eval_decode_patience" in t_config)):
         beam = {"beam_size": t_config.get("wft_eval_decode_beam_size", 5), "patience": t_config.get("wft_eval_decode_patience", 1.0)}
         bs, pat = beam["beam_size"], beam["patience"]
         if isinstance(bs, bool) or not isinstance(bs, int) or not 1 <= bs <= 8:
             raise ValueError(f"wft_eval_decode_beam_size: an integer in [1, 8], got {bs!r}")
         if isinstance(pat, bool) or not isinstance(pat, (int, float)) or not 0 < pat < float("inf") or round(bs * pat) < 1:
             raise ValueError(f"wft_eval_decode_patience: a positive number with round(beam_size * patience) >= 1, got {pat!r}")
+    fallback = _fallback_config(t_config) if decode_mode == "fallback" else None
     decode_step = t_config.get("wft_eval_decode_step")
     if decode_step not in (None, "eager", "graph"):
         raise ValueError(f'wft_eval_decode_step: "eager" (the default) or "graph", got {decode_step!r}')
@@ -123,7 +160,7 @@ def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict
     if not isinstance(decode_ts, bool):
         raise ValueError(f"wft_eval_decode_timestamps: true or false, got {decode_ts!r}")
     if decode_ts and decode_mode is None:
-        raise ValueError('wft_eval_decode_timestamps: true needs wft_eval_decode: "greedy" or "beam_search" (the teacher-forced argmax has no timestamp rules)')
+        raise ValueError('wft_eval_decode_timestamps: true needs wft_eval_decode: "greedy", "beam_search" or "fallback" (the teacher-forced argmax has no timestamp rules)')
     if decode_ts:
         ts_begin = int(tokenizer.timestamp_begin)
 
@@ -141,7 +178,8 @@ def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict
         # prediction TEXT from autoregressive decoding when asked for; NLL / entropy / ECE below stay teacher-forced
         decoded = None
         if decode_mode is not None:
-            decoded = _greedy_predictions(model, tokenizer, x, y_in, decode_step, beam, **({"timestamps": True} if decode_ts else {}))
+            decoded = _greedy_predictions(model, tokenizer, x, y_in, decode_step, beam, **({"timestamps": True} if decode_ts else {}),
+                                          **({} if fallback is None else {"fallback": fallback}))
             if decode_ts:  # the timestamps go the way of the other specials before WER / CER
                 decoded = [[t for t in row if t < ts_begin] for row in decoded]
         for i in range(y_host.shape[0]):
