@@ -100,6 +100,30 @@ def test_f32_ops_match_torch():
     assert abs(loss.item() - lref.item()) < 1e-5 * lref.item() and rel(lgd.grad, lg.grad) < 1e-5
 
 
+@pytest.mark.parametrize("Tq,Tk,causal", [(130, 130, True), (50, 333, False)])
+def test_f32_attention_on_probe_operands(Tq, Tk, causal):
+    """ops32.AttentionFn (wft_gemm_f32 + wft_softmax_fwd_f32 / _bwd_f32, the causal mask and the ld handling) on the probe operands of
+    tests/_attn_probe.py: every row's softmax mass sits on two keys at tile edges, next to a decoy the row must not see (causal:
+    key i + 1; non-causal: the guard row behind key Tk - 1 that the packed k / v views exclude).  Judged per (row, head) against the
+    fp64 oracle of the same fp32 operands, with test_f32_ops_match_torch's figures (1e-5 forward, 1e-4 gradients) applied to each
+    row's own scale and the probe tests' floor, where that test has three flat-softmax shapes under a tensor-wide L2."""
+    from tests import _attn_probe as P
+
+    B, H = 3, 2
+    D = H * 64
+    c = P.probe_case(B, H, Tq, Tk, causal, seed=0)
+    qkv, kv = c.qkv.float().to(DEV), c.kv.float().to(DEV)   # bf16 values held in fp32: the oracle reads the same numbers
+    q, k, v = (t.requires_grad_(True) for t in (qkv[..., :D], kv[:, :Tk, :D], kv[:, :Tk, D:]))
+    assert q.stride(1) == 3 * D and k.stride(0) == (Tk + P.GUARD) * 2 * D
+    o = ops32.AttentionFn.apply(q, k, v, H, causal)
+    o.backward(c.do.float().to(DEV))
+    o64, lse64 = P.oracle_fwd(c)
+    rdq, rdk, rdv = P.oracle_bwd(c, o64, lse64)
+    P.close_rows(o, o64, 1e-5, P.FLOOR, "fp32 o")
+    for name, got, ref in (("dq", q.grad, rdq), ("dk", k.grad, rdk), ("dv", v.grad, rdv)):
+        P.close_rows(got, ref, 1e-4, P.FLOOR, f"fp32 {name}")
+
+
 def _tiny_case(B=2, S=24, seed=0):
     dims = O.DIMS["tiny"]
     params = O.init_params(dims, seed=seed)

@@ -538,16 +538,25 @@ def _attn_view(t: torch.Tensor):
     return t.data_ptr(), t.stride(1), t.stride(0)
 
 
-def attn_fwd(q, k, v, n_head: int, causal: bool, scale: float, q_prescaled: bool = False):
+def attn_fwd(q, k, v, n_head: int, causal: bool, scale: float, q_prescaled: bool = False, o=None, lse=None):
     """q [B,Tq,H*64], k/v [B,Tk,H*64] bf16 views (any row stride) -> o [B,Tq,H*64], lse [B,H,Tq].
-    q_prescaled: q already carries scale * log2(e) (ops.QK_PRESCALE folded into the q projection's forward shadow)."""
+    q_prescaled: q already carries scale * log2(e) (ops.QK_PRESCALE folded into the q projection's forward shadow).
+    o / lse: optional outputs to write into (o: a bf16 [B,Tq,H*64] view of any row stride; lse: contiguous f32 [B,H,Tq])."""
     for n, t in (("q", q), ("k", k), ("v", v)):
         _chk(t, BF16, n)
     B, Tq, D = q.shape
     Tk = k.shape[1]
     assert D == n_head * 64, "head_dim must be 64"
-    o = torch.empty((B, Tq, D), dtype=BF16, device=q.device)
-    lse = torch.empty((B, n_head, Tq), dtype=F32, device=q.device)
+    if o is None:
+        o = torch.empty((B, Tq, D), dtype=BF16, device=q.device)
+    else:
+        _chk(o, BF16, "o")
+        assert o.shape == (B, Tq, D)
+    if lse is None:
+        lse = torch.empty((B, n_head, Tq), dtype=F32, device=q.device)
+    else:
+        _chk(lse, F32, "lse")
+        assert lse.shape == (B, n_head, Tq) and lse.is_contiguous()
     a = L.AttnArgs()
     a.q, a.ldq, a.q_bs = _attn_view(q)
     a.k, a.ldk, a.k_bs = _attn_view(k)
