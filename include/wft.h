@@ -269,8 +269,8 @@ typedef struct {
   int launch_mode; int variant;
 } wft_gemm_args;
 int wft_gemm_nt_bf16(const wft_gemm_args* args, void* stream);
-/* The queries below and wft_gemm_nt_bf16 itself read ONE plan of the call (csrc/gemm.hip nt_plan: kernel, grid, K splits,
- * workspace), so a query answers what the launcher will do with the same arguments; wft_gemm_tn_* likewise (tn_plan).  All pure
+/* The queries below and wft_gemm_nt_bf16 itself read ONE plan of the call (csrc/gemm.hip nt_plan, over the rules kept beside
+ * each kernel in csrc/gemm_*.hip: kernel, grid, K splits, workspace), so a query answers what the launcher will do with the same arguments; wft_gemm_tn_* likewise (tn_plan).  All pure
  * host functions: no device call, nothing launched.
  * Which kernel wft_gemm_nt_bf16 dispatches these arguments to: 4 (gemm_nt4w_kernel: 256x256 tiles, four waves with 128x128
  * accumulators each), 256 (gemm_nt256_kernel, the 8-wave ping-pong 256x256 kernel) or 128 (gemm_nt_kernel and its rank-r form;

@@ -1,7 +1,8 @@
-"""Host side of the GEMM library (csrc/gemm.hip nt_plan / tn_plan): every dispatch and workspace query answers what the recorded
-table says (tests/golden/gemm_dispatch_256cu.json, written by tools/dev/record_gemm_dispatch.py from the library before the
-queries were derived from one plan), and a call the plan refuses returns an error before any device call.  No GPU needed:
-without a device the library assumes 256 CUs, which is also what an MI355X reports."""
+"""Host side of the GEMM library (csrc/gemm.hip nt_plan / tn_plan, over the per-kernel rules of csrc/gemm_*.hip): every dispatch
+and workspace query answers what the recorded table says (tests/golden/gemm_dispatch_256cu.json, written by
+tools/dev/record_gemm_dispatch.py from the library before the queries were derived from one plan), and a call the plan refuses
+returns an error before any device call.  No GPU needed: without a device the library assumes 256 CUs, which is also what an
+MI355X reports."""
 import ctypes
 import json
 

@@ -102,7 +102,7 @@ def test_gemm_nt_and_epilogues(M, N, Kd):
 @pytest.mark.parametrize("M,N,Kd", [(70001, 1280, 128), (20000, 2560, 256), (33000, 1280, 1280)])
 def test_gemm_nt_persistent_epilogues_counted_waits(M, N, Kd):
     """More tiles than CUs (persistent workgroups, continuous staging across tile seams), with the residual / aux operands
-    whose rows the epilogue fetches ahead by inline-asm loads behind hand-counted s_waitcnt (gemm.hip, COUNTED body), and
+    whose rows the epilogue fetches ahead by inline-asm loads behind hand-counted s_waitcnt (gemm_pp256.hip, COUNTED body), and
     a ragged last row tile (general body): results against fp32 torch, and bit-identical over repeats (a miscounted wait
     or a seam race shows up as run-to-run differences)."""
     g = torch.Generator().manual_seed(M)

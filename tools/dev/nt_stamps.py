@@ -51,7 +51,7 @@ def run(M, N, Kd, res=False):
             mm = main.mean(1)  # per workgroup
             print("   per XCD group (blockIdx % 8) mean main:", " ".join(f"{mm[x::8].mean():.2f}" for x in range(8)))
             print("   per local index (blockIdx // 8) mean main:", " ".join(f"{mm[8 * j:8 * j + 8].mean():.1f}" for j in range(32)))
-            # tile coordinates (band order of gemm.hip) of each workgroup's tiles: does the slow set follow the column / row?
+            # tile coordinates (band order of gemm_common.h band_coords) of each workgroup's tiles: does the slow set follow the column / row?
             tiles_r, tiles_c = (M + 255) // 256, N // 256
             ntl = tiles_r * tiles_c
             def coords(t):

@@ -5,7 +5,7 @@
 // relative in that mode.  These kernels are that mode: fp32 tensors in HBM, fp32 MFMA (v_mfma_f32_32x32x2_f32, full fp32
 // multiplies and accumulation — not the bf16 or xf32 pipes), fp32 everywhere else.  It is the PARITY mode (whisper-tiny /
 // base configurations, configs[0]); nothing here is tuned beyond coalesced access and a fixed summation order (bitwise
-// reproducible): the throughput path is the bf16 one (gemm.hip, attn*.hip, norm.hip).
+// reproducible): the throughput path is the bf16 one (gemm*.hip, attn*.hip, norm.hip).
 //
 //   wft_gemm_f32        C = alpha * op(A) op(B) (+ beta * C) (+ bias[n]), batched, arbitrary element strides for A and B
 //                       (NT / TN / NN, and the conv stem's overlapping-window rows without an im2col copy)

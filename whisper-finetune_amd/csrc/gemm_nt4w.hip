@@ -4,7 +4,7 @@
 // /root/reference/src/whisper_finetune/model/model_utils.py:283-285,320-325).  Same C ABI entry as the ping-pong kernel
 // (wft_gemm_nt_bf16 dispatches here; WFT_NT_VARIANT=pp keeps the old kernel).
 //
-// Why a second 256x256 kernel: the 8-wave ping-pong kernel (gemm.hip) re-reads every LDS fragment for 4-8 MFMAs and keeps two
+// Why a second 256x256 kernel: the 8-wave ping-pong kernel (gemm_pp256.hip) re-reads every LDS fragment for 4-8 MFMAs and keeps two
 // waves per SIMD busy issuing loads beside each other's MFMAs; rocprof shows its matrix pipe 51-54 % busy at the board's power
 // cap.  Here each of FOUR waves (one per SIMD) owns a 128 x 128 block of the tile in 256 accumulation registers (a[0:255]) and
 // every fragment it reads from LDS feeds 8 MFMAs: 64 B of LDS traffic per clock per CU instead of 96, a third less LDS energy at

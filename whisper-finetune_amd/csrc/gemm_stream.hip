@@ -2,7 +2,7 @@
 //
 //   C[m][n] = sum_k A[m][k] * B[n][k] (+ bias[n]) (gelu) (+ residual[m][n]),   bf16 in, fp32 accumulation, bf16 out
 //
-// At M = B the 128-tile kernel of gemm.hip runs N / 128 workgroups that each walk all of K through LDS: 10 workgroups x 80
+// At M = B the 128-tile kernel of gemm_nt128.hip runs N / 128 workgroups that each walk all of K through LDS: 10 workgroups x 80
 // k-steps for mlp.2 of large-v3 on a 256-CU chip, 14-47 us per call against 0.5-2 us of weight bytes.  Here
 // the weight matrix is the only operand that matters, nobody shares a weight element, and the work is cut so that the grid
 // covers the chip whatever N is:
