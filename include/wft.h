@@ -414,7 +414,7 @@ int wft_token_stats(const wft_bf16* logits, int64_t ld, const int64_t* targets,
                     int64_t rows, int64_t V, float* out4, int64_t* argmax, void* stream);
 
 /* -------------------------------------------------------- Greedy decoding */
-/* KV-cached greedy decoding (csrc/decode.hip): the single-token shapes of upstream's `whisper.decoding.GreedyDecoder` /
+/* KV-cached greedy decoding (csrc/decode_attn.hip, csrc/decode_pick.hip): the single-token shapes of upstream's `whisper.decoding.GreedyDecoder` /
  * `DecodingTask._main_loop` with `DecodingOptions(without_timestamps=True)` and the `kv_cache` hooks of
  * whisper.model.MultiHeadAttention.forward (none of it is in the reference tree, whose evaluator is teacher-forced:
  * eval/evaluator.py:70-73).  Everything that changes from token to token is DEVICE state — len i32 [B] (tokens a row holds,
@@ -467,7 +467,7 @@ typedef struct {
 int wft_decode_pick(const wft_decode_pick_args* args, void* stream);
 
 /* ---------------------------------------------------------- Beam search */
-/* Beam-search decoding on a KV cache shared between the beams (csrc/decode.hip; DESIGN.md §3 "Beam-search layouts"): upstream's
+/* Beam-search decoding on a KV cache shared between the beams (csrc/decode_attn.hip, csrc/decode_beam.hip; DESIGN.md §3 "Beam-search layouts"): upstream's
  * `BeamSearchDecoder` + `MaximumLikelihoodRanker` with `without_timestamps=True`, restated in engine/decode.py (neither is in the
  * reference tree and openai-whisper is not a dependency: parity with the upstream binary is unpinned).  W = beam size (1..8);
  * audio a owns the R = B*W slot rows r = a*W + j.
@@ -555,7 +555,7 @@ typedef struct {
 int wft_beam_update(const wft_beam_update_args* args, void* stream);
 
 /* ------------------------------------------------------ Sampled decoding */
-/* wft_decode_pick / wft_decode_pick_ts with a temperature per state row (csrc/decode.hip): upstream's `GreedyDecoder.update` at
+/* wft_decode_pick / wft_decode_pick_ts with a temperature per state row (csrc/decode_pick.hip): upstream's `GreedyDecoder.update` at
  * temperature > 0 (`Categorical(logits / temperature).sample()`), restated with a counter-based generator on the device
  * (openai-whisper is not a dependency: parity with the upstream binary and with torch's random stream is unpinned).
  *  rows: args->B = R state rows; state row r reads logits row r / group (group >= 1, R % group == 0), so the prefill's one row per

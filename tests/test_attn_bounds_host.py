@@ -3,7 +3,7 @@ tol = 2^-7): the fp32 -> bf16 emulation of CORRECT single-token attention passes
 deals keys in blocks of 32 over 4 waves can go wrong fails it — on batches in which every row is long, where the batch-wide bound
 (2e-2 of the largest value of the whole batch) has no short row to lean on.
 
-Only arithmetic on the CPU: no kernel runs here, right or wrong.  The mutants restate csrc/decode.hip's dealing (block j of 32 keys
+Only arithmetic on the CPU: no kernel runs here, right or wrong.  The mutants restate csrc/decode_attn.hip's dealing (block j of 32 keys
 belongs to wave j % 4; the key at p_new = n - 1 comes from the step's own k / v row, not from the cache)."""
 import pytest
 import torch

@@ -1,4 +1,4 @@
-"""GPU checks of the beam-search kernels (csrc/decode.hip) through the C ABI: wft_decode_topk against torch.log_softmax(...).topk,
+"""GPU checks of the beam-search kernels (csrc/decode_beam.hip, csrc/decode_attn.hip) through the C ABI: wft_decode_topk against torch.log_softmax(...).topk,
 wft_beam_update against the plain-Python oracle (tests/_beam_oracle.py) on the SAME candidate lists, and the two forms of
 wft_attn_decode_beam_bf16 against wft_attn_decode_bf16 — bit for bit where include/wft.h says so, at the fp32-math bound of
 tests/test_decode_kernels_gpu.py elsewhere."""

@@ -1,4 +1,4 @@
-"""GPU parity of the single-token decoding kernels (csrc/decode.hip) through the C ABI, against fp32 torch math on the same bf16
+"""GPU parity of the single-token decoding kernels (csrc/decode_attn.hip, csrc/decode_pick.hip) through the C ABI, against fp32 torch math on the same bf16
 inputs.  Attention outputs at the tolerance tests/test_kernels_gpu.py holds wft_attn_fwd_bf16 outputs to (2e-2 of the largest
 reference value: the output is rounded to bf16); ids, appended cache rows and the embedding bit-exact."""
 import math

@@ -1,4 +1,4 @@
-"""GPU checks of the sampled pick (csrc/decode.hip: wft_decode_sample, wft_decode_sample_ts) through the C ABI, against the fp64
+"""GPU checks of the sampled pick (csrc/decode_pick.hip: wft_decode_sample, wft_decode_sample_ts) through the C ABI, against the fp64
 oracle (tests/_sample_oracle.py: numpy Philox, Gumbel noise, the rules of tests/_ts_oracle.py) on the same bf16 logits.
 
 Exactness.  The kernel's key x / t + g is fp32, the oracle's fp64; on the random rows below the two differ by at most 2.4e-6

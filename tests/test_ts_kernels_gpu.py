@@ -1,4 +1,4 @@
-"""GPU checks of the timestamp-rule forms of the greedy pick and the top-(W + 1) kernel (csrc/decode.hip: wft_decode_pick_ts,
+"""GPU checks of the timestamp-rule forms of the greedy pick and the top-(W + 1) kernel (csrc/decode_pick.hip, csrc/decode_beam.hip: wft_decode_pick_ts,
 wft_decode_topk_ts) through the C ABI, against the fp64 rule oracle (tests/_ts_oracle.py) on the same bf16 logits: picks and
 candidate columns exact, log-probabilities within the 1e-4 absolute of test_pick_matches_masked_argmax_and_log_softmax /
 test_topk_on_crafted_rows (the same arithmetic: an fp32 sum of V exponentials in another order)."""

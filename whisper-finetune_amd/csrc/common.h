@@ -43,14 +43,15 @@ static inline const char* wft_dev_getenv(const char*) { return nullptr; }
   } while (0)
 #define WFT_CHECK_ARG(cond, msg) WFT_CHECK_ARG_AS(__func__, cond, msg)
 
-#define WFT_CHECK_LAUNCH()                                         \
+#define WFT_CHECK_LAUNCH_AS(who)                                   \
   do {                                                             \
     hipError_t e_ = hipGetLastError();                             \
     if (e_ != hipSuccess) {                                        \
-      wft_set_error("%s: launch failed: %s", __func__, hipGetErrorString(e_)); \
+      wft_set_error("%s: launch failed: %s", who, hipGetErrorString(e_)); \
       return WFT_ERR_LAUNCH;                                       \
     }                                                              \
   } while (0)
+#define WFT_CHECK_LAUNCH() WFT_CHECK_LAUNCH_AS(__func__)
 
 // ---- bf16 <-> f32 (round to nearest even; plain casts so hipcc emits v_cvt_pk_bf16_f32)
 __device__ __forceinline__ float bf2f(unsigned short u) {

@@ -13,7 +13,7 @@ detection or long-audio `transcribe()` (INTEGRATION.md).
 
 Everything that changes from token to token lives in device memory (`KVCache`: len / tokens / finished / sum_logprob), so a
 step is a fixed sequence of launches whose arguments never change: LayerNorm and every projection through the existing
-kernels at M = B, attention / embedding / the pick through csrc/decode.hip.  The host reads one counter every `sync_every`
+kernels at M = B, attention / embedding / the pick through csrc/decode_attn.hip and csrc/decode_pick.hip.  The host reads one counter every `sync_every`
 steps.
 
 Cache layout (DESIGN.md §3 "Greedy-decoding layouts"): per decoder layer one self-attention buffer bf16 [B, n_text_ctx, 2d] whose row (b, t) is
@@ -401,7 +401,7 @@ def _check_mode(model, who: str, step: str, sync_every: int) -> None:
     if step not in STEP_MODES:
         raise ValueError(f"step must be one of {STEP_MODES}, got {step!r}")
     if getattr(model, "compute_dtype", "bf16") != "bf16":
-        raise NotImplementedError(f"{who} runs in the bf16 compute mode only: the single-token kernels (csrc/decode.hip) are bf16; "
+        raise NotImplementedError(f"{who} runs in the bf16 compute mode only: the single-token kernels (csrc/decode_*.hip) are bf16; "
                                   "call model.set_compute_dtype('bf16') to decode")
     if sync_every < 1:
         raise ValueError("sync_every must be >= 1")
@@ -492,7 +492,7 @@ def greedy_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=Non
 # Upstream's `BeamSearchDecoder` + `MaximumLikelihoodRanker` under `without_timestamps=True`, restated (neither is in the reference
 # tree and openai-whisper is not a dependency: parity with the upstream binary is unpinned).  W = beam_size; audio a owns the rows
 # r = a*W + j; all rows of an audio hold the same `len`; C = round(W * patience) finished sequences end an audio.  One step, per
-# audio that is not done (csrc/decode.hip: wft_decode_topk, wft_beam_update; include/wft.h states the order rules):
+# audio that is not done (csrc/decode_beam.hip: wft_decode_topk, wft_beam_update; include/wft.h states the order rules):
 #   the W + 1 most probable continuations of every beam -> candidates scored sum_logprob + logp -> walked in descending order: an
 #   `eot` candidate joins the audio's finished list (while that holds fewer than C), any other becomes the next beam, until W beams.
 # What makes it cheap (DESIGN.md §3 "Beam-search layouts"): the cross keys / values exist once per AUDIO and are read once per step

@@ -605,7 +605,7 @@ def attn_bwd(q, k, v, o, lse, do, n_head: int, causal: bool, scale: float, dq=No
     return dq, dk, dv
 
 
-# --------------------------------------------------------------------------- greedy decoding (csrc/decode.hip)
+# --------------------------------------------------------------------------- greedy decoding (csrc/decode_attn.hip, csrc/decode_pick.hip)
 def _attn_decode_call(a, stem: str, q, cache, n_head: int, scale: float, new_kv, lens, q_prescaled: bool, out, args_only: bool, group: int = 1):
     """What AttnDecodeArgs and AttnDecodeBeamArgs share: the layout checks, q / cache / o, the step's k / v rows with `lens`, the
     workspace slot and the call of `stem`_bf16.  The caller has set the fields of its own struct (rows, group, anc) before."""
@@ -705,17 +705,20 @@ def _pick_args(logits, V: int, tokens, lens, finished, sum_logprob, unfinished, 
     return a, pick, lp
 
 
+def _pick_call(entry, ts_rules, *structs):
+    """entry(*structs, stream), or with ts_rules its _ts form: the timestamp rules follow the structs."""
+    if ts_rules is not None:
+        entry, structs = entry + "_ts", structs + (_ts_rules(ts_rules),)
+    L.check(getattr(L.load(), entry)(*map(C.byref, structs), L.stream_ptr()), entry)
+
+
 def decode_pick(logits, V: int, tokens, lens, finished, sum_logprob, unfinished, *, eot: int, max_len: int, suppress=None,
                 suppress_first=None, first_len=None, want_pick: bool = False, ts_rules=None):
     """Greedy pick + state update (wft_decode_pick; include/wft.h).  logits bf16 [B, ld >= V]; suppress / suppress_first u8 [V] or None.
     want_pick -> (pick i64 [B], logprob f32 [B]) as computed for EVERY row, finished or not.
     ts_rules = (ts_begin, no_timestamps or None, max_initial or None): the pick under the timestamp rules (wft_decode_pick_ts)."""
     a, pick, lp = _pick_args(logits, V, tokens, lens, finished, sum_logprob, unfinished, eot, max_len, suppress, suppress_first, first_len, want_pick)
-    if ts_rules is not None:
-        ru = _ts_rules(ts_rules)
-        L.check(L.load().wft_decode_pick_ts(C.byref(a), C.byref(ru), L.stream_ptr()), "wft_decode_pick_ts")
-    else:
-        L.check(L.load().wft_decode_pick(C.byref(a), L.stream_ptr()), "wft_decode_pick")
+    _pick_call("wft_decode_pick", ts_rules, a)
     return pick, lp
 
 
@@ -736,15 +739,11 @@ def decode_sample(logits, V: int, tokens, lens, finished, sum_logprob, unfinishe
         raise ValueError(f"decode_sample: temperature f32 / seed i64 must be contiguous [{a.B}]")
     s = L.SampleRules()
     s.temperature, s.seed, s.group = temperature.data_ptr(), seed.data_ptr(), group
-    if ts_rules is not None:
-        ru = _ts_rules(ts_rules)
-        L.check(L.load().wft_decode_sample_ts(C.byref(a), C.byref(s), C.byref(ru), L.stream_ptr()), "wft_decode_sample_ts")
-    else:
-        L.check(L.load().wft_decode_sample(C.byref(a), C.byref(s), L.stream_ptr()), "wft_decode_sample")
+    _pick_call("wft_decode_sample", ts_rules, a, s)
     return pick, lp
 
 
-# --------------------------------------------------------------------------- beam-search decoding (csrc/decode.hip)
+# --------------------------------------------------------------------------- beam-search decoding (csrc/decode_attn.hip, csrc/decode_beam.hip)
 def attn_decode_beam(q, cache, n_head: int, scale: float, *, new_kv=None, lens=None, anc=None, group: int = 1, q_prescaled: bool = False,
                      out=None, _args_only=False):
     """Single-token attention for beams (wft_attn_decode_beam_bf16).  q bf16 [R, H*64] (any row stride).

@@ -207,7 +207,7 @@ class MultiHeadAttention(nn.Module):
 
     def _forward_cached(self, x: Tensor, xa: Optional[Tensor], cache: "_decode.KVCache", residual: Optional[Tensor]):
         """Inference with a KVCache (engine/decode.py).  T > 1: the prefill — the teacher-forced kernels over the right-padded prompts,
-        the k / v rows stored into the cache.  T = 1: a cached step on the single-token kernel (csrc/decode.hip), which appends
+        the k / v rows stored into the cache.  T = 1: a cached step on the single-token kernel (csrc/decode_attn.hip), which appends
         the step's k / v itself.  Cross-attention keys / values are projected once per audio batch.
         The cache hides its layout (store_prefill / self_step / cross_step): with a BeamCache the prefill carries ONE row per audio
         and a step all audios * W hypotheses — self keys through the ancestry table, cross keys once per audio for its W rows."""
