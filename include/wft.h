@@ -378,7 +378,9 @@ int wft_attn_variant(const wft_attn_args* args, int which);
  * pos f32 [n_ctx, d]; out bf16 [B*S, d].                                     */
 int wft_embed_fwd(const int64_t* tokens, const float* emb, const float* pos,
                   wft_bf16* out, int64_t B, int64_t S, int d, int64_t V, void* stream);
-/* demb[tokens[i], :] += dout[i, :] (f32 atomics), dpos[s, :] += sum_b dout.   */
+/* demb[tokens[i], :] += dout[i, :], dpos[s, :] += sum_b dout[b, s, :].  No atomics: every embedding row adds the positions
+ * that hold its id in position order (i = 0, 1, ...), dpos the clips in order (b = 0, 1, ...), so the result is the same bits
+ * on every run.  An id outside [0, V) (wft_embed_fwd clamps it) adds nothing to demb and still counts in dpos.                 */
 int wft_embed_bwd(const int64_t* tokens, const wft_bf16* dout, float* demb, float* dpos,
                   int64_t B, int64_t S, int d, int64_t V, void* stream);
 
@@ -720,7 +722,9 @@ int wft_gelu_fwd_f32(const float* x, float* y, int64_t n, void* stream);        
 int wft_gelu_bwd_f32(const float* dy, const float* x, float* dx, int64_t n, void* stream);
 int wft_axpby_f32(float a, const float* x, float b, const float* y, float* out, int64_t n, void* stream); /* y may be NULL */
 int wft_colsum_f32(const float* x, int64_t rows, int64_t cols, int64_t ld, float* out, void* stream);     /* bias grads   */
-/* out[b, s, :] = emb[tokens[b, s], :] + pos[s, :]  (model/model_utils.py:316-318); the backward needs demb zero-filled. */
+/* out[b, s, :] = emb[tokens[b, s], :] + pos[s, :]  (model/model_utils.py:316-318); the backward needs demb zero-filled and
+ * overwrites dpos[0..S).  Both kernels index emb / demb with the id as it is: every id must lie in [0, V) (there is no V
+ * argument; unlike wft_embed_fwd / wft_embed_bwd nothing is clamped or skipped).  Sums in position / clip order, no atomics.   */
 int wft_embed_fwd_f32(const int64_t* tokens, const float* emb, const float* pos, float* out, int64_t B, int64_t S, int d,
                       void* stream);
 int wft_embed_bwd_f32(const int64_t* tokens, const float* dout, float* demb, float* dpos, int64_t B, int64_t S, int d,

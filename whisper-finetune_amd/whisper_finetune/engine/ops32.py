@@ -386,6 +386,7 @@ class CrossEntropyFn(torch.autograd.Function):
     def forward(ctx, logits, targets, eps):
         M, V = logits.shape
         dev = logits.device
+        targets = targets.contiguous()   # the kernels read targets[row]: a strided view would hand them other elements
         row_loss = torch.empty(M, dtype=F32, device=dev)
         row_lse = torch.empty(M, dtype=F32, device=dev)
         stats = torch.empty(2, dtype=F32, device=dev)
