@@ -585,6 +585,61 @@ typedef struct { const float* temperature; const uint64_t* seed; int group; } wf
 int wft_decode_sample(const wft_decode_pick_args* args, const wft_sample_rules* sample, void* stream);
 int wft_decode_sample_ts(const wft_decode_pick_args* args, const wft_sample_rules* sample, const wft_ts_rules* rules, void* stream);
 
+/* ------------------------------------------------- Word-level alignment */
+/* The device stages of upstream's `whisper/timing.py: find_alignment` (csrc/align.hip; DESIGN.md §3 "Word timestamps"): the
+ * cross-attention probabilities of the alignment heads, their standardisation / median filter / head mean, and dynamic time
+ * warping with its backtrace.  Upstream's behaviour is restated (openai-whisper is not a dependency: parity with its binary is
+ * unpinned); the reference tree only carries the `alignment_heads` state (model/model_utils.py:171-174, :363-377).
+ * Per-audio lengths are DEVICE int32 [B] arrays, as in the decode kernels; every kernel clamps them to its static extents (a
+ * negative length is 0, a length above the extent is the extent), so no length can make a kernel address out of bounds.
+ *
+ * wft_attn_probs_bf16: probs[b, s, t, j] = softmax_j(scale * q[b, t, heads[s]] . k[b, j, heads[s]]) over j < n_key[b], for
+ *  t < n_tok[b], in fp32.
+ *  args: q / ldq / q_bs, k / ldk / k_bs, B, H, Tq, Tk, scale of wft_attn_args, in its addressing (element (b, t, h, d) at
+ *    q + b*q_bs + t*ldq + h*64 + d, so the cross-attention [B, Tk, 2d] {k | v} buffer is consumed in place); rows 16-byte
+ *    aligned; q_prescaled must be 0 (only the self-attention q projection is prescaled) — the kernel multiplies the fp32
+ *    score by scale * log2(e), callers fold a `qk_scale` into scale; the other fields are not read;
+ *  heads i32 [n_heads]: distinct head indices in any order (an index outside [0, H) is clamped); slice s of the output belongs
+ *    to heads[s];
+ *  n_tok[b] query rows are used, n_key[b] keys take part: upstream's `weights[:, :, :num_frames // 2]` cut BEFORE the softmax,
+ *    so keys at or beyond n_key[b] carry no mass;
+ *  probs f32: element (b, s, t, j) at probs + b*p_bs + s*p_hs + t*ldp + j (an offset pointer per layer fills one
+ *    [B, n_sel_total, Tq, Tk] buffer); rows t >= n_tok[b] and columns j >= n_key[b] are NOT written;
+ *  scores: bf16 MFMA products with fp32 accumulation, recomputed for the second pass; exp2 of the hardware; one normalised
+ *    write (p = exp2(s - max) * (1 / sum)).  No atomics: reruns are bit-identical.
+ *
+ * wft_align_matrix: matrix[b, t, j] = mean over the n_sel heads of median_filter_j((p - mean_t p) / std_t p), t < n_tok[b],
+ *  j < n_key[b]; other elements are NOT written.
+ *  1. every frame column of every head is standardised over the n_tok[b] token rows with the BIASED deviation (upstream's
+ *     `torch.std_mean(weights, dim=-2, unbiased=False)`), the mean first and the deviation from the differences, in fp32, IEEE division and square root; a column that is
+ *     constant over the tokens has deviation 0 and yields non-finite values, as upstream;
+ *  2. median over a window of `width` (odd, 1..31; upstream's default 7) frames, reflect-padded by width / 2 (torch's
+ *     F.pad(mode="reflect"): column -i reads column i, column n - 1 + i reads n - 1 - i);
+ *  3. n_key[b] <= width / 2: no filter for that audio (upstream's early return of `median_filter`);
+ *  4. the heads are summed in slice order in fp32 and divided by n_sel.
+ *  probs: as written by wft_attn_probs_bf16 with n_sel slices; Tq <= 448; matrix element (b, t, j) at matrix + b*m_bs + t*ldm + j.
+ *
+ * wft_dtw_f32: the path of upstream's `dtw_cpu` / `dtw_cuda` in fp32 (its CUDA path is fp32, its CPU path fp64: this is the
+ *  fp32 one) over x = -matrix[b, row0 : row0 + n_rows[b], 0 : n_cols[b]] (negate != 0; negate == 0 reads the matrix as it is —
+ *  negation is exact), N = n_rows[b] <= n_rows_max <= 448, M = n_cols[b] <= n_cols_max:
+ *    cost[0, 0] = 0, cost[0, j] = cost[i, 0] = inf; for i in 1..N, j in 1..M with c0 = cost[i-1, j-1], c1 = cost[i-1, j],
+ *    c2 = cost[i, j-1]:  c0 < c1 && c0 < c2 -> (c0, trace 0);  else c1 < c0 && c1 < c2 -> (c1, trace 1);  else (c2, trace 2);
+ *    cost[i, j] = x[i-1, j-1] + c.
+ *  Every cell is ONE fp32 add of a fixed pair of operands, so the anti-diagonal sweep gives the serial loop's bits and path.
+ *  Backtrace from (N, M): record (i-1, j-1), then trace 0 -> (i-1, j-1), 1 -> (i-1, j), 2 -> (i, j-1), until (0, 0).
+ *  path_text / path_time i32 [B, ld_path] (ld_path >= n_rows_max + n_cols_max - 1): the recorded pairs in FORWARD order,
+ *    path_len[b] of them; entries beyond path_len[b] are not written; N == 0 or M == 0 gives path_len[b] = 0.
+ *  matrix_rows: the rows a matrix holds per audio (row0 + n_rows_max <= matrix_rows is checked on the host).
+ *  workspace: wft_dtw_workspace_bytes(B, n_rows_max, n_cols_max) bytes (the trace, kernel-internal).                              */
+int wft_attn_probs_bf16(const wft_attn_args* args, const int32_t* heads, int n_heads, const int32_t* n_tok, const int32_t* n_key,
+                        float* probs, int64_t p_bs, int64_t p_hs, int64_t ldp, void* stream);
+int wft_align_matrix(const float* probs, int64_t p_bs, int64_t p_hs, int64_t ldp, const int32_t* n_tok, const int32_t* n_key,
+                     float* matrix, int64_t m_bs, int64_t ldm, int B, int n_sel, int Tq, int Tk, int width, void* stream);
+int64_t wft_dtw_workspace_bytes(int B, int n_rows_max, int n_cols_max);
+int wft_dtw_f32(const float* matrix, int64_t m_bs, int64_t ldm, int matrix_rows, int row0, const int32_t* n_rows,
+                const int32_t* n_cols, int B, int n_rows_max, int n_cols_max, int negate, int32_t* path_text, int32_t* path_time,
+                int64_t ld_path, int32_t* path_len, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------- Log-mel + SpecAugment */
 /* whisper.audio.log_mel_spectrogram (data/data_loader.py:278; SURVEY.md App.
  * A.2): reflect-pad 200, Hann-400 STFT hop 160, |.|^2, mel filterbank,

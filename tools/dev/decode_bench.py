@@ -29,7 +29,14 @@
          beam_decode(W = 5) over B audios and greedy_decode at batch 5 * B, eager and graph: tokens/s, ms per step.
          (profiles/decode_bench_sample.jsonl: --parts sample --batches 1,4,6 --out profiles/decode_bench_sample.jsonl)
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,beam,ts,sample] [--batches 1,8,32] [--out FILE]
+  align  word-level timestamps at whisper-large-v3 dimensions (10 alignment heads, T = 448 tokens, 1500 frames; --batches = audios,
+         e.g. 1,4): the three kernels of csrc/align.hip one by one, Whisper.find_alignment as a whole, beside them a torch-on-GPU
+         restatement of stages a and b (softmax, std_mean, unfold + sort) and the host route for DTW (copy the matrix to the host,
+         a vectorised numpy wavefront).  What to expect: stage a is bound by its 27 MB per audio of output, stage b reads that once, DTW is latency-bound by N + M - 1 = 1 945 dependent
+         wavefront steps per audio.
+         (profiles/decode_bench_align.jsonl: --parts align --batches 1,4 --out profiles/decode_bench_align.jsonl)
+
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,beam,ts,sample,align] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -626,6 +633,122 @@ def bench_sample(batches, N=5, new_tokens=64, runs=3):
         Dm.release_graphs(m)
 
 
+def bench_align(batches, n_heads=10, T=CAP, frames=2 * TA, rounds=5):
+    """The alignment kernels at large-v3 dimensions: the 10 heads spread over 5 layers' q / kv buffers (2 heads each, as the capture
+    issues them: 5 launches of wft_attn_probs_bf16), scores spread to a standard deviation of about 2; then the whole call."""
+    import numpy as np
+
+    from whisper_finetune.engine import decode as Dm
+
+    g = torch.Generator(device="cuda").manual_seed(0)
+    sot, row0 = 3, 3
+    for B in batches:
+        lens, keys = [T] * B, [frames // 2] * B
+        n_tok, n_key = torch.tensor(lens, dtype=torch.int32, device=DEV), torch.tensor(keys, dtype=torch.int32, device=DEV)
+        n_rows = [T - sot - 1] * B
+        n_rows_d = torch.tensor(n_rows, dtype=torch.int32, device=DEV)
+        layers = n_heads // 2
+        qs = [(torch.randn(B, T, D, device=DEV, generator=g) * 2 ** 0.5).to(BF) for _ in range(layers)]
+        kvs = [(torch.randn(B, TA, 2 * D, device=DEV, generator=g) * 2 ** 0.5).to(BF) for _ in range(layers)]
+        heads = [torch.tensor([3 + 2 * i, 11 + i], dtype=torch.int32, device=DEV) for i in range(layers)]
+        probs = torch.zeros(B, n_heads, T, TA, device=DEV)
+        matrix = torch.zeros(B, T, TA, device=DEV)
+
+        def stage_a():
+            for i in range(layers):
+                K.attn_probs(qs[i], kvs[i][..., :D], heads[i], n_tok, n_key, H, 0.125, probs[:, 2 * i:2 * i + 2], host_lens=(lens, keys))
+
+        def stage_b():
+            K.align_matrix(probs, n_tok, n_key, 7, out=matrix, host_lens=(lens, keys))
+
+        paths = None
+
+        def stage_c():
+            nonlocal paths
+            paths = K.dtw(matrix, row0, n_rows_d, n_key, host_lens=(n_rows, keys), paths=paths)
+
+        def torch_a():
+            out = []
+            for i in range(layers):
+                hs = heads[i].tolist()
+                qh = qs[i].view(B, T, H, 64)[:, :, hs].permute(0, 2, 1, 3).float()
+                kh = kvs[i][..., :D].reshape(B, TA, H, 64)[:, :, hs].permute(0, 2, 1, 3).float()
+                out.append(torch.softmax(qh @ kh.transpose(-1, -2) * 0.125, dim=-1))
+            return torch.cat(out, 1)
+
+        def torch_b():
+            std, mean = torch.std_mean(probs, dim=-2, keepdim=True, unbiased=False)
+            z = (probs - mean) / std
+            z = torch.nn.functional.pad(z, (3, 3, 0, 0), mode="reflect")
+            return z.unfold(-1, 7, 1).sort()[0][..., 3].mean(1)
+
+        def host_c():
+            x = -matrix[:, row0:row0 + n_rows[0]].cpu().numpy()
+            for b in range(B):
+                N, M = x[b].shape
+                cost = np.full((N + 1, M + 1), np.inf, dtype=np.float32)
+                trace = np.zeros((N + 1, M + 1), dtype=np.int8)
+                cost[0, 0] = 0
+                for s_ in range(2, N + M + 1):
+                    i = np.arange(max(1, s_ - M), min(N, s_ - 1) + 1)
+                    j = s_ - i
+                    c0, c1, c2 = cost[i - 1, j - 1], cost[i - 1, j], cost[i, j - 1]
+                    t = np.where((c0 < c1) & (c0 < c2), 0, np.where((c1 < c0) & (c1 < c2), 1, 2))
+                    cost[i, j] = x[b][i - 1, j - 1] + np.where(t == 0, c0, np.where(t == 1, c1, c2))
+                    trace[i, j] = t
+                i, j, n = N, M, 0
+                while i > 0 or j > 0:  # the backtrace
+                    t = trace[i, j] if i > 0 and j > 0 else (2 if i == 0 else 1)
+                    i, j, n = i - (t != 2), j - (t != 1), n + 1
+
+        stage_a(); stage_b(); stage_c()
+        same = torch.allclose(torch_a(), probs, rtol=1e-3, atol=1e-7), torch.allclose(torch_b(), matrix, rtol=0, atol=1e-3)
+        res = ab({"attn_probs": stage_a, "align_matrix": stage_b, "dtw": stage_c, "torch_softmax": torch_a, "torch_filter": torch_b}, rounds=rounds, iters=2)
+        t0 = time.perf_counter()
+        host_c()
+        host_ms = (time.perf_counter() - t0) * 1e3
+        rec = dict(part="align", what="kernels", audios=B, heads=n_heads, tokens=T, frames=TA, dtw_rows=n_rows[0],
+                   probs_MB=round(B * n_heads * T * TA * 4 / 1e6, 1), torch_matches=list(map(bool, same)), dtw_host_numpy_ms=round(host_ms, 1),
+                   note="ms per call, median of alternating rounds; attn_probs = the 5 launches of one pass; dtw_host = copy + numpy wavefront, one run")
+        for n, (med, mn, spread) in res.items():
+            rec[n + "_ms"] = round(med, 3)
+            rec[n + "_min_ms"] = round(mn, 3)
+            rec[n + "_spread"] = round(spread, 3)
+        rec["attn_probs_write_TBps"] = round(B * n_heads * T * TA * 4 / (res["attn_probs"][0] * 1e-3) / 1e12, 3)
+        rec["align_matrix_read_TBps"] = round(B * n_heads * T * TA * 4 / (res["align_matrix"][0] * 1e-3) / 1e12, 3)
+        rec["dtw_us_per_wavefront_step"] = round(res["dtw"][0] * 1e3 / (n_rows[0] + TA - 1), 3)
+        emit(rec)
+        del qs, kvs, probs, matrix
+    m, dims = _random_large_v3()
+    mask = torch.zeros(dims.n_text_layer, dims.n_text_head, dtype=torch.bool)
+    for i in range(n_heads // 2):
+        mask[10 + 4 * i, [3 + 2 * i, 11 + i]] = True
+    m.set_alignment_heads(mask)
+    with torch.no_grad():  # the cross query / key weights of the alignment layers scaled up to a score deviation of about 2
+        for i in range(n_heads // 2):
+            ca = m.decoder.blocks[10 + 4 * i].cross_attn
+            ca.query.weight.mul_(5.0); ca.key.weight.mul_(5.0)
+    eot, kw = 50257, dict(sot_sequence=[50258, 50259, 50360], no_timestamps=50364, eot=50257, num_frames=frames)
+    for B in batches:
+        mel = torch.randn(B, dims.n_mels, frames, device=DEV, generator=g) * 0.5
+        texts = [torch.randint(0, eot, (T - 5,), generator=torch.Generator().manual_seed(b)).tolist() for b in range(B)]
+        fwd_tokens = torch.tensor([kw["sot_sequence"] + [kw["no_timestamps"]] + t + [eot] for t in texts], device=DEV)
+        for _ in range(2):
+            m.find_alignment(mel, texts, **kw)
+        ts, tf = [], []
+        for _ in range(rounds):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            m.find_alignment(mel, texts, **kw)
+            torch.cuda.synchronize(); ts.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                m.decoder.hidden(fwd_tokens, m.embed_audio(mel))
+            torch.cuda.synchronize(); tf.append((time.perf_counter() - t0) * 1e3)
+        emit(dict(part="align", what="find_alignment", audios=B, heads=n_heads, tokens=T, frames=TA, find_alignment_ms=round(statistics.median(ts), 2),
+                  find_alignment_min_ms=round(min(ts), 2), encoder_plus_decoder_pass_ms=round(statistics.median(tf), 2),
+                  note="wall ms per call, host work included; beside it the teacher-forced encoder + decoder pass alone"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="attn,gemm,e2e")
@@ -638,7 +761,7 @@ def main():
     emit(dict(part="env", device=torch.cuda.get_device_name(0), lib=L.load().wft_version().decode(), torch=torch.__version__))
     for part in a.parts.split(","):
         {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": bench_gemm_stream, "e2e_step": bench_e2e_step,
-         "beam": bench_beam, "ts": bench_ts, "sample": bench_sample}[part](batches)
+         "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

@@ -1067,3 +1067,196 @@ def timestamp_segments(tokens, prompt_len, lengths, timestamp_begin: int, eot: i
             segs.append((start, None, text))
         out.append(segs)
     return out
+
+
+# ============================================================================= word-level timestamps
+# Upstream's `whisper/timing.py: find_alignment`, restated (openai-whisper is not a dependency: parity with its binary is unpinned).
+# Device stages: csrc/align.hip (include/wft.h "Word-level alignment"); the rest is upstream's numpy on the host.  Its string-level
+# post-processing (`merge_punctuations`, the long-word heuristics of `add_word_timestamps`) is not built.
+TOKENS_PER_SECOND = 50  # one cross-attention frame = 20 ms
+
+
+def dump_alignment_heads(mask) -> bytes:
+    """A bool [n_text_layer, n_text_head] mask -> upstream's dump format: base85 of the gzipped bool bytes."""
+    import base64
+    import gzip
+
+    import numpy as np
+
+    return base64.b85encode(gzip.compress(np.ascontiguousarray(np.asarray(mask, dtype=bool)).tobytes()))
+
+
+def parse_alignment_heads(heads, n_layer: int, n_head: int) -> torch.Tensor:
+    """A bool [n_layer, n_head] mask (tensor, array, nested list) or upstream's base85-gzip dump of one -> bool tensor [n_layer, n_head]."""
+    if isinstance(heads, (bytes, str)):
+        import base64
+        import gzip
+
+        import numpy as np
+
+        arr = np.frombuffer(gzip.decompress(base64.b85decode(heads)), dtype=bool).copy()
+        if arr.size != n_layer * n_head:
+            raise ValueError(f"alignment-head dump holds {arr.size} entries, the model has {n_layer} x {n_head} heads")
+        return torch.from_numpy(arr).reshape(n_layer, n_head)
+    if isinstance(heads, torch.Tensor) and heads.is_sparse:
+        heads = heads.to_dense()
+    mask = torch.as_tensor(heads).cpu()
+    if mask.dtype != torch.bool or tuple(mask.shape) != (n_layer, n_head):
+        raise ValueError(f"alignment heads must be a bool [{n_layer}, {n_head}] mask or a base85 dump, got {mask.dtype} {tuple(mask.shape)}")
+    return mask.clone()
+
+
+class AlignCapture:
+    """What one `find_alignment` pass collects: for every cross-attention module named in `slots` the probabilities of its
+    alignment heads go into that module's slice of `probs` [B, n_sel, Tq, Tk] (K.attn_probs on the q / kv the module has at hand)."""
+
+    def __init__(self, slots: dict, probs: torch.Tensor, n_tok, n_key, host_lens, scale: float, keep_views: bool):
+        self.slots, self.probs, self.n_tok, self.n_key, self.host_lens, self.scale = slots, probs, n_tok, n_key, host_lens, scale
+        self.views = {} if keep_views else None
+
+    def record(self, module, q: torch.Tensor, k: torch.Tensor, n_head: int) -> None:
+        slot = self.slots.get(module)
+        if slot is None:
+            return
+        heads, at = slot
+        K.attn_probs(q, k, heads, self.n_tok, self.n_key, n_head, self.scale, self.probs[:, at:at + heads.numel()], host_lens=self.host_lens)
+        if self.views is not None:
+            self.views[module] = (q, k)
+
+
+def alignment_capture() -> Optional[AlignCapture]:
+    return getattr(_TLS, "align_capture", None)
+
+
+@contextlib.contextmanager
+def capture_alignment(cap: AlignCapture):
+    """Inside this context, under torch.no_grad(), the uncached cross-attention forward of every module `cap` names also writes its
+    alignment-head probabilities.  Thread-local, in the style of runtime.exchange_launch_mode: nothing is stored in the library or
+    on a module, and outside it nothing runs differently."""
+    old = alignment_capture()
+    _TLS.align_capture = cap
+    try:
+        yield cap
+    finally:
+        _TLS.align_capture = old
+
+
+def alignment_words(path_text, path_time, word_token_counts, token_probs, text) -> list:
+    """Upstream's host arithmetic behind the DTW path of ONE audio -> [(start_s, end_s, probability, [token ids])].
+    path_text / path_time: the path in forward order (row 0 = the no-timestamps token, then the text tokens); word_token_counts: the
+    tokens per word over text + [eot] (the last word, the eot, is dropped as upstream drops it); token_probs: one per text token."""
+    import numpy as np
+
+    counts = [int(c) for c in word_token_counts]
+    if len(counts) <= 1:
+        return []
+    if sum(counts) != len(text) + 1 or min(counts) < 1:
+        raise ValueError(f"word_token_counts {counts} must be positive and sum to len(text) + 1 = {len(text) + 1}")
+    ti, tj = np.asarray(path_text, dtype=np.int64), np.asarray(path_time, dtype=np.int64)
+    bounds = np.pad(np.cumsum(counts[:-1]), (1, 0))
+    jumps = np.pad(np.diff(ti), (1, 0), constant_values=1).astype(bool)
+    jump_times = tj[jumps] / TOKENS_PER_SECOND
+    starts, ends = jump_times[bounds[:-1]], jump_times[bounds[1:]]
+    probs = np.asarray(token_probs, dtype=np.float64)
+    return [(float(s), float(e), float(np.mean(probs[i:j])), [int(t) for t in text[i:j]])
+            for s, e, i, j in zip(starts, ends, bounds[:-1], bounds[1:])]
+
+
+def alignment_slots(model, device) -> tuple:
+    """model.alignment_heads -> ({cross_attn module: (heads i32 on the device, first slice)}, n_sel): the heads of a layer in the
+    buffer's order, the layers in ascending order — the order of upstream's `alignment_heads.indices().T`."""
+    mask = model.alignment_heads
+    mask = (mask.to_dense() if mask.is_sparse else mask).cpu()
+    blocks = model.decoder.blocks
+    if tuple(mask.shape) != (len(blocks), model.dims.n_text_head):
+        raise ValueError(f"alignment_heads {tuple(mask.shape)} does not fit {len(blocks)} decoder layers of {model.dims.n_text_head} heads")
+    slots, at = {}, 0
+    for layer, block in enumerate(blocks):
+        hs = torch.nonzero(mask[layer]).flatten().tolist()
+        if hs:
+            slots[block.cross_attn] = (torch.tensor(hs, dtype=torch.int32, device=device), at)
+            at += len(hs)
+    if at == 0:
+        raise ValueError("alignment_heads selects no head")
+    return slots, at
+
+
+@torch.no_grad()
+def find_alignment(model, mel: torch.Tensor, text_tokens, *, sot_sequence: Sequence[int], no_timestamps: int, eot: int, num_frames,
+                   word_token_counts=None, medfilt_width: int = 7, qk_scale: float = 1.0, return_debug: bool = False):
+    """Word-level timestamps for already-decoded text -> per audio [(start_s, end_s, probability, [token ids])].
+
+    mel f32 [B, n_mels, 2 * n_audio_ctx]; text_tokens: one list of text token ids (< eot) per audio, ragged; num_frames: the mel
+    frames that hold audio, an int or one per audio (keys at or beyond num_frames // 2 take no part in the softmax);
+    word_token_counts: per audio the tokens per word over text + [eot] (what upstream's `tokenizer.split_to_word_tokens` gives;
+    None: every token is its own word).  One teacher-forced pass over [*sot_sequence, no_timestamps, *text, eot] (right padding lies
+    behind the eot: causal attention never sees it) with the alignment-head probabilities captured (wft_attn_probs_bf16), then
+    wft_align_matrix, wft_dtw_f32 on rows len(sot_sequence) .. of the matrix, the paths to the host, `alignment_words` there.  A
+    word's probability is the mean over its tokens of softmax(logits[:eot]) at the token's position (wft_token_stats with V = eot).
+    An audio with no text gives [].  return_debug adds a dict: "q" / "k" (per captured module, the views the kernel read), "probs",
+    "matrix", "paths", "n_tok", "n_key", "rows" (the audios that ran), "token_probs".  Call it in eval mode; the fp32 compute mode raises."""
+    if getattr(model, "compute_dtype", "bf16") != "bf16":
+        raise NotImplementedError("find_alignment runs in the bf16 compute mode only: the alignment kernels (csrc/align.hip) read bf16 q / k; "
+                                  "call model.set_compute_dtype('bf16')")
+    B = mel.shape[0]
+    texts = [[int(t) for t in row] for row in text_tokens]
+    if len(texts) != B:
+        raise ValueError(f"text_tokens holds {len(texts)} rows for {B} audios")
+    sot = [int(t) for t in sot_sequence]
+    eot = int(eot)
+    frames = [int(num_frames)] * B if isinstance(num_frames, int) else [int(f) for f in num_frames]
+    n_ctx, Ta = model.dims.n_text_ctx, model.dims.n_audio_ctx
+    if len(frames) != B or any(f < 2 or f // 2 > Ta for f in frames):
+        raise ValueError(f"num_frames must be an int or one per audio with 1 <= num_frames // 2 <= {Ta}")
+    if any(t < 0 or t >= eot for row in texts for t in row):
+        raise ValueError("text tokens must lie in [0, eot)")
+    if any(len(sot) + len(row) + 2 > n_ctx for row in texts):
+        raise ValueError(f"sot_sequence + no_timestamps + text + eot must fit the text context of {n_ctx}")
+    counts = [None] * B if word_token_counts is None else list(word_token_counts)
+    if len(counts) != B:
+        raise ValueError(f"word_token_counts holds {len(counts)} rows for {B} audios")
+    rows = [b for b in range(B) if texts[b]]
+    result = [[] for _ in range(B)]
+    if not rows:
+        return (result, {}) if return_debug else result
+    dev = model.device
+    n = len(rows)
+    head = sot + [int(no_timestamps)]
+    lens = [len(head) + len(texts[b]) + 1 for b in rows]
+    T = max(lens)
+    tokens = torch.full((n, T), eot, dtype=torch.int64)
+    for i, b in enumerate(rows):
+        tokens[i, :lens[i] - 1] = torch.tensor(head + texts[b], dtype=torch.int64)
+    tokens = tokens.to(dev)
+    keys = [frames[b] // 2 for b in rows]
+    n_tok, n_key = torch.tensor(lens, dtype=torch.int32, device=dev), torch.tensor(keys, dtype=torch.int32, device=dev)
+    slots, n_sel = alignment_slots(model, dev)
+    probs = torch.zeros((n, n_sel, T, Ta), dtype=torch.float32, device=dev)
+    cap = AlignCapture(slots, probs, n_tok, n_key, (lens, keys), 64 ** -0.5 * float(qk_scale), return_debug)
+    mel = mel.to(dev)
+    xa = model.embed_audio(mel if n == B else mel[torch.tensor(rows, device=dev)])
+    with capture_alignment(cap):
+        h = model.decoder.hidden(tokens, xa)  # [n, T, d]
+    matrix = K.align_matrix(probs, n_tok, n_key, medfilt_width, host_lens=(lens, keys))
+    n_rows = [len(texts[b]) + 1 for b in rows]
+    paths = K.dtw(matrix, len(sot), torch.tensor(n_rows, dtype=torch.int32, device=dev), n_key, host_lens=(n_rows, keys))
+    # softmax(logits[:eot]) at the positions that predict the text tokens: position len(sot) + i predicts text[i]
+    pos = torch.tensor([i * T + len(sot) + j for i, b in enumerate(rows) for j in range(len(texts[b]))], dtype=torch.int64, device=dev)
+    tgt = torch.tensor([t for b in rows for t in texts[b]], dtype=torch.int64, device=dev)
+    logits = model.decoder.padded_logits(h.reshape(n * T, -1).index_select(0, pos).view(pos.numel(), 1, -1))
+    stats, _ = K.token_stats(logits, tgt, eot)
+    token_probs = torch.exp(stats[:, 3] - stats[:, 0]).cpu().tolist()
+    pt, pj, pl = (t.cpu() for t in paths)
+    at = 0
+    for i, b in enumerate(rows):
+        L_ = int(pl[i])
+        tp = token_probs[at:at + len(texts[b])]
+        at += len(texts[b])
+        wc = counts[b] if counts[b] is not None else [1] * (len(texts[b]) + 1)
+        result[b] = alignment_words(pt[i, :L_].numpy(), pj[i, :L_].numpy(), wc, tp, texts[b])
+    if not return_debug:
+        return result
+    debug = {"q": {m: v[0] for m, v in cap.views.items()}, "k": {m: v[1] for m, v in cap.views.items()}, "probs": probs, "matrix": matrix,
+             "paths": (pt, pj, pl), "n_tok": lens, "n_key": keys, "rows": rows, "token_probs": token_probs, "slots": slots,
+             "logits": logits, "token_stats": stats}
+    return result, debug

@@ -836,6 +836,94 @@ def beam_update(cand_tok, cand_logp, tokens, anc, lens, sum_logprob, done, unfin
     L.check(L.load().wft_beam_update(C.byref(a), L.stream_ptr()), "wft_beam_update")
 
 
+# --------------------------------------------------------------------------- word-level alignment (csrc/align.hip)
+def _host_lens(host, n: int, hi: int, name: str) -> list:
+    """The host copy of a device length array: n ints inside [0, hi] — checked before any launch (the kernels clamp as well)."""
+    vals = [int(v) for v in host]
+    if len(vals) != n or any(v < 0 or v > hi for v in vals):
+        raise ValueError(f"{name}: expected {n} lengths inside 0..{hi}, got {vals}")
+    return vals
+
+
+def attn_probs(q, k, heads, n_tok, n_key, n_head: int, scale: float, out, *, host_lens):
+    """Alignment-head probabilities (wft_attn_probs_bf16; include/wft.h "Word-level alignment").  q bf16 [B, Tq, H*64] / k bf16
+    [B, Tk, H*64] views (any row stride: the k half of the cross kv buffer in place); heads i32 [n] on the device; n_tok / n_key
+    i32 [B] on the device with host_lens = (their values on the host); out f32 [B, n, Tq, Tk] view with contiguous rows (a slice of
+    the [B, n_sel_total, Tq, Tk] buffer) -> out, rows >= n_tok[b] and columns >= n_key[b] untouched."""
+    _chk(q, BF16, "q"); _chk(k, BF16, "k"); _chk(heads, torch.int32, "heads"); _chk(out, F32, "out")
+    B, Tq, D = q.shape
+    Tk = k.shape[1]
+    n = heads.numel()
+    if D != n_head * 64 or k.shape[0] != B or k.shape[2] != D or q.stride(2) != 1 or k.stride(2) != 1:
+        raise ValueError(f"attn_probs: q {tuple(q.shape)} / k {tuple(k.shape)} do not fit {n_head} heads of 64")
+    if n < 1 or not heads.is_contiguous() or tuple(out.shape) != (B, n, Tq, Tk) or out.stride(3) != 1 or out.stride(2) < Tk \
+            or out.stride(1) < Tq * out.stride(2):
+        raise ValueError(f"attn_probs: heads must be contiguous i32 [n >= 1] and out an f32 [{B}, n, {Tq}, {Tk}] view with contiguous rows")
+    _chk_flag(n_tok, B, "n_tok"); _chk_flag(n_key, B, "n_key")
+    _host_lens(host_lens[0], B, Tq, "n_tok"); _host_lens(host_lens[1], B, Tk, "n_key")
+    a = L.AttnArgs()
+    a.q, a.ldq, a.q_bs = _attn_view(q)
+    a.k, a.ldk, a.k_bs = _attn_view(k)
+    a.B, a.H, a.Tq, a.Tk, a.scale = B, n_head, Tq, Tk, scale
+    L.check(L.load().wft_attn_probs_bf16(C.byref(a), _p(heads), n, _p(n_tok), _p(n_key), _p(out), out.stride(0), out.stride(1), out.stride(2),
+                                         L.stream_ptr()), "wft_attn_probs_bf16")
+    return out
+
+
+def align_matrix(probs, n_tok, n_key, width: int = 7, out=None, *, host_lens):
+    """Standardise over the tokens, median-filter along the frames, average the heads (wft_align_matrix).  probs f32 [B, n_sel, Tq, Tk]
+    with contiguous rows -> matrix f32 [B, Tq, Tk]; elements at rows >= n_tok[b] or columns >= n_key[b] are not written (a fresh
+    `out` is zero-filled)."""
+    _chk(probs, F32, "probs")
+    if probs.dim() != 4 or probs.stride(3) != 1:
+        raise ValueError("align_matrix: probs must be f32 [B, n_sel, Tq, Tk] with contiguous rows")
+    B, n_sel, Tq, Tk = probs.shape
+    width = int(width)
+    if width < 1 or width > 31 or width % 2 == 0:
+        raise ValueError(f"align_matrix: the filter width must be odd and lie in 1..31, got {width}")
+    if out is None:
+        out = torch.zeros((B, Tq, Tk), dtype=F32, device=probs.device)
+    _chk(out, F32, "out")
+    if tuple(out.shape) != (B, Tq, Tk) or out.stride(2) != 1:
+        raise ValueError(f"align_matrix: out must be f32 [{B}, {Tq}, {Tk}] with contiguous rows")
+    _chk_flag(n_tok, B, "n_tok"); _chk_flag(n_key, B, "n_key")
+    _host_lens(host_lens[0], B, Tq, "n_tok"); _host_lens(host_lens[1], B, Tk, "n_key")
+    L.check(L.load().wft_align_matrix(_p(probs), probs.stride(0), probs.stride(1), probs.stride(2), _p(n_tok), _p(n_key), _p(out), out.stride(0),
+                                      out.stride(1), B, n_sel, Tq, Tk, width, L.stream_ptr()), "wft_align_matrix")
+    return out
+
+
+def dtw(matrix, row0: int, n_rows, n_cols, *, host_lens, negate: bool = True, paths=None):
+    """Dynamic time warping with the backtrace (wft_dtw_f32): per audio the path through -matrix[b, row0 : row0 + n_rows[b], : n_cols[b]]
+    (negate=False: the matrix as it is).  matrix f32 [B, rows, cols] with contiguous rows; n_rows / n_cols i32 [B] on the device with
+    host_lens = (their values on the host) -> (path_text i32 [B, ld], path_time i32 [B, ld], path_len i32 [B]) in forward order;
+    entries beyond path_len[b] keep what `paths` = (path_text, path_time, path_len) held (fresh buffers: -1)."""
+    _chk(matrix, F32, "matrix")
+    if matrix.dim() != 3 or matrix.stride(2) != 1:
+        raise ValueError("dtw: matrix must be f32 [B, rows, cols] with contiguous rows")
+    B, R, Cn = matrix.shape
+    _chk_flag(n_rows, B, "n_rows"); _chk_flag(n_cols, B, "n_cols")
+    row0 = int(row0)
+    if row0 < 0 or row0 >= R:
+        raise ValueError(f"dtw: row0={row0} is outside the {R} matrix rows")
+    rows = _host_lens(host_lens[0], B, min(R - row0, 448), "n_rows")
+    cols = _host_lens(host_lens[1], B, Cn, "n_cols")
+    nr, nc = max(max(rows), 1), max(max(cols), 1)
+    ld = nr + nc - 1
+    if paths is None:
+        paths = (torch.full((B, ld), -1, dtype=torch.int32, device=matrix.device), torch.full((B, ld), -1, dtype=torch.int32, device=matrix.device),
+                 torch.zeros(B, dtype=torch.int32, device=matrix.device))
+    pt, pj, pl = paths
+    _chk(pt, torch.int32, "path_text"); _chk(pj, torch.int32, "path_time"); _chk_flag(pl, B, "path_len")
+    if pt.shape != pj.shape or pt.dim() != 2 or pt.shape[0] != B or pt.shape[1] < ld or not pt.is_contiguous() or not pj.is_contiguous():
+        raise ValueError(f"dtw: path_text / path_time must be contiguous i32 [{B}, >= {ld}]")
+    need = L.load().wft_dtw_workspace_bytes(B, nr, nc)
+    ws = _tn_workspace(matrix.device, need, slot="dtw")
+    L.check(L.load().wft_dtw_f32(_p(matrix), matrix.stride(0), matrix.stride(1), R, row0, _p(n_rows), _p(n_cols), B, nr, nc, int(bool(negate)),
+                                 _p(pt), _p(pj), pt.stride(0), _p(pl), _p(ws), ws.numel(), L.stream_ptr()), "wft_dtw_f32")
+    return pt, pj, pl
+
+
 # --------------------------------------------------------------------------- embedding / CE
 def embed_fwd(tokens, emb, pos):
     _chk(tokens, torch.int64, "tokens"); _chk(emb, F32, "emb"); _chk(pos, F32, "pos")

@@ -213,6 +213,11 @@ SIGNATURES = {
     "wft_beam_update": [C.POINTER(BeamUpdateArgs), c_vp],
     "wft_decode_sample": [C.POINTER(DecodePickArgs), C.POINTER(SampleRules), c_vp],
     "wft_decode_sample_ts": [C.POINTER(DecodePickArgs), C.POINTER(SampleRules), C.POINTER(TsRules), c_vp],
+    "wft_attn_probs_bf16": [C.POINTER(AttnArgs), c_vp, C.c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp],
+    "wft_align_matrix": [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_vp],
+    "wft_dtw_workspace_bytes": [C.c_int, C.c_int, C.c_int],
+    "wft_dtw_f32": [c_vp, c_i64, c_i64, C.c_int, C.c_int, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_i64, c_vp, c_vp,
+                    c_i64, c_vp],
     "wft_embed_fwd": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_int, c_i64, c_vp],
     "wft_embed_bwd": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_int, c_i64, c_vp],
     "wft_ce_fwd": [c_vp, c_i64, c_vp, c_i64, c_i64, C.c_float, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -250,7 +255,8 @@ SIGNATURES = {
 _RESTYPES = {"wft_last_error": C.c_char_p, "wft_version": C.c_char_p, "wft_layernorm_bwd_workspace": c_i64,
              "wft_gemm_tn_workspace_bytes": c_i64, "wft_gemm_nt_colsum_workspace_bytes": c_i64, "wft_gemm_nt_splitk_workspace_bytes": c_i64, "wft_gemm_nt_aux8_bytes": c_i64, "wft_colsum_workspace_bytes": c_i64,
              "wft_attn_bwd_colsum_workspace_bytes": c_i64, "wft_attn_decode_workspace_bytes": c_i64,
-             "wft_gemm_nt_stream_workspace_bytes": c_i64, "wft_attn_decode_beam_workspace_bytes": c_i64}
+             "wft_gemm_nt_stream_workspace_bytes": c_i64, "wft_attn_decode_beam_workspace_bytes": c_i64,
+             "wft_dtw_workspace_bytes": c_i64}
 
 _lib = None
 

@@ -201,6 +201,9 @@ class MultiHeadAttention(nn.Module):
                 xa, acc = ops.grad_fork(xa)
             kv = ops.linear(_as2d(_to_bf16(xa)), self._kv_group, [m.base_weight() for m in lin], [m.bias for m in lin],
                             [m.lora_spec() for m in lin], dx_accum=acc)
+            cap = _decode.alignment_capture()
+            if cap is not None and T > 1 and not torch.is_grad_enabled():  # find_alignment's pass: the alignment heads' probabilities
+                cap.record(self, q.view(B, T, d), kv.view(B, Ta, 2 * d)[..., :d], self.n_head)
             o = ops.CrossAttnFn.apply(q.view(B, T, d), kv.view(B, Ta, 2 * d), self.n_head)
         out = self.out(o.view(B * T, d), residual=None if residual is None else _as2d(residual))
         return out.view(B, T, d), None
@@ -514,6 +517,20 @@ class Whisper(nn.Module):
         whose result fails the average log-probability / compression ratio / no-speech tests (`decode.needs_fallback`)
         -> (tokens, lengths, sum_logprob, info).  The encoder runs once.  The fp32 compute mode raises."""
         return _decode.decode_with_fallback(self, mel, prompt, prompt_len, **kw)
+
+    def set_alignment_heads(self, heads) -> None:
+        """Replace the `alignment_heads` buffer (upstream's `Whisper.set_alignment_heads`): a bool [n_text_layer, n_text_head] mask, or
+        upstream's dump of one (base85 of the gzipped bool bytes).  The default — every head of the upper half of the decoder —
+        stays until this is called."""
+        mask = _decode.parse_alignment_heads(heads, self.dims.n_text_layer, self.dims.n_text_head)
+        self.register_buffer("alignment_heads", mask.to(self.alignment_heads.device).to_sparse(), persistent=False)
+
+    def find_alignment(self, mel: Tensor, text_tokens, **kw):
+        """Word-level timestamps for decoded text (engine/decode.py find_alignment has the keywords; upstream: whisper/timing.py
+        find_alignment, restated — parity with the upstream binary is unpinned): the cross-attention probabilities of the
+        `alignment_heads`, standardised, median-filtered and averaged, then dynamic time warping, all on the device (csrc/align.hip)
+        -> per audio [(start_s, end_s, probability, [token ids])].  The fp32 compute mode raises."""
+        return _decode.find_alignment(self, mel, text_tokens, **kw)
 
     def forward(self, mel: Tensor, tokens: Tensor, targets: Optional[Tensor] = None, label_smoothing: float = 0.0) -> Tensor:
         """logits f32 [B, S, V] — or, when `targets` is given (engine extension used by train_step, also

@@ -254,7 +254,10 @@ def resize_whisper_layers(model, target_encoder_layers: Optional[int] = None, ta
         model.dims.n_text_layer = target_decoder_layers
         heads = torch.zeros(target_decoder_layers, model.dims.n_text_head, dtype=torch.bool)
         heads[target_decoder_layers // 2:] = True
-        model.register_buffer("alignment_heads", heads.to_sparse(), persistent=False)
+        if hasattr(model, "set_alignment_heads"):  # the default mask of the new depth (model/model_utils.py:171-174)
+            model.set_alignment_heads(heads)
+        else:
+            model.register_buffer("alignment_heads", heads.to_sparse(), persistent=False)
         print(f"Resized decoder layers: {old} -> {target_decoder_layers}")
         changed = True
     return changed
@@ -354,6 +357,10 @@ def load_model_and_set_heads(model: Whisper, name: str, device: Union[str, torch
     else:
         checkpoint = torch.load(name, map_location=device)
     model.load_state_dict(checkpoint["model_state_dict"])
+    # (model/model_utils.py:376-377 sets the heads of an official model name from openai-whisper's table, which this build does not
+    # ship; a checkpoint file may carry its own mask or dump under "alignment_heads")
+    if checkpoint.get("alignment_heads") is not None:
+        model.set_alignment_heads(checkpoint["alignment_heads"])
     return model.to(device)
 
 
