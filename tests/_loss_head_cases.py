@@ -1,5 +1,5 @@
 """Cases, float64 reference, per-element bounds and float32 restatements for the loss-head kernels: wft_ce_fwd, wft_ce_bwd and
-wft_token_stats (csrc/misc.hip) and their fp32-mode twins wft_ce_fwd_f32 / wft_ce_bwd_f32 (csrc/f32.hip).  Shared by
+wft_token_stats (csrc/loss.hip) and their fp32-mode twins wft_ce_fwd_f32 / wft_ce_bwd_f32 (csrc/f32.hip).  Shared by
 tests/test_loss_head_host.py (CPU: the bound accepts the kernels' arithmetic and rejects every listed mutant of it) and
 tests/test_loss_head_gpu.py (the kernels themselves under the same checker).
 

@@ -1,4 +1,4 @@
-"""wft_embed_fwd / wft_embed_bwd (csrc/misc.hip) and wft_embed_fwd_f32 / wft_embed_bwd_f32 (csrc/f32.hip), bit for bit.
+"""wft_embed_fwd / wft_embed_bwd (csrc/embed.hip) and wft_embed_fwd_f32 / wft_embed_bwd_f32 (csrc/f32.hip), bit for bit.
 
 The backward kernels exist for run-to-run determinism: every embedding row is summed over the positions that hold its id in
 position order, without atomics, so the reference is that sum — a float32 loop over the positions on the CPU, not sum() or

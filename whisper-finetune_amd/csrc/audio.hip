@@ -166,9 +166,7 @@ extern "C" int wft_logmel(const float* audio, const float* filters, float* out, 
   hipLaunchKernelGGL(logmel_kernel, grid, dim3(256), 0, s, audio, filters, out, (unsigned int*)clipmax, n_samples, n_mels,
                      n_frames);
   const long per_clip = (long)n_mels * n_frames, total = per_clip * B;
-  long g = (total + 255) / 256;
-  if (g > 4096) g = 4096;
-  hipLaunchKernelGGL(logmel_norm_kernel, dim3((unsigned)g), dim3(256), 0, s, out, (const unsigned int*)clipmax, per_clip,
+  hipLaunchKernelGGL(logmel_norm_kernel, dim3(ew_grid(total)), dim3(256), 0, s, out, (const unsigned int*)clipmax, per_clip,
                      total);
   WFT_CHECK_LAUNCH();
   return WFT_OK;

@@ -68,6 +68,18 @@ __device__ __forceinline__ unsigned int pack2bf(float lo, float hi) {
   const wft_f32x2_t v = {lo, hi};
   return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, wft_bf16x2_t));
 }
+// eight bf16 of one 16-byte access <-> eight floats, element order low half first
+__device__ __forceinline__ void bf8_unpack(u32x4 r, float (&v)[8]) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    v[2 * e] = bf2f((unsigned short)(r[e] & 0xffff));
+    v[2 * e + 1] = bf2f((unsigned short)(r[e] >> 16));
+  }
+}
+__device__ __forceinline__ u32x4 bf8_pack(const float (&v)[8]) {
+  const u32x4 o = {pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
+  return o;
+}
 
 // ---- wave64 reductions
 __device__ __forceinline__ float wave_sum(float v) {
@@ -163,3 +175,10 @@ __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
 }
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// grid of a grid-stride loop over nvec items, 256 per workgroup: at most 4096 workgroups, at least one
+static inline int ew_grid(int64_t nvec) {
+  int64_t g = (nvec + 255) / 256;
+  if (g > 4096) g = 4096;
+  if (g < 1) g = 1;
+  return (int)g;
+}

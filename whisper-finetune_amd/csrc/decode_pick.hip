@@ -9,7 +9,7 @@
 #include "decode_common.h"
 
 // ----------------------------------------------------------------------------- embedding at the device-side position
-// out[b] = emb[tokens[b, len[b] - 1]] + pos[len[b] - 1]: the arithmetic of embed_fwd_kernel (misc.hip), one fp32 add and one rounding.
+// out[b] = emb[tokens[b, len[b] - 1]] + pos[len[b] - 1]: the arithmetic of embed_fwd_kernel (embed.hip), one fp32 add and one rounding.
 __global__ __launch_bounds__(256) void decode_embed_kernel(const long* tokens, long ld_tokens, const int* len, const float* emb,
                                                             const float* pos, unsigned short* out, int B, int n_ctx, int d, long V) {
   const int dv = d >> 3;

@@ -244,25 +244,25 @@ __global__ __launch_bounds__(256) void gelu_bwd_f32_kernel(const float* dy, cons
 __global__ __launch_bounds__(256) void axpby_f32_kernel(float a, const float* x, float b, const float* y, float* out, long n) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) out[i] = y ? a * x[i] + b * y[i] : a * x[i];
 }
-static unsigned ew_grid(int64_t n) {
+static unsigned ew_grid_f32(int64_t n) {
   int64_t g = (n + 255) / 256;
   return (unsigned)(g > 65535 ? 65535 : g);
 }
 extern "C" int wft_gelu_fwd_f32(const float* x, float* y, int64_t n, void* stream) {
   WFT_CHECK_ARG(x && y && n >= 1, "bad arguments");
-  hipLaunchKernelGGL(gelu_fwd_f32_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, x, y, (long)n);
+  hipLaunchKernelGGL(gelu_fwd_f32_kernel, dim3(ew_grid_f32(n)), dim3(256), 0, (hipStream_t)stream, x, y, (long)n);
   WFT_CHECK_LAUNCH();
   return WFT_OK;
 }
 extern "C" int wft_gelu_bwd_f32(const float* dy, const float* x, float* dx, int64_t n, void* stream) {
   WFT_CHECK_ARG(dy && x && dx && n >= 1, "bad arguments");
-  hipLaunchKernelGGL(gelu_bwd_f32_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, dy, x, dx, (long)n);
+  hipLaunchKernelGGL(gelu_bwd_f32_kernel, dim3(ew_grid_f32(n)), dim3(256), 0, (hipStream_t)stream, dy, x, dx, (long)n);
   WFT_CHECK_LAUNCH();
   return WFT_OK;
 }
 extern "C" int wft_axpby_f32(float a, const float* x, float b, const float* y, float* out, int64_t n, void* stream) {
   WFT_CHECK_ARG(x && out && n >= 1, "bad arguments");
-  hipLaunchKernelGGL(axpby_f32_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, a, x, b, y, out, (long)n);
+  hipLaunchKernelGGL(axpby_f32_kernel, dim3(ew_grid_f32(n)), dim3(256), 0, (hipStream_t)stream, a, x, b, y, out, (long)n);
   WFT_CHECK_LAUNCH();
   return WFT_OK;
 }

@@ -76,6 +76,32 @@ extern "C" int wft_mt_sumsq_f32(const void* tab, const int64_t* numel, const int
   return WFT_OK;
 }
 
+// One tensor: atomicAdd of the workgroup sums into *out (the caller zeroes it).
+__global__ __launch_bounds__(256) void sumsq_kernel(const float* g, long n, float* out) {
+  __shared__ float red[4];
+  float s = 0.f;
+  const long nv = n >> 2;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
+    const f32x4 x = *(const f32x4*)(g + i * 4);
+    s += x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3];
+  }
+  if (blockIdx.x == 0) {
+    const long t = (nv << 2) + threadIdx.x;
+    if (t < n) s += g[t] * g[t];
+  }
+  s = block_sum_256(s, red);
+  if (threadIdx.x == 0) atomicAdd(out, s);
+}
+extern "C" int wft_sumsq_f32(const float* g, int64_t n, float* out, void* stream) {
+  WFT_CHECK_ARG(g && out && n >= 1, "bad args");
+  WFT_CHECK_ARG((((uintptr_t)g) & 15) == 0, "16-byte alignment");
+  int grid = ew_grid(n / 4 + 1);
+  if (grid > 1024) grid = 1024;
+  hipLaunchKernelGGL(sumsq_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, g, (long)n, out);
+  WFT_CHECK_LAUNCH();
+  return WFT_OK;
+}
+
 // ------------------------------------------------------------------ AdamW (torch.optim.AdamW semantics)
 // tab rows: 0 p, 1 g, 2 exp_avg, 3 exp_avg_sq.  If sumsq != NULL the gradient is first scaled by
 // min(1, max_norm / (sqrt(*sumsq) + 1e-6)) — exactly torch.nn.utils.clip_grad_norm_'s coefficient.
@@ -128,6 +154,61 @@ extern "C" int wft_mt_adamw(const void* tab, const int64_t* numel, const int32_t
   hipLaunchKernelGGL(mt_adamw_kernel, dim3(total_chunks), dim3(256), 0, (hipStream_t)stream, (const long*)tab,
                      (const long*)numel, (const int*)chunk_start, n, lr, beta1, beta2, eps, weight_decay, bias_corr1,
                      bias_corr2, sumsq, max_norm);
+  WFT_CHECK_LAUNCH();
+  return WFT_OK;
+}
+
+// The same update for ONE tensor (+ an optional bf16 copy of the new parameter); gscale: a device scalar the gradient is
+// multiplied by, or NULL.
+__global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, float* m, float* v, unsigned short* pb,
+                                                     long n, float lr, float b1, float b2, float eps, float wd, float bc1,
+                                                     float bc2, const float* gscale) {
+  const float gs = gscale ? gscale[0] : 1.f;
+  const float step = lr / bc1;
+  const float rbc2 = rsqrtf(bc2);
+  const long nv = n >> 2;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
+    f32x4 pp = *(f32x4*)(p + i * 4);
+    const f32x4 gg = *(const f32x4*)(g + i * 4) * gs;
+    f32x4 mm = *(f32x4*)(m + i * 4), vv = *(f32x4*)(v + i * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      pp[e] *= (1.f - lr * wd);
+      mm[e] = b1 * mm[e] + (1.f - b1) * gg[e];
+      vv[e] = b2 * vv[e] + (1.f - b2) * gg[e] * gg[e];
+      const float denom = sqrtf(vv[e]) * rbc2 + eps;
+      pp[e] -= step * mm[e] / denom;
+    }
+    *(f32x4*)(p + i * 4) = pp;
+    *(f32x4*)(m + i * 4) = mm;
+    *(f32x4*)(v + i * 4) = vv;
+    if (pb) {
+      u32x2 o = {pack2bf(pp[0], pp[1]), pack2bf(pp[2], pp[3])};
+      *(u32x2*)(pb + i * 4) = o;
+    }
+  }
+  if (blockIdx.x == 0) {
+    const long t = (nv << 2) + threadIdx.x;
+    if (t < n) {
+      float pp = p[t] * (1.f - lr * wd);
+      const float gg = g[t] * gs;
+      const float mm = b1 * m[t] + (1.f - b1) * gg;
+      const float vv = b2 * v[t] + (1.f - b2) * gg * gg;
+      pp -= step * mm / (sqrtf(vv) * rbc2 + eps);
+      p[t] = pp; m[t] = mm; v[t] = vv;
+      if (pb) pb[t] = f2bf(pp);
+    }
+  }
+}
+extern "C" int wft_adamw_step(float* p, const float* g, float* m, float* v, wft_bf16* p_bf16, int64_t n, float lr,
+                              float beta1, float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2,
+                              const float* gscale, void* stream) {
+  WFT_CHECK_ARG(p && g && m && v && n >= 1, "bad args");
+  WFT_CHECK_ARG((((uintptr_t)p) & 15) == 0 && (((uintptr_t)g) & 15) == 0 && (((uintptr_t)m) & 15) == 0 &&
+                    (((uintptr_t)v) & 15) == 0 && (!p_bf16 || (((uintptr_t)p_bf16) & 7) == 0),
+                "16-byte alignment");
+  hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, p_bf16, (long)n,
+                     lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, gscale);
   WFT_CHECK_LAUNCH();
   return WFT_OK;
 }
