@@ -640,6 +640,34 @@ int wft_dtw_f32(const float* matrix, int64_t m_bs, int64_t ldm, int matrix_rows,
                 const int32_t* n_cols, int B, int n_rows_max, int n_cols_max, int negate, int32_t* path_text, int32_t* path_time,
                 int64_t ld_path, int32_t* path_len, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------- Language detection and long-form windows */
+/* csrc/transcribe.hip: the two device stages of upstream's `detect_language` and of the window loop of `transcribe()`
+ * (engine/transcribe.py), restated; openai-whisper is not a dependency: parity with its binary is unpinned.
+ *
+ * wft_lang_probs: upstream masks every column that is not a language token with -inf, then takes the argmax and the softmax.
+ *  logits bf16 [B, ld] in the layout of the tied logits product (only columns < V are meaningful); lang_ids i32 [n_lang] in device
+ *    memory, strictly increasing, each in [0, V) (the caller checks that; an id outside is clamped), 1 <= n_lang <= 1024.
+ *  probs[b, j] (at probs + b*ld_probs + j) = exp(x[b, lang_ids[j]] - lse_b) with lse_b over the n_lang language columns only, in
+ *    fp32: d = x - max, s = sum exp(d), p = exp(d - log(s)), accurate expf / logf.
+ *  best[b] = lang_ids[j*], j* the LOWEST j that attains the maximum (the tie rule of wft_token_stats and wft_decode_pick).
+ *  One workgroup per row reads the n_lang gathered values, never the whole row: what the other columns hold (inf, NaN) does not
+ *  matter.  Fixed summation order, no atomics: the same arguments give the same bits.
+ *
+ * wft_mel_windows: out[r] = pad_or_trim(mel_a[:, seek[r] : seek[r] + n_win], n_win) with a = audio[r], for R rows at once.
+ *  mel f32: the A recordings' long log-mels packed in one buffer, recording a = [n_mels, ld_frames[a]] row-major from element
+ *    mel_off[a]; content_frames[a] = ld_frames[a] - n_win, the frames that are not the trailing padding of n_win frames.
+ *    mel_off i64 [A], ld_frames / content_frames i32 [A], audio / seek i32 [R]: all in device memory.
+ *  out f32 [R, n_mels, n_win]: out[r, m, t] = mel_a[m, seek[r] + t] bit for bit for t < min(n_win, content_frames[a] - seek[r]),
+ *    and 0.0f from there on — upstream's zero pad, NOT the log-mel of the padding that the source holds at those frames.
+ *  A seek outside [0, content_frames[a]) is the caller's argument error; the kernel clamps audio, seek and the frame counts so
+ *  that it never addresses anything outside [mel_off[a], mel_off[a] + n_mels * ld_frames[a]).
+ *  n_win % 4 == 0 and mel / out 16-byte aligned: every store is 16 bytes; the source start has any alignment (aligned 16-byte
+ *  loads, the four frames selected from two neighbouring chunks).                                                            */
+int wft_lang_probs(const wft_bf16* logits, int64_t ld, int64_t V, const int32_t* lang_ids, int n_lang, float* probs,
+                   int64_t ld_probs, int64_t* best, int B, void* stream);
+int wft_mel_windows(const float* mel, const int64_t* mel_off, const int32_t* ld_frames, const int32_t* content_frames,
+                    const int32_t* audio, const int32_t* seek, float* out, int R, int A, int n_mels, int n_win, void* stream);
+
 /* ------------------------------------------------- Log-mel + SpecAugment */
 /* whisper.audio.log_mel_spectrogram (data/data_loader.py:278; SURVEY.md App.
  * A.2): reflect-pad 200, Hann-400 STFT hop 160, |.|^2, mel filterbank,

@@ -36,7 +36,16 @@
          wavefront steps per audio.
          (profiles/decode_bench_align.jsonl: --parts align --batches 1,4 --out profiles/decode_bench_align.jsonl)
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,beam,ts,sample,align] [--batches 1,8,32] [--out FILE]
+  transcribe  long-form transcription at whisper-large-v3 dimensions (--batches = recordings, e.g. 4): ragged recordings of seeded
+         noise (95 s, 7 s less for each further one), Whisper.transcribe without timestamps (every window advances whole, so the
+         number of windows is fixed: 4 per 95 s) at temperature 0 with sample_len = 32 and language detection: wall time, windows/s,
+         audio-s/s; beside it the two kernels of csrc/transcribe.hip alone (wft_mel_windows on a full batch with its achieved
+         bytes/s, wft_lang_probs on as many rows) and their share of the wall time against the share of decode_with_fallback.
+         What to expect: the two kernels are a few MB of copy and a 100-value softmax per iteration — far below one per cent.
+         Not measured yet: no figure of this part is recorded under profiles/ or quoted anywhere.
+         (--parts transcribe --batches 4 --out profiles/decode_bench_transcribe.jsonl)
+
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,beam,ts,sample,align,transcribe] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -749,6 +758,57 @@ def bench_align(batches, n_heads=10, T=CAP, frames=2 * TA, rounds=5):
                   note="wall ms per call, host work included; beside it the teacher-forced encoder + decoder pass alone"))
 
 
+def bench_transcribe(batches, seconds=95, sample_len=32, rounds=3):
+    """Whisper.transcribe over ragged noise recordings at large-v3 dimensions, and the two kernels of csrc/transcribe.hip alone."""
+    from whisper_finetune.data.gpu_frontend import mel_filters
+    from whisper_finetune.engine import decode as Dm
+    from whisper_finetune.engine import transcribe as Tm
+
+    m, dims = _random_large_v3()
+    filters = mel_filters(dims.n_mels).to(DEV)
+    langs = list(range(50259, 50359))
+    kw = dict(sot_sequence=[50258, 50259, 50360], eot=50257, language_tokens=langs, temperatures=(0.0,), sample_len=sample_len,
+              logprob_threshold=None, no_speech_threshold=None, filters=filters)
+    for B in batches:
+        g = torch.Generator().manual_seed(B)
+        audios = [torch.randn((seconds - 7 * a) * Tm.SAMPLE_RATE + 53 * a, generator=g) * 0.1 for a in range(B)]
+        audio_s = sum(a.numel() for a in audios) / Tm.SAMPLE_RATE
+        spent = {"decode": 0.0}
+
+        def decode(*args, **kws):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            res = Dm.decode_with_fallback(*args, **kws)
+            torch.cuda.synchronize(); spent["decode"] += time.perf_counter() - t0
+            return res
+
+        m.transcribe(audios, **kw)  # warm-up
+        wall, dec, windows, iters = [], [], 0, 0
+        for _ in range(rounds):
+            spent["decode"] = 0.0
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            res = m.transcribe(audios, _decode=decode, **kw)
+            torch.cuda.synchronize(); wall.append(time.perf_counter() - t0); dec.append(spent["decode"])
+            windows, iters = sum(r["windows"] for r in res), max(r["windows"] for r in res)
+        packed = Tm.pack_logmels(audios, filters)
+        rows, seeks = list(range(B)), [0] * B
+        logits = torch.randn(B, K.round_up(dims.n_vocab, 128), device=DEV).to(BF)
+        res = ab({"mel_windows": lambda: packed.windows(rows, seeks), "lang_probs": lambda: K.lang_probs(logits, dims.n_vocab, langs),
+                  "long_logmel": lambda: Tm.long_logmel(audios[0], filters)}, rounds=5, iters=4)
+        med = statistics.median(wall)
+        kernels_ms = iters * res["mel_windows"][0] + res["lang_probs"][0]
+        rec = dict(part="transcribe", recordings=B, audio_s=round(audio_s, 1), windows=windows, iterations=iters, sample_len=sample_len,
+                   wall_s=round(med, 3), wall_min_s=round(min(wall), 3), windows_per_s=round(windows / med, 2), audio_s_per_s=round(audio_s / med, 1),
+                   decode_share=round(statistics.median(dec) / med, 4), kernels_share=round(kernels_ms * 1e-3 / med, 6),
+                   mel_windows_TBps=round(2 * B * dims.n_mels * 3000 * 4 / (res["mel_windows"][0] * 1e-3) / 1e12, 3),
+                   note="wall s per transcribe() call, host work and the long log-mels included; kernels_share = iterations x mel_windows + "
+                        "one lang_probs, timed alone (upload of the row tables included), over the wall time")
+        for n, (mm, mn, spread) in res.items():
+            rec[n + "_ms"] = round(mm, 4)
+            rec[n + "_min_ms"] = round(mn, 4)
+            rec[n + "_spread"] = round(spread, 3)
+        emit(rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="attn,gemm,e2e")
@@ -761,7 +821,7 @@ def main():
     emit(dict(part="env", device=torch.cuda.get_device_name(0), lib=L.load().wft_version().decode(), torch=torch.__version__))
     for part in a.parts.split(","):
         {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": bench_gemm_stream, "e2e_step": bench_e2e_step,
-         "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align}[part](batches)
+         "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align, "transcribe": bench_transcribe}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

@@ -8,8 +8,8 @@ decode under upstream's `ApplyTimestampRules` (restated in include/wft.h "Timest
 temperature on the device (wft_decode_sample: Gumbel-max over Philox noise, include/wft.h "Sampled decoding") on a cache whose samples
 share the prompt keys and the cross keys / values (`SampleCache`), and `decode_with_fallback` is upstream's temperature ladder of
 `transcribe()` (`decode_with_fallback`, `needs_fallback`: average log-probability, compression ratio, no-speech probability).
-Upstream's behaviour is restated; parity with its binary and with torch's random stream is unpinned.  No tokenizer, language
-detection or long-audio `transcribe()` (INTEGRATION.md).
+Upstream's behaviour is restated; parity with its binary and with torch's random stream is unpinned.  No tokenizer; language
+detection and the long-audio `transcribe()` loop live in engine/transcribe.py.
 
 Everything that changes from token to token lives in device memory (`KVCache`: len / tokens / finished / sum_logprob), so a
 step is a fixed sequence of launches whose arguments never change: LayerNorm and every projection through the existing
@@ -954,7 +954,7 @@ def decode_with_fallback(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_
                          best_of: int = 5, beam_size: Optional[int] = None, patience: float = 1.0, length_penalty: Optional[float] = None,
                          logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
                          compression_ratio_threshold: Optional[float] = None, text_of=None, no_speech: Optional[int] = None, sot_index=None,
-                         seed: int = 0, **decode_kw):
+                         seed: int = 0, _xa=None, **decode_kw):
     """Upstream's temperature ladder (`transcribe()`'s decode_with_fallback) -> (tokens i64 [B, L], lengths i64 [B], sum_logprob f32
     [B], info) in greedy_decode's layout, rows from different rungs padded with `eot` to one width.
 
@@ -970,7 +970,8 @@ def decode_with_fallback(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_
     `no_speech`), "compression_ratio": [B] (None without `text_of`), "rungs": per rung the original indices decoded there}.
     decode_kw: what all three decoders share (eot — required —, max_len, suppress, suppress_first, sync_every, step and the
     timestamp keywords).  Under step="graph" a rung with a new number of pending audios is a new graph session (sessions are keyed
-    by batch size): accepted, not optimised — at most MAX_SESSIONS of a kind are kept, so a long ladder recaptures."""
+    by batch size): accepted, not optimised — at most MAX_SESSIONS of a kind are kept, so a long ladder recaptures.
+    `_xa`: the encoder output of `mel`, when the caller has it already (engine/transcribe.py detects the language on it first)."""
     temps = list(temperatures)
     if not temps:
         raise ValueError("temperatures must not be empty")
@@ -993,7 +994,7 @@ def decode_with_fallback(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_
     was_training = model.training
     model.eval()
     try:
-        xa = model.encoder(mel)
+        xa = model.encoder(mel) if _xa is None else _xa
         nsp = [None] * B
         if no_speech is not None:
             nsp = no_speech_prob(model, xa, prompt, 0 if sot_index is None else sot_index, no_speech).cpu().tolist()

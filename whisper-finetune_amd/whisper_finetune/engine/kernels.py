@@ -924,6 +924,71 @@ def dtw(matrix, row0: int, n_rows, n_cols, *, host_lens, negate: bool = True, pa
     return pt, pj, pl
 
 
+# --------------------------------------------------------------------------- language detection / long-form windows (csrc/transcribe.hip)
+def lang_probs(logits, V: int, lang_ids):
+    """Softmax and argmax over the language columns (wft_lang_probs; include/wft.h "Language detection and long-form windows").
+    logits bf16 [B, ld >= V] with contiguous rows; lang_ids: the language token ids on the HOST (a sequence or a CPU tensor),
+    strictly increasing, each in [0, V), 1..1024 of them — checked here, then uploaded -> (probs f32 [B, n_lang], best i64 [B])."""
+    _chk(logits, BF16, "logits")
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] < 1:
+        raise ValueError("lang_probs: logits must be bf16 [B >= 1, ld] with contiguous rows")
+    B, ld = logits.shape[0], logits.stride(0)
+    V = int(V)
+    if not 1 <= V <= logits.shape[1] or ld < V:
+        raise ValueError(f"lang_probs: V={V} does not fit logits rows of {logits.shape[1]} columns")
+    ids = [int(i) for i in (lang_ids.tolist() if hasattr(lang_ids, "tolist") else lang_ids)]
+    if not 1 <= len(ids) <= 1024:
+        raise ValueError(f"lang_probs: 1..1024 language ids expected, got {len(ids)}")
+    if ids[0] < 0 or ids[-1] >= V or any(a >= b for a, b in zip(ids, ids[1:])):
+        raise ValueError(f"lang_probs: language ids must be strictly increasing and lie in [0, V={V})")
+    dev = logits.device
+    ids_dev = upload_table(ids, torch.int32, dev)
+    probs = torch.empty((B, len(ids)), dtype=F32, device=dev)
+    best = torch.empty(B, dtype=torch.int64, device=dev)
+    L.check(L.load().wft_lang_probs(_p(logits), ld, V, _p(ids_dev), len(ids), _p(probs), probs.stride(0), _p(best), B, L.stream_ptr()),
+            "wft_lang_probs")
+    return probs, best
+
+
+def mel_windows(mel, mel_off, ld_frames, content_frames, audio, seek, n_mels: int, n_win: int = 3000, *, host, out=None):
+    """One zero-padded window per row out of the packed long log-mels (wft_mel_windows): row r is recording audio[r] from frame
+    seek[r].  mel f32 1-D (the packed buffer); mel_off i64 [A], ld_frames / content_frames i32 [A] on the device with host =
+    (their values on the host); audio / seek: R ints each on the HOST, checked against those copies (audio inside [0, A), seek
+    inside [0, content_frames[audio])) and uploaded -> out f32 [R, n_mels, n_win]."""
+    _chk(mel, F32, "mel"); _chk(mel_off, torch.int64, "mel_off")
+    n_mels, n_win = int(n_mels), int(n_win)
+    if mel.dim() != 1 or not mel.is_contiguous():
+        raise ValueError("mel_windows: mel must be the packed 1-D f32 buffer")
+    if n_mels < 1 or n_win < 4 or n_win % 4:
+        raise ValueError(f"mel_windows: n_mels must be >= 1 and n_win a positive multiple of 4, got {n_mels}, {n_win}")
+    offs, lds, cfs = ([int(v) for v in h] for h in host)
+    A = len(offs)
+    if A < 1 or len(lds) != A or len(cfs) != A or mel_off.numel() != A or not mel_off.is_contiguous():
+        raise ValueError("mel_windows: mel_off / ld_frames / content_frames and their host copies must hold one entry per recording")
+    _chk_flag(ld_frames, A, "ld_frames"); _chk_flag(content_frames, A, "content_frames")
+    for a in range(A):
+        if lds[a] < n_win or cfs[a] != lds[a] - n_win or offs[a] < 0 or offs[a] + n_mels * lds[a] > mel.numel():
+            raise ValueError(f"mel_windows: recording {a} (offset {offs[a]}, {lds[a]} frames, {cfs[a]} of content) does not fit: content_frames "
+                             f"must be ld_frames - {n_win} and the recording lie inside the {mel.numel()} packed elements")
+    rows, seeks = [int(v) for v in audio], [int(v) for v in seek]
+    R = len(rows)
+    if R < 1 or len(seeks) != R:
+        raise ValueError(f"mel_windows: audio and seek must hold the same number (>= 1) of rows, got {R} and {len(seeks)}")
+    for r in range(R):
+        if not 0 <= rows[r] < A or not 0 <= seeks[r] < cfs[rows[r]]:
+            raise ValueError(f"mel_windows: row {r} reads recording {rows[r]} at frame {seeks[r]}: outside the {A} recordings or their content frames")
+    dev = mel.device
+    if out is None:
+        out = torch.empty((R, n_mels, n_win), dtype=F32, device=dev)
+    _chk(out, F32, "out")
+    if tuple(out.shape) != (R, n_mels, n_win) or not out.is_contiguous():
+        raise ValueError(f"mel_windows: out must be a contiguous f32 [{R}, {n_mels}, {n_win}]")
+    rs = upload_table(rows + seeks, torch.int32, dev)
+    L.check(L.load().wft_mel_windows(_p(mel), _p(mel_off), _p(ld_frames), _p(content_frames), _p(rs[:R]), _p(rs[R:]), _p(out), R, A, n_mels, n_win,
+                                     L.stream_ptr()), "wft_mel_windows")
+    return out
+
+
 # --------------------------------------------------------------------------- embedding / CE
 def embed_fwd(tokens, emb, pos):
     _chk(tokens, torch.int64, "tokens"); _chk(emb, F32, "emb"); _chk(pos, F32, "pos")

@@ -1,0 +1,351 @@
+"""Language detection and long-form transcription: a recording in, timed segments of token ids out.
+
+Upstream's `whisper.decoding.detect_language` and the window loop of `whisper.transcribe.transcribe`, restated on the window decoders
+of engine/decode.py (openai-whisper is not a dependency: parity with its binary is unpinned).  Ids go in and ids come out — no
+tokenizer, no audio file decoding, no resampling: `audio` is 16 kHz mono f32.
+
+Device stages (csrc/transcribe.hip, include/wft.h "Language detection and long-form windows"): `wft_lang_probs` is the tail of
+detect_language, `wft_mel_windows` cuts one zero-padded 30 s window per batch row out of the packed long log-mels; the long log-mel
+itself is `wft_logmel` over the whole recording (`long_logmel`).  Everything else of a window is `decode_with_fallback`.
+
+Several recordings advance side by side in ONE batch (upstream handles one at a time); `transcribe` states the batching rule.
+The seek arithmetic (`advance_window`) and the previous-text prompt (`window_prompt`) are pure host functions.
+
+Not built: `word_timestamps=True` inside the loop (call `find_alignment` on a segment's window yourself),
+`hallucination_silence_threshold`, `clip_timestamps`, `carry_initial_prompt`, the fp32 compute mode.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import torch
+
+from . import decode as D
+from . import kernels as K
+
+SAMPLE_RATE = 16000
+HOP_LENGTH = 160
+N_FRAMES = 3000                      # frames of one 30 s window
+N_SAMPLES = N_FRAMES * HOP_LENGTH    # 480 000: upstream pads every recording with 30 s of zeros
+
+
+# ============================================================================= pure host functions
+def window_prompt(all_tokens: Sequence[int], prompt_reset_since: int, sot_sequence: Sequence[int], sot_prev: Optional[int], n_text_ctx: int):
+    """Upstream's `DecodingTask._get_initial_tokens` for one window -> (prompt ids, sot_index).
+
+    [sot_prev] + all_tokens[prompt_reset_since:][-(n_text_ctx // 2 - 1):] + sot_sequence; without previous tokens, or with sot_prev
+    None, the prompt is sot_sequence alone.  sot_index is the position of sot_sequence[0]."""
+    sot = [int(t) for t in sot_sequence]
+    if not sot:
+        raise ValueError("sot_sequence must not be empty")
+    prev = [int(t) for t in all_tokens[int(prompt_reset_since):]]
+    keep = int(n_text_ctx) // 2 - 1
+    if not prev or sot_prev is None or keep < 1:
+        return sot, 0
+    prev = prev[-keep:]
+    return [int(sot_prev)] + prev + sot, 1 + len(prev)
+
+
+def advance_window(tokens: Sequence[int], *, seek: int, segment_size: int, timestamp_begin: Optional[int], input_stride: int = 2,
+                   time_precision: float = 0.02, frame_s: float = 0.01):
+    """Upstream's segment split and seek rule for the decoded tokens of ONE window -> (segments, new_seek).
+
+    tokens: the generated ids before the eot, timestamps included.  A segment is {"seek", "start", "end", "tokens"}, times in
+    seconds from the start of the recording: seek * frame_s + (id - timestamp_begin) * time_precision.
+    With ts[i] = tokens[i] >= timestamp_begin, single_ending = (ts[-2:] == [False, True]) and cuts = every i + 1 with ts[i] and
+    ts[i + 1]:
+      cuts non-empty: len(tokens) joins the cuts when single_ending; one segment per slice tokens[last:cut], from its first id's
+        time to its last id's; new_seek = seek + segment_size when single_ending, else seek + (tokens[last_cut - 1] -
+        timestamp_begin) * input_stride — the tokens behind the last cut are dropped and decoded again with the next window;
+      cuts empty: one segment with all the tokens, from seek * frame_s for segment_size * frame_s — or, if the last timestamp of the
+        row exists and is not timestamp_begin itself, for that timestamp's time; new_seek = seek + segment_size.
+    timestamp_begin None (upstream's without_timestamps): no id is a timestamp, the second branch always applies.
+    Deviation from upstream, stated: if new_seek == seek (a window that closes at <|0.00|>) the window is stepped over whole,
+    new_seek = seek + segment_size — upstream would decode the same window forever."""
+    toks = [int(t) for t in tokens]
+    seek, size = int(seek), int(segment_size)
+    if size < 1:
+        raise ValueError(f"segment_size must be >= 1, got {segment_size}")
+    offset = seek * frame_s
+    tsb = None if timestamp_begin is None else int(timestamp_begin)
+    ts = [tsb is not None and t >= tsb for t in toks]
+    single_ending = ts[-2:] == [False, True]
+    cuts = [i + 1 for i in range(len(toks) - 1) if ts[i] and ts[i + 1]]
+    segments = []
+    if cuts:
+        if single_ending:
+            cuts.append(len(toks))
+        last = 0
+        for cut in cuts:
+            piece = toks[last:cut]
+            segments.append({"seek": seek, "start": offset + (piece[0] - tsb) * time_precision,
+                             "end": offset + (piece[-1] - tsb) * time_precision, "tokens": piece})
+            last = cut
+        new_seek = seek + size if single_ending else seek + (toks[last - 1] - tsb) * int(input_stride)
+    else:
+        duration = size * frame_s
+        stamps = [t for t, is_ts in zip(toks, ts) if is_ts]
+        if stamps and stamps[-1] != tsb:
+            duration = (stamps[-1] - tsb) * time_precision
+        segments.append({"seek": seek, "start": offset, "end": offset + duration, "tokens": toks})
+        new_seek = seek + size
+    if new_seek == seek:
+        new_seek = seek + size
+    return segments, new_seek
+
+
+# ============================================================================= the long log-mel
+def long_logmel(audio, filters: torch.Tensor) -> torch.Tensor:
+    """Upstream's `log_mel_spectrogram(audio, padding=N_SAMPLES)` for ONE recording (1-D f32, 16 kHz; a tensor or an array)
+    -> f32 [n_mels, content_frames + 3000] on the device of `filters`, content_frames = len(audio) // 160.
+
+    The recording is cut to a multiple of 160 samples, 480 000 zeros are appended and wft_logmel runs once with B = 1, so the
+    maximum behind the `max - 8` floor is taken over the whole recording, as upstream takes it.  The cut is exact: a frame it could
+    touch reads only the zero padding (upstream drops the last STFT frame for the same reason), and the kernel's reflection at the
+    far end sees zeros too."""
+    a = torch.as_tensor(audio)
+    if a.dim() != 1 or a.dtype != torch.float32:
+        raise ValueError(f"a recording must be a 1-D float32 tensor or array, got {a.dtype} {tuple(a.shape)}")
+    frames = a.numel() // HOP_LENGTH
+    dev = filters.device
+    padded = torch.zeros(frames * HOP_LENGTH + N_SAMPLES, dtype=torch.float32, device=dev)
+    padded[:frames * HOP_LENGTH].copy_(a[:frames * HOP_LENGTH])
+    return K.logmel(padded.view(1, -1), filters, n_frames=frames + N_FRAMES)[0]
+
+
+class LongMel:
+    """The packed long log-mels of A recordings, as wft_mel_windows reads them: `mel` f32 1-D, recording a = [n_mels, ld_frames[a]]
+    from element mel_off[a]; content_frames[a] = ld_frames[a] - 3000.  The three tables live on the device and, as `host`, here."""
+
+    def __init__(self, mels: Sequence[torch.Tensor]):
+        if not mels:
+            raise ValueError("at least one recording is needed")
+        n_mels = int(mels[0].shape[0])
+        if any(m.dim() != 2 or m.shape[0] != n_mels or m.shape[1] < N_FRAMES or m.dtype != torch.float32 for m in mels):
+            raise ValueError(f"every long log-mel must be f32 [{n_mels}, >= {N_FRAMES}]")
+        dev = mels[0].device
+        self.n_mels = n_mels
+        lds = [int(m.shape[1]) for m in mels]
+        offs = [0]
+        for ld in lds[:-1]:
+            offs.append(offs[-1] + n_mels * ld)
+        self.host = (offs, lds, [ld - N_FRAMES for ld in lds])
+        self.mel = torch.cat([m.reshape(-1) for m in mels])
+        self.mel_off = torch.tensor(offs, dtype=torch.int64, device=dev)
+        self.ld_frames = torch.tensor(lds, dtype=torch.int32, device=dev)
+        self.content_frames = torch.tensor(self.host[2], dtype=torch.int32, device=dev)
+
+    def windows(self, audio: Sequence[int], seek: Sequence[int]) -> torch.Tensor:
+        """f32 [R, n_mels, 3000]: row r = recording audio[r] from frame seek[r], zero behind its content (K.mel_windows)."""
+        return K.mel_windows(self.mel, self.mel_off, self.ld_frames, self.content_frames, audio, seek, self.n_mels, N_FRAMES, host=self.host)
+
+
+def pack_logmels(audios, filters: torch.Tensor) -> LongMel:
+    """`long_logmel` of every recording (ragged lengths), packed for wft_mel_windows."""
+    return LongMel([long_logmel(a, filters) for a in audios])
+
+
+# ============================================================================= language detection
+def _check_mode(model, who: str) -> None:
+    if getattr(model, "compute_dtype", "bf16") != "bf16":
+        raise NotImplementedError(f"{who} runs in the bf16 compute mode only: wft_lang_probs reads bf16 logits and the window decoders "
+                                  "(csrc/decode_*.hip) are bf16; call model.set_compute_dtype('bf16')")
+
+
+@torch.no_grad()
+def detect_language(model, mel: torch.Tensor, *, sot: int, language_tokens: Sequence[int], _xa: Optional[torch.Tensor] = None):
+    """Upstream's `detect_language` -> (lang_token i64 [B], probs f32 [B, n_lang]).
+
+    mel f32 [B, n_mels, 3000].  The encoder runs once (`_xa`: its output, when the caller has it already), the decoder makes one
+    teacher-forced pass over the single token `sot`, that row goes through the tied logits product, and wft_lang_probs takes the
+    softmax and the argmax over the `language_tokens` columns (strictly increasing ids; ties go to the lowest).  probs[b, j]
+    belongs to language_tokens[j].  eval() semantics; the fp32 compute mode raises NotImplementedError."""
+    _check_mode(model, "detect_language")
+    V = model.dims.n_vocab
+    if not 0 <= int(sot) < V:
+        raise ValueError(f"sot={sot} is outside the vocabulary")
+    was_training = model.training
+    model.eval()
+    try:
+        xa = model.encoder(mel) if _xa is None else _xa
+        tokens = torch.full((xa.shape[0], 1), int(sot), dtype=torch.int64, device=xa.device)
+        logits = model.decoder.padded_logits(model.decoder.hidden(tokens, xa))
+        probs, best = K.lang_probs(logits, V, language_tokens)
+    finally:
+        model.train(was_training)
+    return best, probs
+
+
+# ============================================================================= transcribe
+def _per_recording(sot_sequence, n: int) -> list:
+    seq = list(sot_sequence)
+    if seq and isinstance(seq[0], (list, tuple)):
+        rows = [[int(t) for t in row] for row in seq]
+        if len(rows) != n:
+            raise ValueError(f"sot_sequence: one sequence, or one per recording ({n}), got {len(rows)}")
+    else:
+        rows = [[int(t) for t in seq] for _ in range(n)]
+    if any(not row for row in rows):
+        raise ValueError("sot_sequence must not be empty")
+    return rows
+
+
+def _to_list(v):
+    return v.tolist() if hasattr(v, "tolist") else list(v)
+
+
+@torch.no_grad()
+def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
+               language_tokens: Optional[Sequence[int]] = None, sot_prev: Optional[int] = None, initial_prompt: Optional[Sequence[int]] = None,
+               condition_on_previous_text: bool = True, sample_len: Optional[int] = None, max_windows: Optional[int] = None, text_of=None,
+               temperatures=D.UPSTREAM_TEMPERATURES, best_of: int = 5, beam_size: Optional[int] = None, patience: float = 1.0,
+               length_penalty: Optional[float] = None, logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
+               compression_ratio_threshold: Optional[float] = None, no_speech: Optional[int] = None, seed: int = 0, suppress: Sequence[int] = (),
+               suppress_first: Sequence[int] = (), max_initial_timestamp_index: Optional[int] = 50, sync_every: int = 8, step: str = "eager",
+               filters: Optional[torch.Tensor] = None, _decode=None, _detect=None, _frames: Optional[Sequence[int]] = None) -> list:
+    """Upstream's `transcribe()` over one recording or a list of them -> one dict per recording, in input order:
+      "language": the detected language token id (None without `language_tokens`), "language_probs": f32 [n_lang] or None,
+      "segments": [{"seek", "start", "end", "tokens", "temperature", "avg_logprob", "compression_ratio", "no_speech_prob"}],
+      "tokens": all segment tokens concatenated, "windows": how many windows were decoded, "truncated": True if `max_windows`
+      stopped the recording before its end.
+
+    audio: one 1-D f32 tensor / array at 16 kHz, or a list of them with ragged lengths.  sot_sequence: one sequence for all
+    recordings or one per recording, e.g. (sot, language, task); with `language_tokens` the language is detected on each recording's
+    first window (`detect_language`, sot = sot_sequence[0]) and replaces sot_sequence[1] of that recording.  Ids in, ids out:
+    `text_of` (ids -> str) is needed only for `compression_ratio_threshold` and for the blank-text rule below.  `no_speech`: the id
+    whose probability at the sot position is the window's no-speech probability (None: the silence skip never fires).  The ladder
+    keywords (temperatures, best_of, beam_size, patience, length_penalty, the three thresholds, seed), `suppress`,
+    `suppress_first`, `max_initial_timestamp_index`, `sync_every` and `step` are those of `decode_with_fallback`.  `filters`:
+    the mel filterbank f32 [n_mels, 201] (default: data.gpu_frontend.mel_filters(n_mels)).
+
+    The loop.  Recordings are numbered in input order; the long log-mel of each is computed once (`long_logmel`) and packed;
+    content_frames = len(audio) // 160.  Every recording keeps its own seek (frames), token history and prompt-reset mark.
+    Iteration i = 0, 1, ...:
+      * takes every recording with seek < content_frames that has not decoded `max_windows` windows, in index order, as ONE batch
+        (no such recording: the loop ends); a recording that finishes drops out of the later batches;
+      * ONE wft_mel_windows call cuts the batch's windows (zero behind a recording's content, as upstream's pad_or_trim);
+      * ONE decode_with_fallback call decodes them, with ragged per-row prompts (`window_prompt`, right-padded with eot, their
+        lengths as prompt_len), the per-row sot_index for the no-speech probability, seed + i as the seed, and
+        max_len = min(n_text_ctx, widest prompt of the batch + sample_len);
+      * per row, in upstream's order: the silence skip — no_speech_prob > no_speech_threshold, unless logprob_threshold is set
+        and avg_logprob > logprob_threshold, emits no segments and moves seek by the window's segment_size = min(3000,
+        content_frames - seek); otherwise `advance_window` gives the segments and the new seek; a segment with start == end, and
+        with `text_of` one whose text (of its ids below eot) is blank, loses its tokens but stays in the result; the segment
+        tokens join the history; the prompt-reset mark moves to the end of the history if not condition_on_previous_text or the
+        window's temperature is > 0.5.  `initial_prompt` ids are put into every history first.
+    The encoder runs once per iteration (language detection shares the first iteration's encoder output).
+
+    Deviations from upstream, stated: (1) `sample_len` (default n_text_ctx // 2, as upstream) bounds the row with the WIDEST
+    prompt of a batch exactly; max_len is one absolute length per decode call, so a row with a shorter prompt may generate more
+    than sample_len tokens.  (2) The zero-advance guard of `advance_window`.  (3) Recordings share batches, so a window's bits can
+    depend on its batch partners through the GEMM shapes; replaying the same batches gives the same bits.  (4) Without
+    `text_of` no compression ratio exists and the blank-text rule is off.  A recording shorter than one frame decodes nothing.
+    The fp32 compute mode raises NotImplementedError.  (`_decode`, `_detect`, `_frames`: stand-ins for decode_with_fallback,
+    detect_language and the content frames — the host tests drive the loop through them without a device.)"""
+    _check_mode(model, "transcribe")
+    single = isinstance(audio, torch.Tensor) and audio.dim() == 1 or (not isinstance(audio, (list, tuple)) and getattr(audio, "ndim", 0) == 1)
+    audios = [audio] if single else list(audio)
+    n = len(audios)
+    if n < 1:
+        raise ValueError("transcribe needs at least one recording")
+    n_ctx = int(model.dims.n_text_ctx)
+    sots = _per_recording(sot_sequence, n)
+    if sample_len is None:
+        sample_len = n_ctx // 2
+    if isinstance(sample_len, bool) or not isinstance(sample_len, int) or sample_len < 1:
+        raise ValueError(f"sample_len must be a positive integer, got {sample_len!r}")
+    if max_windows is not None and (isinstance(max_windows, bool) or not isinstance(max_windows, int) or max_windows < 1):
+        raise ValueError(f"max_windows must be None or a positive integer, got {max_windows!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"seed must be an integer, got {seed!r}")
+    if compression_ratio_threshold is not None and text_of is None:
+        raise ValueError("compression_ratio_threshold needs text_of (ids -> str): the ratio is taken over the decoded text")
+    if language_tokens is not None:
+        language_tokens = [int(t) for t in language_tokens]
+        if any(len(s) < 2 for s in sots) or len({s[0] for s in sots}) != 1:
+            raise ValueError("language detection replaces sot_sequence[1]: every sot_sequence needs two ids and the same first id")
+    longest = 1 + (n_ctx // 2 - 1) + max(len(s) for s in sots) if sot_prev is not None else max(len(s) for s in sots)
+    if longest >= n_ctx:
+        raise ValueError(f"sot_sequence of {max(len(s) for s in sots)} ids leaves no room to generate inside n_text_ctx = {n_ctx}")
+    decode = D.decode_with_fallback if _decode is None else _decode
+    detect = detect_language if _detect is None else _detect
+
+    packed = None
+    if _frames is None:
+        if filters is None:
+            from ..data.gpu_frontend import mel_filters
+
+            filters = mel_filters(model.dims.n_mels).to(model.device)
+        packed = pack_logmels(audios, filters)
+        frames = list(packed.host[2])
+    else:
+        frames = [int(f) for f in _frames]
+        if len(frames) != n:
+            raise ValueError(f"_frames: one frame count per recording ({n}), got {len(frames)}")
+
+    history = [[int(t) for t in (initial_prompt or ())] for _ in range(n)]
+    reset = [0] * n
+    seek = [0] * n
+    results = [{"language": None, "language_probs": None, "segments": [], "tokens": [], "windows": 0, "truncated": False} for _ in range(n)]
+    shared = dict(temperatures=temperatures, best_of=best_of, beam_size=beam_size, patience=patience, length_penalty=length_penalty,
+                  logprob_threshold=logprob_threshold, no_speech_threshold=no_speech_threshold,
+                  compression_ratio_threshold=compression_ratio_threshold, text_of=text_of, no_speech=no_speech, eot=int(eot),
+                  suppress=suppress, suppress_first=suppress_first, sync_every=sync_every, step=step, timestamp_begin=timestamp_begin,
+                  no_timestamps=no_timestamps, max_initial_timestamp_index=max_initial_timestamp_index)
+    was_training = model.training
+    model.eval()
+    try:
+        i = 0
+        while True:
+            rows = [a for a in range(n) if seek[a] < frames[a] and (max_windows is None or results[a]["windows"] < max_windows)]
+            if not rows:
+                break
+            mel = None if packed is None else packed.windows(rows, [seek[a] for a in rows])
+            xa = None
+            if i == 0 and language_tokens is not None:
+                xa = None if packed is None else model.encoder(mel)
+                best, probs = detect(model, mel, sot=sots[rows[0]][0], language_tokens=language_tokens, _xa=xa)
+                best, probs = _to_list(best), (probs.cpu() if hasattr(probs, "cpu") else probs)
+                for j, a in enumerate(rows):
+                    results[a]["language"], results[a]["language_probs"] = int(best[j]), probs[j]
+                    sots[a][1] = int(best[j])
+            prompts = [window_prompt(history[a], reset[a], sots[a], sot_prev, n_ctx) for a in rows]
+            width = max(len(p) for p, _ in prompts)
+            prompt = torch.full((len(rows), width), int(eot), dtype=torch.int64)
+            for j, (p, _) in enumerate(prompts):
+                prompt[j, :len(p)] = torch.tensor(p, dtype=torch.int64)
+            plen = [len(p) for p, _ in prompts]
+            kw = dict(shared, sot_index=[s for _, s in prompts], seed=seed + i, max_len=min(n_ctx, width + sample_len))
+            if xa is not None:
+                kw["_xa"] = xa
+            toks, lens, _, info = decode(model, mel, prompt if mel is None else prompt.to(mel.device), torch.tensor(plen), **kw)
+            toks, lens = _to_list(toks), _to_list(lens)
+            for j, a in enumerate(rows):
+                ids, _ = D.generated_ids(toks[j], plen[j], lens[j], eot)
+                size = min(N_FRAMES, frames[a] - seek[a])
+                res = results[a]
+                res["windows"] += 1
+                nsp, alp, temp = info["no_speech_prob"][j], info["avg_logprob"][j], info["temperature"][j]
+                skip = no_speech_threshold is not None and nsp is not None and nsp > no_speech_threshold
+                if skip and logprob_threshold is not None and alp > logprob_threshold:
+                    skip = False
+                if skip:
+                    seek[a] += size
+                    continue
+                segments, seek[a] = advance_window(ids, seek=seek[a], segment_size=size, timestamp_begin=timestamp_begin)
+                for seg in segments:
+                    blank = text_of is not None and text_of([t for t in seg["tokens"] if t < int(eot)]).strip() == ""
+                    if seg["start"] == seg["end"] or blank:
+                        seg["tokens"] = []
+                    seg.update(temperature=temp, avg_logprob=alp, compression_ratio=info["compression_ratio"][j], no_speech_prob=nsp)
+                    res["segments"].append(seg)
+                    res["tokens"].extend(seg["tokens"])
+                    history[a].extend(seg["tokens"])
+                if not condition_on_previous_text or temp > 0.5:
+                    reset[a] = len(history[a])
+            i += 1
+    finally:
+        model.train(was_training)
+    for a in range(n):
+        results[a]["truncated"] = seek[a] < frames[a]
+    return results

@@ -532,6 +532,25 @@ class Whisper(nn.Module):
         -> per audio [(start_s, end_s, probability, [token ids])].  The fp32 compute mode raises."""
         return _decode.find_alignment(self, mel, text_tokens, **kw)
 
+    def detect_language(self, mel: Tensor, *, sot: int, language_tokens, _xa: Optional[Tensor] = None):
+        """Upstream's `detect_language` (engine/transcribe.py; parity with the upstream binary is unpinned): the encoder once, one
+        teacher-forced decoder pass over the single token `sot`, the tied logits product of that row, then softmax and argmax over
+        the `language_tokens` columns on the device (csrc/transcribe.hip wft_lang_probs) -> (lang_token i64 [B], probs f32
+        [B, n_lang]).  mel f32 [B, n_mels, 3000]; `_xa`: the encoder output, when the caller has it.  The fp32 compute mode raises."""
+        from . import transcribe as _transcribe
+
+        return _transcribe.detect_language(self, mel, sot=sot, language_tokens=language_tokens, _xa=_xa)
+
+    def transcribe(self, audio, **kw):
+        """Upstream's `transcribe()` over one 16 kHz recording or a ragged list of them, ids in and ids out (engine/transcribe.py
+        transcribe has the keywords and states the loop; parity with the upstream binary is unpinned): the long log-mel once per
+        recording, then 30 s windows — cut on the device (wft_mel_windows), decoded with `decode_with_fallback`, advanced by the
+        timestamp tokens — with the recordings that are still running batched side by side -> one dict per recording
+        ("language", "language_probs", "segments", "tokens", "windows", "truncated").  The fp32 compute mode raises."""
+        from . import transcribe as _transcribe
+
+        return _transcribe.transcribe(self, audio, **kw)
+
     def forward(self, mel: Tensor, tokens: Tensor, targets: Optional[Tensor] = None, label_smoothing: float = 0.0) -> Tensor:
         """logits f32 [B, S, V] — or, when `targets` is given (engine extension used by train_step, also
         through a DDP wrapper), the fused label-smoothed cross-entropy loss."""
