@@ -690,6 +690,27 @@ int wft_specaug(const float* in, float* out, const int32_t* params, const int32_
 int wft_mel_to_tmajor_bf16(const float* mel, wft_bf16* out, int B, int n_mels, int T,
                            int c_pad, void* stream);
 /* d(mel) is never needed (inputs carry no grad). */
+/* Sample-rate conversion in front of the log-mel: torchaudio's `sinc_interp_hann` resampler with its defaults
+ * (lowpass_filter_width 6, rolloff 0.99), restated; torchaudio is not a dependency: parity with its binary is unpinned.
+ *  With o = orig, n = new_rate (already divided by their gcd), base = 0.99 * min(o, n), width = ceil(6 * o / base) and
+ *    g(t) = (base / o) * sinc(pi t) * cos^2(pi t / 12) for |t| < 6, exactly 0 otherwise:
+ *    out[m] = sum_j x[j] * g((j / o - m / n) * base), 0 <= m < n_out = ceil(n_in * n / o), x[j] = 0 outside [0, n_in).
+ *  Polyphase form: m * o = j0 * n + r, 0 <= r < n; only j = j0 + k, k in [-width + 1, width], can contribute, with the weight
+ *    taps[r][k + width - 1] = g((k - r / n) * base / o).  taps f32 [new_rate, 2 * width] in device memory, 8-byte aligned: the
+ *    caller builds it (data/gpu_frontend.py `resample_taps`: float64, rounded once to f32).
+ *  Row b reads in + b * ld_in and writes out + b * ld_out, B <= 65535.  Elements j >= n_in of an input row are never read (they
+ *    count as zeros, like j < 0); elements m >= n_out of an output row are never written.
+ *  Each output is ONE f32 fma chain in ascending k from 0.0f: its bits do not depend on B, on the row, or on how the outputs
+ *    are tiled over workgroups.  No atomics.  m * o is formed in 64 bits (at 44.1 kHz it passes 2^31 after 304 s of audio).
+ *  WFT_ERR_ARG, before any launch: orig / new_rate not coprime, n_out != ceil(n_in * new_rate / orig), a leading dimension
+ *    smaller than its row, or a rate pair whose tile does not fit (wft_resample_tile == 0).  Loads of the input are 16 bytes
+ *    wherever a chunk lies inside the row; stores are 4 bytes per lane, neighbouring lanes writing neighbouring outputs (a thread
+ *    holds outputs of ONE phase r, n apart, so that a table row is loaded once for all of them).
+ * wft_resample_tile: outputs per workgroup for a rate pair — a pure host function, at most 1024 and a multiple of 4, smaller when
+ *  the input span of 1024 outputs would not fit the 8192-float staging buffer; 0 = the pair is not supported.              */
+int wft_resample_f32(const float* in, int64_t ld_in, int64_t n_in, const float* taps, int orig, int new_rate, int width,
+                     float* out, int64_t ld_out, int64_t n_out, int B, void* stream);
+int wft_resample_tile(int orig, int new_rate, int width);
 
 /* ---------------------------------------------------------------- AdamW */
 /* torch.optim.AdamW single-tensor step over a flat f32 range

@@ -45,7 +45,13 @@
          Not measured yet: no figure of this part is recorded under profiles/ or quoted anywhere.
          (--parts transcribe --batches 4 --out profiles/decode_bench_transcribe.jsonl)
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,beam,ts,sample,align,transcribe] [--batches 1,8,32] [--out FILE]
+  resample  wft_resample_f32 alone (--batches is not used): 48 000 -> 16 000 and 44 100 -> 16 000 on one 10-minute recording and on a
+         [32, 30 * rate] batch (what GpuMelLoader resamples per step): ms per call (output buffer preallocated, table cached) and
+         the achieved bytes/s against the read-once, write-once byte count 4 * B * (n_in + n_out), the table not counted.
+         The kernel should be HBM-bound; no figure is claimed in advance.
+         (--parts resample --out profiles/decode_bench_resample.jsonl)
+
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,beam,ts,sample,align,transcribe,resample] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -809,6 +815,28 @@ def bench_transcribe(batches, seconds=95, sample_len=32, rounds=3):
         emit(rec)
 
 
+def bench_resample(batches):
+    """wft_resample_f32: ms per call and achieved bytes/s against the read-once, write-once byte count."""
+    from whisper_finetune.data.gpu_frontend import resample_taps
+
+    for rate in (48000, 44100):
+        _, o, n, width = resample_taps(rate, 16000)
+        for name, B, n_in in (("10 min recording", 1, 600 * rate), ("[32, 30 s] batch", 32, 30 * rate)):
+            g = torch.Generator().manual_seed(rate + B)
+            x = (torch.randn(B, n_in, generator=g) * 0.1).to(DEV)
+            out = K.resample(x, rate, 16000)
+            n_out = out.shape[1]
+            res = ab({"resample": lambda: K.resample(x, rate, 16000, out=out), "copy": lambda: out.copy_(x[:, :n_out])}, rounds=7, iters=20)
+            nbytes = 4 * B * (n_in + n_out)
+            med, mn, spread = res["resample"]
+            emit(dict(part="resample", shape=name, orig=rate, new=16000, o=o, n=n, taps=2 * width, tile=L.load().wft_resample_tile(o, n, width),
+                      B=B, n_in=n_in, n_out=n_out, bytes=nbytes, ms=round(med, 4), min_ms=round(mn, 4), spread=round(spread, 3),
+                      TBps=round(nbytes / (med * 1e-3) / 1e12, 3), share_of_hbm=round(nbytes / (med * 1e-3) / HBM, 3),
+                      copy_ms=round(res["copy"][0], 4), copy_TBps=round(8 * B * n_out / (res["copy"][0] * 1e-3) / 1e12, 3),
+                      note="ms per K.resample call into a preallocated output; bytes = 4 * B * (n_in + n_out), the table not counted; "
+                           "copy = torch's copy of n_out samples per row from the same buffer, for the launch floor at this size"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="attn,gemm,e2e")
@@ -821,7 +849,7 @@ def main():
     emit(dict(part="env", device=torch.cuda.get_device_name(0), lib=L.load().wft_version().decode(), torch=torch.__version__))
     for part in a.parts.split(","):
         {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": bench_gemm_stream, "e2e_step": bench_e2e_step,
-         "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align, "transcribe": bench_transcribe}[part](batches)
+         "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align, "transcribe": bench_transcribe, "resample": bench_resample}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

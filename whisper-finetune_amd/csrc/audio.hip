@@ -263,3 +263,120 @@ extern "C" int wft_mel_to_tmajor_bf16(const float* mel, wft_bf16* out, int B, in
   WFT_CHECK_LAUNCH();
   return WFT_OK;
 }
+
+// --------------------------------------------------------------------------------- resampling
+// Polyphase windowed-sinc FIR (include/wft.h "wft_resample_f32"): out[m] = sum_k taps[r][k + width - 1] * x[j0 + k] over
+// k = -width + 1 .. width, with m * orig = j0 * new_rate + r.  One workgroup per (tile of outputs, row): the tile's input span
+// [j0(first) - width + 1, j0(last) + width] is staged once in LDS with 16-byte loads (the span start is moved back to the row's
+// 16-byte grid; a chunk that crosses 0 or n_in is read element by element, zero outside), then a thread computes up to four outputs
+// of one phase r — each one f32 fma chain in ascending k, so its bits do not depend on the tiling.  The table goes through the
+// cache: 8 bytes (two taps) per load, one row per thread, shared by its outputs; neighbouring lanes hold neighbouring outputs.
+// m * orig is formed in 64 bits once per workgroup (the tile's first output); inside a tile the phase advances in 32 bits,
+// r0 + i * orig < new_rate + tile * orig < 2^31 (checked by the entry point).
+#define RS_THREADS 256
+#define RS_PER 4                          // outputs per thread (of one phase)
+#define RS_TILE_MAX (RS_THREADS * RS_PER)  // outputs per workgroup
+#define RS_SPAN 8192                      // floats of LDS for the input span (32 KiB)
+
+// outputs per workgroup for a rate pair: the largest multiple of 4, at most RS_TILE_MAX, whose input span fits RS_SPAN floats
+//   span <= floor((new_rate - 1 + (tile - 1) * orig) / new_rate) + 2 * width   (first to last tap)
+//           + 3 (alignment in front) + 3 (the last chunk rounded up);  0: not even four outputs fit.
+extern "C" int wft_resample_tile(int orig, int new_rate, int width) {
+  if (orig < 1 || new_rate < 1 || width < 1) return 0;
+  const int64_t room = (int64_t)RS_SPAN - 2 * (int64_t)width - 6;
+  if (room < 0) return 0;
+  int64_t t = room * new_rate / orig + 1;  // (tile - 1) * orig <= room * new_rate
+  if (t > RS_TILE_MAX) t = RS_TILE_MAX;
+  t &= ~(int64_t)3;
+  if (t * orig + new_rate >= ((int64_t)1 << 31)) return 0;
+  return (int)t;
+}
+
+__global__ __launch_bounds__(RS_THREADS) void resample_kernel(const float* in, long ld_in, long n_in, const float* taps, int o, int n,
+                                                              int width, float* out, long ld_out, long n_out, int tile) {
+  __shared__ __attribute__((aligned(16))) float xs[RS_SPAN];
+  const int tid = threadIdx.x;
+  const long m0 = (long)blockIdx.x * tile;
+  const int cnt = (int)min((long)tile, n_out - m0);  // outputs of this tile, >= 1
+  const unsigned long p0 = (unsigned long)m0 * (unsigned long)o;
+  const long j0t = (long)(p0 / (unsigned long)n);
+  const unsigned r0 = (unsigned)(p0 % (unsigned long)n);
+  const float* x = in + blockIdx.y * ld_in;
+  const long js = j0t - width + 1;                                   // first input element any output of the tile reads
+  const int mis = (int)(((long)((uintptr_t)x >> 2) + js) & 3);       // its distance behind the row's 16-byte grid
+  const long ja = js - mis;                                          // xs[i] = x[ja + i]
+  const long je = j0t + (r0 + (unsigned)(cnt - 1) * (unsigned)o) / (unsigned)n + width;  // last one (inclusive)
+  const int n_chunk = (int)((je - ja) / 4) + 1;                      // 4 * n_chunk <= RS_SPAN by the choice of `tile`
+  for (int c = tid; c < n_chunk; c += RS_THREADS) {
+    const long j = ja + 4 * c;
+    f32x4 v;
+    if (j >= 0 && j + 3 < n_in) {
+      v = *(const f32x4*)(x + j);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = (j + e >= 0 && j + e < n_in) ? x[j + e] : 0.f;
+    }
+    *(f32x4*)&xs[4 * c] = v;
+  }
+  __syncthreads();
+  // Outputs of one phase share a table row: a thread takes up to four outputs i = c + n * q of phase c (q = qb, qb + QB, qb + 2 QB,
+  // qb + 3 QB), loads each pair of taps once for all of them, and neighbouring lanes hold neighbouring phases c, so their LDS windows
+  // start o / n floats apart and their stores are neighbours.  For n = 1 that is outputs tid, tid + 256, ... with a wave-uniform row.
+  const int nt = 2 * width;
+  const int C = min(n, tile);                  // phases that occur in a tile
+  const int Q = (tile + n - 1) / n;            // outputs per phase, at most
+  const int QB = (Q + RS_PER - 1) / RS_PER;    // groups per phase
+  float* orow = out + blockIdx.y * ld_out + m0;
+  for (int g = tid; g < C * QB; g += RS_THREADS) {
+    const int qb = g / C, c = g - qb * C;
+    const int i0 = c + n * qb;                 // the group's first output; >= cnt: the whole group lies behind the tile's end
+    if (i0 >= cnt) continue;
+    const unsigned t = r0 + (unsigned)i0 * (unsigned)o;
+    const int dj = (int)(t / (unsigned)n);     // j0 of output m0 + i0, relative to the tile's
+    const int r = (int)(t - (unsigned)dj * (unsigned)n);
+    const float* tp = taps + (long)r * nt;     // the phase's table row
+    const int step = QB * o;                   // i grows by n * QB from one output of the group to the next: j0 by QB * o, r stays
+    const float* xp[RS_PER];                   // &x[j0 - width + 1] in LDS
+    bool live[RS_PER];
+#pragma unroll
+    for (int e = 0; e < RS_PER; ++e) {
+      live[e] = (long)i0 + (long)e * n * QB < cnt;         // an output behind the tile's end repeats the group's first one and is not stored
+      xp[e] = xs + mis + dj + (live[e] ? e * step : 0);
+    }
+    // four independent fma chains, each in ascending k from 0.0f; two taps (8 bytes) per table load
+    float acc[RS_PER] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+    for (int k = 0; k < nt; k += 2) {
+      const f32x2 w = *(const f32x2*)(tp + k);
+#pragma unroll
+      for (int e = 0; e < RS_PER; ++e) {
+        acc[e] = fmaf(w[0], xp[e][k], acc[e]);
+        acc[e] = fmaf(w[1], xp[e][k + 1], acc[e]);
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < RS_PER; ++e)
+      if (live[e]) orow[i0 + e * n * QB] = acc[e];
+  }
+}
+
+extern "C" int wft_resample_f32(const float* in, int64_t ld_in, int64_t n_in, const float* taps, int orig, int new_rate, int width,
+                                float* out, int64_t ld_out, int64_t n_out, int B, void* stream) {
+  WFT_CHECK_ARG(in && taps && out, "null pointer");
+  WFT_CHECK_ARG(orig >= 1 && new_rate >= 1 && width >= 1 && B >= 1 && B <= 65535 && n_in >= 1, "bad shape");
+  int a = orig, b = new_rate;
+  while (b) { const int t = a % b; a = b; b = t; }
+  WFT_CHECK_ARG(a == 1, "orig and new_rate must be reduced (coprime)");
+  WFT_CHECK_ARG(n_in <= (INT64_MAX - orig) / new_rate, "n_in * new_rate overflows");
+  WFT_CHECK_ARG(n_out == (n_in * new_rate + orig - 1) / orig, "n_out must be ceil(n_in * new_rate / orig)");
+  WFT_CHECK_ARG(ld_in >= n_in && ld_out >= n_out, "leading dimension smaller than the row");
+  WFT_CHECK_ARG((uintptr_t)in % 4 == 0 && (uintptr_t)out % 4 == 0 && (uintptr_t)taps % 8 == 0, "in / out must be 4-byte, taps 8-byte aligned");
+  const int tile = wft_resample_tile(orig, new_rate, width);
+  WFT_CHECK_ARG(tile >= 4, "rate pair not supported: the input span of four outputs does not fit the staging buffer");
+  const int64_t n_tiles = cdiv64(n_out, tile);
+  WFT_CHECK_ARG(n_tiles <= 0x7fffffff, "too many output tiles");
+  hipLaunchKernelGGL(resample_kernel, dim3((unsigned)n_tiles, B), dim3(RS_THREADS), 0, (hipStream_t)stream, in, (long)ld_in, (long)n_in,
+                     taps, orig, new_rate, width, out, (long)ld_out, (long)n_out, tile);
+  WFT_CHECK_LAUNCH();
+  return WFT_OK;
+}

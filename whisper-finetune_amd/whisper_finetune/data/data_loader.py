@@ -7,6 +7,10 @@ augmentation parameters (same default-generator draw order as `AudioDataset.__ge
 data_loader.py:322-359,273-301), and the main process turns a pinned batch of raw clips into mels with two kernels
 (`wft_logmel`, `wft_specaug`).  `get_dataloader(...)` still yields `(mel, y_in, y_out)` batches: mel f32
 [B, n_mels, 3000] (on the GPU), y_in padded with 0, y_out padded with -100.
+
+Clips at another rate than 16 kHz (`get_dataloader(..., sample_rate=)`, one rate per loader): a worker pads the clip to
+30 * sample_rate samples and the main process resamples the staged [B, 30 * rate] batch to [B, 480000] with one
+`wft_resample_f32` launch in front of the log-mel.
 """
 from __future__ import annotations
 
@@ -19,7 +23,8 @@ from torch.nn.utils.rnn import pad_sequence
 from torch.utils.data import DataLoader, Dataset
 
 from whisper_finetune.data import transforms as T
-from whisper_finetune.data.gpu_frontend import HOP_LENGTH, N_FFT, N_FRAMES, N_SAMPLES, GpuFrontend, draw_clip_params, mel_filters
+from whisper_finetune.data.gpu_frontend import (HOP_LENGTH, N_FFT, N_FRAMES, N_SAMPLES, SAMPLE_RATE, GpuFrontend, check_rate,
+                                                draw_clip_params, mel_filters)
 from whisper_finetune.data.utils import ExtremesFrequencyMasking, TimeWarpAugmenter, pad_or_trim
 
 CHUNK_LENGTH = 30
@@ -53,21 +58,26 @@ def log_mel_spectrogram(audio, n_mels: int = 80, padding: int = 0, device=None) 
 
 
 class AudioDataset(Dataset):
-    """Items: (audio f32 [480000], decoder_input i64, decoder_output i64, aug i32 [8], extremes i32 [2], cut_frames).
+    """Items: (audio f32 [30 * sample_rate] (480000 at the default 16 kHz), decoder_input i64, decoder_output i64, aug i32 [8], extremes i32 [2], cut_frames).
 
-    hu_dataset: indexable records {"audio": {"array"}, "text", "language", optional "prompt"}; tokenizer: whisper-style
+    hu_dataset: indexable records {"audio": {"array", optional "sampling_rate"}, "text", "language", optional "prompt"}; a record
+    whose "sampling_rate" is present and differs from the dataset's `sample_rate` raises ValueError (no mixed rates); tokenizer: whisper-style
     (sot, eot, sot_prev, no_timestamps, no_speech, timestamp_begin, special_tokens[...], encode(text, **kw)).
 
     Same constructor arguments and attributes as the reference's class (data/data_loader.py:40-160).  `__getitem__`
     ships the raw clip plus the DRAWN augmentation parameters (the batch is turned into mels on the device by
     GpuMelLoader); `_calculate_mel` is the reference's per-clip form of the same arithmetic on the same kernels."""
 
+    sample_rate, n_samples = SAMPLE_RATE, N_SAMPLES  # the defaults, also of an instance built without __init__
+
     def __init__(self, hu_dataset, tokenizer, device=None, no_timestamp_training: bool = False, n_mels: int = 80,
                  max_prompt_length: int = 223, prompt_use_rate: float = 0.5, no_timestamps_rate: float = 0.5,
                  spec_augment: bool = False, spec_augment_params: Optional[dict] = None, extremes_spec_augment: bool = False,
                  extremes_spec_augment_params: Optional[dict] = None, apply_baseline_aug: bool = False, apply_office_aug: bool = False,
                  apply_advanced_aug: bool = False, time_stretch_min_rate: float = 0.8, time_stretch_max_rate: float = 1.25,
-                 bpe_dropout: float = 0.0):
+                 bpe_dropout: float = 0.0, sample_rate: int = SAMPLE_RATE):
+        self.sample_rate = check_rate(sample_rate)
+        self.n_samples = CHUNK_LENGTH * self.sample_rate  # 30 s at the clips' own rate
         if apply_baseline_aug or apply_office_aug or apply_advanced_aug:
             raise NotImplementedError("audio-domain augmentation (model/augment.py) is outside the GPU hot path (SURVEY.md §2)")
         self.hu_dataset, self.tokenizer, self.n_mels, self.device = hu_dataset, tokenizer, n_mels, device
@@ -114,6 +124,8 @@ class AudioDataset(Dataset):
         -> extremes masking, every stage a libwft kernel on the device."""
         if self.aud_augment is not None:
             audio_array = self.aud_augment(audio_array, sample_rate=16000)
+        if self.sample_rate != SAMPLE_RATE:
+            raise ValueError(f"_calculate_mel is the per-clip 16 kHz form; clips at {self.sample_rate} Hz are resampled per batch by GpuMelLoader")
         mel = log_mel_spectrogram(audio_array, n_mels=self.n_mels, device=self.device)
         if no_timestamps and next_partial_segment_start is not None:
             mel = mel[:, : int(next_partial_segment_start * self.num_frames_per_second)]
@@ -228,8 +240,12 @@ class AudioDataset(Dataset):
             prompt = prompt[: -(len(dec_in) - self.model_n_text_ctx)]
             dec_in = prompt + special + text
         dec_out = self._construct_decoder_output(prompt, special, text)
+        rec_rate = rec["audio"].get("sampling_rate") if hasattr(rec["audio"], "get") else None
+        if rec_rate is not None and int(rec_rate) != self.sample_rate:
+            raise ValueError(f"record {index} has sampling_rate {rec_rate}, the loader was built for sample_rate {self.sample_rate}: "
+                             "one rate per loader (get_dataloader(..., sample_rate=))")
         audio = np.asarray(rec["audio"]["array"], dtype=np.float32)
-        audio = np.pad(audio, (0, N_SAMPLES - audio.shape[0]), "constant")  # pad in the audio domain (negative pad raises, as upstream)
+        audio = np.pad(audio, (0, self.n_samples - audio.shape[0]), "constant")  # pad in the audio domain (negative pad raises, as upstream)
         cut = int(seg_start * self.num_frames_per_second) if (no_ts and seg_start is not None) else N_FRAMES
         params, ext = self._draw_aug_params()
         return (torch.from_numpy(audio), torch.tensor(dec_in, dtype=torch.int64), torch.tensor(dec_out, dtype=torch.int64),
@@ -294,10 +310,15 @@ class GpuMelLoader:
     stream while batch i is being consumed; the compute stream waits on the copy's event only when it starts using the
     batch.  With num_workers == 0 the dataset's augmentation draws share the default generator with the model's own draws
     (stochastic depth, deep SpecAugment): fetching ahead would reorder them against the reference, so that case stays
-    strictly sequential.  Yields (mel f32 [B, n_mels, 3000], y_in, y_out), all on the device."""
+    strictly sequential.  Yields (mel f32 [B, n_mels, 3000], y_in, y_out), all on the device.
 
-    def __init__(self, loader, frontend: GpuFrontend, training_aug: bool):
+    sample_rate != 16000: the staged batch is [B, 30 * sample_rate]; ONE K.resample launch turns it into [B, 480000] in front of the
+    log-mel.  It is the resample of the zero-PADDED clip, so the filter's tail behind the clip's end is kept (it rings into the
+    padding for `width` input samples), as it would be for a clip that was padded before an offline resampler."""
+
+    def __init__(self, loader, frontend: GpuFrontend, training_aug: bool, sample_rate: int = SAMPLE_RATE):
         self.loader, self.frontend, self.training_aug = loader, frontend, training_aug
+        self.sample_rate = check_rate(sample_rate)
         self.sampler = getattr(loader, "sampler", None)  # infinite_iter() calls sampler.set_epoch(...)
         self.batch_size = getattr(loader, "batch_size", None)
         self.prefetch = getattr(loader, "num_workers", 0) > 0
@@ -328,6 +349,8 @@ class GpuMelLoader:
             for t in staged:
                 t.record_stream(cur)  # allocated on the copy stream, consumed on the compute stream
         audio, y_in, y_out, params, ext = staged
+        if self.sample_rate != SAMPLE_RATE:
+            audio = K.resample(audio, self.sample_rate, SAMPLE_RATE)  # [B, 30 * rate] -> [B, 480000]
         mel = self.frontend.log_mel(audio)
         for b in (cut < N_FRAMES).nonzero().flatten().tolist():  # rare: cut at a partial segment, pad with the min value
             c = int(cut[b])
@@ -364,14 +387,17 @@ def get_dataloader(hu_dataset, tokenizer, batch_size: int = 1, n_mels: int = 80,
                    spec_augment_params: Optional[dict] = None, extremes_spec_augment: bool = False,
                    extremes_spec_augment_params: Optional[dict] = None, apply_baseline_aug: bool = False, apply_office_aug: bool = False,
                    apply_advanced_aug: bool = False, time_stretch_min_rate: float = 0.8, time_stretch_max_rate: float = 1.25,
-                   bpe_dropout: float = 0.0, drop_last: bool = False):
+                   bpe_dropout: float = 0.0, drop_last: bool = False, sample_rate: int = SAMPLE_RATE):
+    """`sample_rate`: the rate of every clip of `hu_dataset` (default 16000).  At another rate the clips are padded to
+    30 * sample_rate samples and resampled to 16 kHz on the device (GpuMelLoader); without a device the loader yields the padded
+    native-rate clips."""
     print(f"Found {len(hu_dataset)} records in the dataset.")
     ds = AudioDataset(hu_dataset, tokenizer, n_mels=n_mels, device=device, no_timestamp_training=no_timestamp_training,
                       max_prompt_length=max_prompt_length, prompt_use_rate=prompt_use_rate, no_timestamps_rate=no_timestamps_rate,
                       spec_augment=spec_augment, spec_augment_params=spec_augment_params, extremes_spec_augment=extremes_spec_augment,
                       extremes_spec_augment_params=extremes_spec_augment_params, bpe_dropout=bpe_dropout,
                       apply_baseline_aug=apply_baseline_aug, apply_office_aug=apply_office_aug, apply_advanced_aug=apply_advanced_aug,
-                      time_stretch_min_rate=time_stretch_min_rate, time_stretch_max_rate=time_stretch_max_rate)
+                      time_stretch_min_rate=time_stretch_min_rate, time_stretch_max_rate=time_stretch_max_rate, sample_rate=sample_rate)
     if sampler is not None:
         shuffle = False  # DataLoader does not allow both
     loader = DataLoader(ds, batch_size=batch_size, sampler=sampler, shuffle=shuffle, num_workers=num_workers,
@@ -381,7 +407,7 @@ def get_dataloader(hu_dataset, tokenizer, batch_size: int = 1, n_mels: int = 80,
     if device is None or torch.device(device).type != "cuda":
         return loader  # raw-audio batches (CPU plumbing / tests); the GPU front end needs a device
     fe = GpuFrontend(n_mels, device, spec_augment, spec_augment_params, extremes_spec_augment, extremes_spec_augment_params)
-    return GpuMelLoader(loader, fe, training_aug=spec_augment or extremes_spec_augment)
+    return GpuMelLoader(loader, fe, training_aug=spec_augment or extremes_spec_augment, sample_rate=sample_rate)
 
 
 # ---------------------------------------------------------------------------------------------- synthetic provider

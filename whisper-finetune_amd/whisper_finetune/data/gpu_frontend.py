@@ -1,5 +1,5 @@
-"""GPU front end of the data path: raw 30 s / 16 kHz clips -> log-mel -> SpecAugment, batched on
-the device.
+"""GPU front end of the data path: raw 30 s clips (resampled to 16 kHz on the device when they come at another
+rate) -> log-mel -> SpecAugment, batched on the device.
 
 It replaces, arithmetic for arithmetic, what `AudioDataset._calculate_mel`
 (data/data_loader.py:273-292) does per clip in a CPU DataLoader worker:
@@ -12,6 +12,7 @@ run reproduces the reference's augmentation decisions exactly.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -47,6 +48,67 @@ def mel_filters(n_mels: int) -> torch.Tensor:
         w[i] = np.maximum(0.0, np.minimum(up, down))
     w *= (2.0 / (pts[2:] - pts[:-2]))[:, None]
     return torch.from_numpy(w.astype(np.float32))
+
+
+# ------------------------------------------------------------------------------------------------- resampling
+# torchaudio's `sinc_interp_hann` resampler with its defaults (lowpass_filter_width = 6, rolloff = 0.99), restated in its polyphase
+# form (include/wft.h "wft_resample_f32" states the definition).  torchaudio is not a dependency: parity with its binary is unpinned.
+MIN_RATE, MAX_RATE = 1000, 384000
+_LOWPASS_WIDTH, _ROLLOFF = 6, 0.99
+_TAPS = {}
+
+
+def check_rate(rate, what: str = "sample_rate") -> int:
+    """An integer sample rate inside [1000, 384000] -> int; anything else raises ValueError."""
+    if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)):
+        raise ValueError(f"{what} must be an integer number of Hz, got {rate!r}")
+    rate = int(rate)
+    if not MIN_RATE <= rate <= MAX_RATE:
+        raise ValueError(f"{what} must lie in [{MIN_RATE}, {MAX_RATE}] Hz, got {rate}")
+    return rate
+
+
+def resample_taps(orig: int, new: int):
+    """The polyphase table of the rate pair -> (taps f32 [n, 2 * width] on the host, o, n, width), cached per reduced pair.
+
+    o = orig / gcd, n = new / gcd, base = 0.99 * min(o, n), width = ceil(6 * o / base);
+    taps[r][k + width - 1] = g((k - r / n) * base / o) for k = -width + 1 .. width, with
+    g(t) = (base / o) * sinc(pi t) * cos^2(pi t / 12) for |t| < 6 and exactly 0 otherwise.  Built in float64, rounded once to f32."""
+    for name, v in (("orig", orig), ("new", new)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"resample_taps: {name} must be a positive integer, got {v!r}")
+    g = math.gcd(int(orig), int(new))
+    o, n = int(orig) // g, int(new) // g
+    if (o, n) not in _TAPS:
+        base = _ROLLOFF * min(o, n)
+        width = math.ceil(_LOWPASS_WIDTH * o / base)
+        k = np.arange(-width + 1, width + 1, dtype=np.float64)[None, :]
+        r = np.arange(n, dtype=np.float64)[:, None]
+        t = (k - r / n) * base / o
+        w = (base / o) * np.sinc(t) * np.cos(np.pi * t / (2 * _LOWPASS_WIDTH)) ** 2
+        w[np.abs(t) >= _LOWPASS_WIDTH] = 0.0
+        _TAPS[(o, n)] = (torch.from_numpy(w.astype(np.float32)), o, n, width)
+    return _TAPS[(o, n)]
+
+
+def resample(audio, sample_rate, device=None) -> torch.Tensor:
+    """audio at `sample_rate` Hz -> the same audio at 16 kHz, on the device (K.resample, one launch).
+
+    audio: f32, 1-D [n] or 2-D [B, n], a tensor or an array; a host input goes to `device` (default: the current GPU) first.
+    The result has the input's number of dimensions and ceil(n * 16000 / sample_rate) samples per row; at 16 kHz the (device) input
+    is returned as it is.  sample_rate: an integer inside [1000, 384000], else ValueError."""
+    rate = check_rate(sample_rate)
+    a = torch.as_tensor(audio)
+    if a.dim() not in (1, 2) or a.dtype != torch.float32 or a.numel() == 0:
+        raise ValueError(f"resample: audio must be a non-empty float32 [n] or [B, n], got {a.dtype} {tuple(a.shape)}")
+    if device is not None:
+        a = a.to(device)
+    elif not a.is_cuda:
+        a = a.to(torch.device("cuda", torch.cuda.current_device()))
+    if rate == SAMPLE_RATE:
+        return a
+    out = K.resample(a if a.dim() == 2 else a[None], rate, SAMPLE_RATE)
+    return out if a.dim() == 2 else out[0]
 
 
 from whisper_finetune.data.transforms import FrequencyMasking, TimeMasking, draw_mask_span  # noqa: E402,F401

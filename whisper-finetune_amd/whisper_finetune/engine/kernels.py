@@ -6,6 +6,7 @@ kernel on the current stream.  Shapes follow include/wft.h.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -1075,6 +1076,52 @@ def specaug(mel, params, extremes=None):
         _chk(extremes, torch.int32, "extremes")
         extremes = extremes.contiguous()
     L.check(L.load().wft_specaug(_p(mel), _p(out), _p(params), _p(extremes), B, n_mels, T, L.stream_ptr()), "wft_specaug")
+    return out
+
+
+_RESAMPLE_TAPS = {}  # (o, n, device) -> the f32 [n, 2 * width] table on the device
+
+
+def resample(audio, orig: int, new: int, *, out=None):
+    """Sample-rate conversion orig -> new (wft_resample_f32: the polyphase form of torchaudio's default sinc_interp_hann resampler).
+
+    audio f32 [B, n_in] on the device, rows of any stride (stride(1) == 1; what lies behind n_in in a row is never read) ->
+    f32 [B, n_out], n_out = ceil(n_in * new / orig).  orig / new: positive ints, reduced here by their gcd; orig == new returns
+    `audio` unchanged.  `out`: f32 [B, n_out] with stride(1) == 1 to write into (what lies behind n_out in a row is never written).
+    Every argument is checked before the launch."""
+    _chk(audio, F32, "audio")
+    for name, v in (("orig", orig), ("new", new)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"resample: {name} must be a positive integer, got {v!r}")
+    if audio.dim() != 2 or audio.shape[0] < 1 or audio.shape[1] < 1:
+        raise ValueError(f"resample: audio must be [B, n_in] with B >= 1 and n_in >= 1, got {tuple(audio.shape)}")
+    g = math.gcd(orig, new)
+    o, n = orig // g, new // g
+    if o == n:
+        return audio
+    if audio.stride(1) != 1 or (audio.shape[0] > 1 and audio.stride(0) < audio.shape[1]):
+        audio = audio.contiguous()
+    B, n_in = audio.shape
+    if B > 65535:
+        raise ValueError(f"resample: at most 65535 rows per call, got {B}")
+    n_out = -(-n_in * n // o)
+    from ..data.gpu_frontend import resample_taps
+
+    taps, _, _, width = resample_taps(o, n)
+    if L.load().wft_resample_tile(o, n, width) < 4:
+        raise ValueError(f"resample: the rate pair {orig} -> {new} ({2 * width} taps per output) is not supported by wft_resample_f32")
+    key = (o, n, audio.device)
+    if key not in _RESAMPLE_TAPS:
+        _RESAMPLE_TAPS[key] = taps.to(audio.device)
+    if out is None:
+        out = torch.empty((B, n_out), dtype=F32, device=audio.device)
+    _chk(out, F32, "out")
+    if tuple(out.shape) != (B, n_out) or out.stride(1) != 1 or (B > 1 and out.stride(0) < n_out) or out.device != audio.device:
+        raise ValueError(f"resample: out must be f32 [{B}, {n_out}] on {audio.device} with unit column stride and rows that do not overlap")
+    ld_in = audio.stride(0) if B > 1 else max(audio.stride(0), n_in)
+    ld_out = out.stride(0) if B > 1 else max(out.stride(0), n_out)
+    L.check(L.load().wft_resample_f32(_p(audio), ld_in, n_in, _p(_RESAMPLE_TAPS[key]), o, n, width, _p(out), ld_out, n_out, B, L.stream_ptr()),
+            "wft_resample_f32")
     return out
 
 

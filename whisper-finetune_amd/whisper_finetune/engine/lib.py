@@ -228,6 +228,8 @@ SIGNATURES = {
     "wft_logmel": [c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_vp],
     "wft_specaug": [c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, c_vp],
     "wft_mel_to_tmajor_bf16": [c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_vp],
+    "wft_resample_f32": [c_vp, c_i64, c_i64, c_vp, C.c_int, C.c_int, C.c_int, c_vp, c_i64, c_i64, C.c_int, c_vp],
+    "wft_resample_tile": [C.c_int, C.c_int, C.c_int],
     "wft_adamw_step": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float,
                        C.c_float, C.c_float, C.c_float, c_vp, c_vp],
     "wft_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],

@@ -2,7 +2,8 @@
 
 Upstream's `whisper.decoding.detect_language` and the window loop of `whisper.transcribe.transcribe`, restated on the window decoders
 of engine/decode.py (openai-whisper is not a dependency: parity with its binary is unpinned).  Ids go in and ids come out — no
-tokenizer, no audio file decoding, no resampling: `audio` is 16 kHz mono f32.
+tokenizer, no audio file decoding: `audio` is mono f32, at 16 kHz or at the `sample_rate` it is declared with (then it is resampled
+on the device first: data/gpu_frontend.py `resample`, csrc/audio.hip `wft_resample_f32`).
 
 Device stages (csrc/transcribe.hip, include/wft.h "Language detection and long-form windows"): `wft_lang_probs` is the tail of
 detect_language, `wft_mel_windows` cuts one zero-padded 30 s window per batch row out of the packed long log-mels; the long log-mel
@@ -202,14 +203,17 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
                length_penalty: Optional[float] = None, logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
                compression_ratio_threshold: Optional[float] = None, no_speech: Optional[int] = None, seed: int = 0, suppress: Sequence[int] = (),
                suppress_first: Sequence[int] = (), max_initial_timestamp_index: Optional[int] = 50, sync_every: int = 8, step: str = "eager",
-               filters: Optional[torch.Tensor] = None, _decode=None, _detect=None, _frames: Optional[Sequence[int]] = None) -> list:
+               filters: Optional[torch.Tensor] = None, sample_rate=SAMPLE_RATE, _decode=None, _detect=None, _frames: Optional[Sequence[int]] = None) -> list:
     """Upstream's `transcribe()` over one recording or a list of them -> one dict per recording, in input order:
       "language": the detected language token id (None without `language_tokens`), "language_probs": f32 [n_lang] or None,
       "segments": [{"seek", "start", "end", "tokens", "temperature", "avg_logprob", "compression_ratio", "no_speech_prob"}],
       "tokens": all segment tokens concatenated, "windows": how many windows were decoded, "truncated": True if `max_windows`
       stopped the recording before its end.
 
-    audio: one 1-D f32 tensor / array at 16 kHz, or a list of them with ragged lengths.  sot_sequence: one sequence for all
+    audio: one 1-D f32 tensor / array, or a list of them with ragged lengths, at `sample_rate` Hz: one integer for all recordings
+    or one per recording, each inside [1000, 384000] (default 16000).  A recording at another rate than 16 kHz is resampled on the
+    device (data.gpu_frontend.resample: one wft_resample_f32 launch) before its long log-mel, so its content_frames =
+    ceil(len * 16000 / rate) // 160; at 16 kHz nothing runs differently.  sot_sequence: one sequence for all
     recordings or one per recording, e.g. (sot, language, task); with `language_tokens` the language is detected on each recording's
     first window (`detect_language`, sot = sot_sequence[0]) and replaces sot_sequence[1] of that recording.  Ids in, ids out:
     `text_of` (ids -> str) is needed only for `compression_ratio_threshold` and for the blank-text rule below.  `no_speech`: the id
@@ -267,6 +271,14 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
     longest = 1 + (n_ctx // 2 - 1) + max(len(s) for s in sots) if sot_prev is not None else max(len(s) for s in sots)
     if longest >= n_ctx:
         raise ValueError(f"sot_sequence of {max(len(s) for s in sots)} ids leaves no room to generate inside n_text_ctx = {n_ctx}")
+    from ..data.gpu_frontend import check_rate
+
+    if isinstance(sample_rate, (list, tuple)) or getattr(sample_rate, "ndim", 0) == 1:
+        rates = [check_rate(r) for r in sample_rate]
+        if len(rates) != n:
+            raise ValueError(f"sample_rate: one rate, or one per recording ({n}), got {len(rates)}")
+    else:
+        rates = [check_rate(sample_rate)] * n
     decode = D.decode_with_fallback if _decode is None else _decode
     detect = detect_language if _detect is None else _detect
 
@@ -276,6 +288,10 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
             from ..data.gpu_frontend import mel_filters
 
             filters = mel_filters(model.dims.n_mels).to(model.device)
+        if any(r != SAMPLE_RATE for r in rates):
+            from ..data.gpu_frontend import resample
+
+            audios = [a if r == SAMPLE_RATE else resample(a, r, device=filters.device) for a, r in zip(audios, rates)]
         packed = pack_logmels(audios, filters)
         frames = list(packed.host[2])
     else:

@@ -542,8 +542,10 @@ class Whisper(nn.Module):
         return _transcribe.detect_language(self, mel, sot=sot, language_tokens=language_tokens, _xa=_xa)
 
     def transcribe(self, audio, **kw):
-        """Upstream's `transcribe()` over one 16 kHz recording or a ragged list of them, ids in and ids out (engine/transcribe.py
-        transcribe has the keywords and states the loop; parity with the upstream binary is unpinned): the long log-mel once per
+        """Upstream's `transcribe()` over one recording or a ragged list of them, ids in and ids out (engine/transcribe.py
+        transcribe has the keywords and states the loop; parity with the upstream binary is unpinned).  Recordings are mono f32 at
+        16 kHz, or at `sample_rate=` Hz (one integer, or one per recording): those are resampled to 16 kHz on the device first
+        (wft_resample_f32).  The long log-mel once per
         recording, then 30 s windows — cut on the device (wft_mel_windows), decoded with `decode_with_fallback`, advanced by the
         timestamp tokens — with the recordings that are still running batched side by side -> one dict per recording
         ("language", "language_probs", "segments", "tokens", "windows", "truncated").  The fp32 compute mode raises."""

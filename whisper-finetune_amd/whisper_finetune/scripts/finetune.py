@@ -262,7 +262,8 @@ def main(config: dict):
     n_mels = rt.unwrap_model(model).dims.n_mels
     loader_kw = dict(n_mels=n_mels, no_timestamp_training=d_cfg.get("no_timestamp_training", False),
                      max_prompt_length=d_cfg.get("max_prompt_length", 223), prompt_use_rate=d_cfg.get("prompt_use_rate", 0.5),
-                     no_timestamps_rate=d_cfg.get("no_timestamp_rate", 0.5), device=device)
+                     no_timestamps_rate=d_cfg.get("no_timestamp_rate", 0.5), device=device,
+                     sample_rate=d_cfg.get("wft_sample_rate", 16000))  # the clips' own rate: resampled to 16 kHz on the device
     train_loader = get_dataloader(train_ds, tokenizer, batch_size=d_cfg["batch_size"], sampler=sampler, shuffle=True,
                                   num_workers=d_cfg.get("train_num_workers", min(os.cpu_count() or 1, 8)),
                                   spec_augment=sa.get("apply", False), spec_augment_params=sa,
