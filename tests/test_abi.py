@@ -72,6 +72,16 @@ def test_shipped_library_cannot_read_timing_switches():
     assert L.load().wft_version().decode() == "wft 0.1 gfx950"
 
 
+def test_python_package_reads_no_switch_from_the_environment():
+    """The same for the Python engine: the library path and the distributed backend are the only WFT_* variables the package reads.
+    Every A/B switch is decided; the twin paths that tests compare against are module constants a test sets, not the environment."""
+    read = re.compile(r"""os\s*\.\s*(?:environ\s*\.\s*get\s*\(|environ\s*\[|getenv\s*\()\s*["'](WFT_[A-Z0-9_]+)["']""")
+    names = set()
+    for src in (ROOT / "whisper-finetune_amd" / "whisper_finetune").rglob("*.py"):
+        names.update(read.findall(src.read_text()))
+    assert names == {"WFT_LIB", "WFT_DIST_BACKEND"}, sorted(names)
+
+
 def test_library_holds_no_mutable_launch_state():
     """launch mode and kernel variants are per-call fields of the argument structs; no setter is exported."""
     handle = L.load()

@@ -146,7 +146,7 @@ def _model(name, prescale, seed=3):
 
 
 def test_model_with_prescaled_q_matches_the_unscaled_path():
-    """whisper-tiny, 2 clips: loss and every gradient of the prescaled engine against the engine with WFT_QK_PRESCALE=0 (two bf16
+    """whisper-tiny, 2 clips: loss and every gradient of the prescaled engine against the engine with ops.QK_PRESCALE = False (two bf16
     evaluations of the same function: 3e-2 per tensor, 8e-2 for the ill-conditioned decoder q / k, as tests/test_model_gpu.py), and the
     shadows carry the factor where they should."""
     m1, dims = _model("tiny", True)

@@ -52,7 +52,7 @@ def test_unsegmentable_calls_are_refused_by_the_query_not_by_an_error():
 
 def test_training_with_gradient_homes_matches_fresh_gradient_tensors():
     """whisper-base, 12 clips, accumulation 2, four optimizer steps: homes on (gradients written / accumulated in place by the reduce
-    kernel) against WFT_GRAD_HOMES=0 (autograd's own tensors and adds).  The second micro-batch's sum is (g + s0) + s1 + ... instead of
+    kernel) against ops._GRAD_HOMES = False (autograd's own tensors and adds).  The second micro-batch's sum is (g + s0) + s1 + ... instead of
     g + (s0 + s1 + ...): fp32 rounding of the gradients — which the bf16 weight shadows amplify (a parameter that moves by 1e-9
     can cross a bf16 rounding boundary: 0.4 % of that weight), so later losses agree to 1e-4, not to fp32 rounding (measured 1.4e-5)."""
     from oracle import whisper_oracle as O
@@ -106,7 +106,7 @@ def test_two_forwards_one_backward_sum_their_weight_gradients_with_homes_on():
     """one weight feeding two LinearFn nodes of the same backward pass (the model called twice before a single backward —
     the case `ops.grad_fork` documents as supported).  Both nodes see `w.grad is None`; only the first writer of a graph task may take
     the home in overwrite mode, otherwise the result is 2 * dW_second.  Checked from the second optimizer step on (homes exist then)
-    against WFT_GRAD_HOMES=0."""
+    against ops._GRAD_HOMES = False."""
     from oracle import whisper_oracle as O
     from whisper_finetune.engine import ops
     from whisper_finetune.engine.whisper_model import ModelDimensions, Whisper

@@ -496,6 +496,56 @@ def test_lora_dropout_masks_are_redrawn_per_micro_batch():
     assert ad.lora_A.grad[:, dead[0].to(DEV)].abs().max() == 0
 
 
+@pytest.mark.parametrize("frozen", ["lora_A", "lora_B"])
+def test_lora_gradient_of_one_adapter_matrix_with_the_other_frozen(frozen):
+    """The same adapted Linear with a fixed mask and ONE of lora_A / lora_B frozen: not every adapter gradient is wanted, so
+    LinearFn.backward leaves the paired launches (no K.gemm_nt_rank_pair call) for its general form — the wanted gradient from its
+    own two rank-r GEMMs, dA masked and dB sliced out of the padded product by torch ops.  Against the oracle's W + s*B@(A*mask)."""
+    from whisper_finetune.engine.whisper_model import Linear
+    g = torch.Generator().manual_seed(0)
+    lin = Linear(256, 384)
+    lora_mod.add_lora_to_linear(lin, 8, 16, 0.5)
+    lin.to(DEV).train()
+    ad = lin.parametrizations.weight[0]
+    with torch.no_grad():
+        ad.lora_B.copy_(torch.randn(ad.lora_B.shape, generator=g).to(DEV) * 0.1)
+    lin.parametrizations.weight.original.requires_grad_(False)
+    getattr(ad, frozen).requires_grad_(False)
+    mask = (torch.rand(1, 256, generator=g) > 0.5).float() / 0.5
+    mask_dev = mask.to(DEV)
+    ad.draw_mask = lambda training: mask_dev
+    x, w = torch.randn(64, 256, generator=g), torch.randn(64, 384, generator=g)
+    calls = {"pair": 0, "rank_nt": 0}
+    real = (K.gemm_nt_rank_pair, K.gemm_nt)
+
+    def pair(*a, **k):
+        calls["pair"] += 1
+        return real[0](*a, **k)
+
+    def nt(*a, **k):
+        calls["rank_nt"] += int(k.get("p_valid", 0) > 0)
+        return real[1](*a, **k)
+
+    K.gemm_nt_rank_pair, K.gemm_nt = pair, nt
+    try:
+        y = lin(x.to(DEV))
+        (y.float() * w.to(DEV)).sum().backward()
+    finally:
+        K.gemm_nt_rank_pair, K.gemm_nt = real
+    assert calls == {"pair": 0, "rank_nt": 1}, calls
+    A = ad.lora_A.detach().cpu().clone().requires_grad_(True)
+    Bm = ad.lora_B.detach().cpu().clone().requires_grad_(True)
+    W = O.lora_effective_weight(lin.parametrizations.weight.original.detach().cpu(), A, Bm, ad.scaling, mask)
+    ((x.to(torch.bfloat16).float() @ W.T + lin.bias.detach().cpu()) * w).sum().backward()
+    if frozen == "lora_A":
+        assert ad.lora_A.grad is None
+        assert rel(ad.lora_B.grad, Bm.grad) < 3e-2, rel(ad.lora_B.grad, Bm.grad)
+    else:
+        assert ad.lora_B.grad is None
+        assert rel(ad.lora_A.grad, A.grad) < 3e-2, rel(ad.lora_A.grad, A.grad)
+        assert ad.lora_A.grad[:, (mask[0] == 0).to(DEV)].abs().max() == 0  # dropped input columns of A take no gradient
+
+
 def test_lora_masks_survive_a_second_forward_before_the_backward():
     """the mask pool's buffer is overwritten in place by the next draw.  `loss = model(a) + model(b)` runs two
     training forwards before the first backward: the first forward's adapters must back-propagate through THEIR masks (the pool
@@ -726,7 +776,7 @@ def test_lora_batched_refresh_is_bit_identical_to_the_per_linear_kernels():
         m.to(DEV).train()
         pool = m.__dict__["_wft_lora_pool"]
         if not batched:
-            pool.plan = None
+            pool.plan.note = lambda *a: None  # no group ever enters the plan: every forward takes the per-Linear kernels
         opt = torch.optim.SGD([p for p in m.parameters() if p.requires_grad], lr=0.05)
         counts = {"merge": 0, "pack": 0, "mt": 0}
         real = (K.lora_merge, K.lora_pack, K.lora_refresh_mt)
@@ -868,7 +918,7 @@ def test_encoder_output_gradient_fork_survives_two_decoder_passes_and_partial_ba
     """ADVICE r4 on ops.GradAccum: (1) two decoder passes over ONE encoder output with different stochastic-depth skips (31 + 31
     arrivals against 32 registered ids used to hand the sum over early and drop the rest); (2) `autograd.grad(inputs=subset)` in
     front of the real backward used to leave a count behind.  With the fork node both give the encoder the gradient autograd's own
-    summation gives (WFT_XA_ACCUM=0 twin, same skip draws)."""
+    summation gives (whisper_model._XA_ACCUM = False twin, same skip draws)."""
     from whisper_finetune.engine import whisper_model as WM
     from whisper_finetune.model.model_utils import CheckpointedStochasticTextDecoder
     dims, params, audio, y_in, y_out = _tiny_case()

@@ -22,6 +22,7 @@ __device__ __forceinline__ void store4(unsigned short* p, const float* v) {
 // is reduced and written (software prefetch), 4 waves per SIMD at NQ = 5
 // DSPAN: the span (t0, t1, c0, c1) is read from device memory (`span`, int32[4]) instead of the arguments — a captured
 // HIP graph replays the kernel with the values its host wrote there before the replay (engine/draws.py)
+// VAR 1: plain y stores; VAR 2: non-temporal y stores (ln_fwd_impl chooses by tensor size)
 template <int NQ, int VAR, bool DSPAN>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const unsigned short* x, const float* gamma,
                                                       const float* beta, unsigned short* y, float* mean,
@@ -39,15 +40,13 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const unsigned short* x, co
   const int nch = cols >> 2;
   const float inv = 1.f / cols;
   f32x4 gg[NQ], bb[NQ];
-  if (VAR >= 1) {
 #pragma unroll
-    for (int c = 0; c < NQ; ++c) {
-      const int ch = lane + c * 64;
-      gg[c] = bb[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (ch < nch) {
-        gg[c] = *(const f32x4*)(gamma + ch * 4);
-        bb[c] = *(const f32x4*)(beta + ch * 4);
-      }
+  for (int c = 0; c < NQ; ++c) {
+    const int ch = lane + c * 64;
+    gg[c] = bb[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (ch < nch) {
+      gg[c] = *(const f32x4*)(gamma + ch * 4);
+      bb[c] = *(const f32x4*)(beta + ch * 4);
     }
   }
   u32x2 nraw[NQ];
@@ -69,7 +68,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const unsigned short* x, co
 #pragma unroll
       for (int e = 0; e < 4; ++e) s += v[c][e];
     }
-    if (VAR >= 1 && row + nwaves < rows) fetch(row + nwaves);
+    if (row + nwaves < rows) fetch(row + nwaves);
     const float mu = wave_sum(s) * inv;
     float q = 0.f;
 #pragma unroll
@@ -98,10 +97,6 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const unsigned short* x, co
       const int ch = lane + c * 64;
       if (ch < nch) {
         float o[4];
-        if (VAR == 0) {
-          gg[c] = *(const f32x4*)(gamma + ch * 4);
-          bb[c] = *(const f32x4*)(beta + ch * 4);
-        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           o[e] = (v[c][e] - mu) * rs * gg[c][e] + bb[c][e];
@@ -120,7 +115,6 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const unsigned short* x, co
         }
       }
     }
-    if (VAR == 0 && row + nwaves < rows) fetch(row + nwaves);
   }
 }
 
@@ -128,6 +122,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const unsigned short* x, co
 // of a block are summed through LDS and written to partial[block][2 or 3][cols]; ln_bwd_reduce sums the blocks
 // (deterministic, no atomics).  The register file allows two waves per SIMD at d = 1280, so every wave keeps the NEXT
 // row's dy / x / dres loads in flight while it reduces and writes the current one (software prefetch).
+// VAR 0: plain loads and stores; VAR 2: non-temporal dy / x / dres loads and dx stores (ln_bwd_impl chooses by tensor size)
 template <bool DXSUM, int NQ, int VAR, bool DSPAN>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const unsigned short* dy, const unsigned short* x,
                                                       const float* gamma, const float* mean,
@@ -234,7 +229,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const unsigned short* dy, c
 #pragma unroll
           for (int e = 0; e < 4; ++e) dsum[c][e] += bf2f(f2bf(o[e]));  // what wft_colsum_bf16 would read back
         }
-        if (VAR >= 1) {
+        if (VAR == 2) {
           u32x2 r;
           r[0] = pack2bf(o[0], o[1]);
           r[1] = pack2bf(o[2], o[3]);
@@ -361,18 +356,15 @@ static int ln_fwd_impl(const wft_bf16* x, const float* gamma, const float* beta,
   WFT_CHECK_ARG(x && gamma && beta && y && mean && rstd, "null pointer");
   WFT_CHECK_ARG(rows >= 1 && cols >= 8 && cols % 8 == 0 && cols <= 2048, "cols must be a multiple of 8, <= 2048");
   // VAR 1: gamma/beta in registers + next-row prefetch; VAR 2: the same with non-temporal y stores, used when the
-  // tensor is larger than the caches could keep for the consumer anyway (5.4 -> 6.5 TB/s at 68 x 1500 x 1280);
-  // VAR 0 (no prefetch, 3.4 TB/s) only through WFT_LN_FWD_VAR for A/B runs
-  static int forced = -2;
-  if (forced == -2) { const char* e = wft_dev_getenv("WFT_LN_FWD_VAR"); forced = e ? atoi(e) : -1; }
-  const int var = forced >= 0 ? forced : ((long)rows * cols * 2 >= LN_NT_BYTES ? 2 : 1);
+  // tensor is larger than the caches could keep for the consumer anyway (5.4 -> 6.5 TB/s at 68 x 1500 x 1280)
+  const bool nt = (long)rows * cols * 2 >= LN_NT_BYTES;
 #define LN_FWD_LAUNCH_S(NQV, V, S)                                                                                   \
   hipLaunchKernelGGL((ln_fwd_kernel<NQV, V, S>), dim3(ln_fwd_grid<NQV, V>(rows)), dim3(256), 0, (hipStream_t)stream, x, gamma, \
                      beta, y, mean, rstd, (long)rows, cols, eps, rows_per_batch, t0, t1, c0, c1, span)
 #define LN_FWD_LAUNCH_V(NQV, V) \
   do { if (span) LN_FWD_LAUNCH_S(NQV, V, true); else LN_FWD_LAUNCH_S(NQV, V, false); } while (0)
 #define LN_FWD_LAUNCH(NQV) \
-  if (var == 0) LN_FWD_LAUNCH_V(NQV, 0); else if (var == 2) LN_FWD_LAUNCH_V(NQV, 2); else LN_FWD_LAUNCH_V(NQV, 1)
+  if (nt) LN_FWD_LAUNCH_V(NQV, 2); else LN_FWD_LAUNCH_V(NQV, 1)
   LN_NQ_SWITCH((cols + 255) / 256, LN_FWD_LAUNCH)
 #undef LN_FWD_LAUNCH
   WFT_CHECK_LAUNCH();
@@ -407,17 +399,15 @@ static int ln_bwd_impl(const wft_bf16* dy, const wft_bf16* x, const float* gamma
   WFT_CHECK_ARG(rows >= 1 && cols >= 8 && cols % 8 == 0 && cols <= 2048, "cols must be a multiple of 8, <= 2048");
   const int grid = ln_grid(rows);
   if (!want_params && !dx_colsum) partial = nullptr;  // nothing to reduce: the kernel stops after dx, no reduce launches
-  // VAR 2 (non-temporal dy / x / dres loads and dx stores) for tensors the caches cannot keep; WFT_LN_BWD_VAR forces one
-  static int forced = -2;
-  if (forced == -2) { const char* e = wft_dev_getenv("WFT_LN_BWD_VAR"); forced = e ? atoi(e) : -1; }
-  const int var = forced >= 0 ? forced : ((long)rows * cols * 2 >= LN_NT_BYTES ? 2 : 0);
+  // VAR 2 (non-temporal dy / x / dres loads and dx stores) for tensors the caches cannot keep, else VAR 0
+  const bool nt = (long)rows * cols * 2 >= LN_NT_BYTES;
 #define LN_BWD_LAUNCH_S(DX, NCV, V, S)                                                                               \
   hipLaunchKernelGGL((ln_bwd_kernel<DX, NCV, V, S>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, x, gamma, mean, rstd, \
                      dres, dx, (float*)partial, (long)rows, cols, rows_per_batch, t0, t1, c0, c1, span)
 #define LN_BWD_LAUNCH_V(DX, NCV, V) \
   do { if (span) LN_BWD_LAUNCH_S(DX, NCV, V, true); else LN_BWD_LAUNCH_S(DX, NCV, V, false); } while (0)
 #define LN_BWD_LAUNCH(DX, NCV) \
-  if (var == 0) LN_BWD_LAUNCH_V(DX, NCV, 0); else if (var == 2) LN_BWD_LAUNCH_V(DX, NCV, 2); else LN_BWD_LAUNCH_V(DX, NCV, 1)
+  if (nt) LN_BWD_LAUNCH_V(DX, NCV, 2); else LN_BWD_LAUNCH_V(DX, NCV, 0)
   const int nq = (cols + 255) / 256;
 #define LN_BWD_T(NQV) LN_BWD_LAUNCH(true, NQV)
 #define LN_BWD_F(NQV) LN_BWD_LAUNCH(false, NQV)

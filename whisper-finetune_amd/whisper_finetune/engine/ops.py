@@ -13,7 +13,6 @@ import itertools
 import threading
 import weakref
 
-import os
 import torch
 from torch.optim.optimizer import register_optimizer_step_post_hook
 
@@ -31,8 +30,9 @@ F32 = torch.float32
 # exponent's left operand and no attention kernel multiplies its scores (wft_attn_args.q_prescaled; -4 % on the three encoder kernels,
 # profiles/r06_attn_prescale.md).  The backward-data shadow W^T stays unscaled and the dQ kernel returns the gradient w.r.t. the unscaled
 # projection output, so dx, dW, db and the LoRA gradients are computed exactly as before.  Reference: whisper's `q * scale`
-# (MultiHeadAttention.qkv_attention, reached from model/model_utils.py:283-285,320-322).  WFT_QK_PRESCALE=0: the old path (A/B runs).
-QK_PRESCALE = os.environ.get("WFT_QK_PRESCALE", "1") != "0"
+# (MultiHeadAttention.qkv_attention, reached from model/model_utils.py:283-285,320-322).  False: the scale inside the attention kernels, the
+# reference twin of tests/test_attn_prescale_gpu.py.
+QK_PRESCALE = True
 QK_ALPHA = float(torch.tensor(64 ** -0.5, dtype=torch.float32) * torch.tensor(1.4426950408889634, dtype=torch.float32))
 
 # bumped by optimizers that update parameters through raw pointers (torch's in-place ops bump
@@ -459,8 +459,9 @@ class PlainRefreshPlan:
 
 
 _PLAIN_PLAN = PlainRefreshPlan()
-# WFT_SHADOW_BATCH=0: one cast/transpose launch per weight (A/B runs)
-_SHADOW_BATCH = os.environ.get("WFT_SHADOW_BATCH", "1") != "0"
+# False: one cast/transpose launch per weight, the reference twin of tests/test_model_gpu.py
+# (test_batched_weight_shadow_refresh_is_bit_identical_to_the_per_weight_kernel)
+_SHADOW_BATCH = True
 
 
 def _note_lora_group(group: "LinearGroup", weights, loras) -> None:
@@ -468,7 +469,7 @@ def _note_lora_group(group: "LinearGroup", weights, loras) -> None:
     if any(o is None for o in owners):
         return
     pool = getattr(owners[0], "_pool", None)
-    if pool is None or any(getattr(o, "_pool", None) is not pool for o in owners) or getattr(pool, "plan", None) is None:
+    if pool is None or any(getattr(o, "_pool", None) is not pool for o in owners):
         return
     pool.plan.note(group, weights, owners)
 
@@ -546,8 +547,8 @@ def grad_fork(x: torch.Tensor):
 # that memory.  The reducer finds grad.is_alias_of(bucket_view) and skips its copy.  Without DDP the homes are last step's
 # gradient tensors: same code path, and gradient accumulation costs no elementwise add per parameter.  A home that no longer
 # matches (DDP rebuilt its buckets after the first iteration, the user replaced .grad) is simply not used for that call.
-# WFT_GRAD_HOMES=0 restores fresh gradient tensors per backward (A/B runs).
-_GRAD_HOMES = os.environ.get("WFT_GRAD_HOMES", "1") != "0"
+# False: fresh gradient tensors per backward, the reference twin of tests/test_grad_homes_gpu.py.
+_GRAD_HOMES = True
 
 
 def note_grad_homes(params) -> None:
@@ -603,18 +604,11 @@ class _LinearCfg:
         self.gelu_codes = gelu_codes    # gelu_in: the one-byte gelu' buffer the producer returned beside `pre` (None: `pre` holds bf16 gelu')
 
 
-# WFT_LORA_PVALID=0: rank-r weight-gradient GEMMs without the p_valid shortcut (A/B runs)
-_LORA_PVALID = os.environ.get("WFT_LORA_PVALID", "1") != "0"
-# WFT_LORA_FUSED_OUT=0: adapter gradients sliced / masked / transposed by torch ops after the GEMMs (A/B runs)
-_LORA_FUSED_OUT = os.environ.get("WFT_LORA_FUSED_OUT", "1") != "0"
-# WFT_LORA_PAIR=0: the four rank-r products of a group's backward as four launches + two reduces instead of two + one (A/B runs)
-_LORA_PAIR = os.environ.get("WFT_LORA_PAIR", "1") != "0"
-# WFT_GELU_PAIR=0: keep the pre-activation and evaluate gelu' in the backward-data GEMM's epilogue (A/B runs)
-_GELU_PAIR = os.environ.get("WFT_GELU_PAIR", "1") != "0"
-# WFT_GELU_AUX8=0: gelu' travels as bf16 [M, N] everywhere (A/B runs).  Default: ONE BYTE per element in gemm_nt4w_kernel's fragment
-# order wherever both GEMMs of the pair run on that kernel (WFT_EPI_GELU_GRAD8 / WFT_EPI_MUL_AUX8, include/wft.h): half the bytes of
-# the pair's second tensor, 21 GiB less saved-for-backward memory at 87 clips of large-v3.
-_GELU_AUX8 = os.environ.get("WFT_GELU_AUX8", "1") != "0"
+# gelu' travels as ONE BYTE per element in gemm_nt4w_kernel's fragment order wherever both GEMMs of the pair run on that kernel
+# (WFT_EPI_GELU_GRAD8 / WFT_EPI_MUL_AUX8, include/wft.h): half the bytes of the pair's second tensor, 21 GiB less saved-for-backward
+# memory at 87 clips of large-v3.  False: bf16 [M, N] everywhere, the reference twin of tests/test_gelu_aux8_gpu.py and
+# tests/test_dispatch_regime_gpu.py.
+_GELU_AUX8 = True
 
 
 class LinearFn(torch.autograd.Function):
@@ -632,17 +626,10 @@ class LinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, gelu_pre, cfg: _LinearCfg, *params):
         ctx.set_materialize_grads(False)  # no [M, N] zero tensor for the non-differentiable `act` output
-        n_w = cfg.n_w
-        weights = list(params[:n_w])
-        nb = sum(cfg.has_bias)
-        bias_list = list(params[n_w:n_w + nb])
-        biases, bi = [], 0
-        for hb in cfg.has_bias:
-            biases.append(bias_list[bi] if hb else None)
-            bi += int(hb)
+        weights = list(params[:cfg.n_w])
         need_dx = ctx.needs_input_grad[0] or (gelu_pre is not None and ctx.needs_input_grad[2])
         has_lora = any(s is not None for s in cfg.loras)
-        W, WT, bias = cfg.group.shadows(weights, biases, need_t=need_dx, loras=cfg.loras if has_lora else None)
+        W, WT, bias = cfg.group.shadows(weights, _bias_list(cfg, params), need_t=need_dx, loras=cfg.loras if has_lora else None)
         n, k, npad = LinearGroup.dims(weights)
         kpad = k
         assert x.dtype == BF16 and x.dim() == 2 and x.is_contiguous() and x.shape[1] == kpad, (x.shape, kpad)
@@ -652,7 +639,7 @@ class LinearFn(torch.autograd.Function):
             # one-byte gelu' if this GEMM AND the backward-data GEMM of the consuming Linear ([M, next_n] x [npad, next_n]^T with the
             # fused column sums) both run on gemm_nt4w_kernel
             nb8 = 0
-            if _GELU_PAIR and _GELU_AUX8 and residual is None and cfg.gelu_next_n > 0:
+            if _GELU_AUX8 and residual is None and cfg.gelu_next_n > 0:
                 nb8 = K.gemm_nt_aux8_bytes(M, npad, kpad, x.device)
                 if nb8 and not K.gemm_nt_aux8_bytes(M, npad, cfg.gelu_next_n, x.device, epilogue=L.EPI_MUL_AUX8, colsum=BIAS_GRADS[0]):
                     nb8 = 0
@@ -664,7 +651,7 @@ class LinearFn(torch.autograd.Function):
                 out_pre = torch.empty(1, dtype=BF16, device=x.device).expand(M, npad)
             else:
                 out_pre = torch.empty((M, npad), dtype=BF16, device=x.device)
-                y = K.gemm_nt(x, W, bias=bias, epilogue=L.EPI_GELU_GRAD if _GELU_PAIR else L.EPI_GELU, aux=out_pre, residual=residual)
+                y = K.gemm_nt(x, W, bias=bias, epilogue=L.EPI_GELU_GRAD, aux=out_pre, residual=residual)
         else:
             y = K.gemm_nt(x, W, bias=bias, residual=residual)
         ctx.cfg = cfg
@@ -710,7 +697,7 @@ class LinearFn(torch.autograd.Function):
                 # dpre is the dy of the Linear that produced gelu_pre: its bias gradient (column sums) comes out of this
                 # GEMM's epilogue (see _publish_colsum / _fused_colsum)
                 cs = torch.empty(WT.shape[0], dtype=F32, device=dy.device) if ctx.want_cs else None
-                epi = L.EPI_MUL_AUX8 if ctx.pre_is_aux8 else (L.EPI_MUL_AUX if _GELU_PAIR else L.EPI_DGELU)
+                epi = L.EPI_MUL_AUX8 if ctx.pre_is_aux8 else L.EPI_MUL_AUX
                 dpre = K.gemm_nt(dy, WT, epilogue=epi, aux=gelu_pre, colsum=cs, launch=ctx.launch)
                 if cs is not None:
                     _publish_colsum(dpre, cs)
@@ -764,30 +751,22 @@ class LinearFn(torch.autograd.Function):
             # load-stream kernel for rank-r operands (35 us for the 123 MB activation of a 1280-wide Linear at 32 clips, 52 us
             # through the square-tile kernel); the two NT products below already run at the HBM rate of their activation
             # operand through the 128-wide tile kernel (27 us, measured — a dedicated skinny kernel was slower)
-            pv = rtot if (_LORA_PVALID and rtot <= 64) else 0
+            pv = rtot if rtot <= 64 else 0
             specs = [s for s in cfg.loras if s is not None]
             r0, n0 = specs[0].A.shape[0], weights[0].shape[0]
             # every Linear of the group adapted, equal shapes, nothing padded, every adapter gradient wanted (the normal case:
             # q/k/v, k/v or a single Linear): the kernel that sums the split-K partials applies the dropout masks to dA and
             # writes dB as [out, r] blocks, so both leave the library as the contiguous tensors autograd hands on — no
-            # `dA * mask` kernel and no strided-view copy in AccumulateGrad per adapter (WFT_LORA_FUSED_OUT=0: the slicing below)
-            fused = (_LORA_FUSED_OUT and pv > 0 and len(specs) == n_w and all(a_need) and all(b2_need) and kpad == k
+            # `dA * mask` kernel and no strided-view copy in AccumulateGrad per adapter (otherwise: the slicing below)
+            fused = (pv > 0 and len(specs) == n_w and all(a_need) and all(b2_need) and kpad == k
                      and npad == n and all(s.A.shape[0] == r0 for s in specs) and all(w.shape[0] == n0 for w in weights)
                      and all((s.mask is None) == (specs[0].mask is None) for s in specs))
-            if fused and _LORA_PAIR:
+            if fused:
                 # the four rank-r products as two paired launches (+ one reduce launch for both gradients): 3 launches, not 6
                 du, u = K.gemm_nt_rank_pair(dy, BbT, x, Am, pv)          # dy @ (s*B) | x @ (s*A*mask)^T (carries the scaling)
                 dA_full, dB_blocks = K.gemm_tn_rank_pair(
                     dict(a=du, b=x, p_valid=pv, col_scale=_stacked_masks(specs), scale_rows=r0 if n_w > 1 else 0),
                     dict(a=u, b=dy, p_valid=pv, block_n=n0, block_r=r0))
-                out.extend(dA_full[i * r0:(i + 1) * r0] for i in range(n_w))
-                out.extend(dB_blocks[i * n0 * r0:(i + 1) * n0 * r0].view(n0, r0) for i in range(n_w))
-                return tuple(out)
-            if fused:
-                du = K.gemm_nt(dy, BbT, p_valid=pv)                      # [M, Rpad] = dy @ (s*B)
-                dA_full = K.gemm_tn(du, x, p_valid=pv, col_scale=_stacked_masks(specs), scale_rows=r0 if n_w > 1 else 0)
-                u = K.gemm_nt(x, Am, p_valid=pv)                       # [M, Rpad] = x @ (s*A*mask)^T (carries the scaling: wft_lora_pack)
-                dB_blocks = K.gemm_tn(u, dy, p_valid=pv, block_n=n0, block_r=r0)
                 out.extend(dA_full[i * r0:(i + 1) * r0] for i in range(n_w))
                 out.extend(dB_blocks[i * n0 * r0:(i + 1) * n0 * r0].view(n0, r0) for i in range(n_w))
                 return tuple(out)
@@ -850,7 +829,7 @@ def _colsums() -> dict:
 
 # Does any bias of the running model take a gradient?  Set by the model at the start of every forward (Whisper.forward /
 # forward_loss).  False in a LoRA run (frozen base): the producer kernels then skip the fused bias-gradient column sums and
-# their reduce launches (LayerNorm backward, attention backward, the DGELU / MUL_AUX GEMM epilogue).
+# their reduce launches (LayerNorm backward, attention backward, the MUL_AUX GEMM epilogue).
 BIAS_GRADS = [True]
 # whisper's key projection has no bias; a model that gives it one (not whisper) must set this so that the fused q/k/v column
 # sums (which leave the k slice at zero) are not used for it
@@ -872,7 +851,7 @@ def _publish_colsum(t: torch.Tensor, cs: torch.Tensor) -> None:
 
 def _fused_colsum(grad, dy):
     """Column sums a producer kernel already formed for exactly this gradient (LayerNorm backward for the residual
-    stream, the DGELU GEMM epilogue for d(pre-activation)); None if autograd handed over different data (accumulated /
+    stream, the MUL_AUX GEMM epilogue for d(pre-activation)); None if autograd handed over different data (accumulated /
     cast / re-laid-out), in which case the caller falls back to wft_colsum_bf16."""
     ent = _colsums().pop(dy.data_ptr(), None)
     if ent is None:

@@ -18,8 +18,6 @@ import warnings
 from dataclasses import dataclass
 from typing import Dict, Iterable, Optional
 
-import os
-
 import numpy as np
 
 import torch
@@ -35,8 +33,9 @@ from . import ops32
 BF16 = torch.bfloat16
 
 
-# WFT_XA_ACCUM=0: the encoder-output gradient is summed by autograd (A/B runs)
-_XA_ACCUM = os.environ.get("WFT_XA_ACCUM", "1") != "0"
+# False: the encoder-output gradient is summed by autograd, the reference twin of tests/test_model_gpu.py
+# (test_encoder_output_gradient_*)
+_XA_ACCUM = True
 
 
 @dataclass

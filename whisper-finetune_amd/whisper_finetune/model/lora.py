@@ -16,7 +16,6 @@ the effective weight for code that reads it (merge / save / debugging).
 from __future__ import annotations
 
 import math
-import os
 import weakref
 from typing import Optional
 
@@ -122,9 +121,8 @@ class LoraMaskPool:
         # evaluate the ORIGINAL model from the copy — EMA / teacher / eval-on-a-copy flows).
         if callable(getattr(type(root), "forward_loss", None)) and "forward_loss" not in root.__dict__:
             root.__dict__["forward_loss"] = self._forward_loss
-        # all merged shadows / gradient-GEMM operands of the model in one launch per training forward (WFT_LORA_BATCH=0: the
-        # per-Linear kernels, A/B runs)
-        self.plan = ops.LoraRefreshPlan() if os.environ.get("WFT_LORA_BATCH", "1") != "0" else None
+        # all merged shadows / gradient-GEMM operands of the model in one launch per training forward
+        self.plan = ops.LoraRefreshPlan()
 
     def _forward_loss(self, *args, **kwargs):
         root = self.root
@@ -156,7 +154,7 @@ class LoraMaskPool:
         new.depth = 0
         new.handle = copy.deepcopy(self.handle, memo)
         new.handles = [copy.deepcopy(h, memo) for h in self.handles]
-        new.plan = ops.LoraRefreshPlan() if self.plan is not None else None
+        new.plan = ops.LoraRefreshPlan()
         return new
 
     def add(self, adapter: "LoRAParametrization") -> None:
@@ -198,14 +196,13 @@ class LoraMaskPool:
             A0 = self.adapters[0].lora_A
             if self.store is None or self.store.device != A0.device or self.store.dtype != A0.dtype or self.store.numel() != self.total:
                 self.store = torch.empty(self.total, device=A0.device, dtype=A0.dtype)
-                if self.plan is not None:
-                    self.plan.dirty = True
+                self.plan.dirty = True
             self._detach_live_specs()
             self.buf = self.store.bernoulli_(1.0 - p).mul_(1.0 / (1.0 - p))
             self.serial = next(ops.LoraSpec._draws)
         else:
             self.buf = None
-        if self.plan is not None and self.adapters[0].lora_A.is_cuda and getattr(module, "compute_dtype", "bf16") != "fp32":
+        if self.adapters[0].lora_A.is_cuda and getattr(module, "compute_dtype", "bf16") != "fp32":
             self.plan.refresh(self.mask_of, self.serial)
 
     def mask_of(self, adapter) -> Optional[torch.Tensor]:
