@@ -630,7 +630,24 @@ int wft_decode_sample_ts(const wft_decode_pick_args* args, const wft_sample_rule
  *  path_text / path_time i32 [B, ld_path] (ld_path >= n_rows_max + n_cols_max - 1): the recorded pairs in FORWARD order,
  *    path_len[b] of them; entries beyond path_len[b] are not written; N == 0 or M == 0 gives path_len[b] = 0.
  *  matrix_rows: the rows a matrix holds per audio (row0 + n_rows_max <= matrix_rows is checked on the host).
- *  workspace: wft_dtw_workspace_bytes(B, n_rows_max, n_cols_max) bytes (the trace, kernel-internal).                              */
+ *  workspace: wft_dtw_workspace_bytes(B, n_rows_max, n_cols_max) bytes (the trace, kernel-internal).
+ *
+ * wft_word_spans: upstream's arithmetic behind the path (`jumps`, `jump_times`, the word boundaries, the mean token probability)
+ *  for a ragged batch in one launch, on the paths of wft_dtw_f32 where they lie — frames stay integers, the caller divides.
+ *  path_text / path_time i32 [B, ld_path], path_len i32 [B]: as wft_dtw_f32 writes them (rows in [0, n_rows_max), n_rows_max <= 448).
+ *  bounds i32 [B, ld_bounds]: bounds[b, w] = the path row at which word w starts, w = 0 .. n_words[b] (n_words[b] + 1 entries,
+ *    bounds[b, 0] = 0, strictly increasing, the last one the row of the eot): np.pad(np.cumsum(counts[:-1]), (1, 0)) of upstream.
+ *  n_words i32 [B]; token_probs f32 [n_probs], packed over the audios; tok_off i32 [B]: the first element of audio b in it.
+ *  first[b, r] = path_time[b, p] at the LOWEST p < path_len[b] with path_text[b, p] == r — on a DTW path (rows never decrease,
+ *    every row occurs) upstream's `jumps`: position 0 and every position at which the text index changes; a row that does not
+ *    occur gives -1.
+ *  start_frame[b, w] = first[b, bounds[b, w]], end_frame[b, w] = first[b, bounds[b, w + 1]]  (i32, at b*ld_words + w);
+ *  prob[b, w] = (sum in ascending i of token_probs[tok_off[b] + i], bounds[b, w] <= i < bounds[b, w + 1], one fp32 running sum)
+ *    / (float)count, one IEEE division.
+ *  Lengths are clamped to the static extents: path_len to [0, ld_path], n_words to [0, min(ld_bounds - 1, ld_words, n_rows_max)],
+ *    a bound to [0, n_rows_max - 1], tok_off to [0, n_probs]; a token index at or beyond n_probs adds 0.  Elements with
+ *    w >= n_words[b] are NOT written; path_len[b] == 0 or n_words[b] == 0 writes nothing for that audio.
+ *  One workgroup per audio, one owner per row and per word: no atomics, reruns are bit-identical.                                  */
 int wft_attn_probs_bf16(const wft_attn_args* args, const int32_t* heads, int n_heads, const int32_t* n_tok, const int32_t* n_key,
                         float* probs, int64_t p_bs, int64_t p_hs, int64_t ldp, void* stream);
 int wft_align_matrix(const float* probs, int64_t p_bs, int64_t p_hs, int64_t ldp, const int32_t* n_tok, const int32_t* n_key,
@@ -639,6 +656,9 @@ int64_t wft_dtw_workspace_bytes(int B, int n_rows_max, int n_cols_max);
 int wft_dtw_f32(const float* matrix, int64_t m_bs, int64_t ldm, int matrix_rows, int row0, const int32_t* n_rows,
                 const int32_t* n_cols, int B, int n_rows_max, int n_cols_max, int negate, int32_t* path_text, int32_t* path_time,
                 int64_t ld_path, int32_t* path_len, void* workspace, int64_t workspace_bytes, void* stream);
+int wft_word_spans(const int32_t* path_text, const int32_t* path_time, int64_t ld_path, const int32_t* path_len, const int32_t* bounds,
+                   int64_t ld_bounds, const int32_t* n_words, const float* token_probs, int64_t n_probs, const int32_t* tok_off,
+                   int32_t* start_frame, int32_t* end_frame, float* prob, int64_t ld_words, int B, int n_rows_max, void* stream);
 
 /* ------------------------------- Language detection and long-form windows */
 /* csrc/transcribe.hip: the two device stages of upstream's `detect_language` and of the window loop of `transcribe()`

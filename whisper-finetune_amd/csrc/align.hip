@@ -1,8 +1,9 @@
-// align.hip — word-level alignment (include/wft.h "Word-level alignment"): the three device stages of upstream's
+// align.hip — word-level alignment (include/wft.h "Word-level alignment"): the device stages of upstream's
 // `whisper/timing.py: find_alignment` behind the softmax scores of the alignment heads.
 //  attn_probs_kernel    row softmax of the scaled cross-attention scores of a head list, written out in fp32
 //  align_matrix_kernel  standardise over the tokens, median-filter along the frames, average the heads
 //  dtw_kernel           dynamic time warping over one audio's cost matrix, anti-diagonal sweep + backtrace in one launch
+//  word_spans_kernel    the first frame of every path row, then per word its two boundary frames and its mean token probability
 // Per-audio lengths are device int32 arrays; every kernel clamps them to its static extents before it forms an address.
 #include <math.h>
 
@@ -389,6 +390,74 @@ extern "C" int wft_dtw_f32(const float* matrix, int64_t m_bs, int64_t ldm, int m
   hipLaunchKernelGGL(dtw_kernel, dim3(B), dim3(threads), 0, (hipStream_t)stream, matrix, (long)m_bs, (long)ldm, row0, n_rows, n_cols, negate,
                      (unsigned char*)workspace, (long)(wft_dtw_workspace_bytes(B, n_rows_max, n_cols_max) / B), n_rows_max, n_cols_max,
                      path_text, path_time, (long)ld_path, path_len);
+  WFT_CHECK_LAUNCH();
+  return WFT_OK;
+}
+
+// ----------------------------------------------------------------------------- d. word spans
+// One workgroup per audio.  The path's text rows go through LDS in chunks of WS_CHUNK entries; thread r looks for the lowest
+// position that holds row r (16-byte LDS reads, the same address in every lane: a broadcast) and reads that position's frame once.
+// Every row has one owner, so no two threads write the same word of s_first.  Then thread w forms word w: two lookups and a serial
+// fp32 sum over its tokens, in ascending order.
+#define WS_THREADS 512  // >= DTW_MAX_ROWS: one thread per path row
+#define WS_CHUNK 2048
+
+__global__ __launch_bounds__(WS_THREADS) void word_spans_kernel(const int* path_text, const int* path_time, int ld_path, const int* path_len,
+                                                               const int* bounds, long ld_bounds, const int* n_words,
+                                                               const float* token_probs, long n_probs, const int* tok_off, int* start_frame,
+                                                               int* end_frame, float* prob, long ld_words, int n_words_max, int n_rows_max) {
+  __shared__ __attribute__((aligned(16))) int s_text[WS_CHUNK];
+  __shared__ int s_first[WS_THREADS];
+  const int b = blockIdx.x, r = threadIdx.x;
+  const int L = min(max(path_len[b], 0), ld_path), nw = min(max(n_words[b], 0), n_words_max);
+  if (L == 0 || nw == 0) return;  // (the whole workgroup)
+  const int* pt = path_text + (long)b * ld_path;
+  int found = -1;  // the lowest position of row r
+  for (int c0 = 0; c0 < L; c0 += WS_CHUNK) {
+    const int n = min(WS_CHUNK, L - c0);
+    for (int x = r; x < WS_CHUNK; x += WS_THREADS) s_text[x] = x < n ? pt[c0 + x] : -1;  // (-1 is no row)
+    __syncthreads();
+    if (found < 0 && r < n_rows_max) {
+      for (int x = 0; x < n; x += 4) {
+        const int4 v = *(const int4*)(s_text + x);
+        const int hit = v.x == r ? 0 : v.y == r ? 1 : v.z == r ? 2 : v.w == r ? 3 : -1;
+        if (hit >= 0) {
+          found = c0 + x + hit;
+          break;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  s_first[r] = found >= 0 ? path_time[(long)b * ld_path + found] : -1;
+  __syncthreads();
+  const int* bd = bounds + b * ld_bounds;
+  const long off = min(max((long)tok_off[b], 0L), n_probs);
+  for (int w = r; w < nw; w += WS_THREADS) {
+    const int lo = min(max(bd[w], 0), n_rows_max - 1), hi = min(max(bd[w + 1], 0), n_rows_max - 1);
+    float sum = 0.f;
+    for (int i = lo; i < hi; ++i) sum += off + i < n_probs ? token_probs[off + i] : 0.f;
+    start_frame[b * ld_words + w] = s_first[lo];
+    end_frame[b * ld_words + w] = s_first[hi];
+    prob[b * ld_words + w] = hi > lo ? sum / (float)(hi - lo) : 0.f;
+  }
+}
+
+extern "C" int wft_word_spans(const int32_t* path_text, const int32_t* path_time, int64_t ld_path, const int32_t* path_len,
+                              const int32_t* bounds, int64_t ld_bounds, const int32_t* n_words, const float* token_probs, int64_t n_probs,
+                              const int32_t* tok_off, int32_t* start_frame, int32_t* end_frame, float* prob, int64_t ld_words, int B,
+                              int n_rows_max, void* stream) {
+  WFT_CHECK_ARG(path_text && path_time && path_len && bounds && n_words && token_probs && tok_off && start_frame && end_frame && prob,
+                "null pointer");
+  WFT_CHECK_ARG(B >= 1 && n_rows_max >= 1 && n_rows_max <= DTW_MAX_ROWS, "B >= 1 and n_rows_max in 1..448 (one thread per path row)");
+  WFT_CHECK_ARG(ld_path >= 1 && ld_path <= (1 << 30), "ld_path must lie in 1..2^30");
+  WFT_CHECK_ARG(ld_bounds >= 2 && ld_words >= 1 && n_probs >= 1, "bounds rows hold at least 2 entries, word rows and token_probs at least 1");
+  int64_t n_words_max = n_rows_max;  // a word has at least one row: more words than rows cannot be
+  if (ld_bounds - 1 < n_words_max) n_words_max = ld_bounds - 1;
+  if (ld_words < n_words_max) n_words_max = ld_words;
+  hipLaunchKernelGGL(word_spans_kernel, dim3(B), dim3(WS_THREADS), 0, (hipStream_t)stream, path_text, path_time, (int)ld_path, path_len, bounds,
+                     (long)ld_bounds, n_words, token_probs, (long)n_probs, tok_off, start_frame, end_frame, prob, (long)ld_words, (int)n_words_max,
+                     n_rows_max);
   WFT_CHECK_LAUNCH();
   return WFT_OK;
 }

@@ -1072,9 +1072,14 @@ def timestamp_segments(tokens, prompt_len, lengths, timestamp_begin: int, eot: i
 
 # ============================================================================= word-level timestamps
 # Upstream's `whisper/timing.py: find_alignment`, restated (openai-whisper is not a dependency: parity with its binary is unpinned).
-# Device stages: csrc/align.hip (include/wft.h "Word-level alignment"); the rest is upstream's numpy on the host.  Its string-level
-# post-processing (`merge_punctuations`, the long-word heuristics of `add_word_timestamps`) is not built.
+# Device stages: csrc/align.hip (include/wft.h "Word-level alignment"); the rest is upstream's numpy on the host, or — with
+# word_spans="device" — wft_word_spans.  Upstream's string-level post-processing is restated as pure host functions below
+# `alignment_words`: `merge_punctuations`, `add_word_timestamps` (the long-word clamps, the segment-edge preference) and the
+# anomaly scores of its hallucination filter; engine/transcribe.py calls them per window.
 TOKENS_PER_SECOND = 50  # one cross-attention frame = 20 ms
+PREPEND_PUNCTUATIONS = "\"'“¿([{-"
+APPEND_PUNCTUATIONS = "\"'.。,，!！?？:：”)]}、"
+SENTENCE_END_MARKS = ".。!！?？"
 
 
 def dump_alignment_heads(mask) -> bytes:
@@ -1163,6 +1168,129 @@ def alignment_words(path_text, path_time, word_token_counts, token_probs, text) 
             for s, e, i, j in zip(starts, ends, bounds[:-1], bounds[1:])]
 
 
+def merge_punctuations(words: list, prepended: str = PREPEND_PUNCTUATIONS, appended: str = APPEND_PUNCTUATIONS) -> None:
+    """Upstream's `merge_punctuations`, in place, over word dicts {"word", "tokens", ...}: times and probabilities are not touched.
+    Backward pass: a word that starts with " " and whose strip() is in `prepended` gives its string and tokens to the front of the
+    word that follows it and is emptied (word "", tokens []).  Forward pass: a word that is in `appended` is added to the end of
+    the word before it — unless that one ends with " " — and is emptied.  Emptied words stay in the list."""
+    i, j = len(words) - 2, len(words) - 1
+    while i >= 0:
+        prev, nxt = words[i], words[j]
+        if prev["word"].startswith(" ") and prev["word"].strip() in prepended:
+            nxt["word"] = prev["word"] + nxt["word"]
+            nxt["tokens"] = prev["tokens"] + nxt["tokens"]
+            prev["word"], prev["tokens"] = "", []
+        else:
+            j = i
+        i -= 1
+    i, j = 0, 1
+    while j < len(words):
+        prev, nxt = words[i], words[j]
+        if not prev["word"].endswith(" ") and nxt["word"] in appended:
+            prev["word"] = prev["word"] + nxt["word"]
+            prev["tokens"] = prev["tokens"] + nxt["tokens"]
+            nxt["word"], nxt["tokens"] = "", []
+        else:
+            i = j
+        j += 1
+
+
+def add_word_timestamps(segments: list, alignment: list, *, time_offset: float, last_speech_timestamp: float, eot: Optional[int] = None,
+                        prepend_punctuations: str = PREPEND_PUNCTUATIONS, append_punctuations: str = APPEND_PUNCTUATIONS) -> float:
+    """Upstream's `add_word_timestamps` behind its `find_alignment` call, for the segments of ONE window -> last_speech_timestamp.
+
+    alignment: the words of the window in order, dicts {"word": str, "tokens": [ids], "start", "end", "probability"} with times in
+    seconds from the start of the window — `find_alignment` over the concatenated text tokens (ids < eot) of the segments, joined
+    with the strings of `split_words`.  It is edited in place.  A segment's text tokens are its ids below `eot` (None: all of them).
+      1. durations = end - start of the words where that is not zero; median = min(0.7, median(durations)), 0.0 without any;
+         max_duration = 2 * median.
+      2. With durations, for i >= 1 and end - start > max_duration: a word that is a sentence mark (".。!！?？") keeps its start,
+         end = start + max_duration; else, if word i - 1 is one, start = end - max_duration.
+      3. `merge_punctuations`.
+      4. Per segment, words are taken until the taken tokens reach the segment's text-token count; a taken word with a non-empty
+         string is kept as {"word", "tokens", "start": round(time_offset + start, 2), "end": round(time_offset + end, 2),
+         "probability"}.  For a segment with words w0 .. wl, in this order:
+         (a) after a pause — w0.end - last_speech_timestamp > 4 * median — with w0 longer than max_duration, or w0 and w1 together
+             longer than 2 * max_duration: if w1 is longer than max_duration, w0.end = w1.start = max(w1.end / 2, w1.end -
+             max_duration); then w0.start = max(0, w0.end - max_duration);
+         (b) seg.start < w0.end and seg.start - 0.5 > w0.start: w0.start = max(0, min(w0.end - median, seg.start)); otherwise
+             seg.start = w0.start;
+         (c) seg.end > wl.start and seg.end + 0.5 < wl.end: wl.end = max(wl.start + median, seg.end); otherwise seg.end = wl.end;
+         (d) last_speech_timestamp = seg.end.
+      Every segment gets seg["words"]."""
+    import numpy as np
+
+    if not segments:
+        return last_speech_timestamp
+    durations = np.array([w["end"] - w["start"] for w in alignment], dtype=np.float64)
+    durations = durations[durations.nonzero()]
+    median = min(0.7, float(np.median(durations))) if len(durations) else 0.0
+    max_duration = median * 2
+    if len(durations):
+        for i in range(1, len(alignment)):
+            w = alignment[i]
+            if w["end"] - w["start"] > max_duration:
+                if w["word"] in SENTENCE_END_MARKS:
+                    w["end"] = w["start"] + max_duration
+                elif alignment[i - 1]["word"] in SENTENCE_END_MARKS:
+                    w["start"] = w["end"] - max_duration
+    merge_punctuations(alignment, prepend_punctuations, append_punctuations)
+    at = 0
+    for seg in segments:
+        n_text = sum(1 for t in seg["tokens"] if eot is None or t < eot)
+        saved, words = 0, []
+        while at < len(alignment) and saved < n_text:
+            w = alignment[at]
+            if w["word"]:
+                words.append({"word": w["word"], "tokens": list(w["tokens"]), "start": round(time_offset + w["start"], 2),
+                              "end": round(time_offset + w["end"], 2), "probability": w["probability"]})
+            saved += len(w["tokens"])
+            at += 1
+        if words:
+            if words[0]["end"] - last_speech_timestamp > median * 4 and (
+                    words[0]["end"] - words[0]["start"] > max_duration
+                    or (len(words) > 1 and words[1]["end"] - words[0]["start"] > max_duration * 2)):
+                if len(words) > 1 and words[1]["end"] - words[1]["start"] > max_duration:
+                    boundary = max(words[1]["end"] / 2, words[1]["end"] - max_duration)
+                    words[0]["end"] = words[1]["start"] = boundary
+                words[0]["start"] = max(0, words[0]["end"] - max_duration)
+            if seg["start"] < words[0]["end"] and seg["start"] - 0.5 > words[0]["start"]:
+                words[0]["start"] = max(0, min(words[0]["end"] - median, seg["start"]))
+            else:
+                seg["start"] = words[0]["start"]
+            if seg["end"] > words[-1]["start"] and seg["end"] + 0.5 < words[-1]["end"]:
+                words[-1]["end"] = max(words[-1]["start"] + median, seg["end"])
+            else:
+                seg["end"] = words[-1]["end"]
+            last_speech_timestamp = seg["end"]
+        seg["words"] = words
+    return last_speech_timestamp
+
+
+def word_anomaly_score(word: dict) -> float:
+    """Upstream's `word_anomaly_score`: 1.0 for a probability below 0.15, (0.133 - d) * 15 for a duration d = end - start below
+    0.133 s, d - 2.0 for one above 2.0 s."""
+    d = word["end"] - word["start"]
+    score = 0.0
+    if word.get("probability", 0.0) < 0.15:
+        score += 1.0
+    if d < 0.133:
+        score += (0.133 - d) * 15
+    if d > 2.0:
+        score += d - 2.0
+    return score
+
+
+def is_segment_anomaly(segment: Optional[dict]) -> bool:
+    """Upstream's `is_segment_anomaly`: over the first 8 words of the segment that are not punctuation marks, the summed
+    `word_anomaly_score` is >= 3, or (to 0.01) at least the number of those words.  None, or a segment without words: False."""
+    if segment is None or not segment.get("words"):
+        return False
+    words = [w for w in segment["words"] if w["word"] not in PREPEND_PUNCTUATIONS + APPEND_PUNCTUATIONS][:8]
+    score = sum(word_anomaly_score(w) for w in words)
+    return score >= 3 or score + 0.01 >= len(words)
+
+
 def alignment_slots(model, device) -> tuple:
     """model.alignment_heads -> ({cross_attn module: (heads i32 on the device, first slice)}, n_sel): the heads of a layer in the
     buffer's order, the layers in ascending order — the order of upstream's `alignment_heads.indices().T`."""
@@ -1184,7 +1312,8 @@ def alignment_slots(model, device) -> tuple:
 
 @torch.no_grad()
 def find_alignment(model, mel: torch.Tensor, text_tokens, *, sot_sequence: Sequence[int], no_timestamps: int, eot: int, num_frames,
-                   word_token_counts=None, medfilt_width: int = 7, qk_scale: float = 1.0, return_debug: bool = False):
+                   word_token_counts=None, medfilt_width: int = 7, qk_scale: float = 1.0, return_debug: bool = False, word_spans: str = "host",
+                   _xa=None):
     """Word-level timestamps for already-decoded text -> per audio [(start_s, end_s, probability, [token ids])].
 
     mel f32 [B, n_mels, 2 * n_audio_ctx]; text_tokens: one list of text token ids (< eot) per audio, ragged; num_frames: the mel
@@ -1195,11 +1324,21 @@ def find_alignment(model, mel: torch.Tensor, text_tokens, *, sot_sequence: Seque
     wft_align_matrix, wft_dtw_f32 on rows len(sot_sequence) .. of the matrix, the paths to the host, `alignment_words` there.  A
     word's probability is the mean over its tokens of softmax(logits[:eot]) at the token's position (wft_token_stats with V = eot).
     An audio with no text gives [].  return_debug adds a dict: "q" / "k" (per captured module, the views the kernel read), "probs",
-    "matrix", "paths", "n_tok", "n_key", "rows" (the audios that ran), "token_probs".  Call it in eval mode; the fp32 compute mode raises."""
+    "matrix", "paths", "n_tok", "n_key", "rows" (the audios that ran), "token_probs".  Call it in eval mode; the fp32 compute mode raises.
+
+    word_spans="device": the paths and the token probabilities stay on the device, wft_word_spans forms the boundary frames and the
+    mean probabilities of all audios in one launch, and only those three word arrays come to the host; times are frame /
+    TOKENS_PER_SECOND in Python floats, exactly as `alignment_words` forms them, and the probability is the kernel's fp32 mean (the
+    host path takes it in float64: the two differ by rounding only).  `_xa`: the encoder output of `mel`, [B, n_audio_ctx, d],
+    when the caller has it already — `embed_audio` is not called and `mel` is not read then, it may be None (engine/transcribe.py
+    aligns the window it has just decoded).
+    The string-level rules on top of the words are `merge_punctuations` and `add_word_timestamps` above."""
     if getattr(model, "compute_dtype", "bf16") != "bf16":
         raise NotImplementedError("find_alignment runs in the bf16 compute mode only: the alignment kernels (csrc/align.hip) read bf16 q / k; "
                                   "call model.set_compute_dtype('bf16')")
-    B = mel.shape[0]
+    if word_spans not in ("host", "device"):
+        raise ValueError(f"word_spans must be 'host' or 'device', got {word_spans!r}")
+    B = mel.shape[0] if _xa is None else _xa.shape[0]
     texts = [[int(t) for t in row] for row in text_tokens]
     if len(texts) != B:
         raise ValueError(f"text_tokens holds {len(texts)} rows for {B} audios")
@@ -1234,8 +1373,13 @@ def find_alignment(model, mel: torch.Tensor, text_tokens, *, sot_sequence: Seque
     slots, n_sel = alignment_slots(model, dev)
     probs = torch.zeros((n, n_sel, T, Ta), dtype=torch.float32, device=dev)
     cap = AlignCapture(slots, probs, n_tok, n_key, (lens, keys), 64 ** -0.5 * float(qk_scale), return_debug)
-    mel = mel.to(dev)
-    xa = model.embed_audio(mel if n == B else mel[torch.tensor(rows, device=dev)])
+    if _xa is None:
+        mel = mel.to(dev)
+        xa = model.embed_audio(mel if n == B else mel[torch.tensor(rows, device=dev)])
+    else:
+        if mel is not None and mel.shape[0] != B:
+            raise ValueError(f"_xa holds {B} rows, mel {mel.shape[0]}")
+        xa = _xa if n == B else _xa[torch.tensor(rows, device=_xa.device)]
     with capture_alignment(cap):
         h = model.decoder.hidden(tokens, xa)  # [n, T, d]
     matrix = K.align_matrix(probs, n_tok, n_key, medfilt_width, host_lens=(lens, keys))
@@ -1246,15 +1390,40 @@ def find_alignment(model, mel: torch.Tensor, text_tokens, *, sot_sequence: Seque
     tgt = torch.tensor([t for b in rows for t in texts[b]], dtype=torch.int64, device=dev)
     logits = model.decoder.padded_logits(h.reshape(n * T, -1).index_select(0, pos).view(pos.numel(), 1, -1))
     stats, _ = K.token_stats(logits, tgt, eot)
-    token_probs = torch.exp(stats[:, 3] - stats[:, 0]).cpu().tolist()
-    pt, pj, pl = (t.cpu() for t in paths)
-    at = 0
-    for i, b in enumerate(rows):
-        L_ = int(pl[i])
-        tp = token_probs[at:at + len(texts[b])]
-        at += len(texts[b])
-        wc = counts[b] if counts[b] is not None else [1] * (len(texts[b]) + 1)
-        result[b] = alignment_words(pt[i, :L_].numpy(), pj[i, :L_].numpy(), wc, tp, texts[b])
+    if word_spans == "device":
+        probs_dev = torch.exp(stats[:, 3] - stats[:, 0]).contiguous()
+        wcs = [[int(c) for c in counts[b]] if counts[b] is not None else [1] * (len(texts[b]) + 1) for b in rows]
+        for wc, b in zip(wcs, rows):
+            if len(wc) > 1 and (sum(wc) != len(texts[b]) + 1 or min(wc) < 1):
+                raise ValueError(f"word_token_counts {wc} must be positive and sum to len(text) + 1 = {len(texts[b]) + 1}")
+        nw = [max(len(wc) - 1, 0) for wc in wcs]
+        bounds = torch.zeros((n, max(nw) + 1 if max(nw) else 2), dtype=torch.int32)
+        offs, at = [], 0
+        for i, (wc, b) in enumerate(zip(wcs, rows)):
+            if nw[i]:
+                bounds[i, 1:nw[i] + 1] = torch.cumsum(torch.tensor(wc[:-1], dtype=torch.int32), 0)
+            offs.append(at)
+            at += len(texts[b])
+        sf, ef, pr = K.word_spans(paths, bounds.to(dev), torch.tensor(nw, dtype=torch.int32, device=dev), probs_dev,
+                                  torch.tensor(offs, dtype=torch.int32, device=dev), max(n_rows), host_lens=(nw,))
+        sf, ef, pr = sf.cpu().tolist(), ef.cpu().tolist(), pr.cpu().tolist()
+        for i, b in enumerate(rows):
+            bd = bounds[i].tolist()
+            result[b] = [(sf[i][w] / TOKENS_PER_SECOND, ef[i][w] / TOKENS_PER_SECOND, pr[i][w], texts[b][bd[w]:bd[w + 1]]) for w in range(nw[i])]
+        if not return_debug:
+            return result
+        token_probs = probs_dev.cpu().tolist()
+        pt, pj, pl = (t.cpu() for t in paths)
+    else:
+        token_probs = torch.exp(stats[:, 3] - stats[:, 0]).cpu().tolist()
+        pt, pj, pl = (t.cpu() for t in paths)
+        at = 0
+        for i, b in enumerate(rows):
+            L_ = int(pl[i])
+            tp = token_probs[at:at + len(texts[b])]
+            at += len(texts[b])
+            wc = counts[b] if counts[b] is not None else [1] * (len(texts[b]) + 1)
+            result[b] = alignment_words(pt[i, :L_].numpy(), pj[i, :L_].numpy(), wc, tp, texts[b])
     if not return_debug:
         return result
     debug = {"q": {m: v[0] for m, v in cap.views.items()}, "k": {m: v[1] for m, v in cap.views.items()}, "probs": probs, "matrix": matrix,

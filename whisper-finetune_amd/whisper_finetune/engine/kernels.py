@@ -925,6 +925,40 @@ def dtw(matrix, row0: int, n_rows, n_cols, *, host_lens, negate: bool = True, pa
     return pt, pj, pl
 
 
+def word_spans(paths, bounds, n_words, token_probs, tok_off, n_rows_max: int, *, host_lens, out=None):
+    """Word boundary frames and mean token probabilities from DTW paths that stay on the device (wft_word_spans).  paths =
+    (path_text, path_time, path_len) as `dtw` returns them; bounds i32 [B, ld_bounds] (bounds[b, w] = the path row at which word w
+    starts, n_words[b] + 1 entries per audio); n_words, tok_off i32 [B]; token_probs f32 1-D, packed over the audios; n_rows_max:
+    the `n_rows_max` of the dtw call (1..448); host_lens = (n_words on the host,) -> (start_frame i32, end_frame i32, prob f32),
+    each [B, ld_bounds - 1]; elements at w >= n_words[b], and every element of an audio with an empty path, keep what `out` =
+    (start_frame, end_frame, prob) held (fresh buffers: -1, -1, 0)."""
+    pt, pj, pl = paths
+    _chk(pt, torch.int32, "path_text"); _chk(pj, torch.int32, "path_time"); _chk(bounds, torch.int32, "bounds"); _chk(token_probs, F32, "token_probs")
+    if pt.dim() != 2 or pt.shape != pj.shape or pt.shape[1] < 1 or not pt.is_contiguous() or not pj.is_contiguous():
+        raise ValueError("word_spans: path_text / path_time must be contiguous i32 [B, ld >= 1] of one shape")
+    B = pt.shape[0]
+    if bounds.dim() != 2 or bounds.shape[0] != B or bounds.shape[1] < 2 or not bounds.is_contiguous():
+        raise ValueError(f"word_spans: bounds must be contiguous i32 [{B}, >= 2]")
+    if token_probs.dim() != 1 or token_probs.numel() < 1 or not token_probs.is_contiguous():
+        raise ValueError("word_spans: token_probs must be a contiguous f32 vector with at least one element")
+    _chk_flag(pl, B, "path_len"); _chk_flag(n_words, B, "n_words"); _chk_flag(tok_off, B, "tok_off")
+    n_rows_max = int(n_rows_max)
+    if not 1 <= n_rows_max <= 448:
+        raise ValueError(f"word_spans: n_rows_max must lie in 1..448, got {n_rows_max}")
+    ld = bounds.shape[1] - 1
+    _host_lens(host_lens[0], B, min(ld, n_rows_max), "n_words")
+    if out is None:
+        out = (torch.full((B, ld), -1, dtype=torch.int32, device=pt.device), torch.full((B, ld), -1, dtype=torch.int32, device=pt.device),
+               torch.zeros((B, ld), dtype=F32, device=pt.device))
+    sf, ef, pr = out
+    _chk(sf, torch.int32, "start_frame"); _chk(ef, torch.int32, "end_frame"); _chk(pr, F32, "prob")
+    if any(tuple(t.shape) != (B, ld) or not t.is_contiguous() for t in (sf, ef, pr)):
+        raise ValueError(f"word_spans: start_frame / end_frame / prob must be contiguous [{B}, {ld}]")
+    L.check(L.load().wft_word_spans(_p(pt), _p(pj), pt.stride(0), _p(pl), _p(bounds), bounds.stride(0), _p(n_words), _p(token_probs),
+                                    token_probs.numel(), _p(tok_off), _p(sf), _p(ef), _p(pr), ld, B, n_rows_max, L.stream_ptr()), "wft_word_spans")
+    return sf, ef, pr
+
+
 # --------------------------------------------------------------------------- language detection / long-form windows (csrc/transcribe.hip)
 def lang_probs(logits, V: int, lang_ids):
     """Softmax and argmax over the language columns (wft_lang_probs; include/wft.h "Language detection and long-form windows").

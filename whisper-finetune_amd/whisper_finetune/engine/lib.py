@@ -218,6 +218,7 @@ SIGNATURES = {
     "wft_dtw_workspace_bytes": [C.c_int, C.c_int, C.c_int],
     "wft_dtw_f32": [c_vp, c_i64, c_i64, C.c_int, C.c_int, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_vp, c_vp, c_i64, c_vp, c_vp,
                     c_i64, c_vp],
+    "wft_word_spans": [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_int, C.c_int, c_vp],
     "wft_lang_probs": [c_vp, c_i64, c_i64, c_vp, C.c_int, c_vp, c_i64, c_vp, C.c_int, c_vp],
     "wft_mel_windows": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_vp],
     "wft_embed_fwd": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, C.c_int, c_i64, c_vp],

@@ -10,10 +10,16 @@ detect_language, `wft_mel_windows` cuts one zero-padded 30 s window per batch ro
 itself is `wft_logmel` over the whole recording (`long_logmel`).  Everything else of a window is `decode_with_fallback`.
 
 Several recordings advance side by side in ONE batch (upstream handles one at a time); `transcribe` states the batching rule.
-The seek arithmetic (`advance_window`) and the previous-text prompt (`window_prompt`) are pure host functions.
+The seek arithmetic (`advance_window`, and `word_seek` on top of it) and the previous-text prompt (`window_prompt`) are pure host
+functions.
 
-Not built: `word_timestamps=True` inside the loop (call `find_alignment` on a segment's window yourself),
-`hallucination_silence_threshold`, `clip_timestamps`, `carry_initial_prompt`, the fp32 compute mode.
+`word_timestamps=True`: every iteration aligns the windows it has just decoded — ONE `find_alignment` call per distinct sot sequence
+over the rows that have segments, on the encoder output the decoders used, with the word spans formed on the device
+(csrc/align.hip `wft_word_spans`) — then upstream's string rules (engine/decode.py `add_word_timestamps`), its seek-to-the-last-word
+rule and, with `hallucination_silence_threshold`, its hallucination filter (`word_seek`).  Strings come from the caller's
+`split_words`; ids go in and ids come out as before.
+
+Not built: `clip_timestamps`, `carry_initial_prompt`, a tokenizer, the fp32 compute mode.
 """
 from __future__ import annotations
 
@@ -48,7 +54,7 @@ def window_prompt(all_tokens: Sequence[int], prompt_reset_since: int, sot_sequen
 
 
 def advance_window(tokens: Sequence[int], *, seek: int, segment_size: int, timestamp_begin: Optional[int], input_stride: int = 2,
-                   time_precision: float = 0.02, frame_s: float = 0.01):
+                   time_precision: float = 0.02, frame_s: float = 0.01, return_single_ending: bool = False):
     """Upstream's segment split and seek rule for the decoded tokens of ONE window -> (segments, new_seek).
 
     tokens: the generated ids before the eot, timestamps included.  A segment is {"seek", "start", "end", "tokens"}, times in
@@ -62,7 +68,8 @@ def advance_window(tokens: Sequence[int], *, seek: int, segment_size: int, times
         row exists and is not timestamp_begin itself, for that timestamp's time; new_seek = seek + segment_size.
     timestamp_begin None (upstream's without_timestamps): no id is a timestamp, the second branch always applies.
     Deviation from upstream, stated: if new_seek == seek (a window that closes at <|0.00|>) the window is stepped over whole,
-    new_seek = seek + segment_size — upstream would decode the same window forever."""
+    new_seek = seek + segment_size — upstream would decode the same window forever.
+    return_single_ending: -> (segments, new_seek, single_ending), for the word-timestamp seek rule of `transcribe`."""
     toks = [int(t) for t in tokens]
     seek, size = int(seek), int(segment_size)
     if size < 1:
@@ -92,7 +99,7 @@ def advance_window(tokens: Sequence[int], *, seek: int, segment_size: int, times
         new_seek = seek + size
     if new_seek == seek:
         new_seek = seek + size
-    return segments, new_seek
+    return (segments, new_seek, single_ending) if return_single_ending else (segments, new_seek)
 
 
 # ============================================================================= the long log-mel
@@ -195,6 +202,90 @@ def _to_list(v):
     return v.tolist() if hasattr(v, "tolist") else list(v)
 
 
+def get_end(segments: Sequence[dict]) -> Optional[float]:
+    """Upstream's `get_end`: the end of the last word of the segments, else the last segment's end; None without segments."""
+    for seg in reversed(segments):
+        if seg.get("words"):
+            return seg["words"][-1]["end"]
+    return segments[-1]["end"] if segments else None
+
+
+def _next_words_segment(segments: Sequence[dict]) -> Optional[dict]:
+    return next((s for s in segments if s.get("words")), None)
+
+
+def word_seek(segments: list, *, seek: int, new_seek: int, segment_size: int, single_ending: bool, content_frames: int,
+              last_speech_timestamp: float, threshold: Optional[float], frame_s: float = 0.01):
+    """Upstream's seek rules of a window whose segments carry `words` (after `add_word_timestamps`) -> (new_seek, segments).
+
+    seek: the frame the window started at; new_seek: what `advance_window` gave.  With time_offset = seek * frame_s:
+      * not single_ending and get_end(segments) > time_offset: new_seek = round(get_end / frame_s) — the window did not close on a
+        timestamp of its own, so the next one starts where the last word ends;
+      * threshold (hallucination_silence_threshold) set: in that same case new_seek stays at the last word end only if the window
+        goes on for more than `threshold` seconds behind it, otherwise it is seek + segment_size; if the first segment with words
+        is anomalous (`is_segment_anomaly`) and starts more than `threshold` behind time_offset, new_seek = seek + round(gap /
+        frame_s) and the window emits nothing: (new_seek, None); otherwise the first anomalous segment with silence before and
+        after it (transcribe's docstring has the two tests) is dropped together with everything behind it, new_seek =
+        round(max(time_offset + 1, its start) / frame_s), or content_frames if less than `threshold` of content is left behind it."""
+    time_offset = seek * frame_s
+    per_second = round(1.0 / frame_s)
+    if not single_ending:
+        end = get_end(segments)
+        if end is not None and end > time_offset:
+            new_seek = round(end * per_second)
+    if threshold is None:
+        return new_seek, segments
+    window_end = (seek + N_FRAMES) * frame_s
+    if not single_ending:
+        end = get_end(segments)
+        if end is not None and end > time_offset:
+            new_seek = round(end * per_second) if window_end - end > threshold else seek + segment_size
+    first = _next_words_segment(segments)
+    if first is not None and D.is_segment_anomaly(first):
+        gap = first["start"] - time_offset
+        if gap > threshold:
+            return seek + round(gap * per_second), None
+    hal_last_end = last_speech_timestamp
+    for si, seg in enumerate(segments):
+        if not seg["words"]:
+            continue
+        if D.is_segment_anomaly(seg):
+            nxt = _next_words_segment(segments[si + 1:])
+            next_start = nxt["words"][0]["start"] if nxt is not None else time_offset + segment_size * frame_s
+            silence_before = seg["start"] - hal_last_end > threshold or seg["start"] < threshold or seg["start"] - time_offset < 2.0
+            silence_after = next_start - seg["end"] > threshold or D.is_segment_anomaly(nxt) or window_end - seg["end"] < 2.0
+            if silence_before and silence_after:
+                new_seek = round(max(time_offset + 1, seg["start"]) * per_second)
+                if content_frames * frame_s - seg["end"] < threshold:
+                    new_seek = content_frames
+                return new_seek, segments[:si]
+        hal_last_end = seg["end"]
+    return new_seek, segments
+
+
+def _align_windows(model, align, mel, xa, windows: dict, sots: list, split_words, eot: int, no_timestamps: int) -> dict:
+    """The alignment pass of one iteration -> {batch row: the window's words, dicts for `add_word_timestamps`}.  One `align` call
+    per distinct sot sequence over the rows of `windows` that have a text token; a row without one gets []."""
+    texts = {j: [t for seg in w[0] for t in seg["tokens"] if t < eot] for j, w in windows.items()}
+    out = {j: [] for j in windows}
+    groups = {}
+    for j in windows:
+        if texts[j]:
+            groups.setdefault(tuple(sots[j]), []).append(j)
+    for sot, js in groups.items():
+        split = [split_words(texts[j] + [eot]) for j in js]
+        whole = mel is None or len(js) == mel.shape[0]
+        sel = None if whole else torch.tensor(js, device=mel.device)
+        found = align(model, mel if whole else mel[sel], [texts[j] for j in js], sot_sequence=list(sot), no_timestamps=no_timestamps, eot=eot,
+                      num_frames=[max(2, windows[j][2]) for j in js],  # (a last window of one frame still has one key)
+                      word_token_counts=[[len(t) for t in s[1]] for s in split], word_spans="device",
+                      _xa=xa if whole else xa[sel])
+        for j, (strings, _), words in zip(js, split, found):
+            out[j] = [{"word": s, "tokens": list(ids), "start": start, "end": end, "probability": p}
+                      for s, (start, end, p, ids) in zip(strings[:-1], words)]
+    return out
+
+
 @torch.no_grad()
 def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
                language_tokens: Optional[Sequence[int]] = None, sot_prev: Optional[int] = None, initial_prompt: Optional[Sequence[int]] = None,
@@ -203,7 +294,10 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
                length_penalty: Optional[float] = None, logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
                compression_ratio_threshold: Optional[float] = None, no_speech: Optional[int] = None, seed: int = 0, suppress: Sequence[int] = (),
                suppress_first: Sequence[int] = (), max_initial_timestamp_index: Optional[int] = 50, sync_every: int = 8, step: str = "eager",
-               filters: Optional[torch.Tensor] = None, sample_rate=SAMPLE_RATE, _decode=None, _detect=None, _frames: Optional[Sequence[int]] = None) -> list:
+               filters: Optional[torch.Tensor] = None, sample_rate=SAMPLE_RATE, word_timestamps: bool = False, split_words=None,
+               prepend_punctuations: str = D.PREPEND_PUNCTUATIONS, append_punctuations: str = D.APPEND_PUNCTUATIONS,
+               hallucination_silence_threshold: Optional[float] = None, _decode=None, _detect=None, _align=None,
+               _frames: Optional[Sequence[int]] = None) -> list:
     """Upstream's `transcribe()` over one recording or a list of them -> one dict per recording, in input order:
       "language": the detected language token id (None without `language_tokens`), "language_probs": f32 [n_lang] or None,
       "segments": [{"seek", "start", "end", "tokens", "temperature", "avg_logprob", "compression_ratio", "no_speech_prob"}],
@@ -244,8 +338,37 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
     than sample_len tokens.  (2) The zero-advance guard of `advance_window`.  (3) Recordings share batches, so a window's bits can
     depend on its batch partners through the GEMM shapes; replaying the same batches gives the same bits.  (4) Without
     `text_of` no compression ratio exists and the blank-text rule is off.  A recording shorter than one frame decodes nothing.
-    The fp32 compute mode raises NotImplementedError.  (`_decode`, `_detect`, `_frames`: stand-ins for decode_with_fallback,
-    detect_language and the content frames — the host tests drive the loop through them without a device.)"""
+    The fp32 compute mode raises NotImplementedError.  (`_decode`, `_detect`, `_align`, `_frames`: stand-ins for
+    decode_with_fallback, detect_language, find_alignment and the content frames — the host tests drive the loop through them
+    without a device.)
+
+    word_timestamps=True (upstream's rules restated; parity with its binary is unpinned) needs `split_words`: ids + [eot] ->
+    (words, word_tokens), the tokenizer's `split_to_word_tokens` — one string and one id list per word, the eot last — plus
+    `timestamp_begin` and `no_timestamps`; `hallucination_silence_threshold` needs word_timestamps; each raises ValueError
+    otherwise.  With word_timestamps=False nothing runs differently.  With it, per iteration:
+      * the encoder runs once, xa = model.encoder(mel); the decode call and the alignment call both get `_xa=xa`;
+      * behind the silence skip and `advance_window` of every row, ONE `find_alignment(word_spans="device")` call per distinct
+        sot sequence (after language detection usually one) covers the rows that have a text token: num_frames = the row's
+        segment_size, text_tokens = the ids below eot of the row's segments concatenated, word_token_counts from `split_words`;
+        a row without a text token gets words = [] on all its segments;
+      * then per row, in upstream's order: (1) `add_word_timestamps` with time_offset = seek * 0.01 and the recording's running
+        last_speech_timestamp (0.0 at first), which gives every segment its "words": [{"word", "tokens", "start", "end",
+        "probability"}] and may move the segment's start and end; (2) if the window did not end on a single timestamp and the
+        end of its last word (`get_end`: else of its last segment) is > time_offset, seek = round(that end * 100); (3) with a
+        threshold, the hallucination rules of `word_seek`: that seek stays only if the window goes on for more than the
+        threshold behind the last word, else seek = previous seek + segment_size; an anomalous first segment
+        (`is_segment_anomaly`) more than the threshold behind the window start moves seek to previous seek + round(gap * 100)
+        and the window emits nothing; otherwise the first anomalous segment with silence_before = seg.start - hal_last_end >
+        threshold or seg.start < threshold or seg.start - time_offset < 2.0 and silence_after = next_start - seg.end > threshold
+        or the next segment with words is anomalous or window_end - seg.end < 2.0 is dropped with all later segments, seek =
+        round(max(time_offset + 1, seg.start) * 100), or content_frames if content_duration - seg.end < threshold (hal_last_end:
+        the end of the segment with words before it, first last_speech_timestamp; next_start: the first word start of the next
+        segment with words, else the end of the window's content; window_end = (previous seek + 3000) * 0.01);
+        (4) last_speech_timestamp = `get_end` of what is left; (5) the blank-segment cleanup also empties "words".
+      The zero-advance guard holds behind all of it: a seek that did not move goes to previous seek + segment_size.
+    Deviation (5): one alignment call covers the rows of a batch, so a window's word times and probabilities can depend on its
+    batch partners through the GEMM shapes, as for decoding; replaying the same batches gives the same bits.  As upstream,
+    `add_word_timestamps` does not hand its own last_speech_timestamp back to the loop: only step (4) moves the running value."""
     _check_mode(model, "transcribe")
     single = isinstance(audio, torch.Tensor) and audio.dim() == 1 or (not isinstance(audio, (list, tuple)) and getattr(audio, "ndim", 0) == 1)
     audios = [audio] if single else list(audio)
@@ -279,8 +402,17 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
             raise ValueError(f"sample_rate: one rate, or one per recording ({n}), got {len(rates)}")
     else:
         rates = [check_rate(sample_rate)] * n
+    if word_timestamps:
+        if split_words is None:
+            raise ValueError("word_timestamps needs split_words (ids + [eot] -> (words, word_tokens)): the tokenizer's split_to_word_tokens")
+        if timestamp_begin is None or no_timestamps is None:
+            raise ValueError("word_timestamps needs timestamp_begin and no_timestamps: the alignment pass runs behind the no-timestamps token")
+    elif hallucination_silence_threshold is not None:
+        raise ValueError("hallucination_silence_threshold needs word_timestamps=True: the rule reads the word times")
     decode = D.decode_with_fallback if _decode is None else _decode
     detect = detect_language if _detect is None else _detect
+    align = D.find_alignment if _align is None else _align
+    last_speech = [0.0] * n
 
     packed = None
     if _frames is None:
@@ -332,27 +464,55 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
                 prompt[j, :len(p)] = torch.tensor(p, dtype=torch.int64)
             plen = [len(p) for p, _ in prompts]
             kw = dict(shared, sot_index=[s for _, s in prompts], seed=seed + i, max_len=min(n_ctx, width + sample_len))
+            if word_timestamps and xa is None and packed is not None:
+                xa = model.encoder(mel)
             if xa is not None:
                 kw["_xa"] = xa
             toks, lens, _, info = decode(model, mel, prompt if mel is None else prompt.to(mel.device), torch.tensor(plen), **kw)
             toks, lens = _to_list(toks), _to_list(lens)
+            windows = {}  # batch row j -> (segments, seek before, segment_size, single_ending) of a row that was not skipped
             for j, a in enumerate(rows):
                 ids, _ = D.generated_ids(toks[j], plen[j], lens[j], eot)
                 size = min(N_FRAMES, frames[a] - seek[a])
-                res = results[a]
-                res["windows"] += 1
-                nsp, alp, temp = info["no_speech_prob"][j], info["avg_logprob"][j], info["temperature"][j]
+                results[a]["windows"] += 1
+                nsp, alp = info["no_speech_prob"][j], info["avg_logprob"][j]
                 skip = no_speech_threshold is not None and nsp is not None and nsp > no_speech_threshold
                 if skip and logprob_threshold is not None and alp > logprob_threshold:
                     skip = False
                 if skip:
                     seek[a] += size
                     continue
-                segments, seek[a] = advance_window(ids, seek=seek[a], segment_size=size, timestamp_begin=timestamp_begin)
+                before = seek[a]
+                segments, seek[a], single = advance_window(ids, seek=before, segment_size=size, timestamp_begin=timestamp_begin,
+                                                           return_single_ending=True)
+                windows[j] = (segments, before, size, single)
+            aligned = _align_windows(model, align, mel, xa, windows, [sots[a] for a in rows], split_words, int(eot), no_timestamps) \
+                if word_timestamps else {}
+            for j, a in enumerate(rows):
+                if j not in windows:
+                    continue
+                segments, before, size, single = windows[j]
+                res = results[a]
+                nsp, alp, temp = info["no_speech_prob"][j], info["avg_logprob"][j], info["temperature"][j]
+                if word_timestamps:
+                    D.add_word_timestamps(segments, aligned[j], time_offset=before * 0.01, last_speech_timestamp=last_speech[a], eot=int(eot),
+                                          prepend_punctuations=prepend_punctuations, append_punctuations=append_punctuations)
+                    seek[a], segments = word_seek(segments, seek=before, new_seek=seek[a], segment_size=size, single_ending=single,
+                                                  content_frames=frames[a], last_speech_timestamp=last_speech[a],
+                                                  threshold=hallucination_silence_threshold)
+                    if seek[a] <= before:  # the zero-advance guard, after every seek rule
+                        seek[a] = before + size
+                    if segments is None:  # an anomalous first segment behind a silence: the window emits nothing
+                        continue
+                    end = get_end(segments)
+                    if end is not None:
+                        last_speech[a] = end
                 for seg in segments:
                     blank = text_of is not None and text_of([t for t in seg["tokens"] if t < int(eot)]).strip() == ""
                     if seg["start"] == seg["end"] or blank:
                         seg["tokens"] = []
+                        if word_timestamps:
+                            seg["words"] = []
                     seg.update(temperature=temp, avg_logprob=alp, compression_ratio=info["compression_ratio"][j], no_speech_prob=nsp)
                     res["segments"].append(seg)
                     res["tokens"].extend(seg["tokens"])

@@ -528,7 +528,11 @@ class Whisper(nn.Module):
         """Word-level timestamps for decoded text (engine/decode.py find_alignment has the keywords; upstream: whisper/timing.py
         find_alignment, restated — parity with the upstream binary is unpinned): the cross-attention probabilities of the
         `alignment_heads`, standardised, median-filtered and averaged, then dynamic time warping, all on the device (csrc/align.hip)
-        -> per audio [(start_s, end_s, probability, [token ids])].  The fp32 compute mode raises."""
+        -> per audio [(start_s, end_s, probability, [token ids])].  word_spans="device" also forms the word boundaries and mean
+        probabilities on the device (wft_word_spans) and reads back the three word arrays only; `_xa`: the encoder output, when the
+        caller has it (`embed_audio` is not called then).  Upstream's string rules on top of the words (`merge_punctuations`,
+        `add_word_timestamps`) are host functions of engine/decode.py; `transcribe(word_timestamps=True)` applies them.  The fp32
+        compute mode raises."""
         return _decode.find_alignment(self, mel, text_tokens, **kw)
 
     def detect_language(self, mel: Tensor, *, sot: int, language_tokens, _xa: Optional[Tensor] = None):
@@ -547,7 +551,12 @@ class Whisper(nn.Module):
         (wft_resample_f32).  The long log-mel once per
         recording, then 30 s windows — cut on the device (wft_mel_windows), decoded with `decode_with_fallback`, advanced by the
         timestamp tokens — with the recordings that are still running batched side by side -> one dict per recording
-        ("language", "language_probs", "segments", "tokens", "windows", "truncated").  The fp32 compute mode raises."""
+        ("language", "language_probs", "segments", "tokens", "windows", "truncated").  `word_timestamps=True` with `split_words=`
+        (ids + [eot] -> (words, word_tokens): the tokenizer's split_to_word_tokens) gives every segment "words" — one
+        `find_alignment(word_spans="device")` call per iteration on the encoder output the decoders used, upstream's
+        `add_word_timestamps` rules, its seek to the end of the last word when a window does not end on a single timestamp, and
+        with `hallucination_silence_threshold=` its hallucination filter (parity with the upstream binary is unpinned here too).
+        Not built: `clip_timestamps`, `carry_initial_prompt`, a tokenizer.  The fp32 compute mode raises."""
         from . import transcribe as _transcribe
 
         return _transcribe.transcribe(self, audio, **kw)
