@@ -100,6 +100,16 @@ int wft_lora_refresh_mt(const void* tab, const int32_t* tile_start, int n, int t
  * (disjoint ranges).  The host mirror uses it to restack the bias vectors of every fused q/k/v group after an optimizer step
  * (whisper.model.Linear biases: the GEMM epilogue reads ONE bias vector per fused group). */
 int wft_mt_copy_f32(const void* tab, int n, void* stream);
+/* Per-row (output channel) symmetric int8 image of a bf16 shadow, the weight operand of wft_gemm_nt_stream_q8.  W bf16 [rows, cols]
+ * (ldw), Q int8 [rows, cols] (ldq), scale f32 [rows].  Per row, in f32, every operation correctly rounded and none fused:
+ *   amax  = max_k |w[k]|
+ *   scale = amax / 127.0f
+ *   inv   = amax > 0 ? 127.0f / amax : 0.0f
+ *   q[k]  = clamp(rintf(w[k] * inv), -127, 127)        (rintf: round half to even)
+ * so a numpy float32 restatement gives the same bytes (tests/_q8_cases.py).  An all-zero row (the padding rows of a shadow) gives
+ * scale = 0 and q = 0.  cols % 64 == 0, ldw % 8 == 0, ldq % 16 == 0, W and Q 16-byte aligned.  Runs once per shadow refresh.       */
+int wft_quantize_rows_i8(const wft_bf16* W, int64_t rows, int64_t cols, int64_t ldw, int8_t* Q, int64_t ldq, float* scale,
+                         void* stream);
 /* y[i] = a[i] + b[i] (bf16) — gradient accumulation on the residual stream. */
 int wft_add_bf16(const wft_bf16* a, const wft_bf16* b, wft_bf16* y, int64_t n, void* stream);
 /* out = a*x + b*y over n bf16 elements (y may be NULL).  StochasticDepthMixin's train-time rescale
@@ -305,6 +315,19 @@ int64_t wft_gemm_nt_aux8_bytes(const wft_gemm_args* args);
 int wft_gemm_nt_stream_bf16(const wft_gemm_args* args, void* stream);
 int wft_gemm_nt_stream_ok(const wft_gemm_args* args);
 int64_t wft_gemm_nt_stream_workspace_bytes(const wft_gemm_args* args);
+/* Weight-only int8 twin of wft_gemm_nt_stream_bf16 for the same cached steps (CTranslate2's int8 deployment of a fine-tuned checkpoint is
+ * what it stands next to; activations stay bf16 here):
+ *   C[m][n] = bf16( epi( b_scale[n] * sum_k A[m][k] * Q[n][k] + bias[n] ) + residual[m][n] )
+ * args->B points at int8, row-major [N, K], ldb in elements with ldb % 16 == 0, 16-byte aligned; b_scale f32 [N], 16-byte aligned (what
+ * wft_quantize_rows_i8 writes).  Everything else is wft_gemm_nt_stream_bf16's rule, plan (the same split of K: a function of N, K and the
+ * CU count) and workspace layout.  Definition, closed form: every Q[n][k] is converted to bf16 exactly and the products are accumulated
+ * by the same MFMAs in the same order as wft_gemm_nt_stream_bf16 on Q.to(bf16); the slices are summed in slice order; ONE correctly
+ * rounded f32 multiply by b_scale[n] (never fused with the bias add); then bias, gelu (aux = the pre-activation), residual, one bf16
+ * rounding.  With b_scale = 1, or any power of two folded into the bf16 weights instead, the result equals wft_gemm_nt_stream_bf16's bit
+ * for bit.  Refusals: WFT_ERR_UNSUPPORTED before any device call; wft_gemm_nt_stream_bf16 on the bf16 shadow takes those calls.       */
+int wft_gemm_nt_stream_q8(const wft_gemm_args* args, const float* b_scale, void* stream);
+int wft_gemm_nt_stream_q8_ok(const wft_gemm_args* args);
+int64_t wft_gemm_nt_stream_q8_workspace_bytes(const wft_gemm_args* args);
 /* C[p, q] (+)= alpha * sum_r A[r, p] * B[r, q]   (weight gradients dW = dY^T X:
  * what autograd's mm-backward computes for whisper.model.Linear).
  *  A bf16 [R, P] (row r at A + r*lda, P contiguous), B bf16 [R, Q];

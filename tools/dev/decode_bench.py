@@ -9,9 +9,14 @@
   e2e    tokens/s of Whisper.greedy_decode against a loop of model.logits(tokens, xa) re-forwards (same prompts, 64 new tokens).
   gemm_stream  the same seven calls through wft_gemm_nt_stream_bf16 (csrc/gemm_stream.hip) against wft_gemm_nt_bf16 on the same
          arguments, alternating, 32 distinct weight buffers in rotation; max difference of the two outputs at the size timed.
-         The table wft_gemm_nt_stream_ok's rule is set from (arm = "stream_vs_nt").
+         The table wft_gemm_nt_stream_ok's rule is set from (arm = "stream_vs_nt").  Then the int8 twin (arm = "q8_vs_stream"):
+         wft_gemm_nt_stream_q8 on the quantiser's image of the same weights against wft_gemm_nt_stream_bf16, alternating, at the
+         large-v3 step shapes (N, K) = (1280, 1280), (3840, 1280), (5120, 1280), (1280, 5120), (51968, 1280): us, spread, ratio, achieved
+         weight bytes/s of each — the table wft_gemm_nt_stream_q8_ok's rule is set from (the ceiling is 2x: half the weight bytes).
   e2e_step     greedy_decode's four step arms, alternating: step="eager" (the baseline), eager steps on the streaming GEMMs, the
-         captured step on the old GEMMs, step="graph"; tokens/s, ms per token, launches per step, share of equal tokens.
+         captured step on the old GEMMs, step="graph", and step="graph" with weights="int8" (arm = "graph_int8"); tokens/s, ms per
+         token, launches per step, share of equal tokens.
+         (profiles/decode_bench_q8.jsonl: --parts gemm_stream,e2e_step --batches 1,8,32 --out profiles/decode_bench_q8.jsonl)
 
   beam   beam search at W = 5 (--batches = audios, e.g. 1,4,6): (i) the self form of wft_attn_decode_beam_bf16 (identity and
          scrambled ancestry table) against wft_attn_decode_bf16 at the same rows and keys — the price of the indirection; (ii) its
@@ -240,6 +245,53 @@ def bench_gemm_stream(batches):
             del ws, old, new, keep
 
 
+def bench_gemm_stream_q8(batches):
+    """wft_gemm_nt_stream_q8 against wft_gemm_nt_stream_bf16 on the same weights (their int8 image and their bf16 shadow), the
+    same x, bias and epilogue, enough distinct weight buffers in rotation that none is read from the Infinity Cache."""
+    lib = L.load()
+    g = torch.Generator(device="cuda").manual_seed(2)
+    shapes = [("self out / cross q / cross out", D, D, LAYERS, L.EPI_NONE), ("self q/k/v", 3 * D, D, LAYERS, L.EPI_NONE),
+              ("mlp.0 + GELU", 4 * D, D, LAYERS, L.EPI_GELU), ("mlp.2", D, 4 * D, LAYERS, L.EPI_NONE),
+              ("tied logits", K.round_up(51866, 128), D, 4, L.EPI_NONE)]
+    for B in batches:
+        for name, N, Kd, copies, epi in shapes:
+            x = torch.randn(B, Kd, device=DEV, generator=g).to(BF)
+            bias = torch.zeros(N, device=DEV)
+            bf, q8, keep = [], [], []
+            for _ in range(copies):
+                w = torch.randn(N, Kd, device=DEV, generator=g).to(BF) * 0.02
+                qw, qs = K.quantize_rows_i8(w)
+                a = K.gemm_nt_stream(x, w, bias=bias, epilogue=epi, _args_only=True)
+                b = K.gemm_nt_stream_q8(x, qw, qs, bias=bias, epilogue=epi, _args_only=True)
+                if a is None or b is None:
+                    break
+                bf.append(a[0]); q8.append((b[0], qs)); keep += [w, qw, a[1], b[1]]
+            if not q8:
+                emit(dict(part="gemm_stream", arm="q8_vs_stream", B=B, call=name, N=N, K=Kd, served=0))
+                continue
+            st = L.stream_ptr()
+
+            def run_bf():
+                for a in bf:
+                    lib.wft_gemm_nt_stream_bf16(C.byref(a), st)
+
+            def run_q8():
+                for a, qs in q8:
+                    lib.wft_gemm_nt_stream_q8(C.byref(a), qs.data_ptr(), st)
+
+            L.check(lib.wft_gemm_nt_stream_bf16(C.byref(bf[0]), st), "wft_gemm_nt_stream_bf16")
+            L.check(lib.wft_gemm_nt_stream_q8(C.byref(q8[0][0]), q8[0][1].data_ptr(), st), "wft_gemm_nt_stream_q8")
+            diff = (keep[2].float() - keep[3].float()).abs().max().item()
+            res = ab({"bf16": run_bf, "q8": run_q8})
+            us_bf, us_q8 = res["bf16"][0] * 1e3 / copies, res["q8"][0] * 1e3 / copies
+            emit(dict(part="gemm_stream", arm="q8_vs_stream", B=B, call=name, N=N, K=Kd, served=1, bf16_us=round(us_bf, 2),
+                      bf16_spread=round(res["bf16"][2], 3), q8_us=round(us_q8, 2), q8_spread=round(res["q8"][2], 3), ratio=round(us_bf / us_q8, 2),
+                      bf16_TBps=round(N * Kd * 2 / (us_bf * 1e-6) / 1e12, 3), q8_TBps=round(N * Kd / (us_q8 * 1e-6) / 1e12, 3),
+                      q8_weight_floor_us=round(N * Kd / HBM * 1e6, 2), max_abs_diff=diff,
+                      workspace_bytes=int(lib.wft_gemm_nt_stream_q8_workspace_bytes(C.byref(q8[0][0])))))
+            del bf, q8, keep
+
+
 def _random_large_v3():
     dims = MODEL_DIMS["large-v3"]
     with torch.device(DEV):
@@ -262,7 +314,7 @@ def bench_e2e_step(batches, new_tokens=64, runs=3):
     lib = L.load()
     eot = 50257
     arms = {"eager": dict(), "eager_stream": dict(step="graph", _capture=False), "graph_nt": dict(step="graph", _stream_gemm=False),
-            "graph": dict(step="graph")}
+            "graph": dict(step="graph"), "graph_int8": dict(step="graph", weights="int8")}
     for B in batches:
         g = torch.Generator(device="cuda").manual_seed(B)
         mel = torch.randn(B, dims.n_mels, 2 * dims.n_audio_ctx, device=DEV, generator=g)
@@ -271,16 +323,17 @@ def bench_e2e_step(batches, new_tokens=64, runs=3):
         # library calls of one cached step + pick per GEMM route (every call that takes a stream enqueues at least one kernel;
         # a streaming GEMM is two: kernel + reduce).  The graph arms issue the same work as ONE graph launch per step.
         counts = {}
-        for route in (False, True):
+        for route in (False, True, "int8"):
             cache = Dm.KVCache(m.decoder, B, device=DEV)
             with torch.no_grad():
                 cache.start(prompt, None, eot=eot, max_len=max_len, suppress=[eot], n_vocab=dims.n_vocab)
                 lg = Dm.prefill(m.decoder, cache, m.encoder(mel)); Dm.pick(m.decoder, cache, lg)
-                with _CountCalls() as cc, Dm.stream_gemm(route):
+                with _CountCalls() as cc, Dm.stream_gemm(bool(route), "int8" if route == "int8" else "bf16"):
                     lg = Dm.step(m.decoder, cache); Dm.pick(m.decoder, cache, lg)
-            counts[route] = (sum(cc.n.values()), cc.n.get("wft_gemm_nt_stream_bf16", 0), cc.n.get("wft_gemm_nt_bf16", 0))
+            counts[route] = (sum(cc.n.values()), cc.n.get("wft_gemm_nt_stream_bf16", 0), cc.n.get("wft_gemm_nt_bf16", 0),
+                             cc.n.get("wft_gemm_nt_stream_q8", 0))
             del cache
-        route_of = {"eager": False, "eager_stream": True, "graph_nt": False, "graph": True}
+        route_of = {"eager": False, "eager_stream": True, "graph_nt": False, "graph": True, "graph_int8": "int8"}
         times, outs = {a: [] for a in arms}, {}
         for a, kw in arms.items():  # warm-up: shadows, workspaces, code objects, the capture
             m.greedy_decode(mel, prompt, None, eot=eot, max_len=max_len, suppress=[eot], **kw)
@@ -302,9 +355,10 @@ def bench_e2e_step(batches, new_tokens=64, runs=3):
                       spread=round((max(times[a]) - min(times[a])) / med, 3), tok_s=round(B * new_tokens / med, 1),
                       encoder_prefill_s=round(pre_s, 4), ms_per_step=round((med - pre_s) / (new_tokens - 1) * 1e3, 3),
                       library_calls_per_step=counts[route_of[a]][0], stream_gemm_calls=counts[route_of[a]][1],
-                      nt_gemm_calls=counts[route_of[a]][2], host_launches_per_step=1 if a.startswith("graph") else counts[route_of[a]][0],
+                      nt_gemm_calls=counts[route_of[a]][2], q8_gemm_calls=counts[route_of[a]][3], host_launches_per_step=1 if a.startswith("graph") else counts[route_of[a]][0],
                       same_tokens_as_eager=round((outs[a][0] == outs["eager"][0]).float().mean().item(), 4),
-                      speedup_vs_eager=round(statistics.median(times["eager"]) / med, 2)))
+                      speedup_vs_eager=round(statistics.median(times["eager"]) / med, 2),
+                      speedup_vs_graph=round(statistics.median(times["graph"]) / med, 2)))
         Dm.release_graphs(m)
 
 
@@ -848,7 +902,7 @@ def main():
     batches = [int(b) for b in a.batches.split(",")]
     emit(dict(part="env", device=torch.cuda.get_device_name(0), lib=L.load().wft_version().decode(), torch=torch.__version__))
     for part in a.parts.split(","):
-        {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": bench_gemm_stream, "e2e_step": bench_e2e_step,
+        {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": lambda b: (bench_gemm_stream(b), bench_gemm_stream_q8(b)), "e2e_step": bench_e2e_step,
          "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align, "transcribe": bench_transcribe, "resample": bench_resample}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)

@@ -379,3 +379,59 @@ extern "C" int wft_mt_copy_f32(const void* tab, int n, void* stream) {
   WFT_CHECK_LAUNCH();
   return WFT_OK;
 }
+
+// ----------------------------------------------------------------------------- int8 image of a shadow
+// Per-row symmetric quantisation (wft.h states the definition): one wave per row, four rows per workgroup; a lane takes 16 columns
+// per pass (two 16-byte loads, one 16-byte store).  Two sweeps over the row — amax, then the bytes; the second one hits L2.  Every
+// f32 operation is a correctly rounded one of its own (__fdiv_rn / __fmul_rn: nothing for the compiler to contract).
+__global__ __launch_bounds__(256) void quantize_rows_i8_kernel(const unsigned short* __restrict__ W, long rows, int cols, long ldw,
+                                                               signed char* __restrict__ Q, long ldq, float* __restrict__ scale) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const unsigned short* w = W + row * ldw;
+  float amax = 0.f;
+  for (int c = lane * 16; c < cols; c += 1024) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      float v[8];
+      bf8_unpack(*(const u32x4*)(w + c + 8 * h), v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(v[e]));
+    }
+  }
+  amax = wave_max(amax);
+  const float inv = amax > 0.f ? __fdiv_rn(127.0f, amax) : 0.0f;
+  if (lane == 0) scale[row] = __fdiv_rn(amax, 127.0f);
+  signed char* q = Q + row * ldq;
+  for (int c = lane * 16; c < cols; c += 1024) {
+    u32x4 out;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      float v[8];
+      bf8_unpack(*(const u32x4*)(w + c + 8 * h), v);
+#pragma unroll
+      for (int d = 0; d < 2; ++d) {
+        unsigned pk = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float t = fminf(fmaxf(rintf(__fmul_rn(v[4 * d + e], inv)), -127.0f), 127.0f);
+          pk |= ((unsigned)(int)t & 0xffu) << (8 * e);
+        }
+        out[2 * h + d] = pk;
+      }
+    }
+    *(u32x4*)(q + c) = out;
+  }
+}
+extern "C" int wft_quantize_rows_i8(const wft_bf16* W, int64_t rows, int64_t cols, int64_t ldw, int8_t* Q, int64_t ldq, float* scale,
+                                    void* stream) {
+  WFT_CHECK_ARG(W && Q && scale, "null pointer");
+  WFT_CHECK_ARG(rows >= 1 && cols >= 64 && cols % 64 == 0 && cols < (1ll << 31), "cols must be a multiple of 64");
+  WFT_CHECK_ARG(ldw >= cols && ldw % 8 == 0 && ldq >= cols && ldq % 16 == 0, "ldw % 8 == 0 and ldq % 16 == 0");
+  WFT_CHECK_ARG((((uintptr_t)W | (uintptr_t)Q) & 15) == 0 && ((uintptr_t)scale & 3) == 0, "W and Q must be 16-byte aligned");
+  hipLaunchKernelGGL(quantize_rows_i8_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)W,
+                     (long)rows, (int)cols, (long)ldw, (signed char*)Q, (long)ldq, scale);
+  WFT_CHECK_LAUNCH();
+  return WFT_OK;
+}

@@ -38,22 +38,35 @@ BF16 = torch.bfloat16
 _TLS = threading.local()
 
 
+WEIGHT_MODES = ("bf16", "int8")
+
+
 def stream_gemm_active() -> bool:
     return getattr(_TLS, "stream_gemm", False)
 
 
+def stream_gemm_weights() -> str:
+    """"int8" inside an active stream_gemm(weights="int8") context, else "bf16"."""
+    return getattr(_TLS, "stream_weights", "bf16") if stream_gemm_active() else "bf16"
+
+
 @contextlib.contextmanager
-def stream_gemm(enabled: bool = True):
+def stream_gemm(enabled: bool = True, weights: str = "bf16"):
     """Inside this context, under torch.no_grad(), `ops.linear` and the tied logits product send a GEMM to the weight-streaming
     kernel for M <= 32 (csrc/gemm_stream.hip, wft_gemm_nt_stream_bf16) when wft_gemm_nt_stream_ok serves it, and to
     wft_gemm_nt_bf16 otherwise.  Thread-local, in the style of runtime.exchange_launch_mode; outside it nothing changes.  A context
-    and not a model attribute: whoever drives prefill / step / pick itself runs under it unchanged."""
-    old = stream_gemm_active()
-    _TLS.stream_gemm = bool(enabled)
+    and not a model attribute: whoever drives prefill / step / pick itself runs under it unchanged.
+    weights="int8" (thread-local with the switch): the products that wft_gemm_nt_stream_q8_ok serves read the int8 image of the group's
+    shadow (LinearGroup.shadows_q8, wft_gemm_nt_stream_q8) — weight-only: activations stay bf16; a call it does not serve goes on as
+    under "bf16".  Everything that is not such a step (the prefill at M > 32, the encoder, training) never looks at the mode."""
+    if weights not in WEIGHT_MODES:
+        raise ValueError(f"weights must be one of {WEIGHT_MODES}, got {weights!r}")
+    old = stream_gemm_active(), getattr(_TLS, "stream_weights", "bf16")
+    _TLS.stream_gemm, _TLS.stream_weights = bool(enabled), weights
     try:
         yield
     finally:
-        _TLS.stream_gemm = old
+        _TLS.stream_gemm, _TLS.stream_weights = old
 
 
 class _Cache:
@@ -298,10 +311,12 @@ class _GraphSession:
                 buf.copy_(m)
             setattr(c, name, buf)
 
-    def _fingerprint(self, decoder, stream: bool, slots=None):
+    def _fingerprint(self, decoder, stream, slots=None):
+        """stream: False, or the weights mode of the streaming GEMMs ("bf16" / "int8"; True is read as "bf16")."""
         c = self.cache
         dev = c.tokens.device
-        fp = [bool(stream), c.eot, c.max_len, decoder.token_embedding.weight.shape[0]]
+        stream = "bf16" if stream is True else stream
+        fp = [stream, c.eot, c.max_len, decoder.token_embedding.weight.shape[0]]
         keep = []
         for p in decoder.parameters():
             fp.append(p.data_ptr()); keep.append(p.data)
@@ -309,6 +324,9 @@ class _GraphSession:
             fp.append((None if g.W is None else g.W.data_ptr(), None if g.bias is None else g.bias.data_ptr(), g.lkey is not None,
                        "parametrizations" in mod._modules))
             keep += [g.W, g.bias]
+            if stream == "int8":  # the int8 images a captured step reads: replaced, dropped or first made later -> never replayed
+                fp.append((None if g.Q is None else g.Q.data_ptr(), None if g.qscale is None else g.qscale.data_ptr()))
+                keep += [g.Q, g.qscale]
         fp.append(("adapted", sum("parametrizations" in mod._modules for mod in decoder.modules())))
         # scratch slots of this device: all of them when capturing, afterwards the captured ones (a slot that appears later — a
         # training step in between — is not in the graph; one that was replaced or dropped is a mismatch)
@@ -319,10 +337,10 @@ class _GraphSession:
             fp.append((name, None if ws is None else ws.data_ptr())); keep.append(ws)
         return tuple(fp) + self._extra, keep, tuple(slots)
 
-    def valid(self, decoder, stream: bool) -> bool:
+    def valid(self, decoder, stream) -> bool:
         return self.graph is not None and self.fingerprint == self._fingerprint(decoder, stream, self.slots)[0]
 
-    def capture(self, decoder, stream: bool) -> None:
+    def capture(self, decoder, stream) -> None:
         """Called behind one EAGER step of the same kind in the same decode (the warm-up: scratch slots, dynamic-LDS attributes and
         code objects exist, so nothing lazy falls into the capture).  A linear graph: one side stream, no forks."""
         self.graph = self.keep = self.fingerprint = None
@@ -336,7 +354,7 @@ class _GraphSession:
         try:
             with torch.cuda.stream(side):
                 with torch.cuda.graph(g, stream=side):
-                    with stream_gemm(stream):
+                    with stream_gemm(bool(stream), "int8" if stream == "int8" else "bf16"):
                         logits = self._body(decoder, c)
         except Exception as exc:
             # (tensors first allocated inside a failed capture must not be used: nothing of this session survives)
@@ -397,9 +415,13 @@ def release_graphs(model) -> None:
 STEP_MODES = ("eager", "graph")
 
 
-def _check_mode(model, who: str, step: str, sync_every: int) -> None:
+def _check_mode(model, who: str, step: str, sync_every: int, weights: str = "bf16") -> None:
     if step not in STEP_MODES:
         raise ValueError(f"step must be one of {STEP_MODES}, got {step!r}")
+    if weights not in WEIGHT_MODES:
+        raise ValueError(f"weights must be one of {WEIGHT_MODES}, got {weights!r}")
+    if weights == "int8" and step != "graph":
+        raise ValueError(f"{who}(weights='int8') needs step='graph': only the captured steps run on the weight-streaming kernels that read int8")
     if getattr(model, "compute_dtype", "bf16") != "bf16":
         raise NotImplementedError(f"{who} runs in the bf16 compute mode only: the single-token kernels (csrc/decode_*.hip) are bf16; "
                                   "call model.set_compute_dtype('bf16') to decode")
@@ -408,10 +430,11 @@ def _check_mode(model, who: str, step: str, sync_every: int) -> None:
 
 
 def _decode(model, mel: torch.Tensor, start: dict, *, who: str, table, key: tuple, make_cache, prefill, first, body, readout, extra=(),
-            graph: bool, stream: bool, sync_every: int, xa: Optional[torch.Tensor] = None):
+            graph: bool, stream, sync_every: int, xa: Optional[torch.Tensor] = None):
     """The loop of greedy_decode and beam_decode -> readout(cache) after the last step (read while the model is still in eval mode).  make_cache(decoder) builds the cache (kept in a
     graph session of `table` under key + (device,) when `graph`), start: the arguments of its start(); prefill(decoder, cache, xa)
     -> logits, first(decoder, cache, logits): the update they feed, body(decoder, cache): one cached step with its update.
+    stream: False, or the weights mode of the cached steps' streaming GEMMs ("bf16" / "int8"); an int8 session is kept under its own key.
     Host reads: the fingerprint check once after the prefill, the `unfinished` counter every `sync_every` steps.
     xa: the encoder output of `mel` when the caller already has it (decode_with_fallback runs the encoder once for all rungs)."""
     was_training = model.training
@@ -420,7 +443,7 @@ def _decode(model, mel: torch.Tensor, start: dict, *, who: str, table, key: tupl
         dec = model.decoder
         sess = None
         if graph:
-            sess = _session(table, model, key + (str(mel.device),), lambda: _GraphSession(dec, make_cache(dec), body, extra, who))
+            sess = _session(table, model, key + (str(mel.device),) + (("int8",) if stream == "int8" else ()), lambda: _GraphSession(dec, make_cache(dec), body, extra, who))
             sess._extra = tuple(extra)  # (a kept session may have been captured under other timestamp rules: then it recaptures)
         cache = sess.cache if graph else make_cache(dec)
         cache.start(**start, n_vocab=model.dims.n_vocab)
@@ -430,6 +453,11 @@ def _decode(model, mel: torch.Tensor, start: dict, *, who: str, table, key: tupl
             logits = prefill(dec, cache, model.encoder(mel) if xa is None else xa)
             if graph:
                 sess.adopt_prefill()
+            if stream == "int8":
+                # the prefill (bf16) has brought every weight shadow up to date; their int8 images follow here, in place — a replayed
+                # step runs no Python that could notice a stale one
+                for _, g in _groups(dec):
+                    g.refresh_q8()
             first(dec, cache, logits)
             ready = graph and sess.valid(dec, stream)  # (the fingerprint check a replay cannot make: once per decode, after the prefill)
             warmed = False
@@ -442,7 +470,7 @@ def _decode(model, mel: torch.Tensor, start: dict, *, who: str, table, key: tupl
                 if ready:
                     sess.replay()
                     continue
-                with stream_gemm(stream):
+                with stream_gemm(bool(stream), "int8" if stream == "int8" else "bf16"):
                     body(dec, cache)
                 warmed = True
         return readout(cache)
@@ -454,7 +482,7 @@ def _decode(model, mel: torch.Tensor, start: dict, *, who: str, table, key: tupl
 def greedy_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None, *, eot: int, max_len: Optional[int] = None,
                   suppress: Sequence[int] = (), suppress_first: Sequence[int] = (), sync_every: int = 8, step: str = "eager",
                   timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
-                  max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True, _stream_gemm: bool = True, _xa=None):
+                  max_initial_timestamp_index: Optional[int] = 50, weights: str = "bf16", _capture: bool = True, _stream_gemm: bool = True, _xa=None):
     """-> (tokens i64 [B, L] — prompt included, padded with `eot` behind each row's end —, lengths i64 [B], sum_logprob f32 [B]).
 
     timestamp_begin (default None: no rules, today's path exactly): the first timestamp id; every pick then runs under upstream's
@@ -468,9 +496,12 @@ def greedy_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=Non
     step="eager": every cached step is issued launch by launch.  step="graph": the cached steps run on the weight-streaming GEMMs
     (`stream_gemm`) and are replayed from ONE captured HIP graph per (batch, device) session — the first step of a decode that
     has no valid graph runs eagerly, the second is captured; at most MAX_SESSIONS sessions per model, `release_graphs(model)` frees
-    them.  The prefill and the encoder keep their kernels in both modes.  `_capture=False` / `_stream_gemm=False` switch off one
+    them.  The prefill and the encoder keep their kernels in both modes.  weights="int8" (needs step="graph"; ValueError otherwise,
+    before any device work): the cached steps read per-row int8 images of the weight shadows (wft_gemm_nt_stream_q8) — weight-only,
+    activations stay bf16; the encoder, the prefill and the cross key / value projections stay bf16; "bf16" is today's path, bit
+    for bit; the captured int8 steps live in sessions of their own (key + ("int8",)).  `_capture=False` / `_stream_gemm=False` switch off one
     half each (tests and the A/B bench only); `_xa`: the encoder output of `mel`, when decode_with_fallback has it already."""
-    _check_mode(model, "greedy_decode", step, sync_every)
+    _check_mode(model, "greedy_decode", step, sync_every, weights)
     rules = check_ts_rules(model.dims.n_vocab, eot, suppress, suppress_first, timestamp_begin, no_timestamps, max_initial_timestamp_index)
     ts_kw = dict(timestamp_begin=timestamp_begin, no_timestamps=no_timestamps, max_initial_timestamp_index=max_initial_timestamp_index)
     B = prompt.shape[0]
@@ -485,7 +516,7 @@ def greedy_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=Non
     return _decode(model, mel, dict(prompt=prompt, prompt_len=prompt_len, eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first, **ts_kw),
                    who="greedy_decode", table=_SESSIONS, key=(int(B),), make_cache=lambda dec: KVCache(dec, B, device=mel.device),
                    prefill=prefill, first=pick, body=_greedy_body, readout=readout, extra=ts_extra(rules), graph=step == "graph" and _capture,
-                   stream=step == "graph" and _stream_gemm, sync_every=sync_every, xa=_xa)
+                   stream=step == "graph" and _stream_gemm and weights, sync_every=sync_every, xa=_xa)
 
 
 # ============================================================================= beam search
@@ -675,7 +706,7 @@ def beam_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None,
                 length_penalty: Optional[float] = None, eot: int, max_len: Optional[int] = None, suppress: Sequence[int] = (),
                 suppress_first: Sequence[int] = (), sync_every: int = 8, step: str = "eager", return_all: bool = False,
                 timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
-                max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True, _stream_gemm: bool = True, _xa=None):
+                max_initial_timestamp_index: Optional[int] = 50, weights: str = "bf16", _capture: bool = True, _stream_gemm: bool = True, _xa=None):
     """Beam search -> (tokens i64 [B, L], lengths i64 [B], sum_logprob f32 [B]) of the winning hypothesis per audio, in greedy_decode's
     layout: prompt included, the `eot` that ended the hypothesis included (one that ran into `max_len` has none), padded with `eot`.
     return_all: a fourth value, per audio the list of (tokens, sum_logprob, score) of all its entries, best score first (stable).
@@ -684,13 +715,13 @@ def beam_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None,
     sum_logprob / n over the generated tokens (n without the final eot), or sum_logprob / ((5 + n) / 6) ** length_penalty.
     timestamp_begin / no_timestamps / max_initial_timestamp_index: as greedy_decode (default: no rules), every hypothesis under
     its own history; beam search needs max_initial_timestamp_index >= beam_size - 1 or None (check_ts_rules says why).
-    Argument errors are raised before any device work.  `step`, `sync_every`, `_capture`, `_stream_gemm`, `_xa`: as greedy_decode; the
+    Argument errors are raised before any device work.  `step`, `weights`, `sync_every`, `_capture`, `_stream_gemm`, `_xa`: as greedy_decode; the
     captured beam steps live in their own sessions (`beam_sessions`), freed by `release_graphs` too."""
     C = beam_candidates(beam_size, patience)
     if length_penalty is not None and (isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float))):
         raise ValueError(f"length_penalty must be None or a number, got {length_penalty!r}")
     _check_live_columns(beam_size, model.dims.n_vocab, suppress, suppress_first)
-    _check_mode(model, "beam_decode", step, sync_every)
+    _check_mode(model, "beam_decode", step, sync_every, weights)
     rules = check_ts_rules(model.dims.n_vocab, eot, suppress, suppress_first, timestamp_begin, no_timestamps, max_initial_timestamp_index,
                            beam_size=beam_size)
     ts_kw = dict(timestamp_begin=timestamp_begin, no_timestamps=no_timestamps, max_initial_timestamp_index=max_initial_timestamp_index)
@@ -714,7 +745,7 @@ def beam_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None,
                    who="beam_decode", table=_BEAM_SESSIONS, key=(int(B), int(beam_size), int(C)),
                    make_cache=lambda dec: BeamCache(dec, B, beam_size, C, device=mel.device), prefill=beam_prefill, first=_beam_first,
                    body=_beam_body, readout=readout, extra=(("beam", beam_size, C),) + ts_extra(rules), graph=step == "graph" and _capture,
-                   stream=step == "graph" and _stream_gemm, sync_every=sync_every, xa=_xa)
+                   stream=step == "graph" and _stream_gemm and weights, sync_every=sync_every, xa=_xa)
 
 
 # ============================================================================= sampling and the temperature ladder
@@ -822,7 +853,7 @@ def sample_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=Non
                   length_penalty: Optional[float] = None, return_all: bool = False, eot: int, max_len: Optional[int] = None,
                   suppress: Sequence[int] = (), suppress_first: Sequence[int] = (), sync_every: int = 8, step: str = "eager",
                   timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
-                  max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True, _stream_gemm: bool = True, _xa=None):
+                  max_initial_timestamp_index: Optional[int] = 50, weights: str = "bf16", _capture: bool = True, _stream_gemm: bool = True, _xa=None):
     """`best_of` samples per audio at `temperature`, the best of them -> (tokens i64 [B, L], lengths i64 [B], sum_logprob f32 [B]) in
     greedy_decode's layout.  return_all: a fourth value, per audio the list of (tokens, sum_logprob, score) of its samples, best
     score first (stable).
@@ -835,18 +866,18 @@ def sample_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=Non
     seed: an int — audio a then draws with seed + a — or one int per audio; sample j of an audio with seed s draws with
     (8*s + j) mod 2^64.  The noise depends on (that seed, position, column) only, so a result does not depend on the batch an audio
     is decoded in.  Errors (temperature < 0, best_of outside 1..8, ...) are raised before any device work.
-    `step`, `sync_every`, `_capture`, `_stream_gemm`, `_xa`: as greedy_decode.  The captured steps live in a third table
+    `step`, `weights`, `sync_every`, `_capture`, `_stream_gemm`, `_xa`: as greedy_decode.  The captured steps live in a third table
     (`sample_sessions`, keyed (audios, best_of, device)); temperature and seeds are device memory, so a second call with other
     values replays the same graph."""
     _check_sampling(temperature, best_of, length_penalty)
     B, N = int(prompt.shape[0]), int(best_of)
     seeds = sample_seeds(seed, B, N)
-    _check_mode(model, "sample_decode", step, sync_every)
+    _check_mode(model, "sample_decode", step, sync_every, weights)
     rules = check_ts_rules(model.dims.n_vocab, eot, suppress, suppress_first, timestamp_begin, no_timestamps, max_initial_timestamp_index)
     ts_kw = dict(timestamp_begin=timestamp_begin, no_timestamps=no_timestamps, max_initial_timestamp_index=max_initial_timestamp_index)
     if temperature == 0:
         res = greedy_decode(model, mel, prompt, prompt_len, eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first,
-                            sync_every=sync_every, step=step, _capture=_capture, _stream_gemm=_stream_gemm, _xa=_xa, **ts_kw)
+                            sync_every=sync_every, step=step, weights=weights, _capture=_capture, _stream_gemm=_stream_gemm, _xa=_xa, **ts_kw)
         if return_all:
             toks, lens, slp = res[0].cpu().tolist(), res[1].cpu().tolist(), res[2].cpu().tolist()
             first = [int(prompt.shape[1])] * B if prompt_len is None else torch.as_tensor(prompt_len).reshape(B).tolist()
@@ -875,7 +906,7 @@ def sample_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=Non
                                     suppress=suppress, suppress_first=suppress_first, **ts_kw),
                    who="sample_decode", table=_SAMPLE_SESSIONS, key=(B, N), make_cache=lambda dec: SampleCache(dec, B, N, device=mel.device),
                    prefill=beam_prefill, first=sample_pick, body=_sample_body, readout=readout, extra=ts_extra(rules),
-                   graph=step == "graph" and _capture, stream=step == "graph" and _stream_gemm, sync_every=sync_every, xa=_xa)
+                   graph=step == "graph" and _capture, stream=step == "graph" and _stream_gemm and weights, sync_every=sync_every, xa=_xa)
 
 
 def _generated_n(row, first: int, length: int, eot: int) -> int:
@@ -968,7 +999,7 @@ def decode_with_fallback(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_
     threshold switches its test off.
     info: {"temperature": [B] the rung that produced each result, "avg_logprob": [B], "no_speech_prob": [B] (None without
     `no_speech`), "compression_ratio": [B] (None without `text_of`), "rungs": per rung the original indices decoded there}.
-    decode_kw: what all three decoders share (eot — required —, max_len, suppress, suppress_first, sync_every, step and the
+    decode_kw: what all three decoders share (eot — required —, max_len, suppress, suppress_first, sync_every, step, weights and the
     timestamp keywords).  Under step="graph" a rung with a new number of pending audios is a new graph session (sessions are keyed
     by batch size): accepted, not optimised — at most MAX_SESSIONS of a kind are kept, so a long ladder recaptures.
     `_xa`: the encoder output of `mel`, when the caller has it already (engine/transcribe.py detects the language on it first)."""
@@ -985,7 +1016,7 @@ def decode_with_fallback(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_
         raise TypeError("decode_with_fallback needs eot=")
     if isinstance(seed, bool) or not isinstance(seed, int):
         raise ValueError(f"seed must be an integer, got {seed!r}")
-    _check_mode(model, "decode_with_fallback", decode_kw.get("step", "eager"), decode_kw.get("sync_every", 8))
+    _check_mode(model, "decode_with_fallback", decode_kw.get("step", "eager"), decode_kw.get("sync_every", 8), decode_kw.get("weights", "bf16"))
     eot, ts_begin = int(decode_kw["eot"]), decode_kw.get("timestamp_begin")
     thresholds = {"compression_ratio": compression_ratio_threshold, "logprob": logprob_threshold, "no_speech": no_speech_threshold}
     B = int(prompt.shape[0])

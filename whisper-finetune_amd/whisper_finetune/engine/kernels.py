@@ -367,13 +367,10 @@ def gemm_nt(a, b, *, M=None, N=None, K=None, lda=None, ldb=None, out=None, out_f
     return out
 
 
-def gemm_nt_stream(a, b, *, M=None, N=None, K=None, lda=None, ldb=None, out=None, bias=None, residual=None, aux=None,
-                   epilogue=L.EPI_NONE, ldc=None, ldaux=None, ldr=None, _args_only=False):
-    """C[M,N] = A[M,K] @ B[N,K]^T (+bias) (gelu) (+residual) on the weight-streaming kernel for M <= 32 (csrc/gemm_stream.hip,
-    wft_gemm_nt_stream_bf16): the keywords of `gemm_nt` that apply.  Returns None — nothing launched — when the library does not
-    serve the call in that form (wft_gemm_nt_stream_ok): the caller sends it to `gemm_nt`.  The fp32 partials live in a scratch
-    slot of their own ("nt_stream")."""
-    _chk(a, BF16, "A"); _chk(b, BF16, "B")
+def _stream_args(a, b, b_dtype, query, M, N, K, lda, ldb, out, bias, residual, aux, epilogue, ldc, ldaux, ldr):
+    """The wft_gemm_args of both streaming entry points -> (args, out), or None when `query` (the workspace query of the entry point)
+    says the library does not serve the call."""
+    _chk(a, BF16, "A"); _chk(b, b_dtype, "B")
     if M is None:
         M = a.shape[0]
     if K is None:
@@ -397,15 +394,72 @@ def gemm_nt_stream(a, b, *, M=None, N=None, K=None, lda=None, ldb=None, out=None
         args.C, args.ldc = out.data_ptr(), out.stride(-2) if ldc is None else ldc
     else:
         args.C, args.ldc = 1 << 20, N  # (a placeholder with the alignment a fresh tensor has: nothing is allocated for a refused call)
-    if _grant_workspace(args, "wft_gemm_nt_stream_workspace_bytes", a.device, "nt_stream") <= 0:
+    if _grant_workspace(args, query, a.device, "nt_stream") <= 0:
         return None
     if out is None:
         out = torch.empty((M, N), dtype=BF16, device=a.device)
         args.C, args.ldc = out.data_ptr(), out.stride(-2)
-    if _args_only:
-        return args, out
+    return args, out
+
+
+def gemm_nt_stream(a, b, *, M=None, N=None, K=None, lda=None, ldb=None, out=None, bias=None, residual=None, aux=None,
+                   epilogue=L.EPI_NONE, ldc=None, ldaux=None, ldr=None, _args_only=False):
+    """C[M,N] = A[M,K] @ B[N,K]^T (+bias) (gelu) (+residual) on the weight-streaming kernel for M <= 32 (csrc/gemm_stream.hip,
+    wft_gemm_nt_stream_bf16): the keywords of `gemm_nt` that apply.  Returns None — nothing launched — when the library does not
+    serve the call in that form (wft_gemm_nt_stream_ok): the caller sends it to `gemm_nt`.  The fp32 partials live in a scratch
+    slot of their own ("nt_stream")."""
+    served = _stream_args(a, b, BF16, "wft_gemm_nt_stream_workspace_bytes", M, N, K, lda, ldb, out, bias, residual, aux, epilogue, ldc, ldaux, ldr)
+    if served is None or _args_only:
+        return served
+    args, out = served
     L.check(L.load().wft_gemm_nt_stream_bf16(C.byref(args), L.stream_ptr()), "wft_gemm_nt_stream_bf16")
     return out
+
+
+def gemm_nt_stream_q8(a, q, scale, *, M=None, N=None, K=None, lda=None, ldb=None, out=None, bias=None, residual=None, aux=None,
+                      epilogue=L.EPI_NONE, ldc=None, ldaux=None, ldr=None, _args_only=False):
+    """gemm_nt_stream on int8 weights: C = (A[M,K] @ Q[N,K]^T) * scale[N] (+bias) (gelu) (+residual) (wft_gemm_nt_stream_q8; q int8
+    [N, K], scale f32 [N] — what `quantize_rows_i8` made of a bf16 shadow).  None — nothing launched — when wft_gemm_nt_stream_q8_ok
+    does not serve the call: the caller sends it to `gemm_nt_stream` on the bf16 shadow.  The partials share the "nt_stream" slot."""
+    _chk(scale, F32, "scale")
+    served = _stream_args(a, q, torch.int8, "wft_gemm_nt_stream_q8_workspace_bytes", M, N, K, lda, ldb, out, bias, residual, aux, epilogue, ldc,
+                          ldaux, ldr)
+    if served is None or _args_only:
+        return served
+    args, out = served
+    if scale.numel() < args.N or not scale.is_contiguous():
+        raise L.WftError(f"scale: expected a contiguous f32 vector of at least N={args.N} elements, got {tuple(scale.shape)}")
+    L.check(L.load().wft_gemm_nt_stream_q8(C.byref(args), _p(scale), L.stream_ptr()), "wft_gemm_nt_stream_q8")
+    return out
+
+
+def gemm_nt_stream_q8_serves(M: int, N: int, K: int, epilogue=L.EPI_NONE) -> bool:
+    """Shapes only (wft_gemm_nt_stream_q8_ok on placeholder pointers with the alignment real operands have): would the int8 streaming
+    kernel take an [M, K] x [N, K]^T product?  Asked BEFORE an int8 image is built for a group, so a product the kernel never serves
+    (the prefill's cross key / value projection, M = B * n_audio_ctx) never gets one."""
+    args = L.GemmArgs()
+    args.A = args.B = args.C = 1 << 20
+    args.lda, args.ldb, args.ldc = K, K, N
+    args.M, args.N, args.K, args.batch, args.alpha, args.beta = M, N, K, 1, 1.0, 1.0
+    args.epilogue = epilogue
+    return bool(L.load().wft_gemm_nt_stream_q8_ok(C.byref(args)))
+
+
+def quantize_rows_i8(w, out=None, scale=None):
+    """bf16 [rows, cols] (row stride ldw) -> (int8 [rows, cols], f32 [rows]): per-row symmetric quantisation of a weight shadow
+    (wft_quantize_rows_i8; include/wft.h states the definition).  `out` / `scale`: buffers to write in place."""
+    _chk(w, BF16, "w")
+    rows, cols = w.shape
+    if out is None:
+        out = torch.empty((rows, cols), dtype=torch.int8, device=w.device)
+    if scale is None:
+        scale = torch.empty(rows, dtype=F32, device=w.device)
+    _chk(out, torch.int8, "out"); _chk(scale, F32, "scale")
+    if w.stride(1) != 1 or out.stride(1) != 1 or tuple(out.shape) != (rows, cols) or scale.numel() < rows or not scale.is_contiguous():
+        raise L.WftError("quantize_rows_i8: w and out must be [rows, cols] with unit column stride, scale a contiguous f32 [rows]")
+    L.check(L.load().wft_quantize_rows_i8(_p(w), rows, cols, w.stride(0), _p(out), out.stride(0), _p(scale), L.stream_ptr()),
+            "wft_quantize_rows_i8")
+    return out, scale
 
 
 def gemm_nt_aux8_bytes(M: int, N: int, K: int, device, epilogue=None, colsum: bool = False) -> int:

@@ -173,6 +173,7 @@ SIGNATURES = {
     "wft_dgelu_mul_bf16": [c_vp, c_vp, c_vp, c_i64, c_vp],
     "wft_colsum_bf16": [c_vp, c_i64, c_i64, c_i64, c_vp, C.c_int, c_vp],
     "wft_mt_copy_f32": [c_vp, C.c_int, c_vp],
+    "wft_quantize_rows_i8": [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp],
     "wft_colsum_bf16_ws": [c_vp, c_i64, c_i64, c_i64, c_vp, C.c_int, c_vp, c_i64, c_vp],
     "wft_colsum_workspace_bytes": [c_i64, c_i64],
     "wft_layernorm_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_int, C.c_float,
@@ -192,6 +193,9 @@ SIGNATURES = {
     "wft_gemm_nt_stream_bf16": [C.POINTER(GemmArgs), c_vp],
     "wft_gemm_nt_stream_ok": [C.POINTER(GemmArgs)],
     "wft_gemm_nt_stream_workspace_bytes": [C.POINTER(GemmArgs)],
+    "wft_gemm_nt_stream_q8": [C.POINTER(GemmArgs), c_vp, c_vp],
+    "wft_gemm_nt_stream_q8_ok": [C.POINTER(GemmArgs)],
+    "wft_gemm_nt_stream_q8_workspace_bytes": [C.POINTER(GemmArgs)],
     "wft_gemm_tn_bf16": [C.POINTER(GemmArgs), c_vp],
     "wft_gemm_tn_variant": [C.POINTER(GemmArgs)],
     "wft_gemm_nt_rank_pair_bf16": [C.POINTER(GemmArgs), C.POINTER(GemmArgs), c_vp],
@@ -260,7 +264,8 @@ SIGNATURES = {
 _RESTYPES = {"wft_last_error": C.c_char_p, "wft_version": C.c_char_p, "wft_layernorm_bwd_workspace": c_i64,
              "wft_gemm_tn_workspace_bytes": c_i64, "wft_gemm_nt_colsum_workspace_bytes": c_i64, "wft_gemm_nt_splitk_workspace_bytes": c_i64, "wft_gemm_nt_aux8_bytes": c_i64, "wft_colsum_workspace_bytes": c_i64,
              "wft_attn_bwd_colsum_workspace_bytes": c_i64, "wft_attn_decode_workspace_bytes": c_i64,
-             "wft_gemm_nt_stream_workspace_bytes": c_i64, "wft_attn_decode_beam_workspace_bytes": c_i64,
+             "wft_gemm_nt_stream_workspace_bytes": c_i64, "wft_gemm_nt_stream_q8_workspace_bytes": c_i64,
+             "wft_attn_decode_beam_workspace_bytes": c_i64,
              "wft_dtw_workspace_bytes": c_i64}
 
 _lib = None

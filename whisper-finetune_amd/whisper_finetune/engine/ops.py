@@ -119,6 +119,9 @@ class LinearGroup:
         self.W = self.WT = self.bias = None
         self.lkey = None
         self.Am = self.AmT = self.Bb = self.BbT = None
+        # int8 image of W with one f32 scale per row (shadows_q8): allocated when first asked for, current while qkey == key
+        self.qkey = None
+        self.Q = self.qscale = None
         # per weight of the group: factor folded into the FORWARD shadow W (and the matching slice of the stacked bias) in fp32
         # before the bf16 rounding; the transposed shadow W^T (backward-data) and the rank-r LoRA operands stay unscaled.
         # Self-attention q/k/v groups: (QK_ALPHA, 1, 1) — see QK_PRESCALE above.  A constant of the group: not part of the keys.
@@ -210,6 +213,27 @@ class LinearGroup:
             elif lkey is None and _SHADOW_BATCH and want_t and all(w.requires_grad for w in weights):
                 _PLAIN_PLAN.note(self, weights, biases)
         return self.W, self.WT, self.bias
+
+    def shadows_q8(self, weights, biases, loras=None):
+        """(Q int8 [Npad, K], scale f32 [Npad], bias): the per-row int8 image of this group's OWN bf16 shadow `W`
+        (wft_quantize_rows_i8) — with it the merged LoRA delta and the folded query scale — for the weight-only int8 steps of
+        decoding (decode.stream_gemm(weights="int8")).  Cached under the key of `W`: whatever refreshes `W` (an optimizer step, a new
+        LoRA mask, a batched refresh plan) makes the next call requantise, in place.  Nothing in training asks for it."""
+        W, _, bias = self.shadows(weights, biases, need_t=False, loras=loras)
+        if self.Q is None or self.Q.shape != W.shape:
+            self.Q = torch.empty(W.shape, dtype=torch.int8, device=W.device)
+            self.qscale = torch.empty(W.shape[0], dtype=F32, device=W.device)
+            self.qkey = None
+        self.refresh_q8()
+        return self.Q, self.qscale, bias
+
+    def refresh_q8(self) -> None:
+        """Requantise an existing int8 image, in place, if `W` was rewritten since (qkey != key).  Also called for every group of the
+        decoder behind a prefill, before a captured int8 step is replayed: a replay runs no Python, so nothing else would notice that
+        the prefill has just refreshed `W` after an optimizer step."""
+        if self.Q is not None and self.W is not None and self.qkey != self.key and self.Q.shape == self.W.shape:
+            K.quantize_rows_i8(self.W, out=self.Q, scale=self.qscale)
+            self.qkey = self.key
 
     @staticmethod
     def _bias_key(biases):
@@ -885,8 +909,16 @@ def linear(x, group: LinearGroup, weights, biases, loras=None, residual=None, ge
         # a cached decoding step (decode.stream_gemm): the weight-streaming kernel where the library serves the call; there is no
         # backward, so the GELU call stores no gelu' and the stand-ins for the pre-activation are None
         has_lora = any(sp is not None for sp in loras)
-        W, _, bias = group.shadows(weights, biases, need_t=False, loras=loras if has_lora else None)
-        y = K.gemm_nt_stream(x, W, bias=bias, residual=residual, epilogue=L.EPI_GELU if gelu_out else L.EPI_NONE)
+        epi = L.EPI_GELU if gelu_out else L.EPI_NONE
+        y = None
+        # int8 weights where wft_gemm_nt_stream_q8_ok serves the shape (asked first: no image is built for a group it never serves);
+        # otherwise the bf16 shadow, below
+        if _decode.stream_gemm_weights() == "int8" and K.gemm_nt_stream_q8_serves(x.shape[0], group.dims(weights)[2], x.shape[-1], epi):
+            Q, qs, bias = group.shadows_q8(weights, biases, loras=loras if has_lora else None)
+            y = K.gemm_nt_stream_q8(x, Q, qs, bias=bias, residual=residual, epilogue=epi)
+        if y is None:
+            W, _, bias = group.shadows(weights, biases, need_t=False, loras=loras if has_lora else None)
+            y = K.gemm_nt_stream(x, W, bias=bias, residual=residual, epilogue=epi)
         if y is not None:
             return (None, y, None) if gelu_out else y
     cfg = _LinearCfg(group, len(weights), tuple(b is not None for b in biases), tuple(loras), gelu_out,
@@ -1177,8 +1209,13 @@ class TiedLogitsFn(torch.autograd.Function):
 def tied_logits(x, emb, group: LinearGroup):
     """Front door of TiedLogitsFn; under decode.stream_gemm() and no_grad the product goes to the weight-streaming kernel where served."""
     if _decode.stream_gemm_active() and not torch.is_grad_enabled():
-        W, _, _ = group.shadows([emb], [None], need_t=True)
-        y = K.gemm_nt_stream(x, W)
+        y = None
+        if _decode.stream_gemm_weights() == "int8" and K.gemm_nt_stream_q8_serves(x.shape[0], group.dims([emb])[2], x.shape[-1]):
+            Q, qs, _ = group.shadows_q8([emb], [None])
+            y = K.gemm_nt_stream_q8(x, Q, qs)
+        if y is None:
+            W, _, _ = group.shadows([emb], [None], need_t=True)
+            y = K.gemm_nt_stream(x, W)
         if y is not None:
             return y
     return TiedLogitsFn.apply(x, emb, group)

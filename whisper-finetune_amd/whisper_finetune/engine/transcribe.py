@@ -294,7 +294,7 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
                length_penalty: Optional[float] = None, logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
                compression_ratio_threshold: Optional[float] = None, no_speech: Optional[int] = None, seed: int = 0, suppress: Sequence[int] = (),
                suppress_first: Sequence[int] = (), max_initial_timestamp_index: Optional[int] = 50, sync_every: int = 8, step: str = "eager",
-               filters: Optional[torch.Tensor] = None, sample_rate=SAMPLE_RATE, word_timestamps: bool = False, split_words=None,
+               weights: str = "bf16", filters: Optional[torch.Tensor] = None, sample_rate=SAMPLE_RATE, word_timestamps: bool = False, split_words=None,
                prepend_punctuations: str = D.PREPEND_PUNCTUATIONS, append_punctuations: str = D.APPEND_PUNCTUATIONS,
                hallucination_silence_threshold: Optional[float] = None, _decode=None, _detect=None, _align=None,
                _frames: Optional[Sequence[int]] = None) -> list:
@@ -313,7 +313,8 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
     `text_of` (ids -> str) is needed only for `compression_ratio_threshold` and for the blank-text rule below.  `no_speech`: the id
     whose probability at the sot position is the window's no-speech probability (None: the silence skip never fires).  The ladder
     keywords (temperatures, best_of, beam_size, patience, length_penalty, the three thresholds, seed), `suppress`,
-    `suppress_first`, `max_initial_timestamp_index`, `sync_every` and `step` are those of `decode_with_fallback`.  `filters`:
+    `suppress_first`, `max_initial_timestamp_index`, `sync_every`, `step` and `weights` ("int8": the cached steps of every window read int8 weights, needs step="graph"; the alignment
+    pass of word_timestamps stays bf16) are those of `decode_with_fallback`.  `filters`:
     the mel filterbank f32 [n_mels, 201] (default: data.gpu_frontend.mel_filters(n_mels)).
 
     The loop.  Recordings are numbered in input order; the long log-mel of each is computed once (`long_logmel`) and packed;
@@ -370,6 +371,7 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
     batch partners through the GEMM shapes, as for decoding; replaying the same batches gives the same bits.  As upstream,
     `add_word_timestamps` does not hand its own last_speech_timestamp back to the loop: only step (4) moves the running value."""
     _check_mode(model, "transcribe")
+    D._check_mode(model, "transcribe", step, sync_every, weights)
     single = isinstance(audio, torch.Tensor) and audio.dim() == 1 or (not isinstance(audio, (list, tuple)) and getattr(audio, "ndim", 0) == 1)
     audios = [audio] if single else list(audio)
     n = len(audios)
@@ -440,6 +442,8 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
                   compression_ratio_threshold=compression_ratio_threshold, text_of=text_of, no_speech=no_speech, eot=int(eot),
                   suppress=suppress, suppress_first=suppress_first, sync_every=sync_every, step=step, timestamp_begin=timestamp_begin,
                   no_timestamps=no_timestamps, max_initial_timestamp_index=max_initial_timestamp_index)
+    if weights != "bf16":
+        shared["weights"] = weights
     was_training = model.training
     model.eval()
     try:

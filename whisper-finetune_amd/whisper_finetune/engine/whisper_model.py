@@ -463,27 +463,31 @@ class Whisper(nn.Module):
 
     def greedy_decode(self, mel: Tensor, prompt: Tensor, prompt_len=None, *, eot: int, max_len: Optional[int] = None,
                       suppress=(), suppress_first=(), sync_every: int = 8, step: str = "eager", timestamp_begin: Optional[int] = None,
-                      no_timestamps: Optional[int] = None, max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True,
-                      _stream_gemm: bool = True):
+                      no_timestamps: Optional[int] = None, max_initial_timestamp_index: Optional[int] = 50, weights: str = "bf16",
+                      _capture: bool = True, _stream_gemm: bool = True):
         """KV-cached greedy decoding, token ids in and out (engine/decode.py; upstream: whisper.decoding's greedy path with
         DecodingOptions(without_timestamps=True)).  mel f32 [B, n_mels, 2 * n_audio_ctx]; prompt i64 [B, T] right-padded, prompt_len [B]
         (None: all T long) -> (tokens i64 [B, L] padded with `eot` behind each row's end, lengths [B], sum_logprob f32 [B]).
         eval() semantics, no gradients; the host looks at the unfinished-row counter every `sync_every` steps only.
         step="graph": the cached steps run on the weight-streaming small-M GEMMs (csrc/gemm_stream.hip) and are replayed from one
         captured HIP graph per (batch, device) — engine/decode.py; `decode.release_graphs(model)` frees what that pins.  "eager"
-        (default): every step launch by launch on the kernels of the prefill.  (`_capture` / `_stream_gemm`: decode.greedy_decode's two private A/B keywords.)
+        (default): every step launch by launch on the kernels of the prefill.  weights="int8" (with step="graph"): the cached steps
+        read per-row int8 images of the weight shadows (wft_gemm_nt_stream_q8; weight-only, activations stay bf16; encoder, prefill and
+        cross key / value projections stay bf16); beam_decode, sample_decode and decode_with_fallback take it too.  (`_capture` / `_stream_gemm`: decode.greedy_decode's two private A/B keywords.)
         timestamp_begin (None: off): decode under upstream's timestamp rules, applied inside the pick kernel (include/wft.h
         "Timestamp rules"); no_timestamps / max_initial_timestamp_index: that column is removed / the first timestamp is at most
         this index.  `decode.timestamp_segments` turns the result into timed segments."""
         return _decode.greedy_decode(self, mel, prompt, prompt_len, eot=eot, max_len=max_len, suppress=suppress,
                                      suppress_first=suppress_first, sync_every=sync_every, step=step, timestamp_begin=timestamp_begin,
                                      no_timestamps=no_timestamps, max_initial_timestamp_index=max_initial_timestamp_index,
+                                     weights=weights,
                                      _capture=_capture, _stream_gemm=_stream_gemm)
 
     def beam_decode(self, mel: Tensor, prompt: Tensor, prompt_len=None, *, beam_size: int, patience: float = 1.0, length_penalty=None,
                     eot: int, max_len: Optional[int] = None, suppress=(), suppress_first=(), sync_every: int = 8, step: str = "eager",
                     return_all: bool = False, timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
-                    max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True, _stream_gemm: bool = True):
+                    max_initial_timestamp_index: Optional[int] = 50, weights: str = "bf16", _capture: bool = True,
+                      _stream_gemm: bool = True):
         """KV-cached beam search (engine/decode.py beam_decode; upstream: whisper.decoding's BeamSearchDecoder + MaximumLikelihoodRanker
         with DecodingOptions(without_timestamps=True), restated there — parity with the upstream binary is unpinned).  Arguments and
         result layout as greedy_decode, for the winning hypothesis of every audio; beam_size 1..8; the beams of an audio share its
@@ -492,12 +496,14 @@ class Whisper(nn.Module):
         return _decode.beam_decode(self, mel, prompt, prompt_len, beam_size=beam_size, patience=patience, length_penalty=length_penalty,
                                    eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first, sync_every=sync_every,
                                    step=step, return_all=return_all, timestamp_begin=timestamp_begin, no_timestamps=no_timestamps,
-                                   max_initial_timestamp_index=max_initial_timestamp_index, _capture=_capture, _stream_gemm=_stream_gemm)
+                                   max_initial_timestamp_index=max_initial_timestamp_index, weights=weights,
+                                     _capture=_capture, _stream_gemm=_stream_gemm)
 
     def sample_decode(self, mel: Tensor, prompt: Tensor, prompt_len=None, *, temperature: float, best_of: int = 1, seed=0,
                       length_penalty=None, return_all: bool = False, eot: int, max_len: Optional[int] = None, suppress=(), suppress_first=(),
                       sync_every: int = 8, step: str = "eager", timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
-                      max_initial_timestamp_index: Optional[int] = 50, _capture: bool = True, _stream_gemm: bool = True):
+                      max_initial_timestamp_index: Optional[int] = 50, weights: str = "bf16", _capture: bool = True,
+                      _stream_gemm: bool = True):
         """KV-cached sampling (engine/decode.py sample_decode; upstream: GreedyDecoder at temperature > 0 with best_of samples and the
         MaximumLikelihoodRanker, restated there — parity with the upstream binary and with torch's random stream is unpinned).
         Arguments and result layout as greedy_decode, for the best of the `best_of` (1..8) samples of every audio; every token is
@@ -508,6 +514,7 @@ class Whisper(nn.Module):
                                      length_penalty=length_penalty, return_all=return_all, eot=eot, max_len=max_len, suppress=suppress,
                                      suppress_first=suppress_first, sync_every=sync_every, step=step, timestamp_begin=timestamp_begin,
                                      no_timestamps=no_timestamps, max_initial_timestamp_index=max_initial_timestamp_index,
+                                     weights=weights,
                                      _capture=_capture, _stream_gemm=_stream_gemm)
 
     def decode_with_fallback(self, mel: Tensor, prompt: Tensor, prompt_len=None, **kw):

@@ -41,13 +41,14 @@ def _batch_token_stats(model, x, y_in, y_out):
 
 
 def _greedy_predictions(model, tokenizer, x, y_in, step: str = "eager", beam: dict = None, timestamps: bool = False,
-                        fallback: dict = None) -> List[List[int]]:
+                        fallback: dict = None, weights: str = "bf16") -> List[List[int]]:
     """t_config["wft_eval_decode"] = "greedy": every utterance's predicted ids from KV-cached greedy decoding
     (Whisper.greedy_decode) instead of the teacher-forced argmax.  The decoding prefix of a row is its y_in up to and including
     the start-of-transcript sequence; every special token but eot is suppressed (upstream's notimestamps decoding plus its
     SuppressTokens list of specials; `tokenizer.non_speech_tokens` too when the tokenizer has them), eot and the blank for a
     row's first token (upstream's SuppressBlank); at most n_text_ctx // 2 new tokens (upstream's sample_len).
     `step` is t_config["wft_eval_decode_step"]: "graph" = the captured step on the weight-streaming GEMMs (engine/decode.py).
+    `weights` is t_config["wft_eval_decode_weights"]: "int8" = those steps read int8 weights (weight-only; the WER of THIS int8 path).
     `beam` = {"beam_size", "patience"} (t_config["wft_eval_decode"] = "beam_search"): the same prefix, suppression and length rules
     through Whisper.beam_decode, the winning hypothesis of every utterance.
     `timestamps` (t_config["wft_eval_decode_timestamps"]): decode under upstream's timestamp rules, its command line's default mode —
@@ -75,7 +76,7 @@ def _greedy_predictions(model, tokenizer, x, y_in, step: str = "eager", beam: di
     blank = [int(t) for t in tokenizer.encode(" ")] if hasattr(tokenizer, "encode") else []
     n_ctx = getattr(getattr(model, "dims", None), "n_text_ctx", 448)
     kw = dict(eot=eot, max_len=min(n_ctx, width + n_ctx // 2), suppress=suppress, suppress_first=[eot] + blank,
-              **({} if step == "eager" else {"step": step}))
+              **({} if step == "eager" else {"step": step}), **({} if weights == "bf16" else {"weights": weights}))
     if timestamps:
         ts_begin = int(tokenizer.timestamp_begin)
         kw["suppress"] = [t for t in suppress if t < ts_begin]
@@ -156,6 +157,13 @@ def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict
     if decode_step not in (None, "eager", "graph"):
         raise ValueError(f'wft_eval_decode_step: "eager" (the default) or "graph", got {decode_step!r}')
     decode_step = decode_step or "eager"
+    decode_weights = t_config.get("wft_eval_decode_weights")
+    if decode_weights not in (None, "bf16", "int8"):
+        raise ValueError(f'wft_eval_decode_weights: "bf16" (the default) or "int8", got {decode_weights!r}')
+    decode_weights = decode_weights or "bf16"
+    if decode_weights == "int8" and (decode_mode is None or decode_step != "graph"):
+        raise ValueError('wft_eval_decode_weights: "int8" needs wft_eval_decode and wft_eval_decode_step: "graph" (only the captured '
+                         'steps run on the kernels that read int8 weights)')
     decode_ts = t_config.get("wft_eval_decode_timestamps", False)
     if not isinstance(decode_ts, bool):
         raise ValueError(f"wft_eval_decode_timestamps: true or false, got {decode_ts!r}")
@@ -179,7 +187,8 @@ def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict
         decoded = None
         if decode_mode is not None:
             decoded = _greedy_predictions(model, tokenizer, x, y_in, decode_step, beam, **({"timestamps": True} if decode_ts else {}),
-                                          **({} if fallback is None else {"fallback": fallback}))
+                                          **({} if fallback is None else {"fallback": fallback}),
+                                          **({} if decode_weights == "bf16" else {"weights": decode_weights}))
             if decode_ts:  # the timestamps go the way of the other specials before WER / CER
                 decoded = [[t for t in row if t < ts_begin] for row in decoded]
         for i in range(y_host.shape[0]):
