@@ -328,6 +328,30 @@ int64_t wft_gemm_nt_stream_workspace_bytes(const wft_gemm_args* args);
 int wft_gemm_nt_stream_q8(const wft_gemm_args* args, const float* b_scale, void* stream);
 int wft_gemm_nt_stream_q8_ok(const wft_gemm_args* args);
 int64_t wft_gemm_nt_stream_q8_workspace_bytes(const wft_gemm_args* args);
+/* W8A8 product on the int8 matrix cores (csrc/gemm_i8.hip; v_mfma_i32_16x16x64_i8) for the products of decoding's weights="w8a8" mode
+ * with M > 32 — the encoder, the prefill, the cross key / value projections; CTranslate2's int8 deployment quantises every Linear and its
+ * activations per row, which is what this stands next to.  args->A is int8 [M, K] row-major (lda), args->B int8 [N, K] row-major (ldb),
+ * a_scale f32 [M], b_scale f32 [N] — what wft_quantize_rows_i8 writes for an activation matrix and for a weight shadow —, C bf16 [M, N].
+ * Definition, closed form; every f32 operation correctly rounded and none fused:
+ *   acc  = sum_k (int32)A[m][k] * (int32)B[n][k]          exact, order-free
+ *   f    = (float)acc                                      round to nearest even (matters above 2^24)
+ *   s    = a_scale[m] * b_scale[n]
+ *   v    = f * s
+ *   v    = v + bias[n]                                     if bias
+ *   v    = gelu(v)                                         if WFT_EPI_GELU (the formula of the bf16 kernels' epilogue)
+ *   v    = v + (float)residual[m][n]                       if residual (residual_first 0, beta 1)
+ *   C    = bf16(v)                                         one rounding
+ * One launch, no workspace, no split of K, no atomics; bitwise reproducible; row m of C does not depend on M.
+ * Served (wft_gemm_nt_i8_ok = 1, a pure host function): any M >= 1 (rows past M of the last row tile are neither read into a result nor
+ * written), N % 128 == 0, K % 64 == 0 and K <= 65536 (|acc| < 2^31 even for -128 bytes), batch 1, bf16 C, alpha 1, the plain or the gelu
+ * epilogue with aux NULL, optional f32 bias, optional bf16 residual added after the epilogue; lda % 16 == 0, ldb % 16 == 0, ldc % 4 == 0,
+ * A / B / C 16-byte aligned, the bias / residual alignment rules of wft_gemm_nt_stream_bf16.  Everything else — an f32 or accumulated C,
+ * batch > 1, colsum, p_valid, valid_rows_period, the other epilogues, aux — is refused with WFT_ERR_UNSUPPORTED and the reason in
+ * wft_last_error() before any device call.  A NULL or not 16-byte aligned scale vector is WFT_ERR_ARG.
+ * What still reads bf16 under weights="w8a8": the cached steps' activations (their weights are int8: wft_gemm_nt_stream_q8), products with
+ * M <= 32, the conv stem, the embedding lookup, the prefill's tied logits product, attention (DESIGN.md §3 "W8A8").                    */
+int wft_gemm_nt_i8(const wft_gemm_args* args, const float* a_scale, const float* b_scale, void* stream);
+int wft_gemm_nt_i8_ok(const wft_gemm_args* args);
 /* C[p, q] (+)= alpha * sum_r A[r, p] * B[r, q]   (weight gradients dW = dY^T X:
  * what autograd's mm-backward computes for whisper.model.Linear).
  *  A bf16 [R, P] (row r at A + r*lda, P contiguous), B bf16 [R, Q];

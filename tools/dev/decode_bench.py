@@ -18,6 +18,12 @@
          token, launches per step, share of equal tokens.
          (profiles/decode_bench_q8.jsonl: --parts gemm_stream,e2e_step --batches 1,8,32 --out profiles/decode_bench_q8.jsonl)
 
+  gemm_i8      the W8A8 product of weights="w8a8" (the quantiser pass over the activation + wft_gemm_nt_i8, csrc/gemm_i8.hip) against
+         wft_gemm_nt_bf16 on the bf16 shadow, alternating, at the large-v3 encoder / prefill shapes (N, K) = (3840, 1280), (1280, 1280),
+         (5120, 1280), (1280, 5120), (2560, 1280) with M = 1500 * B (--batches = B); wft_gemm_nt_i8 alone as a third arm; then
+         arm = "e2e": encoder + prefill under weights="bf16" and under "w8a8".  A numerics feature: no speed-up is claimed.
+         (profiles/decode_bench_w8a8.jsonl: --parts gemm_i8 --batches 1,8,32 --out profiles/decode_bench_w8a8.jsonl)
+
   beam   beam search at W = 5 (--batches = audios, e.g. 1,4,6): (i) the self form of wft_attn_decode_beam_bf16 (identity and
          scrambled ancestry table) against wft_attn_decode_bf16 at the same rows and keys — the price of the indirection; (ii) its
          grouped cross form at R = B * W rows against wft_attn_decode_bf16 at R rows on W-times replicated caches: us, K/V bytes,
@@ -56,7 +62,7 @@
          The kernel should be HBM-bound; no figure is claimed in advance.
          (--parts resample --out profiles/decode_bench_resample.jsonl)
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,beam,ts,sample,align,transcribe,resample] [--batches 1,8,32] [--out FILE]
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -290,6 +296,70 @@ def bench_gemm_stream_q8(batches):
                       q8_weight_floor_us=round(N * Kd / HBM * 1e6, 2), max_abs_diff=diff,
                       workspace_bytes=int(lib.wft_gemm_nt_stream_q8_workspace_bytes(C.byref(q8[0][0])))))
             del bf, q8, keep
+
+
+def bench_gemm_i8(batches, copies=4):
+    """The W8A8 product as ops.linear issues it under decode.int8_gemm() — wft_quantize_rows_i8 on the activation, then wft_gemm_nt_i8
+    on the int8 image of the weights — against wft_gemm_nt_bf16 on the bf16 shadow, alternating, at the large-v3 encoder / prefill
+    shapes with M = 1500 * B (--batches = B); a third arm times wft_gemm_nt_i8 alone (the quantiser's share is the difference).
+    All arms go through the Python wrappers into preallocated outputs, `copies` weight buffers in rotation.  Then arm = "e2e":
+    encoder + prefill (40-token prompts) of a random large-v3 model under weights="bf16" and under "w8a8"."""
+    from whisper_finetune.engine import decode as Dm
+
+    g = torch.Generator(device="cuda").manual_seed(3)
+    shapes = [("self q/k/v", 3 * D, D, L.EPI_NONE), ("attention out / cross q", D, D, L.EPI_NONE), ("mlp.0 + GELU", 4 * D, D, L.EPI_GELU),
+              ("mlp.2", D, 4 * D, L.EPI_NONE), ("cross k/v", 2 * D, D, L.EPI_NONE)]
+    for B in batches:
+        M = TA * B
+        for name, N, Kd, epi in shapes:
+            x = torch.randn(M, Kd, device=DEV, generator=g).to(BF)
+            bias = torch.zeros(N, device=DEV)
+            ws = [torch.randn(N, Kd, device=DEV, generator=g).to(BF) * 0.02 for _ in range(copies)]
+            qs = [K.quantize_rows_i8(w) for w in ws]
+            out_bf, out_i8 = torch.empty(M, N, dtype=BF, device=DEV), torch.empty(M, N, dtype=BF, device=DEV)
+            xq, xs = K.quantize_rows_i8(x)
+            assert K.gemm_nt_i8_serves(M, N, Kd, epi)
+
+            def run_bf():
+                for w in ws:
+                    K.gemm_nt(x, w, bias=bias, epilogue=epi, out=out_bf)
+
+            def run_i8():
+                for qw, sc in qs:
+                    K.quantize_rows_i8(x, out=xq, scale=xs)
+                    K.gemm_nt_i8(xq, xs, qw, sc, bias=bias, epilogue=epi, out=out_i8)
+
+            def run_i8_gemm():
+                for qw, sc in qs:
+                    K.gemm_nt_i8(xq, xs, qw, sc, bias=bias, epilogue=epi, out=out_i8)
+
+            run_bf(); run_i8()
+            diff = (out_bf.float() - out_i8.float()).abs().max().item()
+            res = ab({"bf16": run_bf, "i8": run_i8, "i8_gemm": run_i8_gemm}, rounds=5, iters=2)
+            us = {k: v[0] * 1e3 / copies for k, v in res.items()}
+            emit(dict(part="gemm_i8", arm="i8_vs_nt", B=B, M=M, call=name, N=N, K=Kd, bf16_us=round(us["bf16"], 1), bf16_spread=round(res["bf16"][2], 3),
+                      i8_us=round(us["i8"], 1), i8_spread=round(res["i8"][2], 3), i8_gemm_only_us=round(us["i8_gemm"], 1),
+                      quantiser_us=round(us["i8"] - us["i8_gemm"], 1), ratio=round(us["bf16"] / us["i8"], 3),
+                      bf16_TFps=round(2.0 * M * N * Kd / (us["bf16"] * 1e-6) / 1e12, 1), i8_gemm_TOps=round(2.0 * M * N * Kd / (us["i8_gemm"] * 1e-6) / 1e12, 1),
+                      max_abs_diff=diff))
+            del x, ws, qs, out_bf, out_i8, xq, xs
+    m, dims = _random_large_v3()
+    for B in batches:
+        mel = torch.randn(B, dims.n_mels, 2 * TA, device=DEV, generator=g)
+        prompt = torch.randint(0, 50000, (B, 40), device=DEV, generator=g)
+        cache = Dm.KVCache(m.decoder, B, device=DEV)
+
+        def run(weights):
+            with torch.no_grad():
+                xa = Dm.encode(m, mel, weights)
+                cache.start(prompt, None, eot=50257, max_len=41, n_vocab=dims.n_vocab)
+                with Dm.int8_gemm(weights == "w8a8"):
+                    Dm.prefill(m.decoder, cache, xa)
+
+        res = ab({"bf16": lambda: run("bf16"), "w8a8": lambda: run("w8a8")}, rounds=5, iters=1)
+        emit(dict(part="gemm_i8", arm="e2e", B=B, what="encoder + prefill of 40-token prompts, large-v3, random weights", bf16_ms=round(res["bf16"][0], 2),
+                  bf16_spread=round(res["bf16"][2], 3), w8a8_ms=round(res["w8a8"][0], 2), w8a8_spread=round(res["w8a8"][2], 3),
+                  ratio=round(res["bf16"][0] / res["w8a8"][0], 3)))
 
 
 def _random_large_v3():
@@ -903,7 +973,7 @@ def main():
     emit(dict(part="env", device=torch.cuda.get_device_name(0), lib=L.load().wft_version().decode(), torch=torch.__version__))
     for part in a.parts.split(","):
         {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": lambda b: (bench_gemm_stream(b), bench_gemm_stream_q8(b)), "e2e_step": bench_e2e_step,
-         "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align, "transcribe": bench_transcribe, "resample": bench_resample}[part](batches)
+         "gemm_i8": bench_gemm_i8, "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align, "transcribe": bench_transcribe, "resample": bench_resample}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

@@ -1,7 +1,8 @@
 // gemm_common.h — what the GEMM translation units share: the parameter block, tile-order helpers, per-device host helpers, and
 // what each kernel file offers nt_plan / tn_plan and the entry points of gemm.hip (the host file).  Kernel files: gemm_nt4w.hip /
 // gemm_tn4w.hip (256x256, one wave per SIMD), gemm_pp256.hip (256x256 8-wave ping-pong), gemm_nt128.hip / gemm_tn128.hip
-// (128x128), gemm_rank.hip (rank-r operands); gemm_stream.hip (small-M weight streaming) has entry points of its own.
+// (128x128), gemm_rank.hip (rank-r operands); gemm_stream.hip (small-M weight streaming) and gemm_i8.hip (int8 x int8 -> int32, the W8A8
+// product of decoding) have entry points of their own.
 #pragma once
 #include "common.h"
 #include <type_traits>

@@ -38,7 +38,14 @@ BF16 = torch.bfloat16
 _TLS = threading.local()
 
 
-WEIGHT_MODES = ("bf16", "int8")
+WEIGHT_MODES = ("bf16", "int8")  # what the streaming GEMMs of a cached step read (stream_gemm(weights=...))
+# the `weights=` keyword of every decode call: "w8a8" = the "int8" steps behind an encoder and a prefill on the W8A8 kernel (int8_gemm)
+DECODE_WEIGHTS = ("bf16", "int8", "w8a8")
+
+
+def step_weights(weights: str) -> str:
+    """The weights mode of the CACHED steps: those of "w8a8" are the weight-only "int8" steps (wft_gemm_nt_stream_q8)."""
+    return "int8" if weights == "w8a8" else weights
 
 
 def stream_gemm_active() -> bool:
@@ -67,6 +74,34 @@ def stream_gemm(enabled: bool = True, weights: str = "bf16"):
         yield
     finally:
         _TLS.stream_gemm, _TLS.stream_weights = old
+
+
+def int8_gemm_active() -> bool:
+    return getattr(_TLS, "int8_gemm", False)
+
+
+@contextlib.contextmanager
+def int8_gemm(enabled: bool = True):
+    """Inside this context, under torch.no_grad(), `ops.linear` sends a product with M > 32 that wft_gemm_nt_i8_ok serves to the W8A8
+    kernel (csrc/gemm_i8.hip): the input is quantised per row once per call (wft_quantize_rows_i8, the kernel that quantises the weight
+    shadows), the weight operand is the int8 image of the group's shadow (LinearGroup.shadows_q8: merged LoRA delta and folded query
+    scale included) and wft_gemm_nt_i8 multiplies them on the int8 matrix cores.  A fused q/k/v group is one call, so one quantiser
+    pass.  Every other call — M <= 32, grad mode, the tied logits product, the fp32 compute mode — goes on exactly as outside.
+    Thread-local beside `stream_gemm` and independent of it; decoding's weights="w8a8" runs the encoder and the prefill under it."""
+    old = int8_gemm_active()
+    _TLS.int8_gemm = bool(enabled)
+    try:
+        yield
+    finally:
+        _TLS.int8_gemm = old
+
+
+def encode(model, mel: torch.Tensor, weights: str = "bf16") -> torch.Tensor:
+    """model.encoder(mel) as a decode under `weights` runs it: under int8_gemm() when weights == "w8a8", else today's call.  Every
+    group asks for its image through LinearGroup.shadows_q8 at its product, which first brings the bf16 shadow up to date and then
+    the image (an optimizer step between two calls is seen here, in front of the first int8 product — not only behind the prefill)."""
+    with int8_gemm(weights == "w8a8"):
+        return model.encoder(mel)
 
 
 class _Cache:
@@ -418,10 +453,10 @@ STEP_MODES = ("eager", "graph")
 def _check_mode(model, who: str, step: str, sync_every: int, weights: str = "bf16") -> None:
     if step not in STEP_MODES:
         raise ValueError(f"step must be one of {STEP_MODES}, got {step!r}")
-    if weights not in WEIGHT_MODES:
-        raise ValueError(f"weights must be one of {WEIGHT_MODES}, got {weights!r}")
-    if weights == "int8" and step != "graph":
-        raise ValueError(f"{who}(weights='int8') needs step='graph': only the captured steps run on the weight-streaming kernels that read int8")
+    if weights not in DECODE_WEIGHTS:
+        raise ValueError(f"weights must be one of {DECODE_WEIGHTS}, got {weights!r}")
+    if weights != "bf16" and step != "graph":
+        raise ValueError(f"{who}(weights={weights!r}) needs step='graph': only the captured steps run on the weight-streaming kernels that read int8")
     if getattr(model, "compute_dtype", "bf16") != "bf16":
         raise NotImplementedError(f"{who} runs in the bf16 compute mode only: the single-token kernels (csrc/decode_*.hip) are bf16; "
                                   "call model.set_compute_dtype('bf16') to decode")
@@ -430,13 +465,15 @@ def _check_mode(model, who: str, step: str, sync_every: int, weights: str = "bf1
 
 
 def _decode(model, mel: torch.Tensor, start: dict, *, who: str, table, key: tuple, make_cache, prefill, first, body, readout, extra=(),
-            graph: bool, stream, sync_every: int, xa: Optional[torch.Tensor] = None):
+            graph: bool, stream, sync_every: int, xa: Optional[torch.Tensor] = None, weights: str = "bf16"):
     """The loop of greedy_decode and beam_decode -> readout(cache) after the last step (read while the model is still in eval mode).  make_cache(decoder) builds the cache (kept in a
     graph session of `table` under key + (device,) when `graph`), start: the arguments of its start(); prefill(decoder, cache, xa)
     -> logits, first(decoder, cache, logits): the update they feed, body(decoder, cache): one cached step with its update.
     stream: False, or the weights mode of the cached steps' streaming GEMMs ("bf16" / "int8"); an int8 session is kept under its own key.
     Host reads: the fingerprint check once after the prefill, the `unfinished` counter every `sync_every` steps.
-    xa: the encoder output of `mel` when the caller already has it (decode_with_fallback runs the encoder once for all rungs)."""
+    xa: the encoder output of `mel` when the caller already has it (decode_with_fallback runs the encoder once for all rungs).
+    weights: the caller's mode; "w8a8" runs the encoder and the prefill (with the cross key / value projections it stores) under
+    int8_gemm(), and its cached steps are the "int8" ones (`stream` is then "int8": they share that mode's session)."""
     was_training = model.training
     model.eval()
     try:
@@ -450,7 +487,8 @@ def _decode(model, mel: torch.Tensor, start: dict, *, who: str, table, key: tupl
         # updates until the shortest prompt reaches max_len (start() has just set len to the prompt lengths; nothing ran since)
         most = cache.max_len - int(cache.len.min())
         if most > 0:
-            logits = prefill(dec, cache, model.encoder(mel) if xa is None else xa)
+            with int8_gemm(weights == "w8a8"):
+                logits = prefill(dec, cache, encode(model, mel, weights) if xa is None else xa)
             if graph:
                 sess.adopt_prefill()
             if stream == "int8":
@@ -499,7 +537,12 @@ def greedy_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=Non
     them.  The prefill and the encoder keep their kernels in both modes.  weights="int8" (needs step="graph"; ValueError otherwise,
     before any device work): the cached steps read per-row int8 images of the weight shadows (wft_gemm_nt_stream_q8) — weight-only,
     activations stay bf16; the encoder, the prefill and the cross key / value projections stay bf16; "bf16" is today's path, bit
-    for bit; the captured int8 steps live in sessions of their own (key + ("int8",)).  `_capture=False` / `_stream_gemm=False` switch off one
+    for bit; the captured int8 steps live in sessions of their own (key + ("int8",)).  weights="w8a8" (needs step="graph" likewise):
+    in addition the encoder, the prefill and the cross key / value projections it stores run every Linear product with M > 32 on
+    per-row quantised activations and the int8 images of the shadows (`int8_gemm`, wft_gemm_nt_i8); its cached steps are the "int8"
+    steps and share their session.  Still bf16 under "w8a8": the cached steps' activations, products with M <= 32 in a short
+    prefill, the conv stem, the embedding lookup, the prefill's tied-logits product, find_alignment's teacher-forced pass; attention
+    is unchanged.  `_capture=False` / `_stream_gemm=False` switch off one
     half each (tests and the A/B bench only); `_xa`: the encoder output of `mel`, when decode_with_fallback has it already."""
     _check_mode(model, "greedy_decode", step, sync_every, weights)
     rules = check_ts_rules(model.dims.n_vocab, eot, suppress, suppress_first, timestamp_begin, no_timestamps, max_initial_timestamp_index)
@@ -516,7 +559,7 @@ def greedy_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=Non
     return _decode(model, mel, dict(prompt=prompt, prompt_len=prompt_len, eot=eot, max_len=max_len, suppress=suppress, suppress_first=suppress_first, **ts_kw),
                    who="greedy_decode", table=_SESSIONS, key=(int(B),), make_cache=lambda dec: KVCache(dec, B, device=mel.device),
                    prefill=prefill, first=pick, body=_greedy_body, readout=readout, extra=ts_extra(rules), graph=step == "graph" and _capture,
-                   stream=step == "graph" and _stream_gemm and weights, sync_every=sync_every, xa=_xa)
+                   stream=step == "graph" and _stream_gemm and step_weights(weights), sync_every=sync_every, xa=_xa, weights=weights)
 
 
 # ============================================================================= beam search
@@ -745,7 +788,7 @@ def beam_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=None,
                    who="beam_decode", table=_BEAM_SESSIONS, key=(int(B), int(beam_size), int(C)),
                    make_cache=lambda dec: BeamCache(dec, B, beam_size, C, device=mel.device), prefill=beam_prefill, first=_beam_first,
                    body=_beam_body, readout=readout, extra=(("beam", beam_size, C),) + ts_extra(rules), graph=step == "graph" and _capture,
-                   stream=step == "graph" and _stream_gemm and weights, sync_every=sync_every, xa=_xa)
+                   stream=step == "graph" and _stream_gemm and step_weights(weights), sync_every=sync_every, xa=_xa, weights=weights)
 
 
 # ============================================================================= sampling and the temperature ladder
@@ -906,7 +949,7 @@ def sample_decode(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_len=Non
                                     suppress=suppress, suppress_first=suppress_first, **ts_kw),
                    who="sample_decode", table=_SAMPLE_SESSIONS, key=(B, N), make_cache=lambda dec: SampleCache(dec, B, N, device=mel.device),
                    prefill=beam_prefill, first=sample_pick, body=_sample_body, readout=readout, extra=ts_extra(rules),
-                   graph=step == "graph" and _capture, stream=step == "graph" and _stream_gemm and weights, sync_every=sync_every, xa=_xa)
+                   graph=step == "graph" and _capture, stream=step == "graph" and _stream_gemm and step_weights(weights), sync_every=sync_every, xa=_xa, weights=weights)
 
 
 def _generated_n(row, first: int, length: int, eot: int) -> int:
@@ -1025,7 +1068,7 @@ def decode_with_fallback(model, mel: torch.Tensor, prompt: torch.Tensor, prompt_
     was_training = model.training
     model.eval()
     try:
-        xa = model.encoder(mel) if _xa is None else _xa
+        xa = encode(model, mel, decode_kw.get("weights", "bf16")) if _xa is None else _xa
         nsp = [None] * B
         if no_speech is not None:
             nsp = no_speech_prob(model, xa, prompt, 0 if sot_index is None else sot_index, no_speech).cpu().tolist()

@@ -445,6 +445,56 @@ def gemm_nt_stream_q8_serves(M: int, N: int, K: int, epilogue=L.EPI_NONE) -> boo
     return bool(L.load().wft_gemm_nt_stream_q8_ok(C.byref(args)))
 
 
+def _i8_shape_args(M: int, N: int, K: int, epilogue) -> "L.GemmArgs":
+    args = L.GemmArgs()
+    args.A = args.B = args.C = 1 << 20  # (placeholders with the alignment real operands have)
+    args.lda, args.ldb, args.ldc = K, K, N
+    args.M, args.N, args.K, args.batch, args.alpha, args.beta = M, N, K, 1, 1.0, 1.0
+    args.epilogue = epilogue
+    return args
+
+
+def gemm_nt_i8(a_q, a_scale, b_q, b_scale, *, bias=None, residual=None, epilogue=L.EPI_NONE, out=None):
+    """W8A8 product on the int8 matrix cores (wft_gemm_nt_i8; include/wft.h states the definition):
+    C[M,N] = bf16(epi((a_q[M,K] @ b_q[N,K]^T) * (a_scale[M] x b_scale[N]) + bias) + residual); a_q / b_q int8 with unit column stride,
+    the scales contiguous f32 — what `quantize_rows_i8` makes of an activation matrix and of a weight shadow.  A call the library
+    does not serve raises WftError with its reason (ask `gemm_nt_i8_serves` first): there is no other kernel behind this one."""
+    _chk(a_q, torch.int8, "a_q"); _chk(b_q, torch.int8, "b_q"); _chk(a_scale, F32, "a_scale"); _chk(b_scale, F32, "b_scale")
+    if a_q.dim() != 2 or b_q.dim() != 2 or a_q.stride(1) != 1 or b_q.stride(1) != 1 or a_q.shape[1] != b_q.shape[1]:
+        raise L.WftError(f"gemm_nt_i8: a_q [M, K] and b_q [N, K] with unit column stride, got {tuple(a_q.shape)} and {tuple(b_q.shape)}")
+    M, Kd = a_q.shape
+    N = b_q.shape[0]
+    if a_scale.numel() < M or b_scale.numel() < N or not a_scale.is_contiguous() or not b_scale.is_contiguous():
+        raise L.WftError(f"gemm_nt_i8: the scales must be contiguous f32 vectors of at least M={M} and N={N} elements")
+    args = _i8_shape_args(M, N, Kd, epilogue)
+    args.A, args.lda = a_q.data_ptr(), a_q.stride(0)
+    args.B, args.ldb = b_q.data_ptr(), b_q.stride(0)
+    if bias is not None:
+        _chk(bias, F32, "bias")
+        if bias.numel() < N or not bias.is_contiguous():
+            raise L.WftError(f"gemm_nt_i8: bias must be a contiguous f32 vector of at least N={N} elements")
+        args.bias = bias.data_ptr()
+    if residual is not None:
+        _chk(residual, BF16, "residual")
+        if residual.dim() != 2 or residual.stride(1) != 1 or residual.shape[0] < M or residual.shape[1] < N:
+            raise L.WftError(f"gemm_nt_i8: residual must cover [M={M}, N={N}] with unit column stride, got {tuple(residual.shape)}")
+        args.residual, args.ldr = residual.data_ptr(), residual.stride(0)
+    if out is None:
+        out = torch.empty((M, N), dtype=BF16, device=a_q.device)
+    _chk(out, BF16, "out")
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < M or out.shape[1] < N:
+        raise L.WftError(f"gemm_nt_i8: out must cover [M={M}, N={N}] with unit column stride, got {tuple(out.shape)}")
+    args.C, args.ldc = out.data_ptr(), out.stride(0)
+    L.check(L.load().wft_gemm_nt_i8(C.byref(args), _p(a_scale), _p(b_scale), L.stream_ptr()), "wft_gemm_nt_i8")
+    return out
+
+
+def gemm_nt_i8_serves(M: int, N: int, K: int, epilogue=L.EPI_NONE) -> bool:
+    """Shapes only (wft_gemm_nt_i8_ok on placeholder pointers with the alignment real operands have): would the W8A8 kernel take an
+    [M, K] x [N, K]^T product?  Asked before the activation is quantised and before an int8 image is built for a group."""
+    return bool(L.load().wft_gemm_nt_i8_ok(C.byref(_i8_shape_args(M, N, K, epilogue))))
+
+
 def quantize_rows_i8(w, out=None, scale=None):
     """bf16 [rows, cols] (row stride ldw) -> (int8 [rows, cols], f32 [rows]): per-row symmetric quantisation of a weight shadow
     (wft_quantize_rows_i8; include/wft.h states the definition).  `out` / `scale`: buffers to write in place."""

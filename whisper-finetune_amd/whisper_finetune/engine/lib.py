@@ -196,6 +196,8 @@ SIGNATURES = {
     "wft_gemm_nt_stream_q8": [C.POINTER(GemmArgs), c_vp, c_vp],
     "wft_gemm_nt_stream_q8_ok": [C.POINTER(GemmArgs)],
     "wft_gemm_nt_stream_q8_workspace_bytes": [C.POINTER(GemmArgs)],
+    "wft_gemm_nt_i8": [C.POINTER(GemmArgs), c_vp, c_vp, c_vp],
+    "wft_gemm_nt_i8_ok": [C.POINTER(GemmArgs)],
     "wft_gemm_tn_bf16": [C.POINTER(GemmArgs), c_vp],
     "wft_gemm_tn_variant": [C.POINTER(GemmArgs)],
     "wft_gemm_nt_rank_pair_bf16": [C.POINTER(GemmArgs), C.POINTER(GemmArgs), c_vp],

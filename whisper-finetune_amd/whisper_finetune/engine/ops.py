@@ -921,6 +921,17 @@ def linear(x, group: LinearGroup, weights, biases, loras=None, residual=None, ge
             y = K.gemm_nt_stream(x, W, bias=bias, residual=residual, epilogue=epi)
         if y is not None:
             return (None, y, None) if gelu_out else y
+    if _decode.int8_gemm_active() and not torch.is_grad_enabled() and x.shape[0] > 32:
+        # the encoder / the prefill of decoding's weights="w8a8" (decode.int8_gemm): x quantised per row once per call, the int8 image of
+        # the group's shadow (asked for here: shadow first, then image, both brought up to date in front of the product), one
+        # wft_gemm_nt_i8.  No shape is excluded for speed: the mode is about uniform numerics.  M <= 32 stays on the bf16 kernels.
+        epi = L.EPI_GELU if gelu_out else L.EPI_NONE
+        if K.gemm_nt_i8_serves(x.shape[0], group.dims(weights)[2], x.shape[-1], epi):
+            has_lora = any(sp is not None for sp in loras)
+            Q, qs, bias = group.shadows_q8(weights, biases, loras=loras if has_lora else None)
+            xq, xs = K.quantize_rows_i8(x)
+            y = K.gemm_nt_i8(xq, xs, Q, qs, bias=bias, residual=residual, epilogue=epi)
+            return (None, y, None) if gelu_out else y
     cfg = _LinearCfg(group, len(weights), tuple(b is not None for b in biases), tuple(loras), gelu_out,
                      gelu_pre is not None, sum(w.shape[0] for w in weights), dx_accum, int(gelu_next_n), gelu_codes)
     params = list(weights) + [b for b in biases if b is not None]

@@ -313,7 +313,8 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
     `text_of` (ids -> str) is needed only for `compression_ratio_threshold` and for the blank-text rule below.  `no_speech`: the id
     whose probability at the sot position is the window's no-speech probability (None: the silence skip never fires).  The ladder
     keywords (temperatures, best_of, beam_size, patience, length_penalty, the three thresholds, seed), `suppress`,
-    `suppress_first`, `max_initial_timestamp_index`, `sync_every`, `step` and `weights` ("int8": the cached steps of every window read int8 weights, needs step="graph"; the alignment
+    `suppress_first`, `max_initial_timestamp_index`, `sync_every`, `step` and `weights` ("int8": the cached steps of every window read int8 weights, needs step="graph"; "w8a8": in addition the encoder
+    of every window — language detection's and word_timestamps' included — and the prefill run int8 x int8, decode.encode / decode.int8_gemm; the alignment
     pass of word_timestamps stays bf16) are those of `decode_with_fallback`.  `filters`:
     the mel filterbank f32 [n_mels, 201] (default: data.gpu_frontend.mel_filters(n_mels)).
 
@@ -455,7 +456,7 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
             mel = None if packed is None else packed.windows(rows, [seek[a] for a in rows])
             xa = None
             if i == 0 and language_tokens is not None:
-                xa = None if packed is None else model.encoder(mel)
+                xa = None if packed is None else D.encode(model, mel, weights)
                 best, probs = detect(model, mel, sot=sots[rows[0]][0], language_tokens=language_tokens, _xa=xa)
                 best, probs = _to_list(best), (probs.cpu() if hasattr(probs, "cpu") else probs)
                 for j, a in enumerate(rows):
@@ -469,7 +470,7 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
             plen = [len(p) for p, _ in prompts]
             kw = dict(shared, sot_index=[s for _, s in prompts], seed=seed + i, max_len=min(n_ctx, width + sample_len))
             if word_timestamps and xa is None and packed is not None:
-                xa = model.encoder(mel)
+                xa = D.encode(model, mel, weights)
             if xa is not None:
                 kw["_xa"] = xa
             toks, lens, _, info = decode(model, mel, prompt if mel is None else prompt.to(mel.device), torch.tensor(plen), **kw)

@@ -473,7 +473,10 @@ class Whisper(nn.Module):
         captured HIP graph per (batch, device) — engine/decode.py; `decode.release_graphs(model)` frees what that pins.  "eager"
         (default): every step launch by launch on the kernels of the prefill.  weights="int8" (with step="graph"): the cached steps
         read per-row int8 images of the weight shadows (wft_gemm_nt_stream_q8; weight-only, activations stay bf16; encoder, prefill and
-        cross key / value projections stay bf16); beam_decode, sample_decode and decode_with_fallback take it too.  (`_capture` / `_stream_gemm`: decode.greedy_decode's two private A/B keywords.)
+        cross key / value projections stay bf16).  weights="w8a8" (with step="graph"): those three run int8 x int8 on per-row quantised
+        activations as well (wft_gemm_nt_i8, every Linear product with M > 32), the cached steps are the "int8" ones; the cached
+        steps' activations, products with M <= 32, the conv stem, the embedding lookup, the prefill's tied-logits product and
+        attention stay bf16 (engine/decode.py greedy_decode).  beam_decode, sample_decode and decode_with_fallback take it too.  (`_capture` / `_stream_gemm`: decode.greedy_decode's two private A/B keywords.)
         timestamp_begin (None: off): decode under upstream's timestamp rules, applied inside the pick kernel (include/wft.h
         "Timestamp rules"); no_timestamps / max_initial_timestamp_index: that column is removed / the first timestamp is at most
         this index.  `decode.timestamp_segments` turns the result into timed segments."""

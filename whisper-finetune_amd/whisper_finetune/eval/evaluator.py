@@ -48,7 +48,9 @@ def _greedy_predictions(model, tokenizer, x, y_in, step: str = "eager", beam: di
     SuppressTokens list of specials; `tokenizer.non_speech_tokens` too when the tokenizer has them), eot and the blank for a
     row's first token (upstream's SuppressBlank); at most n_text_ctx // 2 new tokens (upstream's sample_len).
     `step` is t_config["wft_eval_decode_step"]: "graph" = the captured step on the weight-streaming GEMMs (engine/decode.py).
-    `weights` is t_config["wft_eval_decode_weights"]: "int8" = those steps read int8 weights (weight-only; the WER of THIS int8 path).
+    `weights` is t_config["wft_eval_decode_weights"]: "int8" = those steps read int8 weights (weight-only; the WER of THIS int8 path);
+    "w8a8" = in addition the encoder, the prefill and the cross key / value projections run int8 x int8 on per-row quantised activations
+    (wft_gemm_nt_i8; engine/decode.py says what stays bf16).
     `beam` = {"beam_size", "patience"} (t_config["wft_eval_decode"] = "beam_search"): the same prefix, suppression and length rules
     through Whisper.beam_decode, the winning hypothesis of every utterance.
     `timestamps` (t_config["wft_eval_decode_timestamps"]): decode under upstream's timestamp rules, its command line's default mode —
@@ -158,12 +160,12 @@ def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict
         raise ValueError(f'wft_eval_decode_step: "eager" (the default) or "graph", got {decode_step!r}')
     decode_step = decode_step or "eager"
     decode_weights = t_config.get("wft_eval_decode_weights")
-    if decode_weights not in (None, "bf16", "int8"):
-        raise ValueError(f'wft_eval_decode_weights: "bf16" (the default) or "int8", got {decode_weights!r}')
+    if decode_weights not in (None, "bf16", "int8", "w8a8"):
+        raise ValueError(f'wft_eval_decode_weights: "bf16" (the default), "int8" or "w8a8", got {decode_weights!r}')
     decode_weights = decode_weights or "bf16"
-    if decode_weights == "int8" and (decode_mode is None or decode_step != "graph"):
-        raise ValueError('wft_eval_decode_weights: "int8" needs wft_eval_decode and wft_eval_decode_step: "graph" (only the captured '
-                         'steps run on the kernels that read int8 weights)')
+    if decode_weights in ("int8", "w8a8") and (decode_mode is None or decode_step != "graph"):
+        raise ValueError(f'wft_eval_decode_weights: "{decode_weights}" (one of "bf16", "int8", "w8a8") needs wft_eval_decode and '
+                         'wft_eval_decode_step: "graph" (only the captured steps run on the kernels that read int8 weights)')
     decode_ts = t_config.get("wft_eval_decode_timestamps", False)
     if not isinstance(decode_ts, bool):
         raise ValueError(f"wft_eval_decode_timestamps: true or false, got {decode_ts!r}")
