@@ -92,7 +92,10 @@ def test_one_dropped_key_of_448_is_reported():
     2.4e-1 of the head's own largest value, median 1.6e-2; 123 of 160 heads lie above 2^-7 and 37 below it.  So the bound does NOT
     separate a single lost key head by head, but a row of 20 heads (or 6) always has heads above it: the worst head of a row was
     never below 4.9e-2, six times the bound, and the row as a whole fails.  That, and that the mutant is never closer to the
-    reference than correct attention, is what is asserted."""
+    reference than correct attention, is what is asserted.
+    Separating a single key head by head is not this file's job any more: on the probe operands of tests/_decode_probe.py one lost,
+    leaked or double-counted key moves its (row, head) by at least 4 x 2^-7 (tests/test_decode_probe_host.py on the CPU,
+    tests/test_decode_probe_gpu.py for every decode kernel and split regime)."""
     H = 20
     above = total = 0
     for seed in range(8):
