@@ -5,6 +5,7 @@
 //
 // All kernels are HBM-bound: 4 B read and 2 + 2 B written per weight element, 64x64 tiles through LDS for the transposed side,
 // 16-byte loads and 8-byte stores where the layout allows (checked on the host: `fast`).
+// Per-element tests, bit for bit on whole buffers: tests/test_shadow_gpu.py (cases and references: tests/_shadow_cases.py).
 #include "common.h"
 
 // ----------------------------------------------------------------------------- casts
