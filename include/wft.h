@@ -517,7 +517,7 @@ int wft_decode_pick(const wft_decode_pick_args* args, void* stream);
 
 /* ---------------------------------------------------------- Beam search */
 /* Beam-search decoding on a KV cache shared between the beams (csrc/decode_attn.hip, csrc/decode_beam.hip; DESIGN.md §3 "Beam-search layouts"): upstream's
- * `BeamSearchDecoder` + `MaximumLikelihoodRanker` with `without_timestamps=True`, restated in engine/decode.py (neither is in the
+ * `BeamSearchDecoder` + `MaximumLikelihoodRanker` with `without_timestamps=True`, restated in engine/decode/beam.py (neither is in the
  * reference tree and openai-whisper is not a dependency: parity with the upstream binary is unpinned).  W = beam size (1..8);
  * audio a owns the R = B*W slot rows r = a*W + j.
  *

@@ -1,5 +1,5 @@
 """Test helper: beam search as its definition, in plain Python (lists and dictionaries, fp32 adds through numpy).  Imports nothing
-from the engine.  Written from the algorithm the package documents (engine/decode.py "beam search", include/wft.h), which restates
+from the engine.  Written from the algorithm the package documents (engine/decode/beam.py, include/wft.h), which restates
 upstream whisper's BeamSearchDecoder + MaximumLikelihoodRanker under without_timestamps=True:
 
   W = beam size, audio a owns rows r = a*W + j; C = round(W * patience) (Python's round).  One step per audio that is not done:

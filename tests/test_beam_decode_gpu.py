@@ -1,4 +1,4 @@
-"""Beam-search decoding end to end on the GPU (engine/decode.py beam_decode, BeamCache): whisper-tiny, B = 4 audios with ragged
+"""Beam-search decoding end to end on the GPU (engine/decode/beam.py beam_decode, BeamCache): whisper-tiny, B = 4 audios with ragged
 prompts of 4 + 2b tokens, W = 5 beams (20 rows per cached step).
 
 What is checked and against what:
@@ -183,7 +183,7 @@ def test_c_small_live_vocabulary_fills_the_lists_and_stops_early(case, monkeypat
     _check_final(cache, st)
     calls = []
     real = D.beam_update
-    monkeypatch.setattr(D, "beam_update", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    monkeypatch.setattr(D.beam, "beam_update", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
     res = {}
     for se in (1, 8):
         calls.clear()

@@ -1,4 +1,4 @@
-"""KV-cached greedy decoding end to end on the GPU (engine/decode.py, Whisper.greedy_decode) against the CPU oracle re-forwarded
+"""KV-cached greedy decoding end to end on the GPU (engine/decode/, Whisper.greedy_decode) against the CPU oracle re-forwarded
 over the growing prefix (tests/_decode_oracle.py): whisper-tiny, B = 4, ragged prompts of 4 + 2b tokens.
 
 Bounds.  Cached logits against the fp32 oracle: relative L2 < 2e-2, the bound tests/test_model_gpu.py holds teacher-forced engine

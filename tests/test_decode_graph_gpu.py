@@ -1,5 +1,5 @@
 """`greedy_decode(step="graph")`: the cached decoding step captured in a HIP graph and run on the weight-streaming small-M GEMMs
-(engine/decode.py, csrc/gemm_stream.hip), on the case of tests/test_decode_gpu.py (whisper-tiny, B = 4, ragged prompts of 4 + 2b
+(engine/decode/, csrc/gemm_stream.hip), on the case of tests/test_decode_gpu.py (whisper-tiny, B = 4, ragged prompts of 4 + 2b
 tokens, 28 steps) and on a large-v3-width model with 2 + 2 layers (the dimensions of tests/test_dispatch_regime_gpu.py) at B = 8
 and B = 32.
 

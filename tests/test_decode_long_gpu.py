@@ -1,4 +1,4 @@
-"""Greedy and beam-search decoding to the END of the cache (engine/decode.py, csrc/decode_*.hip): whisper-tiny, B = 4,
+"""Greedy and beam-search decoding to the END of the cache (engine/decode/, csrc/decode_*.hip): whisper-tiny, B = 4,
 max_len = n_text_ctx = 448, so every row is decoded up to position 447 — the lengths at which all four waves of the attention
 kernels own keys, the double-buffered key loop and the ancestry prefetch make further trips, wft_beam_update permutes columns
 256 and up, rows end at the cache's capacity and a captured step is replayed several hundred times.  The short tests

@@ -1,4 +1,4 @@
-"""Sampled decoding end to end on the GPU (engine/decode.py sample_decode, SampleCache, no_speech_prob, decode_with_fallback and the
+"""Sampled decoding end to end on the GPU (engine/decode/ sample_decode, SampleCache, no_speech_prob, decode_with_fallback and the
 evaluator's `fallback` mode): whisper-tiny, the case of tests/test_beam_decode_gpu.py (B = 4 audios, ragged prompts of 4 + 2b
 tokens), N = 5 samples per audio (20 rows per cached step), 10 steps.
 

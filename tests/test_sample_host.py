@@ -177,7 +177,7 @@ def _ladder(monkeypatch, gen, slp):
         return fn
 
     for kind in ("greedy_decode", "beam_decode", "sample_decode"):
-        monkeypatch.setattr(D, kind, decode(kind))
+        monkeypatch.setattr(D.fallback, kind, decode(kind))
     return calls
 
 

@@ -17,7 +17,7 @@ import torch
 from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from .. import runtime as _rt
-from . import decode as _decode
+from . import gemm_mode as _mode
 from . import kernels as K
 from . import lib as L
 
@@ -217,7 +217,7 @@ class LinearGroup:
     def shadows_q8(self, weights, biases, loras=None):
         """(Q int8 [Npad, K], scale f32 [Npad], bias): the per-row int8 image of this group's OWN bf16 shadow `W`
         (wft_quantize_rows_i8) — with it the merged LoRA delta and the folded query scale — for the weight-only int8 steps of
-        decoding (decode.stream_gemm(weights="int8")).  Cached under the key of `W`: whatever refreshes `W` (an optimizer step, a new
+        decoding (gemm_mode.stream_gemm(weights="int8")).  Cached under the key of `W`: whatever refreshes `W` (an optimizer step, a new
         LoRA mask, a batched refresh plan) makes the next call requantise, in place.  Nothing in training asks for it."""
         W, _, bias = self.shadows(weights, biases, need_t=False, loras=loras)
         if self.Q is None or self.Q.shape != W.shape:
@@ -905,15 +905,15 @@ def linear(x, group: LinearGroup, weights, biases, loras=None, residual=None, ge
     consuming Linear as gelu_pre / gelu_codes.  gelu_next_n (with gelu_out): out-features of that consumer — lets the pair use the
     one-byte form when both of its GEMMs qualify."""
     loras = list(loras) if loras is not None else [None] * len(weights)
-    if _decode.stream_gemm_active() and not torch.is_grad_enabled() and not (gelu_out and residual is not None):
-        # a cached decoding step (decode.stream_gemm): the weight-streaming kernel where the library serves the call; there is no
+    if _mode.stream_gemm_active() and not torch.is_grad_enabled() and not (gelu_out and residual is not None):
+        # a cached decoding step (gemm_mode.stream_gemm): the weight-streaming kernel where the library serves the call; there is no
         # backward, so the GELU call stores no gelu' and the stand-ins for the pre-activation are None
         has_lora = any(sp is not None for sp in loras)
         epi = L.EPI_GELU if gelu_out else L.EPI_NONE
         y = None
         # int8 weights where wft_gemm_nt_stream_q8_ok serves the shape (asked first: no image is built for a group it never serves);
         # otherwise the bf16 shadow, below
-        if _decode.stream_gemm_weights() == "int8" and K.gemm_nt_stream_q8_serves(x.shape[0], group.dims(weights)[2], x.shape[-1], epi):
+        if _mode.stream_gemm_weights() == "int8" and K.gemm_nt_stream_q8_serves(x.shape[0], group.dims(weights)[2], x.shape[-1], epi):
             Q, qs, bias = group.shadows_q8(weights, biases, loras=loras if has_lora else None)
             y = K.gemm_nt_stream_q8(x, Q, qs, bias=bias, residual=residual, epilogue=epi)
         if y is None:
@@ -921,8 +921,8 @@ def linear(x, group: LinearGroup, weights, biases, loras=None, residual=None, ge
             y = K.gemm_nt_stream(x, W, bias=bias, residual=residual, epilogue=epi)
         if y is not None:
             return (None, y, None) if gelu_out else y
-    if _decode.int8_gemm_active() and not torch.is_grad_enabled() and x.shape[0] > 32:
-        # the encoder / the prefill of decoding's weights="w8a8" (decode.int8_gemm): x quantised per row once per call, the int8 image of
+    if _mode.int8_gemm_active() and not torch.is_grad_enabled() and x.shape[0] > 32:
+        # the encoder / the prefill of decoding's weights="w8a8" (gemm_mode.int8_gemm): x quantised per row once per call, the int8 image of
         # the group's shadow (asked for here: shadow first, then image, both brought up to date in front of the product), one
         # wft_gemm_nt_i8.  No shape is excluded for speed: the mode is about uniform numerics.  M <= 32 stays on the bf16 kernels.
         epi = L.EPI_GELU if gelu_out else L.EPI_NONE
@@ -1218,10 +1218,10 @@ class TiedLogitsFn(torch.autograd.Function):
 
 
 def tied_logits(x, emb, group: LinearGroup):
-    """Front door of TiedLogitsFn; under decode.stream_gemm() and no_grad the product goes to the weight-streaming kernel where served."""
-    if _decode.stream_gemm_active() and not torch.is_grad_enabled():
+    """Front door of TiedLogitsFn; under gemm_mode.stream_gemm() and no_grad the product goes to the weight-streaming kernel where served."""
+    if _mode.stream_gemm_active() and not torch.is_grad_enabled():
         y = None
-        if _decode.stream_gemm_weights() == "int8" and K.gemm_nt_stream_q8_serves(x.shape[0], group.dims([emb])[2], x.shape[-1]):
+        if _mode.stream_gemm_weights() == "int8" and K.gemm_nt_stream_q8_serves(x.shape[0], group.dims([emb])[2], x.shape[-1]):
             Q, qs, _ = group.shadows_q8([emb], [None])
             y = K.gemm_nt_stream_q8(x, Q, qs)
         if y is None:

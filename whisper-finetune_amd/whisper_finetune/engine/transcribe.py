@@ -1,7 +1,7 @@
 """Language detection and long-form transcription: a recording in, timed segments of token ids out.
 
 Upstream's `whisper.decoding.detect_language` and the window loop of `whisper.transcribe.transcribe`, restated on the window decoders
-of engine/decode.py (openai-whisper is not a dependency: parity with its binary is unpinned).  Ids go in and ids come out — no
+of engine/decode/ (openai-whisper is not a dependency: parity with its binary is unpinned).  Ids go in and ids come out — no
 tokenizer, no audio file decoding: `audio` is mono f32, at 16 kHz or at the `sample_rate` it is declared with (then it is resampled
 on the device first: data/gpu_frontend.py `resample`, csrc/audio.hip `wft_resample_f32`).
 
@@ -15,7 +15,7 @@ functions.
 
 `word_timestamps=True`: every iteration aligns the windows it has just decoded — ONE `find_alignment` call per distinct sot sequence
 over the rows that have segments, on the encoder output the decoders used, with the word spans formed on the device
-(csrc/align.hip `wft_word_spans`) — then upstream's string rules (engine/decode.py `add_word_timestamps`), its seek-to-the-last-word
+(csrc/align.hip `wft_word_spans`) — then upstream's string rules (engine/decode/words.py `add_word_timestamps`), its seek-to-the-last-word
 rule and, with `hallucination_silence_threshold`, its hallucination filter (`word_seek`).  Strings come from the caller's
 `split_words`; ids go in and ids come out as before.
 

@@ -208,7 +208,7 @@ class MultiHeadAttention(nn.Module):
         return out.view(B, T, d), None
 
     def _forward_cached(self, x: Tensor, xa: Optional[Tensor], cache: "_decode.KVCache", residual: Optional[Tensor]):
-        """Inference with a KVCache (engine/decode.py).  T > 1: the prefill — the teacher-forced kernels over the right-padded prompts,
+        """Inference with a KVCache (engine/decode/).  T > 1: the prefill — the teacher-forced kernels over the right-padded prompts,
         the k / v rows stored into the cache.  T = 1: a cached step on the single-token kernel (csrc/decode_attn.hip), which appends
         the step's k / v itself.  Cross-attention keys / values are projected once per audio batch.
         The cache hides its layout (store_prefill / self_step / cross_step): with a BeamCache the prefill carries ONE row per audio
@@ -465,18 +465,18 @@ class Whisper(nn.Module):
                       suppress=(), suppress_first=(), sync_every: int = 8, step: str = "eager", timestamp_begin: Optional[int] = None,
                       no_timestamps: Optional[int] = None, max_initial_timestamp_index: Optional[int] = 50, weights: str = "bf16",
                       _capture: bool = True, _stream_gemm: bool = True):
-        """KV-cached greedy decoding, token ids in and out (engine/decode.py; upstream: whisper.decoding's greedy path with
+        """KV-cached greedy decoding, token ids in and out (engine/decode/; upstream: whisper.decoding's greedy path with
         DecodingOptions(without_timestamps=True)).  mel f32 [B, n_mels, 2 * n_audio_ctx]; prompt i64 [B, T] right-padded, prompt_len [B]
         (None: all T long) -> (tokens i64 [B, L] padded with `eot` behind each row's end, lengths [B], sum_logprob f32 [B]).
         eval() semantics, no gradients; the host looks at the unfinished-row counter every `sync_every` steps only.
         step="graph": the cached steps run on the weight-streaming small-M GEMMs (csrc/gemm_stream.hip) and are replayed from one
-        captured HIP graph per (batch, device) — engine/decode.py; `decode.release_graphs(model)` frees what that pins.  "eager"
+        captured HIP graph per (batch, device) — engine/decode/; `decode.release_graphs(model)` frees what that pins.  "eager"
         (default): every step launch by launch on the kernels of the prefill.  weights="int8" (with step="graph"): the cached steps
         read per-row int8 images of the weight shadows (wft_gemm_nt_stream_q8; weight-only, activations stay bf16; encoder, prefill and
         cross key / value projections stay bf16).  weights="w8a8" (with step="graph"): those three run int8 x int8 on per-row quantised
         activations as well (wft_gemm_nt_i8, every Linear product with M > 32), the cached steps are the "int8" ones; the cached
         steps' activations, products with M <= 32, the conv stem, the embedding lookup, the prefill's tied-logits product and
-        attention stay bf16 (engine/decode.py greedy_decode).  beam_decode, sample_decode and decode_with_fallback take it too.  (`_capture` / `_stream_gemm`: decode.greedy_decode's two private A/B keywords.)
+        attention stay bf16 (engine/decode/ greedy_decode).  beam_decode, sample_decode and decode_with_fallback take it too.  (`_capture` / `_stream_gemm`: decode.greedy_decode's two private A/B keywords.)
         timestamp_begin (None: off): decode under upstream's timestamp rules, applied inside the pick kernel (include/wft.h
         "Timestamp rules"); no_timestamps / max_initial_timestamp_index: that column is removed / the first timestamp is at most
         this index.  `decode.timestamp_segments` turns the result into timed segments."""
@@ -491,7 +491,7 @@ class Whisper(nn.Module):
                     return_all: bool = False, timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
                     max_initial_timestamp_index: Optional[int] = 50, weights: str = "bf16", _capture: bool = True,
                       _stream_gemm: bool = True):
-        """KV-cached beam search (engine/decode.py beam_decode; upstream: whisper.decoding's BeamSearchDecoder + MaximumLikelihoodRanker
+        """KV-cached beam search (engine/decode/ beam_decode; upstream: whisper.decoding's BeamSearchDecoder + MaximumLikelihoodRanker
         with DecodingOptions(without_timestamps=True), restated there — parity with the upstream binary is unpinned).  Arguments and
         result layout as greedy_decode, for the winning hypothesis of every audio; beam_size 1..8; the beams of an audio share its
         cross keys / values and no self-attention key is ever copied.  return_all adds every audio's ranked hypotheses.
@@ -507,7 +507,7 @@ class Whisper(nn.Module):
                       sync_every: int = 8, step: str = "eager", timestamp_begin: Optional[int] = None, no_timestamps: Optional[int] = None,
                       max_initial_timestamp_index: Optional[int] = 50, weights: str = "bf16", _capture: bool = True,
                       _stream_gemm: bool = True):
-        """KV-cached sampling (engine/decode.py sample_decode; upstream: GreedyDecoder at temperature > 0 with best_of samples and the
+        """KV-cached sampling (engine/decode/ sample_decode; upstream: GreedyDecoder at temperature > 0 with best_of samples and the
         MaximumLikelihoodRanker, restated there — parity with the upstream binary and with torch's random stream is unpinned).
         Arguments and result layout as greedy_decode, for the best of the `best_of` (1..8) samples of every audio; every token is
         drawn on the device from softmax(logits / temperature) (include/wft.h "Sampled decoding"), reproducibly from `seed` (an int,
@@ -521,7 +521,7 @@ class Whisper(nn.Module):
                                      _capture=_capture, _stream_gemm=_stream_gemm)
 
     def decode_with_fallback(self, mel: Tensor, prompt: Tensor, prompt_len=None, **kw):
-        """Upstream's temperature ladder (`transcribe()`'s decode_with_fallback; engine/decode.py decode_with_fallback has the
+        """Upstream's temperature ladder (`transcribe()`'s decode_with_fallback; engine/decode/ decode_with_fallback has the
         keywords): greedy_decode / beam_decode at temperature 0, sample_decode(best_of) at each higher temperature for the audios
         whose result fails the average log-probability / compression ratio / no-speech tests (`decode.needs_fallback`)
         -> (tokens, lengths, sum_logprob, info).  The encoder runs once.  The fp32 compute mode raises."""
@@ -535,13 +535,13 @@ class Whisper(nn.Module):
         self.register_buffer("alignment_heads", mask.to(self.alignment_heads.device).to_sparse(), persistent=False)
 
     def find_alignment(self, mel: Tensor, text_tokens, **kw):
-        """Word-level timestamps for decoded text (engine/decode.py find_alignment has the keywords; upstream: whisper/timing.py
+        """Word-level timestamps for decoded text (engine/decode/ find_alignment has the keywords; upstream: whisper/timing.py
         find_alignment, restated — parity with the upstream binary is unpinned): the cross-attention probabilities of the
         `alignment_heads`, standardised, median-filtered and averaged, then dynamic time warping, all on the device (csrc/align.hip)
         -> per audio [(start_s, end_s, probability, [token ids])].  word_spans="device" also forms the word boundaries and mean
         probabilities on the device (wft_word_spans) and reads back the three word arrays only; `_xa`: the encoder output, when the
         caller has it (`embed_audio` is not called then).  Upstream's string rules on top of the words (`merge_punctuations`,
-        `add_word_timestamps`) are host functions of engine/decode.py; `transcribe(word_timestamps=True)` applies them.  The fp32
+        `add_word_timestamps`) are host functions of engine/decode/; `transcribe(word_timestamps=True)` applies them.  The fp32
         compute mode raises."""
         return _decode.find_alignment(self, mel, text_tokens, **kw)
 

@@ -47,10 +47,10 @@ def _greedy_predictions(model, tokenizer, x, y_in, step: str = "eager", beam: di
     the start-of-transcript sequence; every special token but eot is suppressed (upstream's notimestamps decoding plus its
     SuppressTokens list of specials; `tokenizer.non_speech_tokens` too when the tokenizer has them), eot and the blank for a
     row's first token (upstream's SuppressBlank); at most n_text_ctx // 2 new tokens (upstream's sample_len).
-    `step` is t_config["wft_eval_decode_step"]: "graph" = the captured step on the weight-streaming GEMMs (engine/decode.py).
+    `step` is t_config["wft_eval_decode_step"]: "graph" = the captured step on the weight-streaming GEMMs (engine/decode/).
     `weights` is t_config["wft_eval_decode_weights"]: "int8" = those steps read int8 weights (weight-only; the WER of THIS int8 path);
     "w8a8" = in addition the encoder, the prefill and the cross key / value projections run int8 x int8 on per-row quantised activations
-    (wft_gemm_nt_i8; engine/decode.py says what stays bf16).
+    (wft_gemm_nt_i8; engine/decode/ says what stays bf16).
     `beam` = {"beam_size", "patience"} (t_config["wft_eval_decode"] = "beam_search"): the same prefix, suppression and length rules
     through Whisper.beam_decode, the winning hypothesis of every utterance.
     `timestamps` (t_config["wft_eval_decode_timestamps"]): decode under upstream's timestamp rules, its command line's default mode —
