@@ -779,6 +779,68 @@ int wft_resample_f32(const float* in, int64_t ld_in, int64_t n_in, const float* 
                      float* out, int64_t ld_out, int64_t n_out, int B, void* stream);
 int wft_resample_tile(int orig, int new_rate, int width);
 
+/* ------------------------------------------------- Time stretch (audio-domain augmentation) */
+/* The reference's baseline pipeline is audiomentations' TimeStretch(min_rate, max_rate, leave_length_unchanged=False, p=1.0) on the
+ * raw clip, in front of the log-mel.  The algorithm restated here is the one audiomentations calls `librosa_phase_vocoder`, i.e.
+ * librosa.effects.time_stretch.  Neither library is a dependency: parity with their binaries is unpinned.  DEVIATION: current
+ * audiomentations defaults to a C++ time-stretching library (method "signalsmith_stretch") that cannot be restated; this is the
+ * phase-vocoder method, not that default.
+ *
+ * For one row y of n samples and a float64 rate, with N = 2048 and H = 512:
+ *  1. STFT.  y is zero-padded by N/2 samples on both sides (center=True, pad_mode="constant": NOT reflect).  F = 1 + n / H frames
+ *     (integer division); frame t is the padded samples t H .. t H + N - 1 times the periodic Hann w_i = 0.5 - 0.5 cos(2 pi i / N);
+ *     D[t, k], k = 0 .. 1024, is its one-sided DFT.
+ *  2. Vocoder.  T = ceil(F / rate) in float64 (the length of numpy's arange(0, F, rate)); D is extended by two zero frames.
+ *     For t = 0 .. T - 1: step = t * rate in float64, i = floor(step), alpha = step - i,
+ *       mag = (1 - alpha) |D[i]| + alpha |D[i + 1]|,  S[t] = mag * P[t],
+ *       P[0] = u(D[0]),  P[t + 1] = P[t] * u(D[i + 1]) * conj(u(D[i])),
+ *     u(c) = c / |c|, and u(c) = 1 whenever |c| == 0, whatever the signs of its zeros (numpy's angle(-0 + 0j) = pi must not leak
+ *     into a bin: the loader's clips are zero-padded).  This is librosa's accumulator phase_acc += phi_advance + wrap(dangle -
+ *     phi_advance) taken modulo 2 pi (the phi_advance terms cancel modulo 2 pi); in float64 the two forms agree to 1e-9 on the
+ *     test cases (tests/test_stretch_host.py).  The product needs no fp32 angle accumulator, which would reach 2e6 rad and lose
+ *     every bit of the phase; P is renormalised every step.  step, its floor and alpha are formed in double in the kernel: a
+ *     column pair chosen one off is an O(1) error.
+ *  3. ISTFT.  The inverse one-sided DFT of every S[t] (the imaginary parts of bins 0 and 1024 do not count) times the same window,
+ *     overlap-added at hop H — each output sample sums its <= 4 frames in ascending t — and divided by the window's sum of squares
+ *     over the same frames wherever that exceeds FLT_MIN; the first N/2 samples are dropped; the output has
+ *     n_out = (int)rint(n / rate) samples in float64 (half to even), zeros where no frame reaches.
+ * rate == 1.0 is not special-cased.  Rates lie inside [rate_lo, 2.0] with 0.5 <= rate_lo: rate_lo is the HOST's lower bound of the
+ * device-side rates, and sizes the grids and the workspace.  A row whose rate lies outside (or is NaN) is not processed: nothing of
+ * its output row is written and n_out[b] = -1; no store leaves the buffers whatever the device-side rates hold.
+ *
+ *  in f32: row b at in + b * ld_in, n_in samples (1 <= n_in <= 2^26), what lies behind them is never read.  rates f64 [B], n_out
+ *  i32 [B] (written), both in device memory.  out f32: row b at out + b * ld_out, ld_out >= rint(n_in / rate_lo); exactly
+ *  n_out[b] samples of row b are written and what lies behind them is left untouched.
+ *  workspace: wft_time_stretch_workspace_bytes(B, n_in, rate_lo) bytes (-1: bad arguments), 8-byte aligned:
+ *    D f32 [B, F, 1025, 2] followed by S f32 [B, T_max, 1025, 2], T_max = ceil(F / rate_lo).  At 30 s (n_in = 480000, F = 938) D
+ *    is 7.7 MB per clip and S up to 15.4 MB at rate_lo = 0.5: the caller may process rows in chunks to cap it.
+ *  The bits of a row depend on its samples, its rate and n_in only: not on B, its batch partners, rate_lo or the launch.  No atomics.
+ *  All entry points enqueue on `stream`, do not synchronise and do not allocate; every argument is checked before the first launch.
+ * The three stages, exported so that a failure can be localised; wft_time_stretch_f32 is exactly these three in order:
+ *  wft_stretch_stft_f32     in -> D.  One workgroup per (frame, row), the 2048-point FFT in LDS (16 KiB of complex f32, twiddles from
+ *                           a sincospif table built once per workgroup).
+ *  wft_stretch_vocoder_f32  D -> S: frames t < T_b of row b are written, the others are left untouched.
+ *  wft_stretch_istft_f32    S -> out, n_out.  S IS OVERWRITTEN: the windowed frame t takes the first 2048 floats of the 2050 that
+ *                           S[b, t] occupies.                                                                                   */
+int64_t wft_time_stretch_workspace_bytes(int B, int64_t n_in, double rate_lo);
+int wft_time_stretch_f32(const float* in, int64_t ld_in, int64_t n_in, const double* rates, double rate_lo, float* out,
+                         int64_t ld_out, int32_t* n_out, void* workspace, int64_t workspace_bytes, int B, void* stream);
+int wft_stretch_stft_f32(const float* in, int64_t ld_in, int64_t n_in, float* D, int B, void* stream);
+int wft_stretch_vocoder_f32(const float* D, int64_t n_in, const double* rates, double rate_lo, float* S, int B, void* stream);
+int wft_stretch_istft_f32(float* S, int64_t n_in, const double* rates, double rate_lo, float* out, int64_t ld_out,
+                          int32_t* n_out, int B, void* stream);
+/* Log-mel of rows of different lengths (the stretched clips), same filters and per-frame arithmetic as wft_logmel (one device
+ * body: equal samples give equal bits).  Row b at audio + b * ld_audio has n_samples[b] samples (device i32, clamped to
+ * [0, max_samples]; max_samples > 400 is the host's upper bound and sizes the grid) and frames_b = n_samples[b] / 160 frames; the
+ * reflect padding uses n_samples[b], which need not be a multiple of 160.  The `max - 8` floor takes the maximum over ALL frames_b
+ * frames, also those at or beyond T_out (the reference takes the log-mel of the whole stretched clip before pad_or_trim).
+ * out f32 [B, n_mels, T_out]: columns < kept = min(keep_frames[b], frames_b, T_out) hold the normalised log-mel, the columns behind
+ * them the minimum of the kept columns (the reference's min-value pad_or_trim and its cut at a partial segment; the clamp and
+ * (v + 4) / 4 are monotone, so it is the minimum of the computed values bit for bit); kept == 0: the whole row is 0.
+ * stats: f32 [2 B] workspace.                                                                                                  */
+int wft_logmel_ragged(const float* audio, int64_t ld_audio, const int32_t* n_samples, const int32_t* keep_frames,
+                      const float* filters, float* out, float* stats, int B, int max_samples, int n_mels, int T_out, void* stream);
+
 /* ---------------------------------------------------------------- AdamW */
 /* torch.optim.AdamW single-tensor step over a flat f32 range
  * (model/optimizer.py:240-262 → optimizer.step() in model_utils.py:122).

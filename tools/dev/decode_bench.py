@@ -62,7 +62,13 @@
          The kernel should be HBM-bound; no figure is claimed in advance.
          (--parts resample --out profiles/decode_bench_resample.jsonl)
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample] [--batches 1,8,32] [--out FILE]
+  stretch  the time-stretch augmentation of the loader (--batches is not used): K.time_stretch + K.logmel_ragged against the plain K.logmel
+         on [B, 480000] batches of 30 s clips, B = 32 and 96, rates uniform in [0.75, 1.25] (the production range) and all 0.5 (the
+         largest workspace): ms per call of each arm, alternating rounds in one process, and the stages of the stretch one by one.
+         A side kernel of the loader; no threshold is set.
+         (--parts stretch --out profiles/decode_bench_stretch.jsonl)
+
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample,stretch] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -961,6 +967,52 @@ def bench_resample(batches):
                            "copy = torch's copy of n_out samples per row from the same buffer, for the launch floor at this size"))
 
 
+def bench_stretch(batches):
+    """K.time_stretch + K.logmel_ragged against K.logmel on 30 s clips, and the three stages of the stretch alone."""
+    import numpy as np
+
+    from whisper_finetune.data.gpu_frontend import mel_filters
+
+    filt = mel_filters(80).to(DEV)
+    lib = L.load()
+    n = 480000
+    for B in (32, 96):
+        g = torch.Generator().manual_seed(B)
+        x = (torch.randn(B, n, generator=g) * 0.1).to(DEV)
+        x[:, 300000:] = 0  # zero-padded clips, as the loader stages them
+        keep = torch.full((B,), 3000, dtype=torch.int32, device=DEV)
+        for name, rates in (("uniform [0.75, 1.25]", np.random.default_rng(B).uniform(0.75, 1.25, B)), ("all 0.5", np.full(B, 0.5))):
+            rate_lo = float(rates.min())
+
+            def stretched():
+                out, n_out = K.time_stretch(x, rates)
+                return K.logmel_ragged(out, n_out, keep, filt, 3000)
+
+            res = ab({"stretch+ragged": stretched, "stretch": lambda: K.time_stretch(x, rates), "logmel": lambda: K.logmel(x, filt, 3000)},
+                     rounds=5, iters=3)
+            # the stages alone, on one chunk of rows that fits the wrapper's workspace cap
+            per_row = lib.wft_time_stretch_workspace_bytes(1, n, rate_lo)
+            nb = max(1, min(B, K.STRETCH_WORKSPACE_CAP // per_row))
+            F, T_max = 1 + n // 512, int(np.ceil((1 + n // 512) / rate_lo))
+            ws = torch.empty(nb * per_row, dtype=torch.uint8, device=DEV)
+            Dp, Sp = ws.data_ptr(), ws.data_ptr() + nb * F * 1025 * 8
+            rd = torch.from_numpy(rates[:nb].copy()).to(DEV)
+            out = torch.zeros(nb, int(round(n / rate_lo)), device=DEV)
+            n_out = torch.empty(nb, dtype=torch.int32, device=DEV)
+            p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+            stages = ab({"stft": lambda: lib.wft_stretch_stft_f32(p(x), n, n, C.c_void_p(Dp), nb, L.stream_ptr()),
+                         "vocoder": lambda: lib.wft_stretch_vocoder_f32(C.c_void_p(Dp), n, p(rd), rate_lo, C.c_void_p(Sp), nb, L.stream_ptr()),
+                         "istft": lambda: lib.wft_stretch_istft_f32(C.c_void_p(Sp), n, p(rd), rate_lo, p(out), out.stride(0), p(n_out), nb,
+                                                                   L.stream_ptr())}, rounds=5, iters=3)
+            emit(dict(part="stretch", B=B, rates=name, rate_lo=round(rate_lo, 4), rows_per_launch=nb, workspace_MB=round(nb * per_row / 1e6, 1),
+                      stretch_ragged_ms=round(res["stretch+ragged"][0], 3), stretch_ms=round(res["stretch"][0], 3), logmel_ms=round(res["logmel"][0], 3),
+                      added_ms=round(res["stretch+ragged"][0] - res["logmel"][0], 3), spread=round(res["stretch+ragged"][2], 3),
+                      stage_ms={k: round(v[0], 3) for k, v in stages.items()}, stage_rows=nb, T_max=T_max,
+                      note="ms per call, medians of alternating rounds; stretch_ms includes the wrapper's allocations (workspace, zeroed "
+                           "output) and its chunking; stage_ms are the three stages alone on stage_rows rows (the istft stage on spectra "
+                           "it has already overwritten: the same work)"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="attn,gemm,e2e")
@@ -973,7 +1025,8 @@ def main():
     emit(dict(part="env", device=torch.cuda.get_device_name(0), lib=L.load().wft_version().decode(), torch=torch.__version__))
     for part in a.parts.split(","):
         {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": lambda b: (bench_gemm_stream(b), bench_gemm_stream_q8(b)), "e2e_step": bench_e2e_step,
-         "gemm_i8": bench_gemm_i8, "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align, "transcribe": bench_transcribe, "resample": bench_resample}[part](batches)
+         "gemm_i8": bench_gemm_i8, "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align, "transcribe": bench_transcribe, "resample": bench_resample,
+         "stretch": bench_stretch}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

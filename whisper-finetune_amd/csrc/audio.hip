@@ -14,17 +14,28 @@
 #define NBIN 201
 #define FPB 16  // frames per block
 
-__global__ __launch_bounds__(256) void logmel_kernel(const float* audio, const float* filters, float* out,
-                                                      unsigned int* clipmax, int n_samples, int n_mels, int n_frames) {
+// One workgroup's 16 frames of one clip `a` of n_samples samples (reflect padding at both ends of THOSE samples).  Frames
+// fr < n_store are written (log10, not yet normalised) to orow[mI * ld_row + fr]; frames fr < n_max enter the clip maximum.
+// RAGGED (wft_logmel_ragged): also the minimum over the frames fr < n_keep, kept as an order-preserving key of the float's bits.
+// wft_logmel is the instantiation with n_store == n_max == n_frames: both entry points run this one body, so equal samples
+// give equal bits.
+__device__ __forceinline__ unsigned int f32_order_key(float f) {
+  const unsigned int u = __builtin_bit_cast(unsigned int, f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float f32_from_order_key(unsigned int k) {
+  return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+template <bool RAGGED>
+__device__ __forceinline__ void logmel_block(const float* a, const float* filters, float* orow, long ld_row, unsigned int* clipmax,
+                                             unsigned int* clipmin, int n_samples, int n_mels, int n_store, int n_max, int n_keep,
+                                             int f0) {
   __shared__ float span[(FPB - 1) * HOP + NFFT];  // 2800
   __shared__ __attribute__((aligned(16))) float frames[FPB][NFFT];  // windowed
   __shared__ __attribute__((aligned(8))) float tw[NFFT][2];         // (cos, sin)(2 pi i / 400)
   __shared__ float power[FPB][NBIN + 3];
   __shared__ float wmax[4];
   const int tid = threadIdx.x;
-  const int f0 = blockIdx.x * FPB;
-  const int b = blockIdx.y;
-  const float* a = audio + (long)b * n_samples;
   for (int i = tid; i < (FPB - 1) * HOP + NFFT; i += 256) {
     int idx = f0 * HOP + i - NFFT / 2;  // position in the un-padded clip
     if (idx < 0) idx = -idx;
@@ -122,7 +133,7 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* audio, const f
     mhi[tid] = (short)hi;
   }
   __syncthreads();
-  float lmax = -1.0e30f;
+  float lmax = -1.0e30f, lmin = 3.0e38f;
   for (int o = tid; o < n_mels * FPB; o += 256) {
     const int mI = o / FPB, f = o - mI * FPB;
     const float* fl = filters + (long)mI * NBIN;
@@ -131,10 +142,9 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* audio, const f
     for (int k = k0; k < k1; ++k) acc = fmaf(fl[k], power[f][k], acc);
     const float lg = log10f(fmaxf(acc, 1.0e-10f));
     const int fr = f0 + f;
-    if (fr < n_frames) {
-      out[((long)b * n_mels + mI) * n_frames + fr] = lg;
-      lmax = fmaxf(lmax, lg);
-    }
+    if (fr < n_store) orow[mI * ld_row + fr] = lg;
+    if (fr < n_max) lmax = fmaxf(lmax, lg);
+    if (RAGGED && fr < n_keep) lmin = fminf(lmin, lg);
   }
   lmax = wave_max(lmax);
   if ((tid & 63) == 0) wmax[tid >> 6] = lmax;
@@ -142,8 +152,22 @@ __global__ __launch_bounds__(256) void logmel_kernel(const float* audio, const f
   if (tid == 0) {
     const float mx = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
     // log10 values are >= -10, so (mx + 20) is a positive float: its bit pattern orders like an int
-    atomicMax(clipmax + b, __builtin_bit_cast(unsigned int, mx + 20.0f));
+    atomicMax(clipmax, __builtin_bit_cast(unsigned int, mx + 20.0f));
   }
+  if (RAGGED) {
+    lmin = -wave_max(-lmin);
+    __syncthreads();
+    if ((tid & 63) == 0) wmax[tid >> 6] = lmin;
+    __syncthreads();
+    if (tid == 0) atomicMin(clipmin, f32_order_key(fminf(fminf(wmax[0], wmax[1]), fminf(wmax[2], wmax[3]))));
+  }
+}
+
+__global__ __launch_bounds__(256) void logmel_kernel(const float* audio, const float* filters, float* out,
+                                                      unsigned int* clipmax, int n_samples, int n_mels, int n_frames) {
+  const int b = blockIdx.y;
+  logmel_block<false>(audio + (long)b * n_samples, filters, out + (long)b * n_mels * n_frames, n_frames, clipmax + b, nullptr,
+                      n_samples, n_mels, n_frames, n_frames, 0, blockIdx.x * FPB);
 }
 
 __global__ __launch_bounds__(256) void logmel_norm_kernel(float* out, const unsigned int* clipmax, long per_clip, long total) {
@@ -168,6 +192,60 @@ extern "C" int wft_logmel(const float* audio, const float* filters, float* out, 
   const long per_clip = (long)n_mels * n_frames, total = per_clip * B;
   hipLaunchKernelGGL(logmel_norm_kernel, dim3(ew_grid(total)), dim3(256), 0, s, out, (const unsigned int*)clipmax, per_clip,
                      total);
+  WFT_CHECK_LAUNCH();
+  return WFT_OK;
+}
+
+// --------------------------------------------------------------------------------- ragged log-mel
+// Row b has n_samples[b] samples (clamped to [0, max_samples]) and frames_b = n_samples[b] / 160 frames; kept = min(keep_frames[b],
+// frames_b, T_out) columns hold its normalised log-mel, the columns behind them the minimum of the kept ones (of none kept: 0).
+// stats u32 [2 B]: {clip maximum over ALL frames_b frames as wft_logmel keeps it, order key of the minimum over the kept frames}.
+__device__ __forceinline__ void ragged_row(const int* n_samples, const int* keep_frames, int b, int max_samples, int T_out, int& ns,
+                                           int& frames, int& kept) {
+  ns = min(max(n_samples[b], 0), max_samples);
+  frames = ns / HOP;
+  kept = min(min(max(keep_frames[b], 0), frames), T_out);
+}
+__global__ __launch_bounds__(256) void logmel_ragged_kernel(const float* audio, long ld_audio, const int* n_samples, const int* keep_frames,
+                                                             const float* filters, float* out, unsigned int* stats, int max_samples,
+                                                             int n_mels, int T_out) {
+  const int b = blockIdx.y, f0 = blockIdx.x * FPB;
+  int ns, frames, kept;
+  ragged_row(n_samples, keep_frames, b, max_samples, T_out, ns, frames, kept);
+  if (f0 >= frames) return;  // uniform over the workgroup, in front of every barrier
+  logmel_block<true>(audio + b * ld_audio, filters, out + (long)b * n_mels * T_out, T_out, stats + 2 * b, stats + 2 * b + 1, ns, n_mels,
+                     min(frames, T_out), frames, kept, f0);
+}
+__global__ __launch_bounds__(256) void logmel_ragged_norm_kernel(float* out, const unsigned int* stats, const int* n_samples,
+                                                                  const int* keep_frames, int max_samples, int T_out, long per_clip,
+                                                                  long total) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int b = (int)(i / per_clip);
+    const int t = (int)((i - b * per_clip) % T_out);
+    int ns, frames, kept;
+    ragged_row(n_samples, keep_frames, b, max_samples, T_out, ns, frames, kept);
+    if (kept == 0) { out[i] = 0.f; continue; }
+    const float mx = __builtin_bit_cast(float, stats[2 * b]) - 20.0f;
+    const float v = fmaxf(t < kept ? out[i] : f32_from_order_key(stats[2 * b + 1]), mx - 8.0f);
+    out[i] = (v + 4.0f) / 4.0f;
+  }
+}
+
+extern "C" int wft_logmel_ragged(const float* audio, int64_t ld_audio, const int32_t* n_samples, const int32_t* keep_frames,
+                                 const float* filters, float* out, float* stats, int B, int max_samples, int n_mels, int T_out,
+                                 void* stream) {
+  WFT_CHECK_ARG(audio && n_samples && keep_frames && filters && out && stats, "null pointer");
+  WFT_CHECK_ARG(B >= 1 && B <= 65535 && n_mels >= 1 && T_out >= 1, "bad shape");
+  WFT_CHECK_ARG(max_samples > NFFT && ld_audio >= max_samples, "max_samples must exceed 400 and fit the row");
+  hipStream_t s = (hipStream_t)stream;
+  (void)hipMemsetAsync(stats, 0, 2 * B * sizeof(float), s);
+  (void)hipMemset2DAsync(stats + 1, 2 * sizeof(float), 0xff, sizeof(float), B, s);  // the minimum's key starts at the largest
+  dim3 grid((max_samples / HOP + FPB - 1) / FPB, B);
+  hipLaunchKernelGGL(logmel_ragged_kernel, grid, dim3(256), 0, s, audio, (long)ld_audio, n_samples, keep_frames, filters, out,
+                     (unsigned int*)stats, max_samples, n_mels, T_out);
+  const long per_clip = (long)n_mels * T_out, total = per_clip * B;
+  hipLaunchKernelGGL(logmel_ragged_norm_kernel, dim3(ew_grid(total)), dim3(256), 0, s, out, (const unsigned int*)stats, n_samples,
+                     keep_frames, max_samples, T_out, per_clip, total);
   WFT_CHECK_LAUNCH();
   return WFT_OK;
 }

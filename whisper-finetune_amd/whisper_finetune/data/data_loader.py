@@ -11,9 +11,15 @@ data_loader.py:322-359,273-301), and the main process turns a pinned batch of ra
 Clips at another rate than 16 kHz (`get_dataloader(..., sample_rate=)`, one rate per loader): a worker pads the clip to
 30 * sample_rate samples and the main process resamples the staged [B, 30 * rate] batch to [B, 480000] with one
 `wft_resample_f32` launch in front of the log-mel.
+
+Time stretch (`apply_baseline_aug=True`: the reference's baseline audio augmentation, TimeStretch(min_rate, max_rate,
+leave_length_unchanged=False, p=1.0)): a worker only DRAWS the clip's rate; the main process stretches the staged zero-padded batch with
+`wft_time_stretch_f32` (the reference stretches the padded clip too) and takes the log-mel of the rows' different lengths with
+`wft_logmel_ragged`.  The reference neither rescales the timestamps nor `next_partial_segment_start` under a stretch; neither does this.
 """
 from __future__ import annotations
 
+import random
 import re
 from typing import Iterator, List, Optional, Sequence, Tuple
 
@@ -24,7 +30,7 @@ from torch.utils.data import DataLoader, Dataset
 
 from whisper_finetune.data import transforms as T
 from whisper_finetune.data.gpu_frontend import (HOP_LENGTH, N_FFT, N_FRAMES, N_SAMPLES, SAMPLE_RATE, GpuFrontend, check_rate,
-                                                draw_clip_params, mel_filters)
+                                                check_stretch_range, draw_clip_params, mel_filters)
 from whisper_finetune.data.utils import ExtremesFrequencyMasking, TimeWarpAugmenter, pad_or_trim
 
 CHUNK_LENGTH = 30
@@ -58,7 +64,15 @@ def log_mel_spectrogram(audio, n_mels: int = 80, padding: int = 0, device=None) 
 
 
 class AudioDataset(Dataset):
-    """Items: (audio f32 [30 * sample_rate] (480000 at the default 16 kHz), decoder_input i64, decoder_output i64, aug i32 [8], extremes i32 [2], cut_frames).
+    """Items: (audio f32 [30 * sample_rate] (480000 at the default 16 kHz), decoder_input i64, decoder_output i64, aug i32 [8], extremes i32 [2], cut_frames);
+    with `apply_baseline_aug` a seventh field, the clip's time-stretch rate as f64 (without it the items are the six fields, unchanged).
+
+    apply_baseline_aug: the rate is drawn as audiomentations draws it — Python's `random` module, one `random.random()` gate against
+    p = 1.0, then `random.uniform(min_rate, max_rate)` (BaseWaveformTransform.randomize_parameters, then TimeStretch's).  That order is
+    restated from the published source; audiomentations is not installed here, so it is unpinned.  The draw does not touch torch's
+    generator: the SpecAugment draw order is the same with and without it.  Rates outside [0.5, 2.0] or min > max raise ValueError.
+    apply_office_aug / apply_advanced_aug (room simulation, mp3 compression, background-noise files, biquad filters, pitch shift)
+    are not implemented and raise NotImplementedError.
 
     hu_dataset: indexable records {"audio": {"array", optional "sampling_rate"}, "text", "language", optional "prompt"}; a record
     whose "sampling_rate" is present and differs from the dataset's `sample_rate` raises ValueError (no mixed rates); tokenizer: whisper-style
@@ -69,6 +83,7 @@ class AudioDataset(Dataset):
     GpuMelLoader); `_calculate_mel` is the reference's per-clip form of the same arithmetic on the same kernels."""
 
     sample_rate, n_samples = SAMPLE_RATE, N_SAMPLES  # the defaults, also of an instance built without __init__
+    apply_baseline_aug = False
 
     def __init__(self, hu_dataset, tokenizer, device=None, no_timestamp_training: bool = False, n_mels: int = 80,
                  max_prompt_length: int = 223, prompt_use_rate: float = 0.5, no_timestamps_rate: float = 0.5,
@@ -78,13 +93,19 @@ class AudioDataset(Dataset):
                  bpe_dropout: float = 0.0, sample_rate: int = SAMPLE_RATE):
         self.sample_rate = check_rate(sample_rate)
         self.n_samples = CHUNK_LENGTH * self.sample_rate  # 30 s at the clips' own rate
-        if apply_baseline_aug or apply_office_aug or apply_advanced_aug:
-            raise NotImplementedError("audio-domain augmentation (model/augment.py) is outside the GPU hot path (SURVEY.md §2)")
+        refused = [name for name, on in (("apply_office_aug", apply_office_aug), ("apply_advanced_aug", apply_advanced_aug)) if on]
+        if refused:
+            raise NotImplementedError(f"{' and '.join(refused)}: the office and advanced audio pipelines (room simulation, mp3 compression, "
+                                      "background-noise files, biquad filters, pitch shift) are not implemented; "
+                                      "apply_baseline_aug (time stretch) is")
+        if apply_baseline_aug:
+            time_stretch_min_rate, time_stretch_max_rate = check_stretch_range(time_stretch_min_rate, time_stretch_max_rate)
         self.hu_dataset, self.tokenizer, self.n_mels, self.device = hu_dataset, tokenizer, n_mels, device
         self.no_timestamp_training = no_timestamp_training
         self.max_prompt_length, self.prompt_use_rate, self.no_timestamps_rate = max_prompt_length, prompt_use_rate, no_timestamps_rate
         self.spec_augment, self.extremes_spec_augment = spec_augment, extremes_spec_augment
-        self.apply_baseline_aug = self.apply_office_aug = self.apply_advanced_aug = False
+        self.apply_baseline_aug = bool(apply_baseline_aug)
+        self.apply_office_aug = self.apply_advanced_aug = False
         self.time_stretch_min_rate, self.time_stretch_max_rate = time_stretch_min_rate, time_stretch_max_rate
         self.bpe_dropout = bpe_dropout
         if spec_augment:
@@ -119,18 +140,36 @@ class AudioDataset(Dataset):
             return False
         return torch.rand(1).item() < self.spec_augment_p
 
+    def _draw_stretch_rate(self) -> float:
+        """audiomentations' draws for TimeStretch(p=1.0): the gate, then the rate (see the class docstring); 1.0 if the gate fails."""
+        if random.random() < 1.0:
+            return random.uniform(self.time_stretch_min_rate, self.time_stretch_max_rate)
+        return 1.0
+
     def _calculate_mel(self, audio_array, next_partial_segment_start: Optional[float], no_timestamps: bool) -> torch.Tensor:
-        """Per-clip form: log-mel -> cut at a partial segment + minimum-value pad -> [warp -> time mask -> freq mask] w.p. p
-        -> extremes masking, every stage a libwft kernel on the device."""
-        if self.aud_augment is not None:
-            audio_array = self.aud_augment(audio_array, sample_rate=16000)
+        """Per-clip form: [time stretch] -> log-mel -> cut at a partial segment + minimum-value pad -> [warp -> time mask -> freq mask]
+        w.p. p -> extremes masking, every stage a libwft kernel on the device."""
         if self.sample_rate != SAMPLE_RATE:
             raise ValueError(f"_calculate_mel is the per-clip 16 kHz form; clips at {self.sample_rate} Hz are resampled per batch by GpuMelLoader")
-        mel = log_mel_spectrogram(audio_array, n_mels=self.n_mels, device=self.device)
-        if no_timestamps and next_partial_segment_start is not None:
-            mel = mel[:, : int(next_partial_segment_start * self.num_frames_per_second)]
-        if mel.shape[1] != N_FRAMES:
-            mel = pad_or_trim(mel, N_FRAMES)
+        cut = (int(next_partial_segment_start * self.num_frames_per_second) if no_timestamps and next_partial_segment_start is not None
+               else N_FRAMES)
+        if self.apply_baseline_aug:  # the same two kernels as GpuMelLoader, on one row
+            from whisper_finetune.engine import kernels as K
+
+            dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+            row = torch.as_tensor(np.asarray(audio_array, dtype=np.float32)).to(dev)[None]
+            stretched, n_out = K.time_stretch(row, [self._draw_stretch_rate()])
+            key = (self.n_mels, row.device)
+            if key not in _FILTERS:
+                _FILTERS[key] = mel_filters(self.n_mels).to(row.device)
+            keep = torch.tensor([min(cut, N_FRAMES)], dtype=torch.int32, device=row.device)
+            mel = K.logmel_ragged(stretched, n_out, keep, _FILTERS[key], N_FRAMES)[0]
+        else:
+            mel = log_mel_spectrogram(audio_array, n_mels=self.n_mels, device=self.device)
+            if no_timestamps and next_partial_segment_start is not None:
+                mel = mel[:, : int(next_partial_segment_start * self.num_frames_per_second)]
+            if mel.shape[1] != N_FRAMES:
+                mel = pad_or_trim(mel, N_FRAMES)
         if self._should_apply_spec_augment():
             mel = self.time_warping(mel)
             mel = self.time_masking(mel)
@@ -248,8 +287,11 @@ class AudioDataset(Dataset):
         audio = np.pad(audio, (0, self.n_samples - audio.shape[0]), "constant")  # pad in the audio domain (negative pad raises, as upstream)
         cut = int(seg_start * self.num_frames_per_second) if (no_ts and seg_start is not None) else N_FRAMES
         params, ext = self._draw_aug_params()
-        return (torch.from_numpy(audio), torch.tensor(dec_in, dtype=torch.int64), torch.tensor(dec_out, dtype=torch.int64),
+        item = (torch.from_numpy(audio), torch.tensor(dec_in, dtype=torch.int64), torch.tensor(dec_out, dtype=torch.int64),
                 params, ext, cut)
+        if self.apply_baseline_aug:
+            item += (torch.tensor(self._draw_stretch_rate(), dtype=torch.float64),)
+        return item
 
 
 def collate_fn(data):
@@ -259,7 +301,8 @@ def collate_fn(data):
     y_out = pad_sequence(cols[2], batch_first=True, padding_value=-100)
     if len(cols) == 3:
         return pad_sequence(cols[0], batch_first=True, padding_value=0), y_in, y_out
-    return torch.stack(cols[0]), y_in, y_out, torch.stack(cols[3]), torch.stack(cols[4]), torch.tensor(cols[5], dtype=torch.int32)
+    out = (torch.stack(cols[0]), y_in, y_out, torch.stack(cols[3]), torch.stack(cols[4]), torch.tensor(cols[5], dtype=torch.int32))
+    return out + (torch.stack(cols[6]),) if len(cols) == 7 else out  # the time-stretch rates, f64 [B]
 
 
 class WarmupDatasetSampler(torch.utils.data.Sampler):
@@ -314,7 +357,11 @@ class GpuMelLoader:
 
     sample_rate != 16000: the staged batch is [B, 30 * sample_rate]; ONE K.resample launch turns it into [B, 480000] in front of the
     log-mel.  It is the resample of the zero-PADDED clip, so the filter's tail behind the clip's end is kept (it rings into the
-    padding for `width` input samples), as it would be for a clip that was padded before an offline resampler."""
+    padding for `width` input samples), as it would be for a clip that was padded before an offline resampler.
+
+    Batches of a dataset built with apply_baseline_aug carry a seventh field, the rates: resample (if any) -> K.time_stretch on the
+    zero-padded [B, 480000] batch -> K.logmel_ragged with keep_frames = min(cut, 3000) -> K.specaug.  Loaders built without the flag
+    (every dev loader) never stretch and run the path above unchanged."""
 
     def __init__(self, loader, frontend: GpuFrontend, training_aug: bool, sample_rate: int = SAMPLE_RATE):
         self.loader, self.frontend, self.training_aug = loader, frontend, training_aug
@@ -332,15 +379,16 @@ class GpuMelLoader:
         dev = self.frontend.device
         if self._copy_stream is None:
             self._copy_stream = torch.cuda.Stream(device=dev)
-        audio, y_in, y_out, params, ext, cut = batch
+        audio, y_in, y_out, params, ext, cut = batch[:6]
+        rates = batch[6] if len(batch) == 7 else None
         need_aug = bool(params[:, 0].any() or ext.any())  # decided on the host copies: no device sync
         with torch.cuda.stream(self._copy_stream):
             staged = [t.to(dev, non_blocking=True) for t in (audio, y_in, y_out, params, ext)]
             ev = torch.cuda.Event()
             ev.record(self._copy_stream)
-        return staged, cut, ev, need_aug
+        return staged, cut, ev, need_aug, rates
 
-    def _to_mel(self, staged, cut, ev, need_aug):
+    def _to_mel(self, staged, cut, ev, need_aug, rates=None):
         from whisper_finetune.engine import kernels as K
 
         cur = torch.cuda.current_stream(self.frontend.device)
@@ -351,10 +399,17 @@ class GpuMelLoader:
         audio, y_in, y_out, params, ext = staged
         if self.sample_rate != SAMPLE_RATE:
             audio = K.resample(audio, self.sample_rate, SAMPLE_RATE)  # [B, 30 * rate] -> [B, 480000]
-        mel = self.frontend.log_mel(audio)
-        for b in (cut < N_FRAMES).nonzero().flatten().tolist():  # rare: cut at a partial segment, pad with the min value
-            c = int(cut[b])
-            mel[b, :, c:] = mel[b, :, :c].min() if c > 0 else mel[b].min()
+        if rates is not None:
+            # the stretch of the zero-PADDED clip, as the reference does it; the rates are host values (they size the launch), the
+            # rows' lengths stay on the device; the cut and the minimum-value pad happen inside the ragged log-mel
+            stretched, n_out = K.time_stretch(audio, rates)
+            keep = cut.clamp(max=N_FRAMES).to(torch.int32).to(audio.device, non_blocking=True)
+            mel = K.logmel_ragged(stretched, n_out, keep, self.frontend.filters, N_FRAMES)
+        else:
+            mel = self.frontend.log_mel(audio)
+            for b in (cut < N_FRAMES).nonzero().flatten().tolist():  # rare: cut at a partial segment, pad with the min value
+                c = int(cut[b])
+                mel[b, :, c:] = mel[b, :, :c].min() if c > 0 else mel[b].min()
         if self.training_aug and need_aug:
             mel = K.specaug(mel, params, ext)
         return mel, y_in, y_out
@@ -362,10 +417,11 @@ class GpuMelLoader:
     def __iter__(self):
         dev = self.frontend.device
         if not self.prefetch:
-            for audio, y_in, y_out, params, ext, cut in self.loader:
+            for batch in self.loader:
+                audio, y_in, y_out, params, ext, cut = batch[:6]
                 need_aug = bool(params[:, 0].any() or ext.any())
                 staged = [t.to(dev, non_blocking=True) for t in (audio, y_in, y_out, params, ext)]
-                yield self._to_mel(staged, cut, None, need_aug)
+                yield self._to_mel(staged, cut, None, need_aug, batch[6] if len(batch) == 7 else None)
             return
         it = iter(self.loader)
         try:

@@ -111,6 +111,44 @@ def resample(audio, sample_rate, device=None) -> torch.Tensor:
     return out if a.dim() == 2 else out[0]
 
 
+# ------------------------------------------------------------------------------------------------- time stretch
+# audiomentations' TimeStretch(leave_length_unchanged=False) in its `librosa_phase_vocoder` form (librosa.effects.time_stretch), restated
+# (include/wft.h "Time stretch" states the definition).  Neither library is a dependency: parity with their binaries is unpinned, and
+# current audiomentations defaults to another method (a C++ library) that cannot be restated.
+STRETCH_MIN_RATE, STRETCH_MAX_RATE = K.STRETCH_MIN_RATE, K.STRETCH_MAX_RATE
+
+
+def check_stretch_range(min_rate, max_rate):
+    """The TimeStretch range of a loader -> (min, max) as floats; outside [0.5, 2.0] or min > max raises ValueError."""
+    lo, hi = float(min_rate), float(max_rate)
+    if not (STRETCH_MIN_RATE <= lo <= STRETCH_MAX_RATE and STRETCH_MIN_RATE <= hi <= STRETCH_MAX_RATE):
+        raise ValueError(f"time_stretch rates must lie in [{STRETCH_MIN_RATE}, {STRETCH_MAX_RATE}], got min_rate {min_rate}, max_rate {max_rate}")
+    if lo > hi:
+        raise ValueError(f"time_stretch_min_rate {min_rate} is larger than time_stretch_max_rate {max_rate}")
+    return lo, hi
+
+
+def time_stretch(audio, rate, device=None):
+    """audio stretched in time by `rate` (> 1: faster and shorter), on the device (K.time_stretch: the phase vocoder).
+
+    audio: f32, 1-D [n] or 2-D [B, n], a tensor or an array; a host input goes to `device` (default: the current GPU) first.
+    rate: one rate, or one per row, inside [0.5, 2.0] (ValueError otherwise).  Returns a list of B device tensors of their own
+    lengths round(n / rate_b) for 2-D input, or one tensor for 1-D input.  rate == 1.0 runs the same kernels."""
+    a = torch.as_tensor(audio)
+    if a.dim() not in (1, 2) or a.dtype != torch.float32 or a.numel() == 0:
+        raise ValueError(f"time_stretch: audio must be a non-empty float32 [n] or [B, n], got {a.dtype} {tuple(a.shape)}")
+    rows = a if a.dim() == 2 else a[None]
+    rates = K.stretch_rates(rate, rows.shape[0])  # before anything touches the device
+    if device is not None:
+        rows = rows.to(device)
+    elif not rows.is_cuda:
+        rows = rows.to(torch.device("cuda", torch.cuda.current_device()))
+    out, _ = K.time_stretch(rows, rates)
+    n = rows.shape[1]
+    parts = [out[b, :int(round(n / float(rates[b])))] for b in range(rows.shape[0])]
+    return parts if a.dim() == 2 else parts[0]
+
+
 from whisper_finetune.data.transforms import FrequencyMasking, TimeMasking, draw_mask_span  # noqa: E402,F401
 
 

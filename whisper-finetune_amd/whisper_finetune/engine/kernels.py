@@ -1263,6 +1263,79 @@ def resample(audio, orig: int, new: int, *, out=None):
     return out
 
 
+STRETCH_MIN_RATE, STRETCH_MAX_RATE = 0.5, 2.0
+STRETCH_WORKSPACE_CAP = 1 << 30  # bytes per launch: rows are processed in chunks above it (30 s at rate 0.5: 23 MB per row)
+
+
+def stretch_rates(rates, B: int):
+    """One rate or one per row (numbers, a list, an array or a HOST tensor) -> float64 numpy [B]; a rate outside [0.5, 2.0]
+    (or NaN) raises ValueError."""
+    import numpy as np
+
+    r = rates.detach().cpu().numpy() if torch.is_tensor(rates) else np.asarray(rates)
+    r = np.asarray(r, dtype=np.float64).reshape(-1)
+    if r.shape[0] == 1 and B > 1:
+        r = np.repeat(r, B)
+    if r.shape[0] != B:
+        raise ValueError(f"time_stretch: {r.shape[0]} rates for {B} rows")
+    if not bool(np.all((r >= STRETCH_MIN_RATE) & (r <= STRETCH_MAX_RATE))):
+        raise ValueError(f"time_stretch: rates must lie in [{STRETCH_MIN_RATE}, {STRETCH_MAX_RATE}], got {r.tolist()}")
+    return r
+
+
+def time_stretch(audio, rates):
+    """Phase-vocoder time stretch (wft_time_stretch_f32, include/wft.h "Time stretch").
+
+    audio f32 [B, n] on the device (stride(1) == 1); rates: one float64 rate or one per row, HOST values inside [0.5, 2.0]
+    (ValueError otherwise: they size the launch, so they are checked here and not on the device).
+    -> (out f32 [B, cap], n_out i32 [B] on the device): row b holds n_out[b] = round(n / rates[b]) samples followed by zeros up to
+    cap = round(n / min(rates)).  A row's bits depend on its samples, its rate and n only.  Rows go through the kernels in chunks
+    so that the workspace of one launch stays below STRETCH_WORKSPACE_CAP."""
+    _chk(audio, F32, "audio")
+    if audio.dim() != 2 or audio.shape[0] < 1 or audio.shape[1] < 1:
+        raise ValueError(f"time_stretch: audio must be [B, n] with B >= 1 and n >= 1, got {tuple(audio.shape)}")
+    if audio.stride(1) != 1 or (audio.shape[0] > 1 and audio.stride(0) < audio.shape[1]):
+        audio = audio.contiguous()
+    B, n = audio.shape
+    r = stretch_rates(rates, B)
+    rate_lo = float(r.min())
+    lib = L.load()
+    per_row = lib.wft_time_stretch_workspace_bytes(1, n, rate_lo)
+    if per_row < 0:
+        raise ValueError(f"time_stretch: rows of {n} samples are not supported by wft_time_stretch_f32")
+    cap = int(round(n / rate_lo))
+    out = torch.zeros((B, max(cap, 1)), dtype=F32, device=audio.device)
+    n_out = torch.empty(B, dtype=torch.int32, device=audio.device)
+    rates_d = torch.from_numpy(r).to(audio.device)
+    chunk = max(1, min(B, STRETCH_WORKSPACE_CAP // per_row))
+    ws = torch.empty(chunk * per_row, dtype=torch.uint8, device=audio.device)
+    ld_in = audio.stride(0) if B > 1 else max(audio.stride(0), n)
+    for b0 in range(0, B, chunk):
+        nb = min(chunk, B - b0)
+        L.check(lib.wft_time_stretch_f32(_p(audio[b0:]), ld_in, n, _p(rates_d[b0:]), rate_lo, _p(out[b0:]), out.stride(0), _p(n_out[b0:]),
+                                         _p(ws), nb * per_row, nb, L.stream_ptr()), "wft_time_stretch_f32")
+    return out, n_out
+
+
+def logmel_ragged(audio, n_samples, keep_frames, filters, T_out: int = 3000):
+    """Log-mel of rows of different lengths (wft_logmel_ragged): audio f32 [B, ld] on the device, n_samples / keep_frames i32 [B]
+    on the device (row b: n_samples[b] <= ld samples, n_samples[b] // 160 frames, the first min(keep_frames[b], frames, T_out)
+    columns kept and the rest filled with their minimum), filters f32 [n_mels, 201] -> f32 [B, n_mels, T_out]."""
+    _chk(audio, F32, "audio"); _chk(filters, F32, "filters")
+    _chk(n_samples, torch.int32, "n_samples"); _chk(keep_frames, torch.int32, "keep_frames")
+    audio = audio.contiguous(); filters = filters.contiguous()
+    n_samples = n_samples.contiguous(); keep_frames = keep_frames.contiguous()
+    B, ld = audio.shape
+    if n_samples.shape != (B,) or keep_frames.shape != (B,):
+        raise ValueError(f"logmel_ragged: n_samples and keep_frames must be [{B}], got {tuple(n_samples.shape)}, {tuple(keep_frames.shape)}")
+    n_mels = filters.shape[0]
+    out = torch.empty((B, n_mels, T_out), dtype=F32, device=audio.device)
+    stats = torch.empty(2 * B, dtype=F32, device=audio.device)
+    L.check(L.load().wft_logmel_ragged(_p(audio), ld, _p(n_samples), _p(keep_frames), _p(filters), _p(out), _p(stats), B, ld, n_mels,
+                                       T_out, L.stream_ptr()), "wft_logmel_ragged")
+    return out
+
+
 def mel_to_tmajor(mel, c_pad: int):
     _chk(mel, F32, "mel")
     mel = mel.contiguous()

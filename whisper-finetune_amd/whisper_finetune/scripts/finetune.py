@@ -258,7 +258,9 @@ def main(config: dict):
                                        sched_cfg["warmup_steps"] * t_cfg["accum_grad_steps"], d_cfg["batch_size"])
     sa = aug.get("spec_augment", {})
     ex = aug.get("extremes_spec_augment", {})
-    aa = aug.get("audio_augment", {})  # forwarded like the reference does: AudioDataset refuses what is out of scope
+    # forwarded like the reference does: apply_baseline_aug (time stretch, on the device: GpuMelLoader) is implemented, AudioDataset
+    # refuses the office and advanced pipelines by name; the dev loaders below never stretch
+    aa = aug.get("audio_augment", {})
     n_mels = rt.unwrap_model(model).dims.n_mels
     loader_kw = dict(n_mels=n_mels, no_timestamp_training=d_cfg.get("no_timestamp_training", False),
                      max_prompt_length=d_cfg.get("max_prompt_length", 223), prompt_use_rate=d_cfg.get("prompt_use_rate", 0.5),
