@@ -841,6 +841,41 @@ int wft_stretch_istft_f32(float* S, int64_t n_in, const double* rates, double ra
 int wft_logmel_ragged(const float* audio, int64_t ld_audio, const int32_t* n_samples, const int32_t* keep_frames,
                       const float* filters, float* out, float* stats, int B, int max_samples, int n_mels, int T_out, void* stream);
 
+/* ------------------------------------------------- IIR filter (audio-domain augmentation) */
+/* A cascade of S second-order sections over every row of a batch, each row with its own coefficients and its own length: the
+ * primitive behind the seven filters of the reference's advanced pipeline (low-/high-/band-pass, band-stop, low/high shelf, peaking;
+ * data/filters.py designs and draws them) and behind any user-supplied filter.
+ *
+ * Arithmetic (the contract).  sos f64 [B, S, 6] in device memory, section s of row b = b0 b1 b2 a0 a1 a2 with a0 == 1 (a0 is NOT
+ * read: the caller normalises).  Every section is direct form II transposed in fp64, as scipy.signal.sosfilt does it:
+ *     y = b0 x + z0;   z0 = b1 x - a1 y + z1;   z1 = b2 x - a2 y
+ * sections in index order (the y of one is the x of the next), zero initial state.  The input sample is widened to fp64 and the last
+ * section's output is rounded to f32 ONCE.  Row b filters its first n[b] samples (n: device i32 [B], clamped to [0, n_max] inside the
+ * kernels; NULL = n_max for every row); out[b, n[b] .. n_max) is written as zero; nothing at or behind n_max of an output row is
+ * touched and nothing at or behind n[b] of an input row is read.  A row whose S sections are all exactly 1 0 0 . 0 0 is copied bit
+ * for bit (the sign of zero included).  out == in with ld_out == ld_in is allowed (in place); any other overlap is refused.
+ *
+ * Parallel form.  The cascade is one linear system with 2 S states.  A row is cut into chunks of L = wft_sos_filter_chunk() samples:
+ * (1) every chunk runs from zero state and keeps its final state z_c; (2) column j of the L-step zero-input transition matrix M is
+ * the state after L zero-input steps of the same code from the unit state e_j; (3) a sequential scan per row, s_0 = 0,
+ * s_(c+1) = M s_c + z_c (the products summed in ascending column order, then z_c), gives every chunk its true initial state;
+ * (4) every chunk runs again from s_c and writes its outputs.  Exact in exact arithmetic; in fp64, with products and sums free to
+ * contract into FMAs, a row stays within delta = 2^-30 of the sequential recurrence, relative to the row's largest output
+ * (tests/_filter_cases.py measures the scheme and states the bound).  A workgroup owns G = wft_sos_filter_group() consecutive chunks,
+ * staged through LDS so that global traffic is coalesced.  L and G are compile-time constants; the bits of a row depend on its
+ * samples, its coefficients, n[b], L and G only: not on B, its batch partners or the launch.
+ *
+ *  in / out f32: row b at in + b * ld_in / out + b * ld_out, ld >= n_max, 1 <= n_max <= 2^30, 1 <= B <= 65535, 1 <= S <= 4.
+ *  workspace: wft_sos_filter_workspace_bytes(B, n_max, S) bytes (-1: bad arguments), 8-byte aligned: f64 [B, ceil(n_max / L), 2 S].
+ *  No atomics, no allocation, no synchronisation: three launches on `stream`.  Every host-visible argument is checked before the
+ *  first launch (WFT_ERR_ARG: null pointer, S outside 1..4, B or n_max out of range, a leading dimension smaller than n_max, a short
+ *  workspace, misalignment, partial overlap of in and out).                                                                       */
+int64_t wft_sos_filter_workspace_bytes(int B, int64_t n_max, int S);
+int wft_sos_filter_chunk(void);
+int wft_sos_filter_group(void);
+int wft_sos_filter_f32(const float* in, int64_t ld_in, const int32_t* n, int64_t n_max, const double* sos, int S, float* out,
+                       int64_t ld_out, void* workspace, int64_t workspace_bytes, int B, void* stream);
+
 /* ---------------------------------------------------------------- AdamW */
 /* torch.optim.AdamW single-tensor step over a flat f32 range
  * (model/optimizer.py:240-262 → optimizer.step() in model_utils.py:122).

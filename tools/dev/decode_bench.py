@@ -67,8 +67,11 @@
          largest workspace): ms per call of each arm, alternating rounds in one process, and the stages of the stretch one by one.
          A side kernel of the loader; no threshold is set.
          (--parts stretch --out profiles/decode_bench_stretch.jsonl)
+  filter   the filter augmentation of the loader (--batches is not used): wft_sos_filter_f32 on [32, 480000] and [96, 480000], one and
+         four sections, out of place and in place, the K.sos_filter wrapper, and torch's copy of the batch for scale.
+         (--parts filter --out profiles/decode_bench_filter.jsonl)
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample,stretch] [--batches 1,8,32] [--out FILE]
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample,stretch,filter] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -1013,6 +1016,44 @@ def bench_stretch(batches):
                            "it has already overwritten: the same work)"))
 
 
+def bench_filter(batches):
+    """wft_sos_filter_f32 on 30 s clips: ms per call and achieved bytes/s against the 12 bytes per sample of its three passes."""
+    import numpy as np
+
+    from whisper_finetune.data.filters import design
+
+    lib = L.load()
+    n = 480000
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    # gains <= 1, so that the in-place arm can filter its own output again and again without leaving the float32 range
+    filters = {1: design("peaking", center_freq=1000.0, gain_db=-6.0, q=1.0), 4: design("band_pass", center_freq=1000.0, bandwidth_fraction=1.0, order=4)}
+    for B in (32, 96):
+        g = torch.Generator().manual_seed(B)
+        x = (torch.randn(B, n, generator=g) * 0.1).to(DEV)
+        x[:, 300000:] = 0  # zero-padded clips, as the loader stages them
+        out, y = torch.empty_like(x), x.clone()
+        for S, sos in filters.items():
+            assert sos.shape[0] == S
+            sos_h = np.ascontiguousarray(np.broadcast_to(sos, (B, S, 6)))
+            sos_d = torch.from_numpy(sos_h).to(DEV)
+            need = lib.wft_sos_filter_workspace_bytes(B, n, S)
+            ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+            raw = lambda src, dst: lib.wft_sos_filter_f32(p(src), n, None, n, p(sos_d), S, p(dst), n, p(ws), need, B, L.stream_ptr())  # noqa: E731
+            res = ab({"out_of_place": lambda: raw(x, out), "in_place": lambda: raw(y, y), "wrapper": lambda: K.sos_filter(x, sos_h, out=out),
+                      "copy": lambda: out.copy_(x)}, rounds=7, iters=10)
+            nbytes = 12 * B * n
+            rec = dict(part="filter", B=B, n=n, S=S, chunk=lib.wft_sos_filter_chunk(), group=lib.wft_sos_filter_group(), bytes=nbytes,
+                       workspace_MB=round(need / 1e6, 2),
+                       note="ms per call, medians of alternating rounds; out_of_place / in_place: the raw call on a preallocated workspace; "
+                            "wrapper: K.sos_filter with host coefficients (its check, their upload and the workspace allocation included); "
+                            "bytes = 12 per sample (two reads, one write); copy = torch's copy of the batch, 8 bytes per sample")
+            for name, (med, mn, spread) in res.items():
+                rec[name + "_ms"], rec[name + "_min_ms"], rec[name + "_spread"] = round(med, 4), round(mn, 4), round(spread, 3)
+            rec["TBps"] = round(nbytes / (res["out_of_place"][0] * 1e-3) / 1e12, 3)
+            rec["share_of_hbm"] = round(nbytes / (res["out_of_place"][0] * 1e-3) / HBM, 3)
+            emit(rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="attn,gemm,e2e")
@@ -1026,7 +1067,7 @@ def main():
     for part in a.parts.split(","):
         {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": lambda b: (bench_gemm_stream(b), bench_gemm_stream_q8(b)), "e2e_step": bench_e2e_step,
          "gemm_i8": bench_gemm_i8, "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align, "transcribe": bench_transcribe, "resample": bench_resample,
-         "stretch": bench_stretch}[part](batches)
+         "stretch": bench_stretch, "filter": bench_filter}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

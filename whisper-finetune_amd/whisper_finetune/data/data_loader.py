@@ -16,6 +16,11 @@ Time stretch (`apply_baseline_aug=True`: the reference's baseline audio augmenta
 leave_length_unchanged=False, p=1.0)): a worker only DRAWS the clip's rate; the main process stretches the staged zero-padded batch with
 `wft_time_stretch_f32` (the reference stretches the padded clip too) and takes the log-mel of the rows' different lengths with
 `wft_logmel_ragged`.  The reference neither rescales the timestamps nor `next_partial_segment_start` under a stretch; neither does this.
+
+Filter augmentation (`filter_aug={...}`, an option of this project's own: the filter group of the reference's advanced pipeline, NOT
+`apply_advanced_aug`, which stays refused): a worker only DRAWS and designs the clip's filter (data/filters.py FilterAug, after the
+stretch-rate draw: the reference's Compose order); the main process runs `wft_sos_filter_f32` in place on the staged batch behind
+the resample and the stretch and in front of the log-mel.  The zero padding is filtered too, as the reference filters the padded clip.
 """
 from __future__ import annotations
 
@@ -29,6 +34,7 @@ from torch.nn.utils.rnn import pad_sequence
 from torch.utils.data import DataLoader, Dataset
 
 from whisper_finetune.data import transforms as T
+from whisper_finetune.data.filters import FilterAug, identity_sos
 from whisper_finetune.data.gpu_frontend import (HOP_LENGTH, N_FFT, N_FRAMES, N_SAMPLES, SAMPLE_RATE, GpuFrontend, check_rate,
                                                 check_stretch_range, draw_clip_params, mel_filters)
 from whisper_finetune.data.utils import ExtremesFrequencyMasking, TimeWarpAugmenter, pad_or_trim
@@ -65,7 +71,8 @@ def log_mel_spectrogram(audio, n_mels: int = 80, padding: int = 0, device=None) 
 
 class AudioDataset(Dataset):
     """Items: (audio f32 [30 * sample_rate] (480000 at the default 16 kHz), decoder_input i64, decoder_output i64, aug i32 [8], extremes i32 [2], cut_frames);
-    with `apply_baseline_aug` a seventh field, the clip's time-stretch rate as f64 (without it the items are the six fields, unchanged).
+    with `apply_baseline_aug` a seventh field, the clip's time-stretch rate as f64 (without it the items are the six fields, unchanged);
+    with `filter_aug` one more field behind those, the clip's filter as sos f64 [4, 6] (identity sections = "do not filter").
 
     apply_baseline_aug: the rate is drawn as audiomentations draws it — Python's `random` module, one `random.random()` gate against
     p = 1.0, then `random.uniform(min_rate, max_rate)` (BaseWaveformTransform.randomize_parameters, then TimeStretch's).  That order is
@@ -73,6 +80,9 @@ class AudioDataset(Dataset):
     generator: the SpecAugment draw order is the same with and without it.  Rates outside [0.5, 2.0] or min > max raise ValueError.
     apply_office_aug / apply_advanced_aug (room simulation, mp3 compression, background-noise files, biquad filters, pitch shift)
     are not implemented and raise NotImplementedError.
+    filter_aug: None, or a mapping of data/filters.py FilterAug's keywords (`p`, `kinds`); `{}` = its defaults.  It is the filter group
+    of the advanced pipeline alone.  The filter is drawn after the stretch rate, with Python's `random` (FilterAug's docstring states
+    the order), designed for 16 kHz (it runs behind the resample), and never touches torch's generator.
 
     hu_dataset: indexable records {"audio": {"array", optional "sampling_rate"}, "text", "language", optional "prompt"}; a record
     whose "sampling_rate" is present and differs from the dataset's `sample_rate` raises ValueError (no mixed rates); tokenizer: whisper-style
@@ -84,13 +94,14 @@ class AudioDataset(Dataset):
 
     sample_rate, n_samples = SAMPLE_RATE, N_SAMPLES  # the defaults, also of an instance built without __init__
     apply_baseline_aug = False
+    filter_aug = None
 
     def __init__(self, hu_dataset, tokenizer, device=None, no_timestamp_training: bool = False, n_mels: int = 80,
                  max_prompt_length: int = 223, prompt_use_rate: float = 0.5, no_timestamps_rate: float = 0.5,
                  spec_augment: bool = False, spec_augment_params: Optional[dict] = None, extremes_spec_augment: bool = False,
                  extremes_spec_augment_params: Optional[dict] = None, apply_baseline_aug: bool = False, apply_office_aug: bool = False,
                  apply_advanced_aug: bool = False, time_stretch_min_rate: float = 0.8, time_stretch_max_rate: float = 1.25,
-                 bpe_dropout: float = 0.0, sample_rate: int = SAMPLE_RATE):
+                 bpe_dropout: float = 0.0, sample_rate: int = SAMPLE_RATE, filter_aug: Optional[dict] = None):
         self.sample_rate = check_rate(sample_rate)
         self.n_samples = CHUNK_LENGTH * self.sample_rate  # 30 s at the clips' own rate
         refused = [name for name, on in (("apply_office_aug", apply_office_aug), ("apply_advanced_aug", apply_advanced_aug)) if on]
@@ -108,6 +119,9 @@ class AudioDataset(Dataset):
         self.apply_office_aug = self.apply_advanced_aug = False
         self.time_stretch_min_rate, self.time_stretch_max_rate = time_stretch_min_rate, time_stretch_max_rate
         self.bpe_dropout = bpe_dropout
+        if filter_aug is not None and (not hasattr(filter_aug, "keys") or not set(filter_aug.keys()) <= {"p", "kinds"}):
+            raise ValueError(f"filter_aug must be None or a mapping of FilterAug's keywords `p` and `kinds`, got {filter_aug!r}")
+        self.filter_aug = FilterAug(sample_rate=SAMPLE_RATE, **dict(filter_aug)) if filter_aug is not None else None
         if spec_augment:
             self.spec_augment_p = float(spec_augment_params.get("p", 1.0))
             if not 0.0 <= self.spec_augment_p <= 1.0:
@@ -146,8 +160,15 @@ class AudioDataset(Dataset):
             return random.uniform(self.time_stretch_min_rate, self.time_stretch_max_rate)
         return 1.0
 
+    def _draw_filter(self):
+        """The clip's filter for the per-clip form: sos f64 [1, 4, 6], or None without the option or when the draw says "do not filter"."""
+        if self.filter_aug is None:
+            return None
+        kind, _, sos = self.filter_aug.draw()
+        return None if kind is None else sos[None]
+
     def _calculate_mel(self, audio_array, next_partial_segment_start: Optional[float], no_timestamps: bool) -> torch.Tensor:
-        """Per-clip form: [time stretch] -> log-mel -> cut at a partial segment + minimum-value pad -> [warp -> time mask -> freq mask]
+        """Per-clip form: [time stretch] -> [filter] -> log-mel -> cut at a partial segment + minimum-value pad -> [warp -> time mask -> freq mask]
         w.p. p -> extremes masking, every stage a libwft kernel on the device."""
         if self.sample_rate != SAMPLE_RATE:
             raise ValueError(f"_calculate_mel is the per-clip 16 kHz form; clips at {self.sample_rate} Hz are resampled per batch by GpuMelLoader")
@@ -159,12 +180,22 @@ class AudioDataset(Dataset):
             dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
             row = torch.as_tensor(np.asarray(audio_array, dtype=np.float32)).to(dev)[None]
             stretched, n_out = K.time_stretch(row, [self._draw_stretch_rate()])
+            sos = self._draw_filter()
+            if sos is not None:
+                K.sos_filter(stretched, sos, n_out, out=stretched)
             key = (self.n_mels, row.device)
             if key not in _FILTERS:
                 _FILTERS[key] = mel_filters(self.n_mels).to(row.device)
             keep = torch.tensor([min(cut, N_FRAMES)], dtype=torch.int32, device=row.device)
             mel = K.logmel_ragged(stretched, n_out, keep, _FILTERS[key], N_FRAMES)[0]
         else:
+            sos = self._draw_filter()
+            if sos is not None:  # the same kernel as GpuMelLoader, on one row
+                from whisper_finetune.engine import kernels as K
+
+                dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+                row = torch.as_tensor(np.asarray(audio_array, dtype=np.float32)).to(dev)[None].clone()
+                audio_array = K.sos_filter(row, sos, out=row)[0]
             mel = log_mel_spectrogram(audio_array, n_mels=self.n_mels, device=self.device)
             if no_timestamps and next_partial_segment_start is not None:
                 mel = mel[:, : int(next_partial_segment_start * self.num_frames_per_second)]
@@ -291,6 +322,8 @@ class AudioDataset(Dataset):
                 params, ext, cut)
         if self.apply_baseline_aug:
             item += (torch.tensor(self._draw_stretch_rate(), dtype=torch.float64),)
+        if self.filter_aug is not None:
+            item += (torch.from_numpy(self.filter_aug.draw()[2]),)
         return item
 
 
@@ -302,7 +335,7 @@ def collate_fn(data):
     if len(cols) == 3:
         return pad_sequence(cols[0], batch_first=True, padding_value=0), y_in, y_out
     out = (torch.stack(cols[0]), y_in, y_out, torch.stack(cols[3]), torch.stack(cols[4]), torch.tensor(cols[5], dtype=torch.int32))
-    return out + (torch.stack(cols[6]),) if len(cols) == 7 else out  # the time-stretch rates, f64 [B]
+    return out + tuple(torch.stack(c) for c in cols[6:])  # the time-stretch rates f64 [B] and / or the filters f64 [B, 4, 6]
 
 
 class WarmupDatasetSampler(torch.utils.data.Sampler):
@@ -361,10 +394,24 @@ class GpuMelLoader:
 
     Batches of a dataset built with apply_baseline_aug carry a seventh field, the rates: resample (if any) -> K.time_stretch on the
     zero-padded [B, 480000] batch -> K.logmel_ragged with keep_frames = min(cut, 3000) -> K.specaug.  Loaders built without the flag
-    (every dev loader) never stretch and run the path above unchanged."""
+    (every dev loader) never stretch and run the path above unchanged.
 
-    def __init__(self, loader, frontend: GpuFrontend, training_aug: bool, sample_rate: int = SAMPLE_RATE):
+    Batches of a dataset built with filter_aug carry the filters f64 [B, 4, 6] as their last field: K.sos_filter runs in place behind
+    the resample and the stretch, over each row's full stretched length (n = n_out; 480000 without the stretch), so a filter's tail
+    rings into the zero padding as it does in the reference, which filters the padded clip.  A batch whose filters are all identity
+    launches nothing.  Which optional fields a batch carries is read from the dataset's flags (`stretch`, `filter_aug`: None = from
+    `loader.dataset`; a loader without a dataset, e.g. a list of batches, takes a seventh field for the rates as before)."""
+
+    def __init__(self, loader, frontend: GpuFrontend, training_aug: bool, sample_rate: int = SAMPLE_RATE, stretch: Optional[bool] = None,
+                 filter_aug: Optional[bool] = None):
         self.loader, self.frontend, self.training_aug = loader, frontend, training_aug
+        ds = getattr(loader, "dataset", None)
+        if stretch is None and ds is not None:
+            stretch = bool(getattr(ds, "apply_baseline_aug", False))
+        if filter_aug is None:
+            filter_aug = getattr(ds, "filter_aug", None) is not None
+        self.stretch, self.filter_aug = stretch, bool(filter_aug)
+        self._identity = torch.from_numpy(identity_sos())
         self.sample_rate = check_rate(sample_rate)
         self.sampler = getattr(loader, "sampler", None)  # infinite_iter() calls sampler.set_epoch(...)
         self.batch_size = getattr(loader, "batch_size", None)
@@ -374,21 +421,32 @@ class GpuMelLoader:
     def __len__(self):
         return len(self.loader)
 
+    def _optional(self, batch):
+        """(rates or None, sos or None) of a collated batch, by the flags.  An all-identity `sos` counts as None."""
+        stretch = (len(batch) == 7 and not self.filter_aug) if self.stretch is None else self.stretch
+        if len(batch) != 6 + int(stretch) + int(self.filter_aug):
+            raise ValueError(f"a batch of {len(batch)} fields from a loader with stretch={stretch}, filter_aug={self.filter_aug}")
+        rates = batch[6] if stretch else None
+        sos = batch[-1] if self.filter_aug else None
+        if sos is not None and bool((sos == self._identity).all()):
+            sos = None
+        return rates, sos
+
     def _stage(self, batch):
         """Issue the batch's H2D copies on the side stream; returns the device tensors and the event that orders them."""
         dev = self.frontend.device
         if self._copy_stream is None:
             self._copy_stream = torch.cuda.Stream(device=dev)
         audio, y_in, y_out, params, ext, cut = batch[:6]
-        rates = batch[6] if len(batch) == 7 else None
+        rates, sos = self._optional(batch)
         need_aug = bool(params[:, 0].any() or ext.any())  # decided on the host copies: no device sync
         with torch.cuda.stream(self._copy_stream):
             staged = [t.to(dev, non_blocking=True) for t in (audio, y_in, y_out, params, ext)]
             ev = torch.cuda.Event()
             ev.record(self._copy_stream)
-        return staged, cut, ev, need_aug, rates
+        return staged, cut, ev, need_aug, rates, sos
 
-    def _to_mel(self, staged, cut, ev, need_aug, rates=None):
+    def _to_mel(self, staged, cut, ev, need_aug, rates=None, sos=None):
         from whisper_finetune.engine import kernels as K
 
         cur = torch.cuda.current_stream(self.frontend.device)
@@ -403,9 +461,15 @@ class GpuMelLoader:
             # the stretch of the zero-PADDED clip, as the reference does it; the rates are host values (they size the launch), the
             # rows' lengths stay on the device; the cut and the minimum-value pad happen inside the ragged log-mel
             stretched, n_out = K.time_stretch(audio, rates)
+            if sos is not None:
+                K.sos_filter(stretched, sos, n_out, out=stretched)
             keep = cut.clamp(max=N_FRAMES).to(torch.int32).to(audio.device, non_blocking=True)
             mel = K.logmel_ragged(stretched, n_out, keep, self.frontend.filters, N_FRAMES)
         else:
+            if sos is not None:
+                if audio.stride(1) != 1 or not audio.is_contiguous():
+                    audio = audio.contiguous()
+                K.sos_filter(audio, sos, out=audio)  # in place on the staged (or resampled) copy
             mel = self.frontend.log_mel(audio)
             for b in (cut < N_FRAMES).nonzero().flatten().tolist():  # rare: cut at a partial segment, pad with the min value
                 c = int(cut[b])
@@ -421,7 +485,7 @@ class GpuMelLoader:
                 audio, y_in, y_out, params, ext, cut = batch[:6]
                 need_aug = bool(params[:, 0].any() or ext.any())
                 staged = [t.to(dev, non_blocking=True) for t in (audio, y_in, y_out, params, ext)]
-                yield self._to_mel(staged, cut, None, need_aug, batch[6] if len(batch) == 7 else None)
+                yield self._to_mel(staged, cut, None, need_aug, *self._optional(batch))
             return
         it = iter(self.loader)
         try:
@@ -443,8 +507,9 @@ def get_dataloader(hu_dataset, tokenizer, batch_size: int = 1, n_mels: int = 80,
                    spec_augment_params: Optional[dict] = None, extremes_spec_augment: bool = False,
                    extremes_spec_augment_params: Optional[dict] = None, apply_baseline_aug: bool = False, apply_office_aug: bool = False,
                    apply_advanced_aug: bool = False, time_stretch_min_rate: float = 0.8, time_stretch_max_rate: float = 1.25,
-                   bpe_dropout: float = 0.0, drop_last: bool = False, sample_rate: int = SAMPLE_RATE):
-    """`sample_rate`: the rate of every clip of `hu_dataset` (default 16000).  At another rate the clips are padded to
+                   bpe_dropout: float = 0.0, drop_last: bool = False, sample_rate: int = SAMPLE_RATE, filter_aug: Optional[dict] = None):
+    """`filter_aug`: None, or a mapping of FilterAug's keywords (AudioDataset's docstring): the filter augmentation of a TRAINING loader.
+    `sample_rate`: the rate of every clip of `hu_dataset` (default 16000).  At another rate the clips are padded to
     30 * sample_rate samples and resampled to 16 kHz on the device (GpuMelLoader); without a device the loader yields the padded
     native-rate clips."""
     print(f"Found {len(hu_dataset)} records in the dataset.")
@@ -453,7 +518,8 @@ def get_dataloader(hu_dataset, tokenizer, batch_size: int = 1, n_mels: int = 80,
                       spec_augment=spec_augment, spec_augment_params=spec_augment_params, extremes_spec_augment=extremes_spec_augment,
                       extremes_spec_augment_params=extremes_spec_augment_params, bpe_dropout=bpe_dropout,
                       apply_baseline_aug=apply_baseline_aug, apply_office_aug=apply_office_aug, apply_advanced_aug=apply_advanced_aug,
-                      time_stretch_min_rate=time_stretch_min_rate, time_stretch_max_rate=time_stretch_max_rate, sample_rate=sample_rate)
+                      time_stretch_min_rate=time_stretch_min_rate, time_stretch_max_rate=time_stretch_max_rate, sample_rate=sample_rate,
+                      filter_aug=filter_aug)
     if sampler is not None:
         shuffle = False  # DataLoader does not allow both
     loader = DataLoader(ds, batch_size=batch_size, sampler=sampler, shuffle=shuffle, num_workers=num_workers,

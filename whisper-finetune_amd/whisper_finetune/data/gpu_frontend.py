@@ -149,6 +149,31 @@ def time_stretch(audio, rate, device=None):
     return parts if a.dim() == 2 else parts[0]
 
 
+# ------------------------------------------------------------------------------------------------- IIR filters
+# The filter group of the reference's advanced pipeline (data/filters.py designs and draws the seven kinds) and any user-supplied
+# cascade of second-order sections, e.g. pre-emphasis or hum removal (include/wft.h "IIR filter" states the arithmetic).
+from whisper_finetune.data.filters import design as design_filter  # noqa: E402,F401
+
+
+def sos_filter(audio, sos, device=None):
+    """audio filtered by a cascade of second-order sections, on the device (K.sos_filter).
+
+    audio: f32, 1-D [n] or 2-D [B, n], a tensor or an array; a host input goes to `device` (default: the current GPU) first.
+    sos: f64 [S, 6] (one filter for every row) or [B, S, 6], rows b0 b1 b2 a0 a1 a2 with a0 == 1, S in 1..4 (ValueError otherwise),
+    e.g. `design_filter("high_pass", cutoff_freq=80.0, order=2)`.  Returns a new device tensor of the input's shape."""
+    a = torch.as_tensor(audio)
+    if a.dim() not in (1, 2) or a.dtype != torch.float32 or a.numel() == 0:
+        raise ValueError(f"sos_filter: audio must be a non-empty float32 [n] or [B, n], got {a.dtype} {tuple(a.shape)}")
+    rows = a if a.dim() == 2 else a[None]
+    coeffs = K.sos_coefficients(sos.detach().cpu() if torch.is_tensor(sos) else np.asarray(sos), rows.shape[0])  # before the device is touched
+    if device is not None:
+        rows = rows.to(device)
+    elif not rows.is_cuda:
+        rows = rows.to(torch.device("cuda", torch.cuda.current_device()))
+    out = K.sos_filter(rows, coeffs)
+    return out if a.dim() == 2 else out[0]
+
+
 from whisper_finetune.data.transforms import FrequencyMasking, TimeMasking, draw_mask_span  # noqa: E402,F401
 
 

@@ -1336,6 +1336,77 @@ def logmel_ragged(audio, n_samples, keep_frames, filters, T_out: int = 3000):
     return out
 
 
+SOS_MAX_SECTIONS = 4
+
+
+def sos_coefficients(sos, B: int):
+    """sos f64 [B, S, 6] or [S, 6] (one filter for every row), a host or a device tensor or an array -> float64 numpy [B, S, 6].
+    ValueError: a shape other than these, S outside 1..4, a coefficient that is not finite, a0 != 1.  A device tensor is copied to
+    the host for the check (it is B * S * 6 doubles)."""
+    import numpy as np
+
+    c = sos.detach().cpu().numpy() if torch.is_tensor(sos) else np.asarray(sos)
+    if c.dtype != np.float64:
+        raise ValueError(f"sos_filter: sos must be float64, got {c.dtype}")
+    if c.ndim == 2:
+        c = np.broadcast_to(c[None], (B,) + c.shape)
+    if c.ndim != 3 or c.shape[0] != B or c.shape[2] != 6:
+        raise ValueError(f"sos_filter: sos must be [{B}, S, 6] or [S, 6], got {tuple(c.shape)}")
+    if not 1 <= c.shape[1] <= SOS_MAX_SECTIONS:
+        raise ValueError(f"sos_filter: 1 to {SOS_MAX_SECTIONS} sections, got {c.shape[1]}")
+    if not bool(np.all(np.isfinite(c))):
+        raise ValueError("sos_filter: coefficients must be finite")
+    if not bool(np.all(c[:, :, 3] == 1.0)):
+        raise ValueError("sos_filter: every section must be normalised to a0 == 1")
+    return np.array(c, dtype=np.float64, order="C", copy=True)  # (a broadcast view is read-only)
+
+
+def sos_filter(audio, sos, n=None, *, out=None):
+    """A cascade of second-order sections over every row (wft_sos_filter_f32, include/wft.h "IIR filter").
+
+    audio f32 [B, ld] on the device (stride(1) == 1); sos f64 [B, S, 6] or [S, 6] = b0 b1 b2 a0 a1 a2 with a0 == 1, S in 1..4, on the
+    host or the device; n i32 [B] on the device (row b filters its first n[b] samples, clamped to [0, ld], and is zero behind them) or
+    None (every row filters all ld samples).  out: None (a new tensor), `audio` itself (in place) or an f32 [B, ld] tensor with unit
+    column stride that does not overlap `audio`.  Every host-side check raises ValueError before the device is touched."""
+    if not torch.is_tensor(audio) or audio.dtype != F32 or audio.dim() != 2 or audio.shape[0] < 1 or audio.shape[1] < 1:
+        raise ValueError(f"sos_filter: audio must be a float32 tensor [B, n] with B >= 1 and n >= 1, got {getattr(audio, 'dtype', type(audio))} "
+                         f"{tuple(getattr(audio, 'shape', ()))}")
+    B, n_max = audio.shape
+    if B > 65535 or n_max > (1 << 30):
+        raise ValueError(f"sos_filter: at most 65535 rows of 2^30 samples per call, got {tuple(audio.shape)}")
+    c = sos_coefficients(sos, B)
+    S = c.shape[1]
+    if n is not None:
+        if not torch.is_tensor(n) or n.dtype != torch.int32 or tuple(n.shape) != (B,):
+            raise ValueError(f"sos_filter: n must be an int32 tensor [{B}] or None")
+    if audio.stride(1) != 1 or (B > 1 and audio.stride(0) < n_max):
+        if out is audio:
+            raise ValueError("sos_filter: an in-place call needs rows with unit column stride that do not overlap")
+        audio = audio.contiguous()
+    if out is not None and out is not audio:
+        if not torch.is_tensor(out) or out.dtype != F32 or tuple(out.shape) != (B, n_max) or out.stride(1) != 1 or (B > 1 and out.stride(0) < n_max):
+            raise ValueError(f"sos_filter: out must be f32 [{B}, {n_max}] with unit column stride and rows that do not overlap")
+    _chk(audio, F32, "audio")  # (every ValueError above comes before the device is touched)
+    if out is None:
+        out = torch.empty((B, n_max), dtype=F32, device=audio.device)
+    if out.device != audio.device or (n is not None and n.device != audio.device):
+        raise ValueError("sos_filter: audio, out and n must live on the same GPU")
+    lib = L.load()
+    nbytes = lib.wft_sos_filter_workspace_bytes(B, n_max, S)
+    if nbytes < 0:
+        raise ValueError(f"sos_filter: {B} rows of {n_max} samples with {S} sections are not supported by wft_sos_filter_f32")
+    sos_d = sos.contiguous() if (torch.is_tensor(sos) and sos.is_cuda and sos.dim() == 3 and sos.device == audio.device) else \
+        torch.from_numpy(c).to(audio.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=audio.device)
+    if n is not None:
+        n = n.contiguous()
+    ld_in = audio.stride(0) if B > 1 else max(audio.stride(0), n_max)
+    ld_out = out.stride(0) if B > 1 else max(out.stride(0), n_max)
+    L.check(lib.wft_sos_filter_f32(_p(audio), ld_in, _p(n), n_max, _p(sos_d), S, _p(out), ld_out, _p(ws), nbytes, B, L.stream_ptr()),
+            "wft_sos_filter_f32")
+    return out
+
+
 def mel_to_tmajor(mel, c_pad: int):
     _chk(mel, F32, "mel")
     mel = mel.contiguous()

@@ -243,6 +243,10 @@ SIGNATURES = {
     "wft_stretch_vocoder_f32": [c_vp, c_i64, c_vp, C.c_double, c_vp, C.c_int, c_vp],
     "wft_stretch_istft_f32": [c_vp, c_i64, c_vp, C.c_double, c_vp, c_i64, c_vp, C.c_int, c_vp],
     "wft_logmel_ragged": [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, C.c_int, C.c_int, c_vp],
+    "wft_sos_filter_workspace_bytes": [C.c_int, c_i64, C.c_int],
+    "wft_sos_filter_chunk": [],
+    "wft_sos_filter_group": [],
+    "wft_sos_filter_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, C.c_int, c_vp, c_i64, c_vp, c_i64, C.c_int, c_vp],
     "wft_adamw_step": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float,
                        C.c_float, C.c_float, C.c_float, c_vp, c_vp],
     "wft_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],
@@ -274,7 +278,8 @@ _RESTYPES = {"wft_last_error": C.c_char_p, "wft_version": C.c_char_p, "wft_layer
              "wft_attn_bwd_colsum_workspace_bytes": c_i64, "wft_attn_decode_workspace_bytes": c_i64,
              "wft_gemm_nt_stream_workspace_bytes": c_i64, "wft_gemm_nt_stream_q8_workspace_bytes": c_i64,
              "wft_attn_decode_beam_workspace_bytes": c_i64,
-             "wft_dtw_workspace_bytes": c_i64, "wft_time_stretch_workspace_bytes": c_i64}
+             "wft_dtw_workspace_bytes": c_i64, "wft_time_stretch_workspace_bytes": c_i64,
+             "wft_sos_filter_workspace_bytes": c_i64}
 
 _lib = None
 
