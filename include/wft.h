@@ -876,6 +876,81 @@ int wft_sos_filter_group(void);
 int wft_sos_filter_f32(const float* in, int64_t ld_in, const int32_t* n, int64_t n_max, const double* sos, int S, float* out,
                        int64_t ld_out, void* workspace, int64_t workspace_bytes, int B, void* stream);
 
+/* ------------------------------------------------- Wave effects (audio-domain augmentation) */
+/* Additive noise, clipping and level changes over every row of a ragged batch (csrc/wavefx.hip; DESIGN.md §3 "Wave effects"): six
+ * transforms of the reference's advanced pipeline that are plain arithmetic on the waveform (audiomentations' AddGaussianNoise,
+ * AddGaussianSNR, ClippingDistortion, Gain, GainTransition, Shift), restated from the published source; the library is not a
+ * dependency and parity with its binary is unpinned.  ONE call applies ONE stage to every row; composing stages is the caller's job.
+ *
+ * fx: DEVICE array of B records, 8-byte aligned, 88 bytes each.  A kind of 0 (or an unknown kind) means "none" for that stage.
+ *
+ * Shared rules.  Row b covers n[b] samples (n: device i32 [B], clamped to [0, n_max] inside the kernels; NULL = n_max for every row).
+ * Out of place, out[b, n[b] .. n_max) is written as zero; in place nothing behind n[b] is touched.  Nothing at or behind n_max of an
+ * output row is written and nothing at or behind n[b] of an input row is read.  A row whose kind for the stage is "none" passes
+ * through bit for bit.  Arithmetic is fp64 with ONE rounding to f32, products and sums NOT contracted into FMAs (the file is compiled
+ * with contraction off, so the operations are the ones written here).  No float atomics (integer atomics on counts only), no
+ * allocation, no host synchronisation; reruns are bit-identical; a row's bits depend on its samples, its record and n[b] only.
+ *
+ * WFT_FX_NOISE.  out[i] = f32(x[i] + sigma * z(i)).
+ *   WFT_FX_GAUSSIAN_NOISE: sigma = noise_value (an amplitude).
+ *   WFT_FX_GAUSSIAN_SNR:   sigma = rms / 10^(noise_value / 20), noise_value in dB, rms = sqrt(sum x^2 / n[b]) over the row's n[b]
+ *     samples.  The sum is fp64 in a fixed order: chunk c covers samples [c K, (c + 1) K), K = 4096; thread t of 256 adds its samples
+ *     c K + t, c K + t + 256, ... in ascending order; the 256 sums are halved pairwise (s[t] += s[t + h], h = 128 .. 1); the chunks'
+ *     sums are added in ascending order.  rms = 0 or n[b] = 0 gives sigma = 0.
+ *   sigma == 0: the row passes through bit for bit.
+ *   z(i): Philox4x32-10 as in "Sampled decoding" above (same multipliers, Weyl constants and known answers), key = (low, high 32
+ *     bits of seed), counter = (i >> 2, 0, 0, 0); w = 2 * ((i >> 1) & 1); u1 from word w, u2 from word w + 1, each (2k + 1) * 2^-24
+ *     with k = word >> 9 (so u1 is never 0); r = sqrt(-2 ln u1); z = r * cos(t) for even i, r * sin(t) for odd i, t = (2 pi) * u2 with
+ *     2 pi = 6.283185307179586; log, sqrt, cos, sin in fp64.
+ * WFT_FX_CLIP (WFT_FX_CLIPPING).  clip_q: an integer percent, clamped to 0..50 inside the kernels.  With s the row's n[b] samples
+ *   sorted ascending under the total order of the key k(x) = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000) (so -0.0 sorts before
+ *   +0.0): for p in {clip_q, 100 - clip_q}, m = p * (n[b] - 1) in 64-bit integers, j = m / 100, g = (m % 100) / 100.0;
+ *   threshold = s[j] bit for bit when g == 0 (s[j + 1] is not touched), else f32(s[j] + g * (s[j + 1] - s[j])).  lo, hi = the two
+ *   thresholds; out[i] = x[i] < lo ? lo : (x[i] > hi ? hi : x[i]) (a sample equal to a threshold, -0.0 against +0.0 included,
+ *   keeps its own bits; NaN passes).  This is np.percentile(method="linear") and np.clip.  The selection is exact: a radix select over
+ *   the keys in three passes (11, 11, 10 bits), the four ranks side by side; it runs over the clipping rows only (a device-side list;
+ *   the launches are not sized by B).  n[b] = 0 does nothing, n[b] = 1 makes both thresholds the sample.
+ *   The thresholds of row b are left in the workspace as f32 at byte offset 8 + 4 * ((B + 1) / 2 * 2) + 8 * b (lo, hi).
+ * WFT_FX_LEVEL.
+ *   WFT_FX_GAIN:  out[i] = x[i] * gain_ratio, one f32 multiply (the host computes gain_ratio = f32(10^(dB / 20))).
+ *   WFT_FX_GAIN_TRANSITION:  dB(i) = db_start + (db_end - db_start) * min(max((double)(i - t0) / (double)max(ramp_len - 1, 1), 0), 1);
+ *     out[i] = f32(x[i] * 10^(dB(i) / 20)).  t0 may be negative or beyond n[b]: db_start holds before the ramp, db_end after it.
+ *   WFT_FX_SHIFT:  s = (i64) nearbyint(shift_fraction * n[b]) (ties to even), reduced to [0, n[b]); d = (i - s) mod n[b];
+ *     out[i] = x[d] * w(i): a rotation with rollover (the padding inside n[b] rotates with the clip).  F = min(max(fade_len, 0),
+ *     n[b] / 2), D = max(F - 1, 1).  s == 0 or F == 0: w = 1 everywhere (a copy).  Otherwise, with e = n[b] - 1 - d (the distance to
+ *     the seam from below; the seam lies between output indices s - 1 and s, cyclically):
+ *       d < F:  w = d / D   (the fade in: exactly 0 at output index s, exactly 1 at s + F - 1 when F >= 2)
+ *       e < F:  w = e / D   (the fade out: exactly 0 at s - 1, exactly 1 at s - F when F >= 2)
+ *       else    w = 1 and the sample is copied bit for bit.
+ *     A faded sample is f32((double)x[d] * w), w in fp64.  F = 1 zeroes the two samples at the seam.
+ *     A shift row needs out != in.  The records are device memory, so the library cannot see the kinds: a LEVEL call with
+ *     out == in is accepted and is only defined when no row is a shift row (engine/kernels.py wave_fx decides that from its host copy
+ *     of the records and goes through a temporary).
+ *
+ *  in / out f32: row b at in + b * ld_in / out + b * ld_out, ld >= n_max, 1 <= n_max <= 2^30, 1 <= B <= 65535; out == in with
+ *  ld_out == ld_in is in place, any other overlap is refused.  workspace: wft_wave_fx_workspace_bytes(B, n_max, stage) bytes (-1: bad
+ *  arguments), 8-byte aligned.  wft_wave_fx_tile(): the samples of one workgroup trip of the apply pass.
+ *  WFT_ERR_ARG before any launch: null pointer (in, fx, out, workspace), unknown stage, B or n_max out of range, a leading dimension
+ *  below n_max, a short workspace, misalignment (in / out / n 4 bytes, fx / workspace 8), partial overlap of in and out.         */
+enum { WFT_FX_NOISE = 0, WFT_FX_CLIP = 1, WFT_FX_LEVEL = 2 };
+enum { WFT_FX_NONE = 0, WFT_FX_GAUSSIAN_NOISE = 1, WFT_FX_GAUSSIAN_SNR = 2 };     /* noise_kind */
+enum { WFT_FX_CLIPPING = 1 };                                                     /* clip_kind  */
+enum { WFT_FX_GAIN = 1, WFT_FX_GAIN_TRANSITION = 2, WFT_FX_SHIFT = 3 };           /* level_kind */
+typedef struct {
+  int32_t noise_kind, clip_kind, level_kind, clip_q; /*  0  4  8 12 */
+  uint64_t seed;                                     /* 16 */
+  double noise_value;                                /* 24: amplitude (gaussian_noise) or SNR in dB (gaussian_snr) */
+  float gain_ratio; int32_t reserved;                /* 32 36 */
+  double db_start, db_end;                           /* 40 48 */
+  int64_t t0, ramp_len;                              /* 56 64 */
+  double shift_fraction;                             /* 72 */
+  int64_t fade_len;                                  /* 80 */
+} wft_wave_fx;
+int64_t wft_wave_fx_workspace_bytes(int B, int64_t n_max, int stage);
+int wft_wave_fx_tile(void);
+int wft_wave_fx_f32(const float* in, int64_t ld_in, const int32_t* n, int64_t n_max, const wft_wave_fx* fx, int stage, float* out,
+                    int64_t ld_out, void* workspace, int64_t workspace_bytes, int B, void* stream);
+
 /* ---------------------------------------------------------------- AdamW */
 /* torch.optim.AdamW single-tensor step over a flat f32 range
  * (model/optimizer.py:240-262 → optimizer.step() in model_utils.py:122).

@@ -70,8 +70,11 @@
   filter   the filter augmentation of the loader (--batches is not used): wft_sos_filter_f32 on [32, 480000] and [96, 480000], one and
          four sections, out of place and in place, the K.sos_filter wrapper, and torch's copy of the batch for scale.
          (--parts filter --out profiles/decode_bench_filter.jsonl)
+  wavefx   the wave effects of the loader (--batches is not used): every stage of wft_wave_fx_f32 on [32, 480000] and [96, 480000],
+         once with every row active and once with the number of rows the default rates make active, beside the log-mel and torch's
+         copy of the same batch.  (--parts wavefx --out profiles/decode_bench_wavefx.jsonl)
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample,stretch,filter] [--batches 1,8,32] [--out FILE]
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample,stretch,filter,wavefx] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -1054,6 +1057,61 @@ def bench_filter(batches):
             emit(rec)
 
 
+def bench_wavefx(batches):
+    """wft_wave_fx_f32 on 30 s clips, stage by stage and kind by kind: ms per call with every row active and with the expected
+    number of active rows at the default rates (data/wave_fx.py: noise 0.15, clipping 0.6 / 9 * 0.8, level 0.225 * 2.5 / 3)."""
+    from whisper_finetune.data import wave_fx as WF
+    from whisper_finetune.data.gpu_frontend import mel_filters
+
+    lib = L.load()
+    n = 480000
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    kinds = {"gaussian_noise": dict(amplitude=0.001, seed=1), "gaussian_snr": dict(snr_db=30.0, seed=2), "clipping": dict(q=10),
+             "gain": dict(gain_db=0.0), "gain_transition": dict(start_db=-1.0, end_db=1.0, t0=1000, length=48000),
+             "shift": dict(fraction=0.25, fade_len=80)}
+    share = {"noise": 0.15, "clip": 0.6 / 9 * 0.8, "level": 0.225 * 2.5 / 3}
+    filters = mel_filters(80).to(DEV)
+    for B in (32, 96):
+        g = torch.Generator().manual_seed(B)
+        x = (torch.randn(B, n, generator=g) * 0.1).to(DEV)
+        x[:, 300000:] = 0  # zero-padded clips, as the loader stages them
+        out, y = torch.empty_like(x), x.clone()
+        base = ab({"logmel": lambda: K.logmel(x, filters, 3000), "copy": lambda: out.copy_(x)}, rounds=5, iters=5)
+        emit(dict(part="wavefx", arm="context", B=B, n=n, logmel_ms=round(base["logmel"][0], 4), copy_ms=round(base["copy"][0], 4),
+                  note="the log-mel of the same batch and torch's copy of it (8 bytes per sample), for scale"))
+        for kind, params in kinds.items():
+            stage = WF.STAGE_OF[kind]
+            sid = WF.STAGE_ID[stage]
+            need = lib.wft_wave_fx_workspace_bytes(B, n, sid)
+            ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+            arms, active = {}, {"all": B, "default_rates": max(int(round(share[stage] * B)), 1)}
+            keep = []
+            for name, rows in active.items():
+                table = WF.none_table(B)
+                table[:rows] = WF.table_row(kind, **params)
+                rec = WF.check_records(WF.records_from_table(table))
+                fx = torch.from_numpy(rec.view("u1").reshape(B, 88).copy()).to(DEV)
+                keep.append(fx)
+                dst = out if kind == "shift" else y  # the loader runs in place; a shift cannot
+                arms[name] = (lambda fx=fx, dst=dst, src=(x if kind == "shift" else y):
+                              lib.wft_wave_fx_f32(p(src), n, None, n, p(fx), sid, p(dst), n, p(ws), need, B, L.stream_ptr()))
+            table = WF.none_table(B)
+            table[:] = WF.table_row(kind, **params)
+            arms["wrapper_all"] = lambda table=table: K.wave_fx(y, table, stage, out=y)
+            y.copy_(x)
+            res = ab(arms, rounds=7, iters=10)
+            rec = dict(part="wavefx", arm="stage", B=B, n=n, stage=stage, kind=kind, in_place=kind != "shift", tile=lib.wft_wave_fx_tile(),
+                       rows_default_rates=active["default_rates"], workspace_MB=round(need / 1e6, 2),
+                       note="ms per call, medians of 7 alternating rounds of 10 calls; all / default_rates: the raw call on a preallocated "
+                            "workspace with every row active / with the expected number of active rows at the default rates; "
+                            "wrapper_all: K.wave_fx with a host table (its check, the upload, the workspace allocation; a shift goes "
+                            "through its temporary)")
+            for name, (med, mn, spread) in res.items():
+                rec[name + "_ms"], rec[name + "_min_ms"], rec[name + "_spread"] = round(med, 4), round(mn, 4), round(spread, 3)
+            rec["all_vs_logmel"] = round(res["all"][0] / base["logmel"][0], 3)
+            emit(rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="attn,gemm,e2e")
@@ -1067,7 +1125,7 @@ def main():
     for part in a.parts.split(","):
         {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": lambda b: (bench_gemm_stream(b), bench_gemm_stream_q8(b)), "e2e_step": bench_e2e_step,
          "gemm_i8": bench_gemm_i8, "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align, "transcribe": bench_transcribe, "resample": bench_resample,
-         "stretch": bench_stretch, "filter": bench_filter}[part](batches)
+         "stretch": bench_stretch, "filter": bench_filter, "wavefx": bench_wavefx}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

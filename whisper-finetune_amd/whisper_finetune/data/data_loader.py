@@ -21,6 +21,13 @@ Filter augmentation (`filter_aug={...}`, an option of this project's own: the fi
 `apply_advanced_aug`, which stays refused): a worker only DRAWS and designs the clip's filter (data/filters.py FilterAug, after the
 stretch-rate draw: the reference's Compose order); the main process runs `wft_sos_filter_f32` in place on the staged batch behind
 the resample and the stretch and in front of the log-mel.  The zero padding is filtered too, as the reference filters the padded clip.
+
+Wave effects (`wave_aug={...}`, an option of this project's own: additive Gaussian noise, clipping distortion, gain, gain transition
+and shift of the reference's advanced pipeline, NOT `apply_advanced_aug`): a worker only DRAWS the clip's parameters (data/wave_fx.py
+WaveAug, after the filter draw) and ships them as one table row f64 [14]; the main process runs `wft_wave_fx_f32` in place, one stage
+per call, in the reference's Compose order: resample -> stretch -> NOISE -> filter -> CLIP -> LEVEL -> log-mel.  Every stage covers
+the row's full stretched length, padding included (the reference transforms the padded clip), and a stage with no active row launches
+nothing.  Timestamps are not moved under `shift`, as in the reference.
 """
 from __future__ import annotations
 
@@ -38,10 +45,27 @@ from whisper_finetune.data.filters import FilterAug, identity_sos
 from whisper_finetune.data.gpu_frontend import (HOP_LENGTH, N_FFT, N_FRAMES, N_SAMPLES, SAMPLE_RATE, GpuFrontend, check_rate,
                                                 check_stretch_range, draw_clip_params, mel_filters)
 from whisper_finetune.data.utils import ExtremesFrequencyMasking, TimeWarpAugmenter, pad_or_trim
+from whisper_finetune.data.wave_fx import STAGES as WAVE_STAGES, WaveAug, active_rows, check_records, records_from_table
 
 CHUNK_LENGTH = 30
 _TS = re.compile(r"(<\|[123]?[0-9]\.[0-9][0-9]\|>)")  # <|0.00|> .. <|30.00|>
 _FILTERS = {}
+
+
+def apply_wave_stages(audio, n, sos, fx):
+    """The audio-domain stages behind the stretch, in place on audio f32 [B, ld] (device), in the reference's Compose order:
+    NOISE -> filter -> CLIP -> LEVEL.  n: i32 [B] on the device or None; sos: f64 [B, 4, 6] or None; fx: checked wave-effect records
+    [B] (data/wave_fx.py) or None.  A stage with no active row launches nothing."""
+    from whisper_finetune.engine import kernels as K
+
+    if fx is not None:
+        K.wave_fx(audio, fx, "noise", n, out=audio)
+    if sos is not None:
+        K.sos_filter(audio, sos, n, out=audio)
+    if fx is not None:
+        K.wave_fx(audio, fx, "clip", n, out=audio)
+        K.wave_fx(audio, fx, "level", n, out=audio)  # (shift rows go through a temporary inside K.wave_fx)
+    return audio
 
 
 def log_mel_spectrogram(audio, n_mels: int = 80, padding: int = 0, device=None) -> torch.Tensor:
@@ -72,7 +96,8 @@ def log_mel_spectrogram(audio, n_mels: int = 80, padding: int = 0, device=None) 
 class AudioDataset(Dataset):
     """Items: (audio f32 [30 * sample_rate] (480000 at the default 16 kHz), decoder_input i64, decoder_output i64, aug i32 [8], extremes i32 [2], cut_frames);
     with `apply_baseline_aug` a seventh field, the clip's time-stretch rate as f64 (without it the items are the six fields, unchanged);
-    with `filter_aug` one more field behind those, the clip's filter as sos f64 [4, 6] (identity sections = "do not filter").
+    with `filter_aug` one more field behind those, the clip's filter as sos f64 [4, 6] (identity sections = "do not filter");
+    with `wave_aug` one more field behind the filter, the clip's wave effects as a table row f64 [14] (data/wave_fx.py).
 
     apply_baseline_aug: the rate is drawn as audiomentations draws it — Python's `random` module, one `random.random()` gate against
     p = 1.0, then `random.uniform(min_rate, max_rate)` (BaseWaveformTransform.randomize_parameters, then TimeStretch's).  That order is
@@ -83,6 +108,8 @@ class AudioDataset(Dataset):
     filter_aug: None, or a mapping of data/filters.py FilterAug's keywords (`p`, `kinds`); `{}` = its defaults.  It is the filter group
     of the advanced pipeline alone.  The filter is drawn after the stretch rate, with Python's `random` (FilterAug's docstring states
     the order), designed for 16 kHz (it runs behind the resample), and never touches torch's generator.
+    wave_aug: None, or a mapping of data/wave_fx.py WaveAug's groups (`noise`, `clip`, `level`, each None or {p, kinds}; a missing
+    group is off).  The parameters are drawn after the filter, with Python's `random` (WaveAug's docstring states the order).
 
     hu_dataset: indexable records {"audio": {"array", optional "sampling_rate"}, "text", "language", optional "prompt"}; a record
     whose "sampling_rate" is present and differs from the dataset's `sample_rate` raises ValueError (no mixed rates); tokenizer: whisper-style
@@ -95,13 +122,15 @@ class AudioDataset(Dataset):
     sample_rate, n_samples = SAMPLE_RATE, N_SAMPLES  # the defaults, also of an instance built without __init__
     apply_baseline_aug = False
     filter_aug = None
+    wave_aug = None
 
     def __init__(self, hu_dataset, tokenizer, device=None, no_timestamp_training: bool = False, n_mels: int = 80,
                  max_prompt_length: int = 223, prompt_use_rate: float = 0.5, no_timestamps_rate: float = 0.5,
                  spec_augment: bool = False, spec_augment_params: Optional[dict] = None, extremes_spec_augment: bool = False,
                  extremes_spec_augment_params: Optional[dict] = None, apply_baseline_aug: bool = False, apply_office_aug: bool = False,
                  apply_advanced_aug: bool = False, time_stretch_min_rate: float = 0.8, time_stretch_max_rate: float = 1.25,
-                 bpe_dropout: float = 0.0, sample_rate: int = SAMPLE_RATE, filter_aug: Optional[dict] = None):
+                 bpe_dropout: float = 0.0, sample_rate: int = SAMPLE_RATE, filter_aug: Optional[dict] = None,
+                 wave_aug: Optional[dict] = None):
         self.sample_rate = check_rate(sample_rate)
         self.n_samples = CHUNK_LENGTH * self.sample_rate  # 30 s at the clips' own rate
         refused = [name for name, on in (("apply_office_aug", apply_office_aug), ("apply_advanced_aug", apply_advanced_aug)) if on]
@@ -122,6 +151,9 @@ class AudioDataset(Dataset):
         if filter_aug is not None and (not hasattr(filter_aug, "keys") or not set(filter_aug.keys()) <= {"p", "kinds"}):
             raise ValueError(f"filter_aug must be None or a mapping of FilterAug's keywords `p` and `kinds`, got {filter_aug!r}")
         self.filter_aug = FilterAug(sample_rate=SAMPLE_RATE, **dict(filter_aug)) if filter_aug is not None else None
+        if wave_aug is not None and (not hasattr(wave_aug, "keys") or not set(wave_aug.keys()) <= set(WAVE_STAGES)):
+            raise ValueError(f"wave_aug must be None or a mapping of WaveAug's groups {WAVE_STAGES}, got {wave_aug!r}")
+        self.wave_aug = WaveAug(sample_rate=SAMPLE_RATE, **dict(wave_aug)) if wave_aug is not None else None
         if spec_augment:
             self.spec_augment_p = float(spec_augment_params.get("p", 1.0))
             if not 0.0 <= self.spec_augment_p <= 1.0:
@@ -167,8 +199,15 @@ class AudioDataset(Dataset):
         kind, _, sos = self.filter_aug.draw()
         return None if kind is None else sos[None]
 
+    def _draw_wave(self):
+        """The clip's wave effects for the per-clip form: checked records [1], or None without the option or when nothing was drawn."""
+        if self.wave_aug is None:
+            return None
+        names, row = self.wave_aug.draw(N_SAMPLES)
+        return check_records(records_from_table(row[None])) if any(names.values()) else None
+
     def _calculate_mel(self, audio_array, next_partial_segment_start: Optional[float], no_timestamps: bool) -> torch.Tensor:
-        """Per-clip form: [time stretch] -> [filter] -> log-mel -> cut at a partial segment + minimum-value pad -> [warp -> time mask -> freq mask]
+        """Per-clip form: [time stretch] -> [noise] -> [filter] -> [clipping] -> [level] -> log-mel -> cut at a partial segment + minimum-value pad -> [warp -> time mask -> freq mask]
         w.p. p -> extremes masking, every stage a libwft kernel on the device."""
         if self.sample_rate != SAMPLE_RATE:
             raise ValueError(f"_calculate_mel is the per-clip 16 kHz form; clips at {self.sample_rate} Hz are resampled per batch by GpuMelLoader")
@@ -180,22 +219,19 @@ class AudioDataset(Dataset):
             dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
             row = torch.as_tensor(np.asarray(audio_array, dtype=np.float32)).to(dev)[None]
             stretched, n_out = K.time_stretch(row, [self._draw_stretch_rate()])
-            sos = self._draw_filter()
-            if sos is not None:
-                K.sos_filter(stretched, sos, n_out, out=stretched)
+            sos, fx = self._draw_filter(), self._draw_wave()
+            apply_wave_stages(stretched, n_out, sos, fx)
             key = (self.n_mels, row.device)
             if key not in _FILTERS:
                 _FILTERS[key] = mel_filters(self.n_mels).to(row.device)
             keep = torch.tensor([min(cut, N_FRAMES)], dtype=torch.int32, device=row.device)
             mel = K.logmel_ragged(stretched, n_out, keep, _FILTERS[key], N_FRAMES)[0]
         else:
-            sos = self._draw_filter()
-            if sos is not None:  # the same kernel as GpuMelLoader, on one row
-                from whisper_finetune.engine import kernels as K
-
+            sos, fx = self._draw_filter(), self._draw_wave()
+            if sos is not None or fx is not None:  # the same kernels as GpuMelLoader, on one row
                 dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
                 row = torch.as_tensor(np.asarray(audio_array, dtype=np.float32)).to(dev)[None].clone()
-                audio_array = K.sos_filter(row, sos, out=row)[0]
+                audio_array = apply_wave_stages(row, None, sos, fx)[0]
             mel = log_mel_spectrogram(audio_array, n_mels=self.n_mels, device=self.device)
             if no_timestamps and next_partial_segment_start is not None:
                 mel = mel[:, : int(next_partial_segment_start * self.num_frames_per_second)]
@@ -324,6 +360,8 @@ class AudioDataset(Dataset):
             item += (torch.tensor(self._draw_stretch_rate(), dtype=torch.float64),)
         if self.filter_aug is not None:
             item += (torch.from_numpy(self.filter_aug.draw()[2]),)
+        if self.wave_aug is not None:
+            item += (torch.from_numpy(self.wave_aug.draw(N_SAMPLES)[1]),)
         return item
 
 
@@ -335,7 +373,7 @@ def collate_fn(data):
     if len(cols) == 3:
         return pad_sequence(cols[0], batch_first=True, padding_value=0), y_in, y_out
     out = (torch.stack(cols[0]), y_in, y_out, torch.stack(cols[3]), torch.stack(cols[4]), torch.tensor(cols[5], dtype=torch.int32))
-    return out + tuple(torch.stack(c) for c in cols[6:])  # the time-stretch rates f64 [B] and / or the filters f64 [B, 4, 6]
+    return out + tuple(torch.stack(c) for c in cols[6:])  # the time-stretch rates f64 [B], the filters f64 [B, 4, 6], the wave effects f64 [B, 14]
 
 
 class WarmupDatasetSampler(torch.utils.data.Sampler):
@@ -400,17 +438,24 @@ class GpuMelLoader:
     the resample and the stretch, over each row's full stretched length (n = n_out; 480000 without the stretch), so a filter's tail
     rings into the zero padding as it does in the reference, which filters the padded clip.  A batch whose filters are all identity
     launches nothing.  Which optional fields a batch carries is read from the dataset's flags (`stretch`, `filter_aug`: None = from
-    `loader.dataset`; a loader without a dataset, e.g. a list of batches, takes a seventh field for the rates as before)."""
+    `loader.dataset`; a loader without a dataset, e.g. a list of batches, takes a seventh field for the rates as before).
+
+    Batches of a dataset built with wave_aug carry the wave effects f64 [B, 14] as their last field, behind the filters: the stages
+    run in place in the order resample -> stretch -> NOISE -> filter -> CLIP -> LEVEL -> log-mel (apply_wave_stages), each over the
+    row's full stretched length.  The table is turned into checked records on the host; a stage with no active row launches nothing,
+    and a batch with no effect at all is the batch of a loader without the option, bit for bit."""
 
     def __init__(self, loader, frontend: GpuFrontend, training_aug: bool, sample_rate: int = SAMPLE_RATE, stretch: Optional[bool] = None,
-                 filter_aug: Optional[bool] = None):
+                 filter_aug: Optional[bool] = None, wave_aug: Optional[bool] = None):
         self.loader, self.frontend, self.training_aug = loader, frontend, training_aug
         ds = getattr(loader, "dataset", None)
         if stretch is None and ds is not None:
             stretch = bool(getattr(ds, "apply_baseline_aug", False))
         if filter_aug is None:
             filter_aug = getattr(ds, "filter_aug", None) is not None
-        self.stretch, self.filter_aug = stretch, bool(filter_aug)
+        if wave_aug is None:
+            wave_aug = getattr(ds, "wave_aug", None) is not None
+        self.stretch, self.filter_aug, self.wave_aug = stretch, bool(filter_aug), bool(wave_aug)
         self._identity = torch.from_numpy(identity_sos())
         self.sample_rate = check_rate(sample_rate)
         self.sampler = getattr(loader, "sampler", None)  # infinite_iter() calls sampler.set_epoch(...)
@@ -423,14 +468,25 @@ class GpuMelLoader:
 
     def _optional(self, batch):
         """(rates or None, sos or None) of a collated batch, by the flags.  An all-identity `sos` counts as None."""
-        stretch = (len(batch) == 7 and not self.filter_aug) if self.stretch is None else self.stretch
-        if len(batch) != 6 + int(stretch) + int(self.filter_aug):
-            raise ValueError(f"a batch of {len(batch)} fields from a loader with stretch={stretch}, filter_aug={self.filter_aug}")
+        return self._fields(batch)[:2]
+
+    def _fields(self, batch):
+        """(rates or None, sos or None, wave-effect records or None) of a collated batch, by the flags.  An all-identity `sos` and a
+        table without any effect count as None."""
+        stretch = (len(batch) == 7 and not self.filter_aug and not self.wave_aug) if self.stretch is None else self.stretch
+        if len(batch) != 6 + int(stretch) + int(self.filter_aug) + int(self.wave_aug):
+            raise ValueError(f"a batch of {len(batch)} fields from a loader with stretch={stretch}, filter_aug={self.filter_aug}"
+                             + (f", wave_aug={self.wave_aug}" if self.wave_aug else ""))
         rates = batch[6] if stretch else None
-        sos = batch[-1] if self.filter_aug else None
+        sos = batch[6 + int(stretch)] if self.filter_aug else None
         if sos is not None and bool((sos == self._identity).all()):
             sos = None
-        return rates, sos
+        fx = None
+        if self.wave_aug:
+            fx = check_records(records_from_table(batch[-1]))
+            if not any(bool(active_rows(fx, stage).any()) for stage in WAVE_STAGES):
+                fx = None
+        return rates, sos, fx
 
     def _stage(self, batch):
         """Issue the batch's H2D copies on the side stream; returns the device tensors and the event that orders them."""
@@ -438,15 +494,15 @@ class GpuMelLoader:
         if self._copy_stream is None:
             self._copy_stream = torch.cuda.Stream(device=dev)
         audio, y_in, y_out, params, ext, cut = batch[:6]
-        rates, sos = self._optional(batch)
+        rates, sos, fx = self._fields(batch)
         need_aug = bool(params[:, 0].any() or ext.any())  # decided on the host copies: no device sync
         with torch.cuda.stream(self._copy_stream):
             staged = [t.to(dev, non_blocking=True) for t in (audio, y_in, y_out, params, ext)]
             ev = torch.cuda.Event()
             ev.record(self._copy_stream)
-        return staged, cut, ev, need_aug, rates, sos
+        return staged, cut, ev, need_aug, rates, sos, fx
 
-    def _to_mel(self, staged, cut, ev, need_aug, rates=None, sos=None):
+    def _to_mel(self, staged, cut, ev, need_aug, rates=None, sos=None, fx=None):
         from whisper_finetune.engine import kernels as K
 
         cur = torch.cuda.current_stream(self.frontend.device)
@@ -461,15 +517,14 @@ class GpuMelLoader:
             # the stretch of the zero-PADDED clip, as the reference does it; the rates are host values (they size the launch), the
             # rows' lengths stay on the device; the cut and the minimum-value pad happen inside the ragged log-mel
             stretched, n_out = K.time_stretch(audio, rates)
-            if sos is not None:
-                K.sos_filter(stretched, sos, n_out, out=stretched)
+            apply_wave_stages(stretched, n_out, sos, fx)
             keep = cut.clamp(max=N_FRAMES).to(torch.int32).to(audio.device, non_blocking=True)
             mel = K.logmel_ragged(stretched, n_out, keep, self.frontend.filters, N_FRAMES)
         else:
-            if sos is not None:
+            if sos is not None or fx is not None:
                 if audio.stride(1) != 1 or not audio.is_contiguous():
                     audio = audio.contiguous()
-                K.sos_filter(audio, sos, out=audio)  # in place on the staged (or resampled) copy
+                apply_wave_stages(audio, None, sos, fx)  # in place on the staged (or resampled) copy
             mel = self.frontend.log_mel(audio)
             for b in (cut < N_FRAMES).nonzero().flatten().tolist():  # rare: cut at a partial segment, pad with the min value
                 c = int(cut[b])
@@ -485,7 +540,7 @@ class GpuMelLoader:
                 audio, y_in, y_out, params, ext, cut = batch[:6]
                 need_aug = bool(params[:, 0].any() or ext.any())
                 staged = [t.to(dev, non_blocking=True) for t in (audio, y_in, y_out, params, ext)]
-                yield self._to_mel(staged, cut, None, need_aug, *self._optional(batch))
+                yield self._to_mel(staged, cut, None, need_aug, *self._fields(batch))
             return
         it = iter(self.loader)
         try:
@@ -507,8 +562,10 @@ def get_dataloader(hu_dataset, tokenizer, batch_size: int = 1, n_mels: int = 80,
                    spec_augment_params: Optional[dict] = None, extremes_spec_augment: bool = False,
                    extremes_spec_augment_params: Optional[dict] = None, apply_baseline_aug: bool = False, apply_office_aug: bool = False,
                    apply_advanced_aug: bool = False, time_stretch_min_rate: float = 0.8, time_stretch_max_rate: float = 1.25,
-                   bpe_dropout: float = 0.0, drop_last: bool = False, sample_rate: int = SAMPLE_RATE, filter_aug: Optional[dict] = None):
+                   bpe_dropout: float = 0.0, drop_last: bool = False, sample_rate: int = SAMPLE_RATE, filter_aug: Optional[dict] = None,
+                   wave_aug: Optional[dict] = None):
     """`filter_aug`: None, or a mapping of FilterAug's keywords (AudioDataset's docstring): the filter augmentation of a TRAINING loader.
+    `wave_aug`: None, or a mapping of WaveAug's groups (AudioDataset's docstring): noise, clipping and level changes of a TRAINING loader.
     `sample_rate`: the rate of every clip of `hu_dataset` (default 16000).  At another rate the clips are padded to
     30 * sample_rate samples and resampled to 16 kHz on the device (GpuMelLoader); without a device the loader yields the padded
     native-rate clips."""
@@ -519,7 +576,7 @@ def get_dataloader(hu_dataset, tokenizer, batch_size: int = 1, n_mels: int = 80,
                       extremes_spec_augment_params=extremes_spec_augment_params, bpe_dropout=bpe_dropout,
                       apply_baseline_aug=apply_baseline_aug, apply_office_aug=apply_office_aug, apply_advanced_aug=apply_advanced_aug,
                       time_stretch_min_rate=time_stretch_min_rate, time_stretch_max_rate=time_stretch_max_rate, sample_rate=sample_rate,
-                      filter_aug=filter_aug)
+                      filter_aug=filter_aug, wave_aug=wave_aug)
     if sampler is not None:
         shuffle = False  # DataLoader does not allow both
     loader = DataLoader(ds, batch_size=batch_size, sampler=sampler, shuffle=shuffle, num_workers=num_workers,

@@ -174,6 +174,34 @@ def sos_filter(audio, sos, device=None):
     return out if a.dim() == 2 else out[0]
 
 
+# ------------------------------------------------------------------------------------------------- wave effects
+# Additive Gaussian noise, clipping distortion, gain, gain transition and shift (data/wave_fx.py draws them for the loader;
+# include/wft.h "Wave effects" states the arithmetic).
+from whisper_finetune.data.wave_fx import STAGE_OF as _WAVE_STAGE_OF, table_row as _wave_table_row  # noqa: E402
+
+
+def wave_fx(audio, kind, device=None, **params):
+    """audio under ONE wave effect, the same for every row, on the device (K.wave_fx).
+
+    audio: f32, 1-D [n] or 2-D [B, n], a tensor or an array; a host input goes to `device` (default: the current GPU) first.
+    kind and its keywords (ValueError otherwise; data/wave_fx.py table_row):
+      "gaussian_noise", amplitude=, seed=      "gaussian_snr", snr_db=, seed=       "clipping", q= (integer percent 0..50)
+      "gain", gain_db=       "gain_transition", start_db=, end_db=, t0=, length= (samples)       "shift", fraction=, fade_len=0 (samples)
+    Rows of a batch share the seed, so they get the same noise; use K.wave_fx with one record per row for per-row parameters.
+    Returns a new device tensor of the input's shape."""
+    a = torch.as_tensor(audio)
+    if a.dim() not in (1, 2) or a.dtype != torch.float32 or a.numel() == 0:
+        raise ValueError(f"wave_fx: audio must be a non-empty float32 [n] or [B, n], got {a.dtype} {tuple(a.shape)}")
+    row = _wave_table_row(kind, **params)  # before the device is touched
+    rows = a if a.dim() == 2 else a[None]
+    if device is not None:
+        rows = rows.to(device)
+    elif not rows.is_cuda:
+        rows = rows.to(torch.device("cuda", torch.cuda.current_device()))
+    out = K.wave_fx(rows, row, _WAVE_STAGE_OF[kind])
+    return out if a.dim() == 2 else out[0]
+
+
 from whisper_finetune.data.transforms import FrequencyMasking, TimeMasking, draw_mask_span  # noqa: E402,F401
 
 

@@ -1407,6 +1407,95 @@ def sos_filter(audio, sos, n=None, *, out=None):
     return out
 
 
+def wave_fx_records(fx, B: int):
+    """fx -> checked host records [B] (data/wave_fx.py RECORD_DTYPE).  fx: a numpy structured array [B] of that dtype, or the table
+    f64 [B, 14] / [14] (one record for every row) as a host tensor or array.  Every refusal is a ValueError."""
+    import numpy as np
+
+    from whisper_finetune.data import wave_fx as WF
+
+    a = fx.detach().cpu().numpy() if torch.is_tensor(fx) else np.asarray(fx)
+    if a.dtype != WF.RECORD_DTYPE:
+        if a.ndim == 1:
+            a = np.broadcast_to(a[None], (B,) + a.shape)
+        a = WF.records_from_table(np.ascontiguousarray(a))
+    if a.shape != (B,):
+        raise ValueError(f"wave_fx: {B} rows need {B} records, got {tuple(a.shape)}")
+    return WF.check_records(np.ascontiguousarray(a))
+
+
+def wave_fx(audio, fx, stage, n=None, *, out=None):
+    """One stage of the wave effects over every row (wft_wave_fx_f32, include/wft.h "Wave effects").
+
+    audio f32 [B, ld] on the device (stride(1) == 1); fx: the rows' records on the HOST (wave_fx_records states the forms); stage:
+    "noise", "clip" or "level" (or L.FX_NOISE / FX_CLIP / FX_LEVEL); n i32 [B] on the device (row b covers its first n[b] samples,
+    clamped to [0, ld]; out of place the output is zero behind them) or None (every row covers all ld samples).  out: None (a new
+    tensor), `audio` itself (in place) or an f32 [B, ld] tensor with unit column stride that does not overlap `audio`.
+    When no row is active in the stage nothing is launched: in place `audio` is returned as it is, out of place the rows are copied
+    and zeroed behind n by torch.  A `shift` is a rotation and cannot be done in place: an in-place LEVEL call with shift rows runs
+    into a temporary of the batch's size, which is then copied back (one extra read and write of the batch).
+    Every host-side check raises ValueError before the device is touched."""
+    from whisper_finetune.data import wave_fx as WF
+
+    if not torch.is_tensor(audio) or audio.dtype != F32 or audio.dim() != 2 or audio.shape[0] < 1 or audio.shape[1] < 1:
+        raise ValueError(f"wave_fx: audio must be a float32 tensor [B, n] with B >= 1 and n >= 1, got {getattr(audio, 'dtype', type(audio))} "
+                         f"{tuple(getattr(audio, 'shape', ()))}")
+    B, n_max = audio.shape
+    if B > 65535 or n_max > (1 << 30):
+        raise ValueError(f"wave_fx: at most 65535 rows of 2^30 samples per call, got {tuple(audio.shape)}")
+    if isinstance(stage, str):
+        if stage not in WF.STAGE_ID:
+            raise ValueError(f"wave_fx: stage must be one of {WF.STAGES}, got {stage!r}")
+        stage = WF.STAGE_ID[stage]
+    if stage not in (L.FX_NOISE, L.FX_CLIP, L.FX_LEVEL):
+        raise ValueError(f"wave_fx: unknown stage {stage!r}")
+    rec = wave_fx_records(fx, B)
+    if n is not None:
+        if not torch.is_tensor(n) or n.dtype != torch.int32 or tuple(n.shape) != (B,):
+            raise ValueError(f"wave_fx: n must be an int32 tensor [{B}] or None")
+    if audio.stride(1) != 1 or (B > 1 and audio.stride(0) < n_max):
+        if out is audio:
+            raise ValueError("wave_fx: an in-place call needs rows with unit column stride that do not overlap")
+        audio = audio.contiguous()
+    if out is not None and out is not audio:
+        if not torch.is_tensor(out) or out.dtype != F32 or tuple(out.shape) != (B, n_max) or out.stride(1) != 1 or (B > 1 and out.stride(0) < n_max):
+            raise ValueError(f"wave_fx: out must be f32 [{B}, {n_max}] with unit column stride and rows that do not overlap")
+    _chk(audio, F32, "audio")  # (every ValueError above comes before the device is touched)
+    if (out is not None and out.device != audio.device) or (n is not None and n.device != audio.device):
+        raise ValueError("wave_fx: audio, out and n must live on the same GPU")
+    stage_name = WF.STAGES[stage]
+    if not bool(WF.active_rows(rec, stage_name).any()):  # nothing to launch
+        if out is audio:
+            return audio
+        if out is None:
+            out = torch.empty((B, n_max), dtype=F32, device=audio.device)
+        out.copy_(audio)
+        if n is not None:
+            out.masked_fill_(torch.arange(n_max, device=audio.device)[None] >= n.clamp(0, n_max)[:, None], 0.0)
+        return out
+    through_tmp = out is audio and stage == L.FX_LEVEL and bool((rec["level_kind"] == L.FX_SHIFT).any())
+    dst = torch.empty((B, n_max), dtype=F32, device=audio.device) if (out is None or through_tmp) else out
+    lib = L.load()
+    nbytes = lib.wft_wave_fx_workspace_bytes(B, n_max, stage)
+    if nbytes < 0:
+        raise ValueError(f"wave_fx: {B} rows of {n_max} samples are not supported by wft_wave_fx_f32")
+    fx_d = torch.from_numpy(rec.view("u1").reshape(B, WF.RECORD_DTYPE.itemsize).copy()).to(audio.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=audio.device)
+    if n is not None:
+        n = n.contiguous()
+    ld_in = audio.stride(0) if B > 1 else max(audio.stride(0), n_max)
+    ld_out = dst.stride(0) if B > 1 else max(dst.stride(0), n_max)
+    L.check(lib.wft_wave_fx_f32(_p(audio), ld_in, _p(n), n_max, _p(fx_d), stage, _p(dst), ld_out, _p(ws), nbytes, B, L.stream_ptr()),
+            "wft_wave_fx_f32")
+    if through_tmp:
+        if n is None:
+            audio.copy_(dst)
+        else:  # in place nothing behind n[b] is touched
+            torch.where(torch.arange(n_max, device=audio.device)[None] < n.clamp(0, n_max)[:, None], dst, audio, out=audio)
+        return audio
+    return dst
+
+
 def mel_to_tmajor(mel, c_pad: int):
     _chk(mel, F32, "mel")
     mel = mel.contiguous()

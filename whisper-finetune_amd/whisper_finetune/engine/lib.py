@@ -155,6 +155,24 @@ class BeamUpdateArgs(C.Structure):
     ]
 
 
+class WaveFx(C.Structure):
+    """Mirror of wft_wave_fx (include/wft.h "Wave effects"): one row's record, 88 bytes; engine/kernels.py WAVE_FX_DTYPE is the
+    numpy form of the same layout."""
+
+    _fields_ = [
+        ("noise_kind", C.c_int32), ("clip_kind", C.c_int32), ("level_kind", C.c_int32), ("clip_q", C.c_int32),
+        ("seed", C.c_uint64), ("noise_value", C.c_double),
+        ("gain_ratio", C.c_float), ("reserved", C.c_int32),
+        ("db_start", C.c_double), ("db_end", C.c_double), ("t0", C.c_int64), ("ramp_len", C.c_int64),
+        ("shift_fraction", C.c_double), ("fade_len", C.c_int64),
+    ]
+
+
+FX_NOISE, FX_CLIP, FX_LEVEL = 0, 1, 2  # stage
+FX_NONE, FX_GAUSSIAN_NOISE, FX_GAUSSIAN_SNR = 0, 1, 2  # noise_kind
+FX_CLIPPING = 1  # clip_kind
+FX_GAIN, FX_GAIN_TRANSITION, FX_SHIFT = 1, 2, 3  # level_kind
+
 EPI_NONE, EPI_GELU, EPI_DGELU, EPI_GELU_GRAD, EPI_MUL_AUX, EPI_GELU_GRAD8, EPI_MUL_AUX8 = 0, 1, 2, 3, 4, 5, 6
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); this table is also what
@@ -247,6 +265,9 @@ SIGNATURES = {
     "wft_sos_filter_chunk": [],
     "wft_sos_filter_group": [],
     "wft_sos_filter_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, C.c_int, c_vp, c_i64, c_vp, c_i64, C.c_int, c_vp],
+    "wft_wave_fx_workspace_bytes": [C.c_int, c_i64, C.c_int],
+    "wft_wave_fx_tile": [],
+    "wft_wave_fx_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, C.c_int, c_vp, c_i64, c_vp, c_i64, C.c_int, c_vp],
     "wft_adamw_step": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float,
                        C.c_float, C.c_float, C.c_float, c_vp, c_vp],
     "wft_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],
@@ -279,7 +300,7 @@ _RESTYPES = {"wft_last_error": C.c_char_p, "wft_version": C.c_char_p, "wft_layer
              "wft_gemm_nt_stream_workspace_bytes": c_i64, "wft_gemm_nt_stream_q8_workspace_bytes": c_i64,
              "wft_attn_decode_beam_workspace_bytes": c_i64,
              "wft_dtw_workspace_bytes": c_i64, "wft_time_stretch_workspace_bytes": c_i64,
-             "wft_sos_filter_workspace_bytes": c_i64}
+             "wft_sos_filter_workspace_bytes": c_i64, "wft_wave_fx_workspace_bytes": c_i64}
 
 _lib = None
 
