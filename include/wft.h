@@ -951,6 +951,63 @@ int wft_wave_fx_tile(void);
 int wft_wave_fx_f32(const float* in, int64_t ld_in, const int32_t* n, int64_t n_max, const wft_wave_fx* fx, int stage, float* out,
                     int64_t ld_out, void* workspace, int64_t workspace_bytes, int B, void* stream);
 
+/* ------------------------------------------------- Per-row rate conversion (audio-domain augmentation) */
+/* Resampling at a fractional rate that differs from row to row of a ragged batch (csrc/rate.hip; DESIGN.md §3 "Rate effects"): the
+ * missing half of the advanced pipeline's PitchShift and the whole of its Aliasing.  Neither audiomentations nor librosa is a
+ * dependency.  Shared rules: fp64 arithmetic with ONE rounding to f32, products and sums NOT contracted into FMAs (the file is compiled
+ * with contraction off); no atomics, no allocation, no host synchronisation; every argument is checked before the launch; reruns are
+ * bit-identical; a row's bits depend on its samples and its parameters only — not on B, its batch partners, the tiling or the host's
+ * bound; index arithmetic is 64-bit; 1 <= B <= 65535; in and out must not overlap (a workgroup reads neighbours that another may
+ * have written).
+ *
+ * wft_sinc_resample_rows_f32: the resampler of the pitch shift (a time stretch by 2^(-s/12), wft_time_stretch_f32, followed by this
+ *  with the same rate as the ratio and n_out = the original length: librosa.effects.pitch_shift with its fix_length).  It is the
+ *  continuous form of the filter of wft_resample_f32 above (torchaudio's sinc_interp_hann, width 6, rolloff 0.99).  For row b:
+ *    rho = ratio[b] = output rate / input rate, float64 in DEVICE memory, inside [ratio_lo, 2.0], 0.5 <= ratio_lo <= 2.0; ratio_lo is
+ *      the HOST's lower bound of the ratios and sizes the tile and the staging buffer only.
+ *    N = n_in[b] (device i32) clamped to [0, n_in_max]; the -1 that wft_time_stretch_f32 writes for a refused row counts as 0.
+ *    c = 0.99 * min(1, rho);  g(t) = c * sinc(pi c t) * cos^2(pi c t / 12) for |c t| < 6 and exactly 0 otherwise, sinc(0) = 1.
+ *    out[m] = sum_j x[j] * g(j - t0),  t0 = (double)m / rho (ONE IEEE float64 division), x[j] = 0 outside [0, N),
+ *      for 0 <= m < min(n_out, ceil(N * rho)) (the product and its ceil in float64); for m from there up to n_out, out[m] = 0.
+ *    At rho = n / o this is the g((j / o - m / n) * base) of wft_resample_f32 algebraically: (j / o - m / n) * base =
+ *      (j - m o / n) * 0.99 min(o, n) / o = c (j - t0), and base / o = c.
+ *    The taps are summed in ascending j in fp64, t = (double)j - t0 and a = c * t each one rounding, the test |a| < 6 on that a;
+ *      the weight is (c * (sinpi(a) / (pi * a))) * cospi(a / 12)^2, evaluated per tap (13 taps at rho >= 1, up to 25 at rho = 0.5).
+ *    rho == 1.0 is not special-cased: it is a low-pass at 0.99 of Nyquist, not a copy.
+ *    A row whose device-side ratio lies outside [ratio_lo, 2.0], or is NaN, is written as n_out zeros.  No load or store leaves the
+ *      buffers whatever the device-side values hold.  Elements at or behind n_in[b] of an input row are never read; elements at or
+ *      behind n_out of an output row are never written.
+ *  in f32: row b at in + b * ld_in, ld_in >= n_in_max, 1 <= n_in_max <= 2^30; out f32: row b at out + b * ld_out, ld_out >= n_out,
+ *  1 <= n_out <= 2^30.  WFT_ERR_ARG: a null pointer, ratio_lo outside [0.5, 2.0] (or NaN), a bad shape, a short leading dimension,
+ *  misalignment (in / out / n_in 4 bytes, ratio 8), overlap.
+ *  wft_sinc_resample_rows_tile(ratio_lo): outputs per workgroup, a pure host function: at most 1024, a multiple of 4, smaller when
+ *  the input span of 1024 outputs at ratio_lo would not fit the 1600-float staging buffer (784 at 0.5); 0 = ratio_lo not supported.
+ *
+ * wft_alias_f32: audiomentations' Aliasing.apply, restated (parity with its binary unpinned; numpy's arithmetic held bit for bit):
+ *    n = len(samples); x = np.linspace(0, n, num=n); d = round(n * float(new_rate) / sample_rate)
+ *    u = np.linspace(0, n, num=d); out = np.interp(x, u, np.interp(u, x, samples))
+ *  both interpolations in one pass.  In float64, as numpy forms them: step_x = n / (n - 1), x_i = i * step_x with the last point
+ *  exactly n; d = (i64) rint(((double)n * new_rate) / sample_rate), half to even; step_u = n / (d - 1), u_k = k * step_u with the
+ *  last point exactly n.  np.interp(t, grid, f): with j the largest index whose grid point is <= t, the value is f_j when j is the
+ *  last index or grid_j == t, and otherwise ((f_{j+1} - f_j) / (grid_{j+1} - grid_j)) * (t - grid_j) + f_j.  j = floor(t / step),
+ *  corrected against the formed grid values.  The result is numpy's float64 value rounded once to f32 for finite samples (numpy's
+ *  second try after a NaN result, which only infinite samples reach, is not restated).
+ *    n[b]: device i32, clamped to [0, n_max], or NULL (every row covers n_max samples).  new_rate f64 [B] in device memory.
+ *    A row with new_rate[b] == 0, n[b] < 2 or d < 2 (also: a NaN rate, d above 2^32) is a copy of its bits.  out[b, n[b] .. n_max)
+ *    is written as zero.  Nothing at or behind n[b] of an input row is read, nothing at or behind n_max of an output row is written.
+ *  in / out f32: row b at in + b * ld_in / out + b * ld_out, ld >= n_max, 1 <= n_max <= 2^30.  WFT_ERR_ARG: a null pointer (in,
+ *  new_rate, out), sample_rate outside (0, 1e9] (or NaN), a bad shape, a short leading dimension, misalignment, overlap.
+ *  wft_alias_tile(): outputs per workgroup.
+ * DEVIATIONS of the loader option built on these (data/rate_fx.py): its own gates, independent of the wave stages; a default
+ * Aliasing maximum of the clip rate, not audiomentations' 30 000 Hz; the Hann-windowed sinc instead of librosa's soxr_hq; the
+ * phase-vocoder pitch shift, not audiomentations' current default; timestamps untouched, as in the reference.                     */
+int wft_sinc_resample_rows_f32(const float* in, int64_t ld_in, const int32_t* n_in, int64_t n_in_max, const double* ratio,
+                               double ratio_lo, float* out, int64_t ld_out, int64_t n_out, int B, void* stream);
+int wft_sinc_resample_rows_tile(double ratio_lo);
+int wft_alias_f32(const float* in, int64_t ld_in, const int32_t* n, int64_t n_max, const double* new_rate, double sample_rate,
+                  float* out, int64_t ld_out, int B, void* stream);
+int wft_alias_tile(void);
+
 /* ---------------------------------------------------------------- AdamW */
 /* torch.optim.AdamW single-tensor step over a flat f32 range
  * (model/optimizer.py:240-262 → optimizer.step() in model_utils.py:122).

@@ -73,8 +73,11 @@
   wavefx   the wave effects of the loader (--batches is not used): every stage of wft_wave_fx_f32 on [32, 480000] and [96, 480000],
          once with every row active and once with the number of rows the default rates make active, beside the log-mel and torch's
          copy of the same batch.  (--parts wavefx --out profiles/decode_bench_wavefx.jsonl)
+  rate     the rate effects of the loader (--batches is not used): K.alias, K.sinc_resample_rows and pitch_shift on [32, 480000] and
+         [96, 480000] with every row active (alias rates mel-spaced over 8-16 kHz, pitch over -4 .. +4 semitones), beside the log-mel
+         and torch's copy of the same batch.  No threshold is set.  (--parts rate --out profiles/decode_bench_rate.jsonl)
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample,stretch,filter,wavefx] [--batches 1,8,32] [--out FILE]
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample,stretch,filter,wavefx,rate] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -1112,6 +1115,39 @@ def bench_wavefx(batches):
             emit(rec)
 
 
+def bench_rate(batches):
+    """K.alias, K.sinc_resample_rows and gpu_frontend.pitch_shift on 30 s clips with every row active: ms per call beside the log-mel
+    and torch's copy of the same batch."""
+    import numpy as np
+
+    from whisper_finetune.data.gpu_frontend import mel_filters, pitch_rates, pitch_shift
+    from whisper_finetune.data.rate_fx import hz_to_mel, mel_to_hz
+
+    lib = L.load()
+    n = 480000
+    filters = mel_filters(80).to(DEV)
+    for B in (32, 96):
+        g = torch.Generator().manual_seed(B)
+        x = (torch.randn(B, n, generator=g) * 0.1).to(DEV)
+        x[:, 300000:] = 0  # zero-padded clips, as the loader stages them
+        out = torch.empty_like(x)
+        rates = np.array([mel_to_hz(m) for m in np.linspace(hz_to_mel(8000.0), hz_to_mel(16000.0), B)])
+        semis = np.linspace(-4.0, 4.0, B)
+        ratios = pitch_rates(semis, B)
+        n_in = torch.full((B,), n, dtype=torch.int32, device=DEV)
+        res = ab({"alias": lambda: K.alias(x, rates), "sinc_resample_rows": lambda: K.sinc_resample_rows(x, n_in, ratios, n),
+                  "pitch_shift": lambda: pitch_shift(x, semis), "logmel": lambda: K.logmel(x, filters, 3000), "copy": lambda: out.copy_(x)},
+                 rounds=5, iters=5)
+        rec = dict(part="rate", B=B, n=n, alias_tile=lib.wft_alias_tile(), sinc_tile=lib.wft_sinc_resample_rows_tile(float(ratios.min())),
+                   ratio_lo=round(float(ratios.min()), 4),
+                   note="ms per call, medians of 5 alternating rounds of 5 calls, every row active; alias / sinc_resample_rows: the wrappers "
+                        "(host check, upload of the per-row values, output allocation); pitch_shift = K.time_stretch + K.sinc_resample_rows; "
+                        "logmel / copy: the log-mel of the same batch and torch's copy of it, for scale")
+        for name, (med, mn, spread) in res.items():
+            rec[name + "_ms"], rec[name + "_min_ms"], rec[name + "_spread"] = round(med, 4), round(mn, 4), round(spread, 3)
+        emit(rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="attn,gemm,e2e")
@@ -1125,7 +1161,7 @@ def main():
     for part in a.parts.split(","):
         {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": lambda b: (bench_gemm_stream(b), bench_gemm_stream_q8(b)), "e2e_step": bench_e2e_step,
          "gemm_i8": bench_gemm_i8, "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align, "transcribe": bench_transcribe, "resample": bench_resample,
-         "stretch": bench_stretch, "filter": bench_filter, "wavefx": bench_wavefx}[part](batches)
+         "stretch": bench_stretch, "filter": bench_filter, "wavefx": bench_wavefx, "rate": bench_rate}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

@@ -28,6 +28,13 @@ WaveAug, after the filter draw) and ships them as one table row f64 [14]; the ma
 per call, in the reference's Compose order: resample -> stretch -> NOISE -> filter -> CLIP -> LEVEL -> log-mel.  Every stage covers
 the row's full stretched length, padding included (the reference transforms the padded clip), and a stage with no active row launches
 nothing.  Timestamps are not moved under `shift`, as in the reference.
+
+Rate effects (`rate_aug={...}`, an option of this project's own: Aliasing and PitchShift of the reference's advanced pipeline, NOT
+`apply_advanced_aug`): a worker only DRAWS the clip's parameters (data/rate_fx.py RateAug, after the wave-effects draw) and ships them
+as one table row f64 [4]; the main process runs `wft_alias_f32` and the pitch shift (`wft_time_stretch_f32` +
+`wft_sinc_resample_rows_f32`) in the reference's Compose order: resample -> stretch -> NOISE -> ALIAS -> filter -> CLIP -> LEVEL ->
+PITCH -> log-mel, each over the row's full stretched length.  Alias writes into a second buffer that takes the first one's place;
+pitch gathers the pitched rows only.  Timestamps are untouched, as in the reference.
 """
 from __future__ import annotations
 
@@ -45,6 +52,7 @@ from whisper_finetune.data.filters import FilterAug, identity_sos
 from whisper_finetune.data.gpu_frontend import (HOP_LENGTH, N_FFT, N_FRAMES, N_SAMPLES, SAMPLE_RATE, GpuFrontend, check_rate,
                                                 check_stretch_range, draw_clip_params, mel_filters)
 from whisper_finetune.data.utils import ExtremesFrequencyMasking, TimeWarpAugmenter, pad_or_trim
+from whisper_finetune.data.rate_fx import RateAug, check_table as check_rate_table
 from whisper_finetune.data.wave_fx import STAGES as WAVE_STAGES, WaveAug, active_rows, check_records, records_from_table
 
 CHUNK_LENGTH = 30
@@ -52,20 +60,53 @@ _TS = re.compile(r"(<\|[123]?[0-9]\.[0-9][0-9]\|>)")  # <|0.00|> .. <|30.00|>
 _FILTERS = {}
 
 
-def apply_wave_stages(audio, n, sos, fx):
-    """The audio-domain stages behind the stretch, in place on audio f32 [B, ld] (device), in the reference's Compose order:
-    NOISE -> filter -> CLIP -> LEVEL.  n: i32 [B] on the device or None; sos: f64 [B, 4, 6] or None; fx: checked wave-effect records
-    [B] (data/wave_fx.py) or None.  A stage with no active row launches nothing."""
+def pitch_rows(audio, semitones, lengths=None):
+    """The pitch shift of the rows whose entry of `semitones` (host, one per row) is not None, in place on audio f32 [B, ld]: the
+    pitched rows are gathered, shifted (gpu_frontend.pitch_shift_rows: time stretch + sinc resample back to the row's length) and put
+    back; the other rows keep their bits.  lengths: the rows' lengths as HOST integers (the stretched lengths; None = ld for every
+    row).  wft_time_stretch_f32 takes one length per call, so the pitched rows go one call per distinct length."""
+    from whisper_finetune.data.gpu_frontend import pitch_rates, pitch_shift_rows
+
+    groups = {}
+    for b, s in enumerate(semitones):
+        if s is not None:
+            groups.setdefault(int(audio.shape[1]) if lengths is None else int(lengths[b]), []).append(b)
+    for length, rows in groups.items():
+        if length < 1:
+            continue
+        idx = torch.tensor(rows, dtype=torch.int64).to(audio.device, non_blocking=True)
+        part = audio.index_select(0, idx)[:, :length]
+        shifted = pitch_shift_rows(part, pitch_rates([semitones[b] for b in rows], len(rows)))
+        audio[:, :length].index_copy_(0, idx, shifted)
+    return audio
+
+
+def apply_wave_stages(audio, n, sos, fx, rate=None, lengths=None):
+    """The audio-domain stages behind the stretch on audio f32 [B, ld] (device), in the reference's Compose order:
+    NOISE -> ALIAS -> filter -> CLIP -> LEVEL -> PITCH.  n: i32 [B] on the device or None; sos: f64 [B, 4, 6] or None; fx: checked
+    wave-effect records [B] (data/wave_fx.py) or None; rate: the checked rate-effect table f64 [B, 4] (data/rate_fx.py) or None;
+    lengths: the rows' lengths as host integers (what n holds; None with n None).  A stage with no active row launches nothing.
+    Every stage but ALIAS runs in place; ALIAS writes a second buffer, so use the RETURNED tensor."""
     from whisper_finetune.engine import kernels as K
 
     if fx is not None:
         K.wave_fx(audio, fx, "noise", n, out=audio)
+    if rate is not None and bool(rate[:, 0].any()):
+        audio = K.alias(audio, rate[:, 1], n, SAMPLE_RATE)  # out of place; a "none" row (rate 0) is copied
     if sos is not None:
         K.sos_filter(audio, sos, n, out=audio)
     if fx is not None:
         K.wave_fx(audio, fx, "clip", n, out=audio)
         K.wave_fx(audio, fx, "level", n, out=audio)  # (shift rows go through a temporary inside K.wave_fx)
+    if rate is not None and bool(rate[:, 2].any()):
+        pitch_rows(audio, [float(r[3]) if r[2] else None for r in rate], lengths)
     return audio
+
+
+def stretched_lengths(n: int, rates):
+    """The lengths wft_time_stretch_f32 gives rows of n samples, on the host: round(n / rate), the same float64 division and
+    half-even rounding as the kernel's."""
+    return [int(round(n / float(r))) for r in rates]
 
 
 def log_mel_spectrogram(audio, n_mels: int = 80, padding: int = 0, device=None) -> torch.Tensor:
@@ -97,7 +138,8 @@ class AudioDataset(Dataset):
     """Items: (audio f32 [30 * sample_rate] (480000 at the default 16 kHz), decoder_input i64, decoder_output i64, aug i32 [8], extremes i32 [2], cut_frames);
     with `apply_baseline_aug` a seventh field, the clip's time-stretch rate as f64 (without it the items are the six fields, unchanged);
     with `filter_aug` one more field behind those, the clip's filter as sos f64 [4, 6] (identity sections = "do not filter");
-    with `wave_aug` one more field behind the filter, the clip's wave effects as a table row f64 [14] (data/wave_fx.py).
+    with `wave_aug` one more field behind the filter, the clip's wave effects as a table row f64 [14] (data/wave_fx.py);
+    with `rate_aug` one more field behind the wave effects, the clip's rate effects as a table row f64 [4] (data/rate_fx.py).
 
     apply_baseline_aug: the rate is drawn as audiomentations draws it — Python's `random` module, one `random.random()` gate against
     p = 1.0, then `random.uniform(min_rate, max_rate)` (BaseWaveformTransform.randomize_parameters, then TimeStretch's).  That order is
@@ -110,6 +152,8 @@ class AudioDataset(Dataset):
     the order), designed for 16 kHz (it runs behind the resample), and never touches torch's generator.
     wave_aug: None, or a mapping of data/wave_fx.py WaveAug's groups (`noise`, `clip`, `level`, each None or {p, kinds}; a missing
     group is off).  The parameters are drawn after the filter, with Python's `random` (WaveAug's docstring states the order).
+    rate_aug: None, or a mapping of data/rate_fx.py RateAug's groups (`alias`, `pitch`, each None or a mapping of its keywords; a
+    missing group is off).  The parameters are drawn after the wave effects, with Python's `random`.
 
     hu_dataset: indexable records {"audio": {"array", optional "sampling_rate"}, "text", "language", optional "prompt"}; a record
     whose "sampling_rate" is present and differs from the dataset's `sample_rate` raises ValueError (no mixed rates); tokenizer: whisper-style
@@ -123,6 +167,7 @@ class AudioDataset(Dataset):
     apply_baseline_aug = False
     filter_aug = None
     wave_aug = None
+    rate_aug = None
 
     def __init__(self, hu_dataset, tokenizer, device=None, no_timestamp_training: bool = False, n_mels: int = 80,
                  max_prompt_length: int = 223, prompt_use_rate: float = 0.5, no_timestamps_rate: float = 0.5,
@@ -130,7 +175,7 @@ class AudioDataset(Dataset):
                  extremes_spec_augment_params: Optional[dict] = None, apply_baseline_aug: bool = False, apply_office_aug: bool = False,
                  apply_advanced_aug: bool = False, time_stretch_min_rate: float = 0.8, time_stretch_max_rate: float = 1.25,
                  bpe_dropout: float = 0.0, sample_rate: int = SAMPLE_RATE, filter_aug: Optional[dict] = None,
-                 wave_aug: Optional[dict] = None):
+                 wave_aug: Optional[dict] = None, rate_aug: Optional[dict] = None):
         self.sample_rate = check_rate(sample_rate)
         self.n_samples = CHUNK_LENGTH * self.sample_rate  # 30 s at the clips' own rate
         refused = [name for name, on in (("apply_office_aug", apply_office_aug), ("apply_advanced_aug", apply_advanced_aug)) if on]
@@ -154,6 +199,9 @@ class AudioDataset(Dataset):
         if wave_aug is not None and (not hasattr(wave_aug, "keys") or not set(wave_aug.keys()) <= set(WAVE_STAGES)):
             raise ValueError(f"wave_aug must be None or a mapping of WaveAug's groups {WAVE_STAGES}, got {wave_aug!r}")
         self.wave_aug = WaveAug(sample_rate=SAMPLE_RATE, **dict(wave_aug)) if wave_aug is not None else None
+        if rate_aug is not None and (not hasattr(rate_aug, "keys") or not set(rate_aug.keys()) <= {"alias", "pitch"}):
+            raise ValueError(f"rate_aug must be None or a mapping of RateAug's groups ('alias', 'pitch'), got {rate_aug!r}")
+        self.rate_aug = RateAug(sample_rate=SAMPLE_RATE, **dict(rate_aug)) if rate_aug is not None else None
         if spec_augment:
             self.spec_augment_p = float(spec_augment_params.get("p", 1.0))
             if not 0.0 <= self.spec_augment_p <= 1.0:
@@ -206,8 +254,15 @@ class AudioDataset(Dataset):
         names, row = self.wave_aug.draw(N_SAMPLES)
         return check_records(records_from_table(row[None])) if any(names.values()) else None
 
+    def _draw_rate(self):
+        """The clip's rate effects for the per-clip form: the checked table f64 [1, 4], or None without the option or when nothing was drawn."""
+        if self.rate_aug is None:
+            return None
+        names, row = self.rate_aug.draw()
+        return check_rate_table(row[None]) if any(names.values()) else None
+
     def _calculate_mel(self, audio_array, next_partial_segment_start: Optional[float], no_timestamps: bool) -> torch.Tensor:
-        """Per-clip form: [time stretch] -> [noise] -> [filter] -> [clipping] -> [level] -> log-mel -> cut at a partial segment + minimum-value pad -> [warp -> time mask -> freq mask]
+        """Per-clip form: [time stretch] -> [noise] -> [alias] -> [filter] -> [clipping] -> [level] -> [pitch] -> log-mel -> cut at a partial segment + minimum-value pad -> [warp -> time mask -> freq mask]
         w.p. p -> extremes masking, every stage a libwft kernel on the device."""
         if self.sample_rate != SAMPLE_RATE:
             raise ValueError(f"_calculate_mel is the per-clip 16 kHz form; clips at {self.sample_rate} Hz are resampled per batch by GpuMelLoader")
@@ -218,20 +273,21 @@ class AudioDataset(Dataset):
 
             dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
             row = torch.as_tensor(np.asarray(audio_array, dtype=np.float32)).to(dev)[None]
-            stretched, n_out = K.time_stretch(row, [self._draw_stretch_rate()])
-            sos, fx = self._draw_filter(), self._draw_wave()
-            apply_wave_stages(stretched, n_out, sos, fx)
+            stretch_rate = self._draw_stretch_rate()
+            stretched, n_out = K.time_stretch(row, [stretch_rate])
+            sos, fx, rt = self._draw_filter(), self._draw_wave(), self._draw_rate()
+            stretched = apply_wave_stages(stretched, n_out, sos, fx, rt, stretched_lengths(row.shape[1], [stretch_rate]))
             key = (self.n_mels, row.device)
             if key not in _FILTERS:
                 _FILTERS[key] = mel_filters(self.n_mels).to(row.device)
             keep = torch.tensor([min(cut, N_FRAMES)], dtype=torch.int32, device=row.device)
             mel = K.logmel_ragged(stretched, n_out, keep, _FILTERS[key], N_FRAMES)[0]
         else:
-            sos, fx = self._draw_filter(), self._draw_wave()
-            if sos is not None or fx is not None:  # the same kernels as GpuMelLoader, on one row
+            sos, fx, rt = self._draw_filter(), self._draw_wave(), self._draw_rate()
+            if sos is not None or fx is not None or rt is not None:  # the same kernels as GpuMelLoader, on one row
                 dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
                 row = torch.as_tensor(np.asarray(audio_array, dtype=np.float32)).to(dev)[None].clone()
-                audio_array = apply_wave_stages(row, None, sos, fx)[0]
+                audio_array = apply_wave_stages(row, None, sos, fx, rt)[0]
             mel = log_mel_spectrogram(audio_array, n_mels=self.n_mels, device=self.device)
             if no_timestamps and next_partial_segment_start is not None:
                 mel = mel[:, : int(next_partial_segment_start * self.num_frames_per_second)]
@@ -362,6 +418,8 @@ class AudioDataset(Dataset):
             item += (torch.from_numpy(self.filter_aug.draw()[2]),)
         if self.wave_aug is not None:
             item += (torch.from_numpy(self.wave_aug.draw(N_SAMPLES)[1]),)
+        if self.rate_aug is not None:
+            item += (torch.from_numpy(self.rate_aug.draw()[1]),)
         return item
 
 
@@ -373,7 +431,7 @@ def collate_fn(data):
     if len(cols) == 3:
         return pad_sequence(cols[0], batch_first=True, padding_value=0), y_in, y_out
     out = (torch.stack(cols[0]), y_in, y_out, torch.stack(cols[3]), torch.stack(cols[4]), torch.tensor(cols[5], dtype=torch.int32))
-    return out + tuple(torch.stack(c) for c in cols[6:])  # the time-stretch rates f64 [B], the filters f64 [B, 4, 6], the wave effects f64 [B, 14]
+    return out + tuple(torch.stack(c) for c in cols[6:])  # the time-stretch rates f64 [B], the filters f64 [B, 4, 6], the wave effects f64 [B, 14], the rate effects f64 [B, 4]
 
 
 class WarmupDatasetSampler(torch.utils.data.Sampler):
@@ -443,10 +501,16 @@ class GpuMelLoader:
     Batches of a dataset built with wave_aug carry the wave effects f64 [B, 14] as their last field, behind the filters: the stages
     run in place in the order resample -> stretch -> NOISE -> filter -> CLIP -> LEVEL -> log-mel (apply_wave_stages), each over the
     row's full stretched length.  The table is turned into checked records on the host; a stage with no active row launches nothing,
-    and a batch with no effect at all is the batch of a loader without the option, bit for bit."""
+    and a batch with no effect at all is the batch of a loader without the option, bit for bit.
+
+    Batches of a dataset built with rate_aug carry the rate effects f64 [B, 4] as their last field, behind the wave effects: the
+    order becomes resample -> stretch -> NOISE -> ALIAS -> filter -> CLIP -> LEVEL -> PITCH -> log-mel.  ALIAS is one out-of-place
+    launch over the batch ("none" rows are copied) whose output takes the batch's place.  PITCH gathers the pitched rows only: one
+    batched call without the baseline stretch (every row has 480000 samples), one call per distinct stretched length with it
+    (the lengths are known on the host as round(480000 / rate): no synchronisation)."""
 
     def __init__(self, loader, frontend: GpuFrontend, training_aug: bool, sample_rate: int = SAMPLE_RATE, stretch: Optional[bool] = None,
-                 filter_aug: Optional[bool] = None, wave_aug: Optional[bool] = None):
+                 filter_aug: Optional[bool] = None, wave_aug: Optional[bool] = None, rate_aug: Optional[bool] = None):
         self.loader, self.frontend, self.training_aug = loader, frontend, training_aug
         ds = getattr(loader, "dataset", None)
         if stretch is None and ds is not None:
@@ -455,7 +519,9 @@ class GpuMelLoader:
             filter_aug = getattr(ds, "filter_aug", None) is not None
         if wave_aug is None:
             wave_aug = getattr(ds, "wave_aug", None) is not None
-        self.stretch, self.filter_aug, self.wave_aug = stretch, bool(filter_aug), bool(wave_aug)
+        if rate_aug is None:
+            rate_aug = getattr(ds, "rate_aug", None) is not None
+        self.stretch, self.filter_aug, self.wave_aug, self.rate_aug = stretch, bool(filter_aug), bool(wave_aug), bool(rate_aug)
         self._identity = torch.from_numpy(identity_sos())
         self.sample_rate = check_rate(sample_rate)
         self.sampler = getattr(loader, "sampler", None)  # infinite_iter() calls sampler.set_epoch(...)
@@ -473,20 +539,30 @@ class GpuMelLoader:
     def _fields(self, batch):
         """(rates or None, sos or None, wave-effect records or None) of a collated batch, by the flags.  An all-identity `sos` and a
         table without any effect count as None."""
-        stretch = (len(batch) == 7 and not self.filter_aug and not self.wave_aug) if self.stretch is None else self.stretch
-        if len(batch) != 6 + int(stretch) + int(self.filter_aug) + int(self.wave_aug):
+        return self._all_fields(batch)[:3]
+
+    def _all_fields(self, batch):
+        """_fields and, as a fourth item, the checked rate-effect table f64 [B, 4] (numpy) or None (no option, or no row active)."""
+        stretch = (len(batch) == 7 and not self.filter_aug and not self.wave_aug and not self.rate_aug) if self.stretch is None else self.stretch
+        if len(batch) != 6 + int(stretch) + int(self.filter_aug) + int(self.wave_aug) + int(self.rate_aug):
             raise ValueError(f"a batch of {len(batch)} fields from a loader with stretch={stretch}, filter_aug={self.filter_aug}"
-                             + (f", wave_aug={self.wave_aug}" if self.wave_aug else ""))
+                             + (f", wave_aug={self.wave_aug}" if self.wave_aug else "")
+                             + (f", rate_aug={self.rate_aug}" if self.rate_aug else ""))
         rates = batch[6] if stretch else None
         sos = batch[6 + int(stretch)] if self.filter_aug else None
         if sos is not None and bool((sos == self._identity).all()):
             sos = None
         fx = None
         if self.wave_aug:
-            fx = check_records(records_from_table(batch[-1]))
+            fx = check_records(records_from_table(batch[6 + int(stretch) + int(self.filter_aug)]))
             if not any(bool(active_rows(fx, stage).any()) for stage in WAVE_STAGES):
                 fx = None
-        return rates, sos, fx
+        rt = None
+        if self.rate_aug:
+            rt = check_rate_table(batch[-1])
+            if not bool(rt[:, 0].any() or rt[:, 2].any()):
+                rt = None
+        return rates, sos, fx, rt
 
     def _stage(self, batch):
         """Issue the batch's H2D copies on the side stream; returns the device tensors and the event that orders them."""
@@ -494,15 +570,15 @@ class GpuMelLoader:
         if self._copy_stream is None:
             self._copy_stream = torch.cuda.Stream(device=dev)
         audio, y_in, y_out, params, ext, cut = batch[:6]
-        rates, sos, fx = self._fields(batch)
+        rates, sos, fx, rt = self._all_fields(batch)
         need_aug = bool(params[:, 0].any() or ext.any())  # decided on the host copies: no device sync
         with torch.cuda.stream(self._copy_stream):
             staged = [t.to(dev, non_blocking=True) for t in (audio, y_in, y_out, params, ext)]
             ev = torch.cuda.Event()
             ev.record(self._copy_stream)
-        return staged, cut, ev, need_aug, rates, sos, fx
+        return staged, cut, ev, need_aug, rates, sos, fx, rt
 
-    def _to_mel(self, staged, cut, ev, need_aug, rates=None, sos=None, fx=None):
+    def _to_mel(self, staged, cut, ev, need_aug, rates=None, sos=None, fx=None, rt=None):
         from whisper_finetune.engine import kernels as K
 
         cur = torch.cuda.current_stream(self.frontend.device)
@@ -517,14 +593,15 @@ class GpuMelLoader:
             # the stretch of the zero-PADDED clip, as the reference does it; the rates are host values (they size the launch), the
             # rows' lengths stay on the device; the cut and the minimum-value pad happen inside the ragged log-mel
             stretched, n_out = K.time_stretch(audio, rates)
-            apply_wave_stages(stretched, n_out, sos, fx)
+            stretched = apply_wave_stages(stretched, n_out, sos, fx, rt,
+                                          stretched_lengths(audio.shape[1], rates.tolist()) if rt is not None else None)
             keep = cut.clamp(max=N_FRAMES).to(torch.int32).to(audio.device, non_blocking=True)
             mel = K.logmel_ragged(stretched, n_out, keep, self.frontend.filters, N_FRAMES)
         else:
-            if sos is not None or fx is not None:
+            if sos is not None or fx is not None or rt is not None:
                 if audio.stride(1) != 1 or not audio.is_contiguous():
                     audio = audio.contiguous()
-                apply_wave_stages(audio, None, sos, fx)  # in place on the staged (or resampled) copy
+                audio = apply_wave_stages(audio, None, sos, fx, rt)  # in place on the staged (or resampled) copy; alias gives a new one
             mel = self.frontend.log_mel(audio)
             for b in (cut < N_FRAMES).nonzero().flatten().tolist():  # rare: cut at a partial segment, pad with the min value
                 c = int(cut[b])
@@ -540,7 +617,7 @@ class GpuMelLoader:
                 audio, y_in, y_out, params, ext, cut = batch[:6]
                 need_aug = bool(params[:, 0].any() or ext.any())
                 staged = [t.to(dev, non_blocking=True) for t in (audio, y_in, y_out, params, ext)]
-                yield self._to_mel(staged, cut, None, need_aug, *self._fields(batch))
+                yield self._to_mel(staged, cut, None, need_aug, *self._all_fields(batch))
             return
         it = iter(self.loader)
         try:
@@ -563,9 +640,10 @@ def get_dataloader(hu_dataset, tokenizer, batch_size: int = 1, n_mels: int = 80,
                    extremes_spec_augment_params: Optional[dict] = None, apply_baseline_aug: bool = False, apply_office_aug: bool = False,
                    apply_advanced_aug: bool = False, time_stretch_min_rate: float = 0.8, time_stretch_max_rate: float = 1.25,
                    bpe_dropout: float = 0.0, drop_last: bool = False, sample_rate: int = SAMPLE_RATE, filter_aug: Optional[dict] = None,
-                   wave_aug: Optional[dict] = None):
+                   wave_aug: Optional[dict] = None, rate_aug: Optional[dict] = None):
     """`filter_aug`: None, or a mapping of FilterAug's keywords (AudioDataset's docstring): the filter augmentation of a TRAINING loader.
     `wave_aug`: None, or a mapping of WaveAug's groups (AudioDataset's docstring): noise, clipping and level changes of a TRAINING loader.
+    `rate_aug`: None, or a mapping of RateAug's groups (AudioDataset's docstring): aliasing and pitch shift of a TRAINING loader.
     `sample_rate`: the rate of every clip of `hu_dataset` (default 16000).  At another rate the clips are padded to
     30 * sample_rate samples and resampled to 16 kHz on the device (GpuMelLoader); without a device the loader yields the padded
     native-rate clips."""
@@ -576,7 +654,7 @@ def get_dataloader(hu_dataset, tokenizer, batch_size: int = 1, n_mels: int = 80,
                       extremes_spec_augment_params=extremes_spec_augment_params, bpe_dropout=bpe_dropout,
                       apply_baseline_aug=apply_baseline_aug, apply_office_aug=apply_office_aug, apply_advanced_aug=apply_advanced_aug,
                       time_stretch_min_rate=time_stretch_min_rate, time_stretch_max_rate=time_stretch_max_rate, sample_rate=sample_rate,
-                      filter_aug=filter_aug, wave_aug=wave_aug)
+                      filter_aug=filter_aug, wave_aug=wave_aug, rate_aug=rate_aug)
     if sampler is not None:
         shuffle = False  # DataLoader does not allow both
     loader = DataLoader(ds, batch_size=batch_size, sampler=sampler, shuffle=shuffle, num_workers=num_workers,

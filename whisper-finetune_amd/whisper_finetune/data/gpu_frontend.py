@@ -202,6 +202,67 @@ def wave_fx(audio, kind, device=None, **params):
     return out if a.dim() == 2 else out[0]
 
 
+# ------------------------------------------------------------------------------------------------- rate effects
+# Pitch shift and aliasing (data/rate_fx.py draws them for the loader; include/wft.h "Per-row rate conversion" states the arithmetic).
+from whisper_finetune.data.rate_fx import PITCH_MAX_SEMITONES  # noqa: E402  (12: 2^(12/12) = 2.0, the end of the time stretch's range)
+
+
+def pitch_rates(semitones, B: int):
+    """One shift in semitones or one per row -> the float64 [B] rates 2^(-s/12) of the time stretch (and ratios of the resampler);
+    a shift outside [-12, 12] (or NaN) raises ValueError."""
+    s = K._row_values(semitones, B, "pitch_shift", "semitones")
+    if not bool(np.all((s >= -PITCH_MAX_SEMITONES) & (s <= PITCH_MAX_SEMITONES))):
+        raise ValueError(f"pitch_shift: semitones must lie in [{-PITCH_MAX_SEMITONES}, {PITCH_MAX_SEMITONES}], got {s.tolist()}")
+    return np.clip(2.0 ** (-s / 12.0), K.STRETCH_MIN_RATE, K.STRETCH_MAX_RATE)  # (the clip only guards the last ulp at +-12)
+
+
+def pitch_shift_rows(rows, rates):
+    """rows f32 [B, n] on the device, rates float64 [B] from pitch_rates -> f32 [B, n]: K.time_stretch by the rate, then
+    K.sinc_resample_rows by the same ratio back to n samples."""
+    stretched, n_out = K.time_stretch(rows, rates)
+    return K.sinc_resample_rows(stretched, n_out, rates, int(rows.shape[1]))
+
+
+def pitch_shift(audio, semitones, device=None):
+    """audio shifted in pitch by `semitones` at unchanged length, on the device: librosa.effects.pitch_shift's definition, a time
+    stretch by 2^(-s/12) (the phase vocoder) followed by a resample back to the input's length (this project's Hann-windowed sinc;
+    not librosa's soxr_hq: parity unpinned).
+
+    audio: f32, 1-D [n] or 2-D [B, n], a tensor or an array; a host input goes to `device` (default: the current GPU) first.
+    semitones: one value or one per row, inside [-12, 12] (ValueError otherwise).  Returns a new device tensor of the input's shape."""
+    a = torch.as_tensor(audio)
+    if a.dim() not in (1, 2) or a.dtype != torch.float32 or a.numel() == 0:
+        raise ValueError(f"pitch_shift: audio must be a non-empty float32 [n] or [B, n], got {a.dtype} {tuple(a.shape)}")
+    rows = a if a.dim() == 2 else a[None]
+    rates = pitch_rates(semitones, rows.shape[0])  # before the device is touched
+    if device is not None:
+        rows = rows.to(device)
+    elif not rows.is_cuda:
+        rows = rows.to(torch.device("cuda", torch.cuda.current_device()))
+    out = pitch_shift_rows(rows, rates)
+    return out if a.dim() == 2 else out[0]
+
+
+def alias(audio, new_sample_rate, device=None, sample_rate: int = SAMPLE_RATE):
+    """audio under audiomentations' Aliasing: linear interpolation down to `new_sample_rate` Hz and back, without a low-pass, on the
+    device (K.alias: numpy's result bit for bit).
+
+    audio: f32, 1-D [n] or 2-D [B, n], a tensor or an array; a host input goes to `device` (default: the current GPU) first.
+    new_sample_rate: one rate or one per row, inside [1000, 2 * sample_rate], or 0 for "leave the row as it is" (ValueError
+    otherwise).  Returns a new device tensor of the input's shape."""
+    a = torch.as_tensor(audio)
+    if a.dim() not in (1, 2) or a.dtype != torch.float32 or a.numel() == 0:
+        raise ValueError(f"alias: audio must be a non-empty float32 [n] or [B, n], got {a.dtype} {tuple(a.shape)}")
+    rows = a if a.dim() == 2 else a[None]
+    rates = K.alias_rates(new_sample_rate, rows.shape[0], float(check_rate(sample_rate)))  # before the device is touched
+    if device is not None:
+        rows = rows.to(device)
+    elif not rows.is_cuda:
+        rows = rows.to(torch.device("cuda", torch.cuda.current_device()))
+    out = K.alias(rows, rates, None, sample_rate)
+    return out if a.dim() == 2 else out[0]
+
+
 from whisper_finetune.data.transforms import FrequencyMasking, TimeMasking, draw_mask_span  # noqa: E402,F401
 
 

@@ -14,9 +14,11 @@ Deviations from the reference's recipe, all of them deliberate:
   * own outer gates.  The reference draws ONE of four alternatives in its noise group (p = 0.3), one of nine in its filter group
     (p = 0.6) and one of four in its level group (p = 0.3).  Only 2, 1 and 3 of those alternatives are built here, so the default outer
     gates reproduce their MARGINAL rates: noise 0.3 * 2 / 4 = 0.15, clipping 0.6 / 9, level 0.3 * 3 / 4 = 0.225.
-  * PitchShift's slot in the level group is dropped (its quarter of the gate is simply "nothing").
+  * PitchShift's slot in the level group is dropped here (its quarter of the gate is simply "nothing"); the pitch shift has a gate of its
+    own in data/rate_fx.py, independent of this group.
   * clipping sits outside the filter group's OneOf: a clip may be filtered AND clipped, which the reference never does.
-  * background-noise files, LoudnessNormalization, Aliasing, AirAbsorption and PitchShift are not built.
+  * background-noise files, LoudnessNormalization and AirAbsorption need files or libraries and are not built; Aliasing and PitchShift
+    are resampling at a per-row rate and live in data/rate_fx.py (csrc/rate.hip).
 """
 from __future__ import annotations
 

@@ -1496,6 +1496,112 @@ def wave_fx(audio, fx, stage, n=None, *, out=None):
     return dst
 
 
+def _row_values(values, B: int, who: str, what: str):
+    """One value or one per row (numbers, a list, an array or a HOST tensor) -> float64 numpy [B]."""
+    import numpy as np
+
+    v = values.detach().cpu().numpy() if torch.is_tensor(values) else np.asarray(values)
+    if v.dtype == object or v.dtype.kind not in "fiu":
+        raise ValueError(f"{who}: {what} must be numbers, got {v.dtype}")
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    if v.shape[0] == 1 and B > 1:
+        v = np.repeat(v, B)
+    if v.shape[0] != B:
+        raise ValueError(f"{who}: {v.shape[0]} {what} for {B} rows")
+    return np.ascontiguousarray(v)
+
+
+def _rate_rows(audio, who: str):
+    """The shared host-side checks of the per-row rate kernels on their input (ValueError); returns it unchanged."""
+    if not torch.is_tensor(audio) or audio.dtype != F32 or audio.dim() != 2 or audio.shape[0] < 1 or audio.shape[1] < 1:
+        raise ValueError(f"{who}: audio must be a float32 tensor [B, n] with B >= 1 and n >= 1, got {getattr(audio, 'dtype', type(audio))} "
+                         f"{tuple(getattr(audio, 'shape', ()))}")
+    if audio.shape[0] > 65535 or audio.shape[1] > (1 << 30):
+        raise ValueError(f"{who}: at most 65535 rows of 2^30 samples per call, got {tuple(audio.shape)}")
+    return audio
+
+
+def sinc_resample_rows(audio, n_in, ratios, n_out: int):
+    """Resampling by a float64 ratio of its own for every row (wft_sinc_resample_rows_f32, include/wft.h "Per-row rate conversion").
+
+    audio f32 [B, ld] on the device (stride(1) == 1); n_in i32 [B] on the device: row b holds n_in[b] samples (clamped to [0, ld]);
+    ratios: one ratio (output rate / input rate) or one per row, HOST values inside [0.5, 2.0] (ValueError otherwise: their minimum
+    sizes the launch, so they are checked here and not on the device); n_out: the length of every output row.
+    -> f32 [B, n_out]: row b holds min(n_out, ceil(n_in[b] * ratio[b])) resampled samples and zeros behind them.
+    Every host-side check raises ValueError before the device is touched."""
+    import numpy as np
+
+    audio = _rate_rows(audio, "sinc_resample_rows")
+    B, ld = audio.shape
+    if isinstance(n_out, bool) or not isinstance(n_out, int) or not 1 <= n_out <= (1 << 30):
+        raise ValueError(f"sinc_resample_rows: n_out must be an integer inside [1, 2^30], got {n_out!r}")
+    if not torch.is_tensor(n_in) or n_in.dtype != torch.int32 or tuple(n_in.shape) != (B,):
+        raise ValueError(f"sinc_resample_rows: n_in must be an int32 tensor [{B}]")
+    r = _row_values(ratios, B, "sinc_resample_rows", "ratios")
+    if not bool(np.all((r >= STRETCH_MIN_RATE) & (r <= STRETCH_MAX_RATE))):
+        raise ValueError(f"sinc_resample_rows: ratios must lie in [{STRETCH_MIN_RATE}, {STRETCH_MAX_RATE}], got {r.tolist()}")
+    _chk(audio, F32, "audio")  # (every ValueError above comes before the device is touched)
+    if n_in.device != audio.device:
+        raise ValueError("sinc_resample_rows: audio and n_in must live on the same GPU")
+    if audio.stride(1) != 1 or (B > 1 and audio.stride(0) < ld):
+        audio = audio.contiguous()
+    ratio_lo = float(r.min())
+    lib = L.load()
+    if lib.wft_sinc_resample_rows_tile(ratio_lo) < 4:
+        raise ValueError(f"sinc_resample_rows: a lowest ratio of {ratio_lo} is not supported by wft_sinc_resample_rows_f32")
+    out = torch.empty((B, n_out), dtype=F32, device=audio.device)
+    ratio_d = torch.from_numpy(r).to(audio.device)
+    ld_in = audio.stride(0) if B > 1 else max(audio.stride(0), ld)
+    L.check(lib.wft_sinc_resample_rows_f32(_p(audio), ld_in, _p(n_in.contiguous()), ld, _p(ratio_d), ratio_lo, _p(out), out.stride(0),
+                                           n_out, B, L.stream_ptr()), "wft_sinc_resample_rows_f32")
+    return out
+
+
+def alias_rates(new_rates, B: int, sample_rate):
+    """One new rate or one per row -> float64 numpy [B]; a rate is 0 ("none": the row is copied) or lies inside
+    [1000, 2 * sample_rate], anything else (NaN included) raises ValueError."""
+    import numpy as np
+
+    from whisper_finetune.data.rate_fx import ALIAS_MIN_RATE
+
+    r = _row_values(new_rates, B, "alias", "rates")
+    if not bool(np.all((r == 0.0) | ((r >= ALIAS_MIN_RATE) & (r <= 2.0 * sample_rate)))):
+        raise ValueError(f"alias: a new rate must be 0 (none) or lie in [{ALIAS_MIN_RATE}, {2.0 * sample_rate}], got {r.tolist()}")
+    return r
+
+
+def alias(audio, new_rates, n=None, sample_rate=16000):
+    """audiomentations' Aliasing over every row: linear interpolation down to `new_rate` and back without a low-pass
+    (wft_alias_f32, include/wft.h "Per-row rate conversion"; numpy's float64 result rounded once, bit for bit).
+
+    audio f32 [B, ld] on the device (stride(1) == 1); new_rates: one rate in Hz or one per row, HOST values, 0 = "none" (the row is
+    copied) or inside [1000, 2 * sample_rate]; n i32 [B] on the device (row b covers its first n[b] samples, clamped to [0, ld]; the
+    output is zero behind them) or None (every row covers all ld samples); sample_rate: the clips' rate, a positive number.
+    -> a new f32 [B, ld] tensor (the kernel does not run in place).  Every host-side check raises ValueError before the device is
+    touched."""
+    audio = _rate_rows(audio, "alias")
+    B, n_max = audio.shape
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float)) or not 1000 <= sample_rate <= 384000:
+        raise ValueError(f"alias: sample_rate must be a number inside [1000, 384000], got {sample_rate!r}")
+    r = alias_rates(new_rates, B, float(sample_rate))
+    if n is not None:
+        if not torch.is_tensor(n) or n.dtype != torch.int32 or tuple(n.shape) != (B,):
+            raise ValueError(f"alias: n must be an int32 tensor [{B}] or None")
+    _chk(audio, F32, "audio")  # (every ValueError above comes before the device is touched)
+    if n is not None and n.device != audio.device:
+        raise ValueError("alias: audio and n must live on the same GPU")
+    if audio.stride(1) != 1 or (B > 1 and audio.stride(0) < n_max):
+        audio = audio.contiguous()
+    out = torch.empty((B, n_max), dtype=F32, device=audio.device)
+    rate_d = torch.from_numpy(r).to(audio.device)
+    if n is not None:
+        n = n.contiguous()
+    ld_in = audio.stride(0) if B > 1 else max(audio.stride(0), n_max)
+    L.check(L.load().wft_alias_f32(_p(audio), ld_in, _p(n), n_max, _p(rate_d), float(sample_rate), _p(out), out.stride(0), B,
+                                   L.stream_ptr()), "wft_alias_f32")
+    return out
+
+
 def mel_to_tmajor(mel, c_pad: int):
     _chk(mel, F32, "mel")
     mel = mel.contiguous()

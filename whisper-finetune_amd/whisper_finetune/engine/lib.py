@@ -268,6 +268,10 @@ SIGNATURES = {
     "wft_wave_fx_workspace_bytes": [C.c_int, c_i64, C.c_int],
     "wft_wave_fx_tile": [],
     "wft_wave_fx_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, C.c_int, c_vp, c_i64, c_vp, c_i64, C.c_int, c_vp],
+    "wft_sinc_resample_rows_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, C.c_double, c_vp, c_i64, c_i64, C.c_int, c_vp],
+    "wft_sinc_resample_rows_tile": [C.c_double],
+    "wft_alias_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, C.c_double, c_vp, c_i64, C.c_int, c_vp],
+    "wft_alias_tile": [],
     "wft_adamw_step": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float,
                        C.c_float, C.c_float, C.c_float, c_vp, c_vp],
     "wft_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],
