@@ -1008,6 +1008,52 @@ int wft_alias_f32(const float* in, int64_t ld_in, const int32_t* n, int64_t n_ma
                   float* out, int64_t ld_out, int B, void* stream);
 int wft_alias_tile(void);
 
+/* ------------------------------------------------- Office effects (audio-domain augmentation) */
+/* Room reverb and bit crush of the reference's office pipeline (get_audio_augments_office, model/augment.py) over a ragged batch
+ * (csrc/office.hip; DESIGN.md §3 "Office effects").  Neither audiomentations nor pyroomacoustics is a dependency.  Shared rules: no
+ * atomics, no allocation, no host synchronisation; every host-visible argument is checked before the first launch; reruns are
+ * bit-identical; index arithmetic is 64-bit; 1 <= B <= 65535; 1 <= n_max <= 2^30; in / out f32: row b at in + b * ld_in /
+ * out + b * ld_out, ld_in, ld_out >= n_max; N = n[b] (device i32) clamped to [0, n_max], n == NULL = n_max for every row;
+ * out[b, N .. n_max) is written as zero; nothing at or behind n_max of an output row is written; nothing at or behind n[b] of an input
+ * row is read.
+ *
+ * wft_fir_conv_f32: a causal FIR over every row, each row with an impulse response of its own length (the room simulation's shoebox
+ *  response, or a measured one: audiomentations' ApplyImpulseResponse):
+ *    out[b][i] = sum_{j < T} ir[b][j] * x[b][i - j]  for 0 <= i < N, with x = 0 outside [0, N); the tail is chopped at N (the
+ *    reference's leave_length_unchanged=True).  T = n_taps[b] (device i32) clamped to [0, taps_max], n_taps == NULL = taps_max.
+ *    ir f32: row b at ir + b * ld_ir, ld_ir >= taps_max, 1 <= taps_max <= 8192; nothing at or behind n_taps[b] of an IR row is read.
+ *    A row with T == 0 is a copy of its bits.
+ *  Method: uniform-partitioned overlap-save in f32 on a 2048-point radix-2 FFT, L = wft_fir_conv_block() = 1024 new outputs per
+ *  block.  Pass 1: the IR of row b in P = ceil(taps_max / 1024) partitions, each zero-padded to 2048 and transformed into the
+ *  workspace as H[b][p][0..1024].  Pass 2, one workgroup per (output block k, row): for each live partition p in ascending order
+ *  (p < ceil(T / 1024) and p <= k; segments in front of the row's start are all zeros) the FFT of x[(k-p-1) * 1024 .. (k-p+1) * 1024),
+ *  X * H_p accumulated over the one-sided bins, ONE inverse FFT of the Hermitian extension, the last 1024 reals scaled by 1 / 2048.
+ *  The error of an element is bounded by C * 11 * 2^-24 * sum_p ||x_seg(k-p)||_2 * ||h_p||_2 over its block's live partitions
+ *  (tests/_office_cases.py holds C and how it was measured).
+ *    A row's bits depend on its samples, its IR, n[b], n_taps[b] and L only — not on B, its batch partners or taps_max: a partition
+ *    that lies wholly behind n_taps[b] contributes nothing (not a sum with zeros, which would turn a -0.0 into +0.0).
+ *    In place is impossible (a block reads samples that an earlier block's owner may have overwritten): ANY overlap of in and out is
+ *    WFT_ERR_ARG, as is an overlap of either with ir or the workspace.  Also WFT_ERR_ARG: a null pointer (in, ir, out, workspace), a
+ *    bad shape, a short leading dimension, a workspace below wft_fir_conv_workspace_bytes(B, taps_max) = B * P * 1025 * 8 bytes (-1:
+ *    bad arguments), misalignment (in / out / ir / n / n_taps 4 bytes, workspace 8).
+ *
+ * wft_bitcrush_f32: audiomentations' BitCrush.apply, restated: q = 2^(bits-1) + 1 as an exact f32, y = rintf(x * q) / q — an f32
+ *  multiply, round half to even, then a correctly rounded f32 divide, not contracted: numpy's np.round(samples * q) / q on an f32
+ *  array, bit for bit.  bits: device i32 [B]; bits[b] == 0 makes the row a copy of its bits, and so does EVERY value outside
+ *  {0} u [1, 24] (2^24 + 1 is not an f32).  In place (out == in and ld_out == ld_in) is allowed; any other overlap is WFT_ERR_ARG, as
+ *  are a null pointer (in, bits, out), a bad shape, a short leading dimension, misalignment (4 bytes).
+ * DEVIATIONS of the loader option built on these (data/office_fx.py): the image-source method only (audiomentations' default
+ * use_ray_tracing=True is stochastic inside pyroomacoustics and is not restated: no late tail beyond max_order); no air absorption; no
+ * output normalisation; Mp3Compression's slot is dropped; own gates (the reference's marginal rates: crush 0.25, room 0.5);
+ * pyroomacoustics and audiomentations are not available, so parity with their binaries is unpinned; timestamps untouched.           */
+int wft_fir_conv_block(void);
+int64_t wft_fir_conv_workspace_bytes(int B, int taps_max);
+int wft_fir_conv_f32(const float* in, int64_t ld_in, const int32_t* n, int64_t n_max, const float* ir, int64_t ld_ir,
+                     const int32_t* n_taps, int taps_max, float* out, int64_t ld_out, void* workspace, int64_t workspace_bytes, int B,
+                     void* stream);
+int wft_bitcrush_f32(const float* in, int64_t ld_in, const int32_t* n, int64_t n_max, const int32_t* bits, float* out, int64_t ld_out,
+                     int B, void* stream);
+
 /* ---------------------------------------------------------------- AdamW */
 /* torch.optim.AdamW single-tensor step over a flat f32 range
  * (model/optimizer.py:240-262 → optimizer.step() in model_utils.py:122).

@@ -76,8 +76,12 @@
   rate     the rate effects of the loader (--batches is not used): K.alias, K.sinc_resample_rows and pitch_shift on [32, 480000] and
          [96, 480000] with every row active (alias rates mel-spaced over 8-16 kHz, pitch over -4 .. +4 semitones), beside the log-mel
          and torch's copy of the same batch.  No threshold is set.  (--parts rate --out profiles/decode_bench_rate.jsonl)
+  office   the office effects of the loader (--batches is not used): K.fir_conv at P = 1, 2 and 8 partitions (1000, 2000 and 8192 taps)
+         and K.bitcrush on [32, 480000] and [96, 480000] with every row active, beside the log-mel, the time stretch's STFT stage
+         (comparable FFT work per clip) and torch's copy of the same batch.  No threshold is set.
+         (--parts office --out profiles/decode_bench_office.jsonl)
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample,stretch,filter,wavefx,rate] [--batches 1,8,32] [--out FILE]
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample,stretch,filter,wavefx,rate,office] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -1148,6 +1152,39 @@ def bench_rate(batches):
         emit(rec)
 
 
+def bench_office(batches):
+    """K.fir_conv at 1, 2 and 8 partitions and K.bitcrush on 30 s clips with every row active: ms per call beside the log-mel, the
+    time stretch's STFT stage and torch's copy of the same batch."""
+    from whisper_finetune.data.gpu_frontend import mel_filters
+
+    lib = L.load()
+    n = 480000
+    filters = mel_filters(80).to(DEV)
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    for B in (32, 96):
+        g = torch.Generator().manual_seed(B)
+        x = (torch.randn(B, n, generator=g) * 0.1).to(DEV)
+        x[:, 300000:] = 0  # zero-padded clips, as the loader stages them
+        out = torch.empty_like(x)
+        depths = torch.randint(6, 15, (B,), generator=g).to(torch.int32).to(DEV)
+        irs = {P: (torch.randn(B, taps, generator=g) / taps ** 0.5).to(DEV) for P, taps in ((1, 1000), (2, 2000), (8, 8192))}
+        D = torch.empty(B * (1 + n // 512) * 1025 * 2, device=DEV)  # the STFT of the stretch: 938 frames of 2048 per clip
+        arms = {f"fir_conv_P{P}": (lambda h: lambda: K.fir_conv(x, h))(h) for P, h in irs.items()}
+        arms.update({"bitcrush": lambda: K.bitcrush(x, depths, out=out), "bitcrush_in_place": lambda: K.bitcrush(out, depths, out=out),
+                     "stretch_stft": lambda: lib.wft_stretch_stft_f32(p(x), n, n, p(D), B, L.stream_ptr()),
+                     "logmel": lambda: K.logmel(x, filters, 3000), "copy": lambda: out.copy_(x)})
+        res = ab(arms, rounds=5, iters=5)
+        rec = dict(part="office", B=B, n=n, block=lib.wft_fir_conv_block(), taps={str(P): int(h.shape[1]) for P, h in irs.items()},
+                   ffts_per_clip={"fir_conv_P1": 469 * 2 + 1, "fir_conv_P2": 469 * 3 + 2, "fir_conv_P8": 469 * 9 + 8, "stretch_stft": 938},
+                   note="ms per call, medians of 5 alternating rounds of 5 calls, every row active; fir_conv_P*: the wrapper (output and "
+                        "workspace allocation, both passes) at 1000 / 2000 / 8192 taps; ffts_per_clip: 2048-point FFTs per clip — a block "
+                        "of 1024 outputs costs one forward FFT per live partition plus one inverse; stretch_stft: wft_stretch_stft_f32 "
+                        "alone; logmel / copy: the log-mel of the same batch and torch's copy of it, for scale")
+        for name, (med, mn, spread) in res.items():
+            rec[name + "_ms"], rec[name + "_min_ms"], rec[name + "_spread"] = round(med, 4), round(mn, 4), round(spread, 3)
+        emit(rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="attn,gemm,e2e")
@@ -1161,7 +1198,7 @@ def main():
     for part in a.parts.split(","):
         {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": lambda b: (bench_gemm_stream(b), bench_gemm_stream_q8(b)), "e2e_step": bench_e2e_step,
          "gemm_i8": bench_gemm_i8, "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align, "transcribe": bench_transcribe, "resample": bench_resample,
-         "stretch": bench_stretch, "filter": bench_filter, "wavefx": bench_wavefx, "rate": bench_rate}[part](batches)
+         "stretch": bench_stretch, "filter": bench_filter, "wavefx": bench_wavefx, "rate": bench_rate, "office": bench_office}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

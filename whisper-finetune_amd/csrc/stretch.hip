@@ -7,56 +7,21 @@
 //   istft    one workgroup per (output frame, row): the Hermitian extension of S[b][t] -> LDS -> inverse FFT -> real part * window / N,
 //            written IN PLACE over S[b][t] (2048 floats in the 2050 the frame occupies); then one thread per output sample gathers
 //            its <= 4 frames in ascending t and divides by the window's sum of squares.  No atomics anywhere.
-// The FFT is a plain in-place decimation-in-time radix-2 over a bit-reversed load, 11 stages of 1024 butterflies on 256 threads with
-// a barrier between them; twiddles exp(-2 pi i m / 2048), m < 1024, from a sincospif table built once per workgroup.  The stretch
+// The FFT (fft2048.h, shared with office.hip) is a plain in-place decimation-in-time radix-2 over a bit-reversed load.  The stretch
 // is a side kernel of the loader (a few tens of MB per clip): nothing here is hand-scheduled.
 #include <float.h>
 #include "common.h"
+#include "fft2048.h"
 
-#define ST_N 2048
 #define ST_H 512
-#define ST_BINS 1025   // one-sided
-#define ST_LOGN 11
-#define ST_THREADS 256
 #define ST_MAX_IN (1 << 26)  // samples per row: keeps every frame count and sample index far inside 32 bits
 
-__device__ __forceinline__ void st_twiddles(f32x2* tw, int tid) {
-  for (int i = tid; i < ST_N / 2; i += ST_THREADS) {
-    float sn, cs;
-    sincospif((float)i / (float)(ST_N / 2), &sn, &cs);  // angle = 2 pi i / 2048
-    tw[i] = f32x2{cs, -sn};
-  }
-}
 // periodic Hann 0.5 - 0.5 cos(2 pi i / 2048) as sin^2(pi i / 2048): a few ulp RELATIVE to the window's own value.  (0.5 - 0.5 cos
 // is off by an ulp of 1 — a hundredth of the window at its first samples — and the unwindowed synthesis frame is not small there:
 // next to silence, where no other frame covers that error, it showed as 90 times the synthesis' allowance.)
 __device__ __forceinline__ float st_window(int i) {
   const float sn = sinpif((float)i * (1.0f / ST_N));
   return sn * sn;
-}
-__device__ __forceinline__ int st_brev(int i) { return (int)(__brev((unsigned)i) >> (32 - ST_LOGN)); }
-
-// x holds the input in bit-reversed order; on return x[k] is the DFT (inverse: the unscaled inverse DFT) in natural order.
-template <bool INVERSE>
-__device__ __forceinline__ void st_fft(f32x2* x, const f32x2* tw, int tid) {
-#pragma unroll 1
-  for (int s = 0; s < ST_LOGN; ++s) {
-    const int half = 1 << s;
-#pragma unroll
-    for (int r = 0; r < ST_N / 2 / ST_THREADS; ++r) {
-      const int j = tid + r * ST_THREADS;
-      const int pos = j & (half - 1);
-      const int i0 = ((j >> s) << (s + 1)) + pos, i1 = i0 + half;
-      f32x2 w = tw[pos << (ST_LOGN - 1 - s)];
-      if (INVERSE) w[1] = -w[1];
-      const f32x2 a = x[i0], b = x[i1];
-      const float tr = w[0] * b[0] - w[1] * b[1];
-      const float ti = w[0] * b[1] + w[1] * b[0];
-      x[i0] = f32x2{a[0] + tr, a[1] + ti};
-      x[i1] = f32x2{a[0] - tr, a[1] - ti};
-    }
-    __syncthreads();
-  }
 }
 
 // frames of the analysis and, for one row, of the synthesis; n_out.  All in double, as the definition states them.

@@ -35,6 +35,12 @@ as one table row f64 [4]; the main process runs `wft_alias_f32` and the pitch sh
 `wft_sinc_resample_rows_f32`) in the reference's Compose order: resample -> stretch -> NOISE -> ALIAS -> filter -> CLIP -> LEVEL ->
 PITCH -> log-mel, each over the row's full stretched length.  Alias writes into a second buffer that takes the first one's place;
 pitch gathers the pitched rows only.  Timestamps are untouched, as in the reference.
+
+Office effects (`office_aug={...}`, an option of this project's own: BitCrush and the RoomSimulator of the reference's office pipeline,
+NOT `apply_office_aug`): a worker DRAWS the clip's bit depth and DESIGNS its room's impulse response (data/office_fx.py OfficeAug, after
+the rate-effects draw) and ships them as one table row f64 [2 + cap]; the main process runs `wft_bitcrush_f32` (in place) and
+`wft_fir_conv_f32` (into a second buffer) right behind the stretch, the reference's Compose order: resample -> stretch -> CRUSH -> ROOM
+-> NOISE -> ALIAS -> filter -> CLIP -> LEVEL -> PITCH -> log-mel.  Timestamps are untouched.
 """
 from __future__ import annotations
 
@@ -52,6 +58,7 @@ from whisper_finetune.data.filters import FilterAug, identity_sos
 from whisper_finetune.data.gpu_frontend import (HOP_LENGTH, N_FFT, N_FRAMES, N_SAMPLES, SAMPLE_RATE, GpuFrontend, check_rate,
                                                 check_stretch_range, draw_clip_params, mel_filters)
 from whisper_finetune.data.utils import ExtremesFrequencyMasking, TimeWarpAugmenter, pad_or_trim
+from whisper_finetune.data.office_fx import OfficeAug, STAGES as OFFICE_STAGES, check_table as check_office_table
 from whisper_finetune.data.rate_fx import RateAug, check_table as check_rate_table
 from whisper_finetune.data.wave_fx import STAGES as WAVE_STAGES, WaveAug, active_rows, check_records, records_from_table
 
@@ -81,14 +88,34 @@ def pitch_rows(audio, semitones, lengths=None):
     return audio
 
 
-def apply_wave_stages(audio, n, sos, fx, rate=None, lengths=None):
-    """The audio-domain stages behind the stretch on audio f32 [B, ld] (device), in the reference's Compose order:
-    NOISE -> ALIAS -> filter -> CLIP -> LEVEL -> PITCH.  n: i32 [B] on the device or None; sos: f64 [B, 4, 6] or None; fx: checked
-    wave-effect records [B] (data/wave_fx.py) or None; rate: the checked rate-effect table f64 [B, 4] (data/rate_fx.py) or None;
-    lengths: the rows' lengths as host integers (what n holds; None with n None).  A stage with no active row launches nothing.
-    Every stage but ALIAS runs in place; ALIAS writes a second buffer, so use the RETURNED tensor."""
+def office_rows(audio, n, office):
+    """CRUSH -> ROOM on audio f32 [B, ld] (device) from the checked office table f64 [B, 2 + cap] (data/office_fx.py): the bit crush in
+    place over the rows' depths (0 = the row is copied), then the rows' room responses through K.fir_conv, whose output is RETURNED
+    (a row without a response is copied).  A stage with no active row launches nothing."""
+    import numpy as np
+
     from whisper_finetune.engine import kernels as K
 
+    bits, taps = office[:, 0].astype(np.int32), office[:, 1].astype(np.int32)
+    if bool(bits.any()):
+        K.bitcrush(audio, bits, n, out=audio)
+    if bool(taps.any()):
+        ir = torch.from_numpy(office[:, 2:2 + int(taps.max())].astype(np.float32)).to(audio.device, non_blocking=True)
+        audio = K.fir_conv(audio, ir, n, torch.from_numpy(taps).to(audio.device, non_blocking=True))
+    return audio
+
+
+def apply_wave_stages(audio, n, sos, fx, rate=None, lengths=None, office=None):
+    """The audio-domain stages behind the stretch on audio f32 [B, ld] (device), in the reference's Compose order:
+    CRUSH -> ROOM -> NOISE -> ALIAS -> filter -> CLIP -> LEVEL -> PITCH.  n: i32 [B] on the device or None; sos: f64 [B, 4, 6] or
+    None; fx: checked wave-effect records [B] (data/wave_fx.py) or None; rate: the checked rate-effect table f64 [B, 4]
+    (data/rate_fx.py) or None; lengths: the rows' lengths as host integers (what n holds; None with n None); office: the checked
+    office table f64 [B, 2 + cap] (data/office_fx.py) or None.  A stage with no active row launches nothing.
+    Every stage but ROOM and ALIAS runs in place; those two write a second buffer, so use the RETURNED tensor."""
+    from whisper_finetune.engine import kernels as K
+
+    if office is not None:
+        audio = office_rows(audio, n, office)
     if fx is not None:
         K.wave_fx(audio, fx, "noise", n, out=audio)
     if rate is not None and bool(rate[:, 0].any()):
@@ -139,7 +166,8 @@ class AudioDataset(Dataset):
     with `apply_baseline_aug` a seventh field, the clip's time-stretch rate as f64 (without it the items are the six fields, unchanged);
     with `filter_aug` one more field behind those, the clip's filter as sos f64 [4, 6] (identity sections = "do not filter");
     with `wave_aug` one more field behind the filter, the clip's wave effects as a table row f64 [14] (data/wave_fx.py);
-    with `rate_aug` one more field behind the wave effects, the clip's rate effects as a table row f64 [4] (data/rate_fx.py).
+    with `rate_aug` one more field behind the wave effects, the clip's rate effects as a table row f64 [4] (data/rate_fx.py);
+    with `office_aug` one more field behind the rate effects, the clip's office effects as a table row f64 [2 + cap] (data/office_fx.py).
 
     apply_baseline_aug: the rate is drawn as audiomentations draws it — Python's `random` module, one `random.random()` gate against
     p = 1.0, then `random.uniform(min_rate, max_rate)` (BaseWaveformTransform.randomize_parameters, then TimeStretch's).  That order is
@@ -154,6 +182,9 @@ class AudioDataset(Dataset):
     group is off).  The parameters are drawn after the filter, with Python's `random` (WaveAug's docstring states the order).
     rate_aug: None, or a mapping of data/rate_fx.py RateAug's groups (`alias`, `pitch`, each None or a mapping of its keywords; a
     missing group is off).  The parameters are drawn after the wave effects, with Python's `random`.
+    office_aug: None, or a mapping of data/office_fx.py OfficeAug's groups (`crush`, `room`, each None or a mapping of its keywords; a
+    missing group is off).  The parameters are drawn after the rate effects, with Python's `random`, and the room's impulse response
+    is designed in the worker.  It is NOT `apply_office_aug`, which stays refused (mp3 compression is not built).
 
     hu_dataset: indexable records {"audio": {"array", optional "sampling_rate"}, "text", "language", optional "prompt"}; a record
     whose "sampling_rate" is present and differs from the dataset's `sample_rate` raises ValueError (no mixed rates); tokenizer: whisper-style
@@ -168,6 +199,7 @@ class AudioDataset(Dataset):
     filter_aug = None
     wave_aug = None
     rate_aug = None
+    office_aug = None
 
     def __init__(self, hu_dataset, tokenizer, device=None, no_timestamp_training: bool = False, n_mels: int = 80,
                  max_prompt_length: int = 223, prompt_use_rate: float = 0.5, no_timestamps_rate: float = 0.5,
@@ -175,14 +207,15 @@ class AudioDataset(Dataset):
                  extremes_spec_augment_params: Optional[dict] = None, apply_baseline_aug: bool = False, apply_office_aug: bool = False,
                  apply_advanced_aug: bool = False, time_stretch_min_rate: float = 0.8, time_stretch_max_rate: float = 1.25,
                  bpe_dropout: float = 0.0, sample_rate: int = SAMPLE_RATE, filter_aug: Optional[dict] = None,
-                 wave_aug: Optional[dict] = None, rate_aug: Optional[dict] = None):
+                 wave_aug: Optional[dict] = None, rate_aug: Optional[dict] = None, office_aug: Optional[dict] = None):
         self.sample_rate = check_rate(sample_rate)
         self.n_samples = CHUNK_LENGTH * self.sample_rate  # 30 s at the clips' own rate
         refused = [name for name, on in (("apply_office_aug", apply_office_aug), ("apply_advanced_aug", apply_advanced_aug)) if on]
         if refused:
             raise NotImplementedError(f"{' and '.join(refused)}: the office and advanced audio pipelines (room simulation, mp3 compression, "
                                       "background-noise files, biquad filters, pitch shift) are not implemented; "
-                                      "apply_baseline_aug (time stretch) is")
+                                      "apply_baseline_aug (time stretch) is; the office pipeline's bit crush and room simulation run "
+                                      "behind this project's own option audio_augment.wft_office_aug")
         if apply_baseline_aug:
             time_stretch_min_rate, time_stretch_max_rate = check_stretch_range(time_stretch_min_rate, time_stretch_max_rate)
         self.hu_dataset, self.tokenizer, self.n_mels, self.device = hu_dataset, tokenizer, n_mels, device
@@ -202,6 +235,9 @@ class AudioDataset(Dataset):
         if rate_aug is not None and (not hasattr(rate_aug, "keys") or not set(rate_aug.keys()) <= {"alias", "pitch"}):
             raise ValueError(f"rate_aug must be None or a mapping of RateAug's groups ('alias', 'pitch'), got {rate_aug!r}")
         self.rate_aug = RateAug(sample_rate=SAMPLE_RATE, **dict(rate_aug)) if rate_aug is not None else None
+        if office_aug is not None and (not hasattr(office_aug, "keys") or not set(office_aug.keys()) <= set(OFFICE_STAGES)):
+            raise ValueError(f"office_aug must be None or a mapping of OfficeAug's groups {OFFICE_STAGES}, got {office_aug!r}")
+        self.office_aug = OfficeAug(sample_rate=SAMPLE_RATE, **dict(office_aug)) if office_aug is not None else None
         if spec_augment:
             self.spec_augment_p = float(spec_augment_params.get("p", 1.0))
             if not 0.0 <= self.spec_augment_p <= 1.0:
@@ -261,8 +297,15 @@ class AudioDataset(Dataset):
         names, row = self.rate_aug.draw()
         return check_rate_table(row[None]) if any(names.values()) else None
 
+    def _draw_office(self):
+        """The clip's office effects for the per-clip form: the checked table f64 [1, 2 + cap], or None without the option or when nothing was drawn."""
+        if self.office_aug is None:
+            return None
+        names, row = self.office_aug.draw()
+        return check_office_table(row[None]) if any(names.values()) else None
+
     def _calculate_mel(self, audio_array, next_partial_segment_start: Optional[float], no_timestamps: bool) -> torch.Tensor:
-        """Per-clip form: [time stretch] -> [noise] -> [alias] -> [filter] -> [clipping] -> [level] -> [pitch] -> log-mel -> cut at a partial segment + minimum-value pad -> [warp -> time mask -> freq mask]
+        """Per-clip form: [time stretch] -> [crush] -> [room] -> [noise] -> [alias] -> [filter] -> [clipping] -> [level] -> [pitch] -> log-mel -> cut at a partial segment + minimum-value pad -> [warp -> time mask -> freq mask]
         w.p. p -> extremes masking, every stage a libwft kernel on the device."""
         if self.sample_rate != SAMPLE_RATE:
             raise ValueError(f"_calculate_mel is the per-clip 16 kHz form; clips at {self.sample_rate} Hz are resampled per batch by GpuMelLoader")
@@ -275,19 +318,19 @@ class AudioDataset(Dataset):
             row = torch.as_tensor(np.asarray(audio_array, dtype=np.float32)).to(dev)[None]
             stretch_rate = self._draw_stretch_rate()
             stretched, n_out = K.time_stretch(row, [stretch_rate])
-            sos, fx, rt = self._draw_filter(), self._draw_wave(), self._draw_rate()
-            stretched = apply_wave_stages(stretched, n_out, sos, fx, rt, stretched_lengths(row.shape[1], [stretch_rate]))
+            sos, fx, rt, office = self._draw_filter(), self._draw_wave(), self._draw_rate(), self._draw_office()
+            stretched = apply_wave_stages(stretched, n_out, sos, fx, rt, stretched_lengths(row.shape[1], [stretch_rate]), office)
             key = (self.n_mels, row.device)
             if key not in _FILTERS:
                 _FILTERS[key] = mel_filters(self.n_mels).to(row.device)
             keep = torch.tensor([min(cut, N_FRAMES)], dtype=torch.int32, device=row.device)
             mel = K.logmel_ragged(stretched, n_out, keep, _FILTERS[key], N_FRAMES)[0]
         else:
-            sos, fx, rt = self._draw_filter(), self._draw_wave(), self._draw_rate()
-            if sos is not None or fx is not None or rt is not None:  # the same kernels as GpuMelLoader, on one row
+            sos, fx, rt, office = self._draw_filter(), self._draw_wave(), self._draw_rate(), self._draw_office()
+            if sos is not None or fx is not None or rt is not None or office is not None:  # the same kernels as GpuMelLoader, on one row
                 dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
                 row = torch.as_tensor(np.asarray(audio_array, dtype=np.float32)).to(dev)[None].clone()
-                audio_array = apply_wave_stages(row, None, sos, fx, rt)[0]
+                audio_array = apply_wave_stages(row, None, sos, fx, rt, None, office)[0]
             mel = log_mel_spectrogram(audio_array, n_mels=self.n_mels, device=self.device)
             if no_timestamps and next_partial_segment_start is not None:
                 mel = mel[:, : int(next_partial_segment_start * self.num_frames_per_second)]
@@ -420,6 +463,8 @@ class AudioDataset(Dataset):
             item += (torch.from_numpy(self.wave_aug.draw(N_SAMPLES)[1]),)
         if self.rate_aug is not None:
             item += (torch.from_numpy(self.rate_aug.draw()[1]),)
+        if self.office_aug is not None:
+            item += (torch.from_numpy(self.office_aug.draw()[1]),)
         return item
 
 
@@ -431,7 +476,7 @@ def collate_fn(data):
     if len(cols) == 3:
         return pad_sequence(cols[0], batch_first=True, padding_value=0), y_in, y_out
     out = (torch.stack(cols[0]), y_in, y_out, torch.stack(cols[3]), torch.stack(cols[4]), torch.tensor(cols[5], dtype=torch.int32))
-    return out + tuple(torch.stack(c) for c in cols[6:])  # the time-stretch rates f64 [B], the filters f64 [B, 4, 6], the wave effects f64 [B, 14], the rate effects f64 [B, 4]
+    return out + tuple(torch.stack(c) for c in cols[6:])  # the time-stretch rates f64 [B], the filters f64 [B, 4, 6], the wave effects f64 [B, 14], the rate effects f64 [B, 4], the office effects f64 [B, 2 + cap]
 
 
 class WarmupDatasetSampler(torch.utils.data.Sampler):
@@ -507,10 +552,14 @@ class GpuMelLoader:
     order becomes resample -> stretch -> NOISE -> ALIAS -> filter -> CLIP -> LEVEL -> PITCH -> log-mel.  ALIAS is one out-of-place
     launch over the batch ("none" rows are copied) whose output takes the batch's place.  PITCH gathers the pitched rows only: one
     batched call without the baseline stretch (every row has 480000 samples), one call per distinct stretched length with it
-    (the lengths are known on the host as round(480000 / rate): no synchronisation)."""
+    (the lengths are known on the host as round(480000 / rate): no synchronisation).
+
+    Batches of a dataset built with office_aug carry the office effects f64 [B, 2 + cap] as their last field, behind the rate effects:
+    CRUSH (in place) and ROOM (out of place; its output takes the batch's place) run right behind the stretch, in front of NOISE."""
 
     def __init__(self, loader, frontend: GpuFrontend, training_aug: bool, sample_rate: int = SAMPLE_RATE, stretch: Optional[bool] = None,
-                 filter_aug: Optional[bool] = None, wave_aug: Optional[bool] = None, rate_aug: Optional[bool] = None):
+                 filter_aug: Optional[bool] = None, wave_aug: Optional[bool] = None, rate_aug: Optional[bool] = None,
+                 office_aug: Optional[bool] = None):
         self.loader, self.frontend, self.training_aug = loader, frontend, training_aug
         ds = getattr(loader, "dataset", None)
         if stretch is None and ds is not None:
@@ -521,7 +570,10 @@ class GpuMelLoader:
             wave_aug = getattr(ds, "wave_aug", None) is not None
         if rate_aug is None:
             rate_aug = getattr(ds, "rate_aug", None) is not None
+        if office_aug is None:
+            office_aug = getattr(ds, "office_aug", None) is not None
         self.stretch, self.filter_aug, self.wave_aug, self.rate_aug = stretch, bool(filter_aug), bool(wave_aug), bool(rate_aug)
+        self.office_aug = bool(office_aug)
         self._identity = torch.from_numpy(identity_sos())
         self.sample_rate = check_rate(sample_rate)
         self.sampler = getattr(loader, "sampler", None)  # infinite_iter() calls sampler.set_epoch(...)
@@ -543,11 +595,13 @@ class GpuMelLoader:
 
     def _all_fields(self, batch):
         """_fields and, as a fourth item, the checked rate-effect table f64 [B, 4] (numpy) or None (no option, or no row active)."""
-        stretch = (len(batch) == 7 and not self.filter_aug and not self.wave_aug and not self.rate_aug) if self.stretch is None else self.stretch
-        if len(batch) != 6 + int(stretch) + int(self.filter_aug) + int(self.wave_aug) + int(self.rate_aug):
+        stretch = (len(batch) == 7 and not self.filter_aug and not self.wave_aug and not self.rate_aug and not self.office_aug) \
+            if self.stretch is None else self.stretch
+        if len(batch) != 6 + int(stretch) + int(self.filter_aug) + int(self.wave_aug) + int(self.rate_aug) + int(self.office_aug):
             raise ValueError(f"a batch of {len(batch)} fields from a loader with stretch={stretch}, filter_aug={self.filter_aug}"
                              + (f", wave_aug={self.wave_aug}" if self.wave_aug else "")
-                             + (f", rate_aug={self.rate_aug}" if self.rate_aug else ""))
+                             + (f", rate_aug={self.rate_aug}" if self.rate_aug else "")
+                             + (f", office_aug={self.office_aug}" if self.office_aug else ""))
         rates = batch[6] if stretch else None
         sos = batch[6 + int(stretch)] if self.filter_aug else None
         if sos is not None and bool((sos == self._identity).all()):
@@ -559,10 +613,17 @@ class GpuMelLoader:
                 fx = None
         rt = None
         if self.rate_aug:
-            rt = check_rate_table(batch[-1])
+            rt = check_rate_table(batch[6 + int(stretch) + int(self.filter_aug) + int(self.wave_aug)])
             if not bool(rt[:, 0].any() or rt[:, 2].any()):
                 rt = None
         return rates, sos, fx, rt
+
+    def _office_field(self, batch):
+        """The checked office table f64 [B, 2 + cap] (numpy) of a collated batch, its last field, or None (no option, or no row active)."""
+        if not self.office_aug:
+            return None
+        office = check_office_table(batch[-1])
+        return office if bool(office[:, :2].any()) else None
 
     def _stage(self, batch):
         """Issue the batch's H2D copies on the side stream; returns the device tensors and the event that orders them."""
@@ -576,9 +637,9 @@ class GpuMelLoader:
             staged = [t.to(dev, non_blocking=True) for t in (audio, y_in, y_out, params, ext)]
             ev = torch.cuda.Event()
             ev.record(self._copy_stream)
-        return staged, cut, ev, need_aug, rates, sos, fx, rt
+        return staged, cut, ev, need_aug, rates, sos, fx, rt, self._office_field(batch)
 
-    def _to_mel(self, staged, cut, ev, need_aug, rates=None, sos=None, fx=None, rt=None):
+    def _to_mel(self, staged, cut, ev, need_aug, rates=None, sos=None, fx=None, rt=None, office=None):
         from whisper_finetune.engine import kernels as K
 
         cur = torch.cuda.current_stream(self.frontend.device)
@@ -594,14 +655,14 @@ class GpuMelLoader:
             # rows' lengths stay on the device; the cut and the minimum-value pad happen inside the ragged log-mel
             stretched, n_out = K.time_stretch(audio, rates)
             stretched = apply_wave_stages(stretched, n_out, sos, fx, rt,
-                                          stretched_lengths(audio.shape[1], rates.tolist()) if rt is not None else None)
+                                          stretched_lengths(audio.shape[1], rates.tolist()) if rt is not None else None, office)
             keep = cut.clamp(max=N_FRAMES).to(torch.int32).to(audio.device, non_blocking=True)
             mel = K.logmel_ragged(stretched, n_out, keep, self.frontend.filters, N_FRAMES)
         else:
-            if sos is not None or fx is not None or rt is not None:
+            if sos is not None or fx is not None or rt is not None or office is not None:
                 if audio.stride(1) != 1 or not audio.is_contiguous():
                     audio = audio.contiguous()
-                audio = apply_wave_stages(audio, None, sos, fx, rt)  # in place on the staged (or resampled) copy; alias gives a new one
+                audio = apply_wave_stages(audio, None, sos, fx, rt, None, office)  # in place on the staged (or resampled) copy; alias gives a new one
             mel = self.frontend.log_mel(audio)
             for b in (cut < N_FRAMES).nonzero().flatten().tolist():  # rare: cut at a partial segment, pad with the min value
                 c = int(cut[b])
@@ -617,7 +678,7 @@ class GpuMelLoader:
                 audio, y_in, y_out, params, ext, cut = batch[:6]
                 need_aug = bool(params[:, 0].any() or ext.any())
                 staged = [t.to(dev, non_blocking=True) for t in (audio, y_in, y_out, params, ext)]
-                yield self._to_mel(staged, cut, None, need_aug, *self._all_fields(batch))
+                yield self._to_mel(staged, cut, None, need_aug, *self._all_fields(batch), self._office_field(batch))
             return
         it = iter(self.loader)
         try:
@@ -640,10 +701,11 @@ def get_dataloader(hu_dataset, tokenizer, batch_size: int = 1, n_mels: int = 80,
                    extremes_spec_augment_params: Optional[dict] = None, apply_baseline_aug: bool = False, apply_office_aug: bool = False,
                    apply_advanced_aug: bool = False, time_stretch_min_rate: float = 0.8, time_stretch_max_rate: float = 1.25,
                    bpe_dropout: float = 0.0, drop_last: bool = False, sample_rate: int = SAMPLE_RATE, filter_aug: Optional[dict] = None,
-                   wave_aug: Optional[dict] = None, rate_aug: Optional[dict] = None):
+                   wave_aug: Optional[dict] = None, rate_aug: Optional[dict] = None, office_aug: Optional[dict] = None):
     """`filter_aug`: None, or a mapping of FilterAug's keywords (AudioDataset's docstring): the filter augmentation of a TRAINING loader.
     `wave_aug`: None, or a mapping of WaveAug's groups (AudioDataset's docstring): noise, clipping and level changes of a TRAINING loader.
     `rate_aug`: None, or a mapping of RateAug's groups (AudioDataset's docstring): aliasing and pitch shift of a TRAINING loader.
+    `office_aug`: None, or a mapping of OfficeAug's groups (AudioDataset's docstring): bit crush and room reverb of a TRAINING loader.
     `sample_rate`: the rate of every clip of `hu_dataset` (default 16000).  At another rate the clips are padded to
     30 * sample_rate samples and resampled to 16 kHz on the device (GpuMelLoader); without a device the loader yields the padded
     native-rate clips."""
@@ -654,7 +716,7 @@ def get_dataloader(hu_dataset, tokenizer, batch_size: int = 1, n_mels: int = 80,
                       extremes_spec_augment_params=extremes_spec_augment_params, bpe_dropout=bpe_dropout,
                       apply_baseline_aug=apply_baseline_aug, apply_office_aug=apply_office_aug, apply_advanced_aug=apply_advanced_aug,
                       time_stretch_min_rate=time_stretch_min_rate, time_stretch_max_rate=time_stretch_max_rate, sample_rate=sample_rate,
-                      filter_aug=filter_aug, wave_aug=wave_aug, rate_aug=rate_aug)
+                      filter_aug=filter_aug, wave_aug=wave_aug, rate_aug=rate_aug, office_aug=office_aug)
     if sampler is not None:
         shuffle = False  # DataLoader does not allow both
     loader = DataLoader(ds, batch_size=batch_size, sampler=sampler, shuffle=shuffle, num_workers=num_workers,

@@ -263,6 +263,69 @@ def alias(audio, new_sample_rate, device=None, sample_rate: int = SAMPLE_RATE):
     return out if a.dim() == 2 else out[0]
 
 
+# ------------------------------------------------------------------------------------------------- office effects
+# Room reverb and bit crush (data/office_fx.py designs and draws them for the loader; include/wft.h "Office effects" states the arithmetic).
+from whisper_finetune.data.office_fx import room_ir  # noqa: E402,F401  (the shoebox response, designed on the host)
+
+
+def _rows(audio, who: str):
+    """audio (f32 [n] or [B, n], a tensor or an array) -> (the input as a tensor, its rows [B, n]); ValueError otherwise."""
+    a = torch.as_tensor(audio)
+    if a.dim() not in (1, 2) or a.dtype != torch.float32 or a.numel() == 0:
+        raise ValueError(f"{who}: audio must be a non-empty float32 [n] or [B, n], got {a.dtype} {tuple(a.shape)}")
+    return a, (a if a.dim() == 2 else a[None])
+
+
+def _to_device(rows, device):
+    if device is not None:
+        return rows.to(device)
+    return rows if rows.is_cuda else rows.to(torch.device("cuda", torch.cuda.current_device()))
+
+
+def fir_convolve(audio, ir, device=None):
+    """audio convolved with an impulse response at unchanged length, on the device (K.fir_conv: FFT overlap-save in f32; the tail
+    behind the input's end is dropped) — audiomentations' ApplyImpulseResponse with leave_length_unchanged=True, without its
+    normalisation; the form for measured impulse responses.
+
+    audio: f32, 1-D [n] or 2-D [B, n], a tensor or an array; a host input goes to `device` (default: the current GPU) first.
+    ir: ONE response for every row (1-D, a tensor or an array), or a list of B responses of ragged lengths; float32 or float64,
+    1 to 8192 taps each (ValueError otherwise).  Returns a new device tensor of the input's shape."""
+    a, rows = _rows(audio, "fir_convolve")
+    B = rows.shape[0]
+    irs = list(ir) if isinstance(ir, (list, tuple)) else [ir]
+    irs = [np.asarray(h.detach().cpu().numpy() if torch.is_tensor(h) else h) for h in irs]
+    if len(irs) not in (1, B):
+        raise ValueError(f"fir_convolve: {len(irs)} impulse responses for {B} rows")
+    for h in irs:
+        if h.ndim != 1 or h.dtype not in (np.float32, np.float64) or not 1 <= h.shape[0] <= K.FIR_TAPS_MAX or not np.all(np.isfinite(h)):
+            raise ValueError(f"fir_convolve: an impulse response must be 1 to {K.FIR_TAPS_MAX} finite float32 / float64 taps, got "
+                             f"{h.dtype} {tuple(h.shape)}")
+    taps = np.array([h.shape[0] for h in irs], dtype=np.int32)
+    table = np.zeros((len(irs), int(taps.max())), dtype=np.float32)
+    for b, h in enumerate(irs):
+        table[b, :h.shape[0]] = h
+    rows = _to_device(rows, device)
+    ir_d = torch.from_numpy(table).to(rows.device)
+    if len(irs) == 1:
+        out = K.fir_conv(rows, ir_d[0])
+    else:
+        out = K.fir_conv(rows, ir_d, None, torch.from_numpy(taps).to(rows.device))
+    return out if a.dim() == 2 else out[0]
+
+
+def bit_crush(audio, bit_depth, device=None):
+    """audio under audiomentations' BitCrush: round(x * q) / q with q = 2^(bit_depth - 1) + 1, on the device (K.bitcrush: numpy's
+    float32 result bit for bit).
+
+    audio: f32, 1-D [n] or 2-D [B, n], a tensor or an array; a host input goes to `device` (default: the current GPU) first.
+    bit_depth: one integer or one per row, inside [1, 24], or 0 for "leave the row as it is" (ValueError otherwise).
+    Returns a new device tensor of the input's shape."""
+    a, rows = _rows(audio, "bit_crush")
+    depths = K.bitcrush_depths(bit_depth, rows.shape[0])  # before the device is touched
+    out = K.bitcrush(_to_device(rows, device), depths)
+    return out if a.dim() == 2 else out[0]
+
+
 from whisper_finetune.data.transforms import FrequencyMasking, TimeMasking, draw_mask_span  # noqa: E402,F401
 
 

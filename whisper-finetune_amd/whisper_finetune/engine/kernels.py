@@ -1602,6 +1602,109 @@ def alias(audio, new_rates, n=None, sample_rate=16000):
     return out
 
 
+FIR_TAPS_MAX = 8192  # wft_fir_conv_f32's limit on taps_max
+
+
+def _lengths(n, B: int, device, who: str, what: str):
+    """None, or an int32 tensor [B] on `device` -> the same, contiguous (ValueError otherwise)."""
+    if n is None:
+        return None
+    if not torch.is_tensor(n) or n.dtype != torch.int32 or tuple(n.shape) != (B,):
+        raise ValueError(f"{who}: {what} must be an int32 tensor [{B}] or None")
+    if n.device != device:
+        raise ValueError(f"{who}: audio and {what} must live on the same GPU")
+    return n.contiguous()
+
+
+def fir_conv(audio, ir, n=None, n_taps=None):
+    """A causal FIR over every row, each row with an impulse response of its own (wft_fir_conv_f32, include/wft.h "Office effects":
+    FFT overlap-save in f32; the tail is chopped at the row's length).
+
+    audio f32 [B, ld] on the device (stride(1) == 1); ir f32 [B, taps_max] or [taps_max] (one response for every row) on the same
+    device, 1 <= taps_max <= 8192; n i32 [B] on the device (row b covers its first n[b] samples, clamped to [0, ld]; the output is zero
+    behind them) or None (all ld samples); n_taps i32 [B] on the device (row b uses its first n_taps[b] taps, clamped to
+    [0, taps_max]; 0 = the row is copied) or None (all taps_max).
+    -> a new f32 [B, ld] tensor (the kernel cannot run in place).  Every host-side check raises ValueError before the device is
+    touched."""
+    audio = _rate_rows(audio, "fir_conv")
+    B, n_max = audio.shape
+    if not torch.is_tensor(ir) or ir.dtype != F32 or ir.dim() not in (1, 2) or ir.shape[-1] < 1 or ir.shape[-1] > FIR_TAPS_MAX or \
+            (ir.dim() == 2 and ir.shape[0] != B):
+        raise ValueError(f"fir_conv: ir must be a float32 tensor [{B}, taps] or [taps] with 1 <= taps <= {FIR_TAPS_MAX}, got "
+                         f"{getattr(ir, 'dtype', type(ir))} {tuple(getattr(ir, 'shape', ()))}")
+    taps_max = int(ir.shape[-1])
+    _chk(audio, F32, "audio")  # (every ValueError above comes before the device is touched)
+    if ir.device != audio.device:
+        raise ValueError("fir_conv: audio and ir must live on the same GPU")
+    n = _lengths(n, B, audio.device, "fir_conv", "n")
+    n_taps = _lengths(n_taps, B, audio.device, "fir_conv", "n_taps")
+    if ir.dim() == 1:
+        ir = ir[None].expand(B, taps_max)
+    if ir.stride(1) != 1 or (B > 1 and ir.stride(0) < taps_max):
+        ir = ir.contiguous()
+    if audio.stride(1) != 1 or (B > 1 and audio.stride(0) < n_max):
+        audio = audio.contiguous()
+    lib = L.load()
+    nbytes = lib.wft_fir_conv_workspace_bytes(B, taps_max)
+    out = torch.empty((B, n_max), dtype=F32, device=audio.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=audio.device)
+    ld_in = audio.stride(0) if B > 1 else max(audio.stride(0), n_max)
+    ld_ir = ir.stride(0) if B > 1 else max(ir.stride(0), taps_max)
+    L.check(lib.wft_fir_conv_f32(_p(audio), ld_in, _p(n), n_max, _p(ir), ld_ir, _p(n_taps), taps_max, _p(out), out.stride(0), _p(ws),
+                                 nbytes, B, L.stream_ptr()), "wft_fir_conv_f32")
+    return out
+
+
+def bitcrush_depths(bits, B: int):
+    """One bit depth or one per row (host integers) -> int32 numpy [B]; a depth is 0 ("none": the row is copied) or lies inside
+    [1, 24], anything else raises ValueError."""
+    import numpy as np
+
+    v = _row_values(bits, B, "bitcrush", "bit depths")
+    if not bool(np.all((v == np.rint(v)) & (v >= 0) & (v <= 24))):  # (NaN fails)
+        raise ValueError(f"bitcrush: a bit depth must be an integer inside [1, 24], or 0 (none), got {v.tolist()}")
+    return v.astype(np.int32)
+
+
+def bitcrush(audio, bits, n=None, *, out=None):
+    """audiomentations' BitCrush over every row: round(x * q) / q with q = 2^(bits - 1) + 1 in f32 (wft_bitcrush_f32, include/wft.h
+    "Office effects"; numpy's np.round(samples * q) / q bit for bit).
+
+    audio f32 [B, ld] on the device (stride(1) == 1); bits: one depth or one per row as HOST integers inside [1, 24], 0 = "none" (the
+    row is copied), or an int32 tensor [B] on the device (unchecked: the kernel copies a row whose depth lies outside [1, 24]);
+    n i32 [B] on the device (row b covers its first n[b] samples; the output is zero behind them) or None.  out: None (a new
+    tensor), `audio` itself (in place) or an f32 [B, ld] tensor with unit column stride that does not overlap `audio`.  Every
+    host-side check raises ValueError before the device is touched."""
+    audio = _rate_rows(audio, "bitcrush")
+    B, n_max = audio.shape
+    on_device = torch.is_tensor(bits) and bits.is_cuda
+    if on_device:
+        if bits.dtype != torch.int32 or tuple(bits.shape) != (B,):
+            raise ValueError(f"bitcrush: device-side bits must be an int32 tensor [{B}]")
+    else:
+        depths = bitcrush_depths(bits, B)
+    if audio.stride(1) != 1 or (B > 1 and audio.stride(0) < n_max):
+        if out is audio:
+            raise ValueError("bitcrush: an in-place call needs rows with unit column stride that do not overlap")
+        audio = audio.contiguous()
+    if out is not None and out is not audio:
+        if not torch.is_tensor(out) or out.dtype != F32 or tuple(out.shape) != (B, n_max) or out.stride(1) != 1 or (B > 1 and out.stride(0) < n_max):
+            raise ValueError(f"bitcrush: out must be f32 [{B}, {n_max}] with unit column stride and rows that do not overlap")
+    _chk(audio, F32, "audio")  # (every ValueError above comes before the device is touched)
+    if out is None:
+        out = torch.empty((B, n_max), dtype=F32, device=audio.device)
+    if out.device != audio.device:
+        raise ValueError("bitcrush: audio and out must live on the same GPU")
+    n = _lengths(n, B, audio.device, "bitcrush", "n")
+    bits_d = bits.contiguous() if on_device else torch.from_numpy(depths).to(audio.device)
+    if bits_d.device != audio.device:
+        raise ValueError("bitcrush: audio and bits must live on the same GPU")
+    ld_in = audio.stride(0) if B > 1 else max(audio.stride(0), n_max)
+    ld_out = out.stride(0) if B > 1 else max(out.stride(0), n_max)
+    L.check(L.load().wft_bitcrush_f32(_p(audio), ld_in, _p(n), n_max, _p(bits_d), _p(out), ld_out, B, L.stream_ptr()), "wft_bitcrush_f32")
+    return out
+
+
 def mel_to_tmajor(mel, c_pad: int):
     _chk(mel, F32, "mel")
     mel = mel.contiguous()

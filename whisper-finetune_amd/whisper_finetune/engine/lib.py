@@ -272,6 +272,10 @@ SIGNATURES = {
     "wft_sinc_resample_rows_tile": [C.c_double],
     "wft_alias_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, C.c_double, c_vp, c_i64, C.c_int, c_vp],
     "wft_alias_tile": [],
+    "wft_fir_conv_block": [],
+    "wft_fir_conv_workspace_bytes": [C.c_int, C.c_int],
+    "wft_fir_conv_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, C.c_int, c_vp, c_i64, c_vp, c_i64, C.c_int, c_vp],
+    "wft_bitcrush_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, C.c_int, c_vp],
     "wft_adamw_step": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float,
                        C.c_float, C.c_float, C.c_float, c_vp, c_vp],
     "wft_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],
@@ -304,7 +308,8 @@ _RESTYPES = {"wft_last_error": C.c_char_p, "wft_version": C.c_char_p, "wft_layer
              "wft_gemm_nt_stream_workspace_bytes": c_i64, "wft_gemm_nt_stream_q8_workspace_bytes": c_i64,
              "wft_attn_decode_beam_workspace_bytes": c_i64,
              "wft_dtw_workspace_bytes": c_i64, "wft_time_stretch_workspace_bytes": c_i64,
-             "wft_sos_filter_workspace_bytes": c_i64, "wft_wave_fx_workspace_bytes": c_i64}
+             "wft_sos_filter_workspace_bytes": c_i64, "wft_wave_fx_workspace_bytes": c_i64,
+             "wft_fir_conv_workspace_bytes": c_i64}
 
 _lib = None
 
