@@ -1054,6 +1054,82 @@ int wft_fir_conv_f32(const float* in, int64_t ld_in, const int32_t* n, int64_t n
 int wft_bitcrush_f32(const float* in, int64_t ld_in, const int32_t* n, int64_t n_max, const int32_t* bits, float* out, int64_t ld_out,
                      int B, void* stream);
 
+/* ------------------------------------------------- Loudness and background noise (audio-domain augmentation) */
+/* LoudnessNormalization and AddBackgroundNoise of the reference's advanced pipeline (get_audio_augments_advanced, model/augment.py)
+ * over a ragged batch (csrc/mix.hip; DESIGN.md §3 "Mix effects"), restated from the published sources of pyloudnorm
+ * (Meter.integrated_loudness for one channel, normalize.loudness) and audiomentations (AddBackgroundNoise); neither is a dependency
+ * and parity with their binaries is unpinned.  Shared rules: no float atomics, no allocation, no host synchronisation; every
+ * host-visible argument is checked before the first launch; reruns are bit-identical; fp64 products and sums are NOT contracted into
+ * FMAs; 1 <= B <= 65535; 1 <= n_max <= 2^30; in / out f32: row b at in + b * ld_in / out + b * ld_out, ld >= n_max; N = n[b] (device
+ * i32) clamped to [0, n_max], n == NULL = n_max for every row; nothing at or behind n[b] of an input row is read; out == in with
+ * ld_out == ld_in is in place (nothing behind n[b] is touched), any other overlap is WFT_ERR_ARG; out of place out[b, N .. n_max) is
+ * written as zero; nothing at or behind n_max of an output row is written.
+ *
+ * wft_loudness_f32: the ITU-R BS.1770 integrated loudness of every row and, with an output, one gain per row.
+ *   sos: HOST f64 [2][6], the two K-weighting sections b0 b1 b2 a0 a1 a2 with a0 == 1 (data/gpu_frontend.py k_weighting: the RBJ high
+ *   shelf G = 4 dB, Q = 1/sqrt(2), fc = 1500 Hz and high pass Q = 0.5, fc = 38 Hz, each divided by its a0); it is read before the
+ *   call returns.  hop = rate / 10 samples, 512 <= hop <= 2^24; block = 4 * hop.  target: device f64 [B] in LUFS; mode: device i32
+ *   [B], 0 = copy the row, 1 = normalise it.  out == NULL measures only: EVERY row is measured, target and mode may be NULL.  With an
+ *   output target and mode are required and only the rows of mode 1 are measured; a row of mode 0 is copied bit for bit and its
+ *   stats are (-inf, -inf, 0, 1).  stats: device f64 [B, 4] = (L in LUFS, the relative gate Gr, the number of blocks over both
+ *   gates, the gain applied).
+ *   1. y = the two sections over the row's N samples from zero state, fp64, direct form II transposed per section
+ *      (y = b0 x + z0; z0 = b1 x - a1 y + z1; z1 = b2 x - a2 y), the sample widened to fp64; y is never rounded to f32.
+ *   2. with q, r = divmod(N - block, hop): nb = q + 1 + (1 if 2 r > hop or (2 r == hop and q odd) else 0) blocks, which is
+ *      int(np.round((T - 0.4) / 0.1)) + 1 in integers (round half to even).
+ *   3. block j covers samples [j hop, j hop + block); the rounded-up last block is cut at N and still divided by block:
+ *      z_j = sum y^2 / block.   4. l_j = -0.691 + 10 log10(z_j).
+ *   5. J1 = {j : l_j >= -70}; Gr = -0.691 + 10 log10(mean of z over J1) - 10.
+ *   6. J2 = {j : l_j > Gr and l_j > -70}; L = -0.691 + 10 log10(mean of z over J2).
+ *   7. J1 or J2 empty, or N < block: L = -inf (Gr = -inf when J1 is empty) and the row is copied bit for bit (pyloudnorm raises for
+ *      the short clip: a stated deviation).  A target or an L that is not finite copies the row as well.
+ *   8. gain = f32(10^((target - L) / 20)), formed in fp64; out = x * gain, ONE f32 multiply; no clipping afterwards.
+ *   Parallel form.  The recurrence is cut as wft_sos_filter_f32 cuts it, at S = 2: chunks of 512 samples from zero state, the per-row
+ *   scan of the chunk states, the chunks again from their true state (within delta = 2^-30 of the sequential recurrence, relative
+ *   to the row's largest |y|).  The second pass adds y^2 in ascending sample order into the at most two hop-slots
+ *   [k hop, (k + 1) hop) its chunk touches; a slot's sum is its chunks' partials in chunk order; z_j = (((e_j + e_j+1) + e_j+2) +
+ *   e_j+3) / block over the slots that exist.  A gate's mean: thread t of 256 adds its blocks t, t + 256, ... in ascending order,
+ *   the 256 sums are halved pairwise (s[t] += s[t + h], h = 128 .. 1).  A row's bits depend on its samples, N, hop, sos and target
+ *   only — not on B, its batch partners or the launch.
+ *   workspace: wft_loudness_workspace_bytes(B, n_max, hop) bytes (-1: bad arguments), 8-byte aligned.  WFT_ERR_ARG: a null pointer
+ *   (in, sos, stats, workspace; target or mode with an output), a bad shape or hop, a short leading dimension or workspace,
+ *   misalignment (in / out / n / mode 4 bytes, the rest 8), a section that is not finite or has a0 != 1, partial overlap.
+ *
+ * wft_bg_mix_f32: a scaled entry of a noise bank added to every row.  bank: device f32 [total], the entries back to back; bank_off:
+ *   device i64 [K + 1], entry e = bank[bank_off[e] .. bank_off[e + 1]), K >= 1; rec: device array of B records, 8-byte aligned, 24
+ *   bytes each.  kind 0 (or unknown) = none: the row is copied bit for bit, its stats are (0, 0, 0).  entry is clamped to
+ *   [0, K - 1] and offset into the entry inside the kernels (the caller checks them: engine/kernels.py bg_mix).
+ *   stats: device f64 [B, 3] = (clean RMS, noise RMS, scale).
+ *   1. for entry e of length m: s(i) = e[(offset + i) mod m], i < N; offset is 0 when m <= N (a short entry repeats), and at most
+ *      m - N otherwise (a long one does not wrap).
+ *   2. noise RMS over the first min(m, N) samples of s (audiomentations measures the loaded segment before it tiles it).
+ *   3. clean RMS over the row's N samples.
+ *   4. both sums of squares are fp64 in the fixed order of WFT_FX_GAUSSIAN_SNR above: chunks of 4096, thread t of 256 adds its
+ *      samples c K + t, c K + t + 256, ... ascending, the 256 sums are halved pairwise, the chunks' sums are added in ascending order.
+ *   5. noise RMS < 1e-9 (or N == 0, or a db that is not finite): the row is copied bit for bit, scale = 0.
+ *   6. WFT_BG_SNR: desired = clean RMS / 10^(db / 20); WFT_BG_ABSOLUTE: desired = 10^(db / 20).
+ *   7. scale = desired / noise RMS in fp64; out[i] = f32((double)x[i] + scale * (double)s(i)), one rounding.
+ *   The sums run over the rows whose kind is not none.  workspace: wft_bg_mix_workspace_bytes(B, n_max) bytes (-1: bad arguments),
+ *   8-byte aligned.  WFT_ERR_ARG: a null pointer, a bad shape, K < 1, a short leading dimension or workspace, misalignment (in / out
+ *   / n / bank 4 bytes, the rest 8), partial overlap of in and out.
+ * DEVIATIONS of the loader option built on these (data/mix_fx.py): own gates at the reference's marginal rates; the offset is drawn
+ * as an integer, not in seconds; the short clip is copied where pyloudnorm raises; the block count is in integers; no
+ * noise_transform; the bank is .npy arrays (no audio decoding).                                                                 */
+enum { WFT_BG_NONE = 0, WFT_BG_SNR = 1, WFT_BG_ABSOLUTE = 2 };                    /* kind */
+typedef struct {
+  int32_t kind, entry; /*  0  4 */
+  int64_t offset;      /*  8 */
+  double db;           /* 16: the SNR (snr) or the noise's RMS level (absolute), in dB */
+} wft_bg_rec;
+int64_t wft_loudness_workspace_bytes(int B, int64_t n_max, int hop);
+int wft_loudness_f32(const float* in, int64_t ld_in, const int32_t* n, int64_t n_max, const double* sos, int hop, const double* target,
+                     const int32_t* mode, float* out, int64_t ld_out, double* stats, void* workspace, int64_t workspace_bytes, int B,
+                     void* stream);
+int64_t wft_bg_mix_workspace_bytes(int B, int64_t n_max);
+int wft_bg_mix_f32(const float* in, int64_t ld_in, const int32_t* n, int64_t n_max, const float* bank, const int64_t* bank_off, int K,
+                   const wft_bg_rec* rec, float* out, int64_t ld_out, double* stats, void* workspace, int64_t workspace_bytes, int B,
+                   void* stream);
+
 /* ---------------------------------------------------------------- AdamW */
 /* torch.optim.AdamW single-tensor step over a flat f32 range
  * (model/optimizer.py:240-262 → optimizer.step() in model_utils.py:122).

@@ -80,8 +80,12 @@
          and K.bitcrush on [32, 480000] and [96, 480000] with every row active, beside the log-mel, the time stretch's STFT stage
          (comparable FFT work per clip) and torch's copy of the same batch.  No threshold is set.
          (--parts office --out profiles/decode_bench_office.jsonl)
+  mix      the mix effects of the loader (--batches is not used): K.loudness (measure only, and normalise in place) and K.bg_mix (snr and
+         absolute, in place, over a synthetic bank of four entries) on [32, 480000] and [96, 480000] with every row active, beside
+         K.sos_filter at two sections (the same recurrence, with its outputs stored), the log-mel and torch's copy of the same batch.
+         No threshold is set.  (--parts mix --out profiles/decode_bench_mix.jsonl)
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample,stretch,filter,wavefx,rate,office] [--batches 1,8,32] [--out FILE]
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample,stretch,filter,wavefx,rate,office,mix] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -1185,6 +1189,55 @@ def bench_office(batches):
         emit(rec)
 
 
+def bench_mix(batches):
+    """K.loudness (measure only, normalise) and K.bg_mix (snr, absolute) on 30 s clips with every row active: ms per call beside
+    K.sos_filter at two sections, the log-mel and torch's copy of the same batch."""
+    import numpy as np
+
+    from whisper_finetune.data import mix_fx as MF
+    from whisper_finetune.data.gpu_frontend import mel_filters
+
+    n = 480000
+    filters = mel_filters(80).to(DEV)
+    entries = MF.synthetic_bank(4)
+    bank_h, off_h = MF.pack_bank(entries)
+    bank, off = torch.from_numpy(bank_h).to(DEV), torch.from_numpy(off_h).to(DEV)
+    lengths = [int(e.shape[0]) for e in entries]
+    sos = torch.from_numpy(MF.k_weighting(16000))
+    for B in (32, 96):
+        g = torch.Generator().manual_seed(B)
+        x = (torch.randn(B, n, generator=g) * 0.1).to(DEV)
+        x[:, 300000:] = 0  # zero-padded clips, as the loader stages them
+        work, out = x.clone(), torch.empty_like(x)
+        targets = np.linspace(-31.0, -13.0, B)
+        rec = {}
+        for name, kind in (("snr", 1), ("absolute", 2)):
+            r = np.zeros(B, dtype=MF.RECORD_DTYPE)
+            r["kind"], r["entry"] = kind, np.arange(B) % 4
+            r["offset"] = np.where(r["entry"] == 2, 16000 * np.arange(B) // B, 0)  # the one entry that is longer than a clip
+            r["db"] = np.linspace(2.0, 4.0, B) if kind == 1 else np.linspace(-30.0, -10.0, B)
+            rec[name] = r
+        # in place the batch changes from call to call (a gain, added noise); the work per call does not: every row stays active
+        arms = {"loudness_measure": lambda: K.loudness(x, 16000),
+                "loudness_normalize": lambda: K.loudness(x, 16000, targets, out=out),
+                "loudness_normalize_in_place": lambda: K.loudness(work, 16000, targets, out=work),
+                "bg_mix_snr": lambda: K.bg_mix(x, bank, off, rec["snr"], out=out, lengths=lengths),
+                "bg_mix_absolute": lambda: K.bg_mix(x, bank, off, rec["absolute"], out=out, lengths=lengths),
+                "bg_mix_snr_in_place": lambda: K.bg_mix(work, bank, off, rec["snr"], out=work, lengths=lengths),
+                "sos_filter_S2": lambda: K.sos_filter(x, sos, out=out),
+                "logmel": lambda: K.logmel(x, filters, 3000), "copy": lambda: out.copy_(x)}
+        res = ab(arms, rounds=5, iters=5)
+        out_rec = dict(part="mix", B=B, n=n, bank_entries=lengths,
+                       note="ms per call, medians of 5 alternating rounds of 5 calls, every row active; loudness_*: the K.loudness wrapper "
+                            "(workspace and stats allocation, the K-weighting design, local / scan / energy / gate launches, plus the apply "
+                            "pass when it normalises); bg_mix_*: the K.bg_mix wrapper (record upload, sumsq / scale / mix launches); "
+                            "sos_filter_S2: K.sos_filter with the K-weighting's two sections, the same recurrence with its outputs stored; "
+                            "logmel / copy: the log-mel of the same batch and torch's copy of it, for scale")
+        for name, (med, mn, spread) in res.items():
+            out_rec[name + "_ms"], out_rec[name + "_min_ms"], out_rec[name + "_spread"] = round(med, 4), round(mn, 4), round(spread, 3)
+        emit(out_rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="attn,gemm,e2e")
@@ -1198,7 +1251,7 @@ def main():
     for part in a.parts.split(","):
         {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": lambda b: (bench_gemm_stream(b), bench_gemm_stream_q8(b)), "e2e_step": bench_e2e_step,
          "gemm_i8": bench_gemm_i8, "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align, "transcribe": bench_transcribe, "resample": bench_resample,
-         "stretch": bench_stretch, "filter": bench_filter, "wavefx": bench_wavefx, "rate": bench_rate, "office": bench_office}[part](batches)
+         "stretch": bench_stretch, "filter": bench_filter, "wavefx": bench_wavefx, "rate": bench_rate, "office": bench_office, "mix": bench_mix}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

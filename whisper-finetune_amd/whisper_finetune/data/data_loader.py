@@ -41,6 +41,14 @@ NOT `apply_office_aug`): a worker DRAWS the clip's bit depth and DESIGNS its roo
 the rate-effects draw) and ships them as one table row f64 [2 + cap]; the main process runs `wft_bitcrush_f32` (in place) and
 `wft_fir_conv_f32` (into a second buffer) right behind the stretch, the reference's Compose order: resample -> stretch -> CRUSH -> ROOM
 -> NOISE -> ALIAS -> filter -> CLIP -> LEVEL -> PITCH -> log-mel.  Timestamps are untouched.
+
+Mix effects (`mix_aug={...}`, an option of this project's own: AddBackgroundNoise and LoudnessNormalization of the reference's advanced
+pipeline, NOT `apply_advanced_aug`): a worker DRAWS the clip's noise entry, offset and level and its loudness target (data/mix_fx.py
+MixAug, after the office-effects draw; it knows the bank's entry lengths only) and ships them as one table row f64 [6], the LAST field
+of a batch; `GpuMelLoader` loads the noise bank once, keeps it on the device and runs `wft_bg_mix_f32` and `wft_loudness_f32` in place
+at their places of the reference's Compose order: resample -> stretch -> crush -> room -> BACKGROUND -> noise -> LOUDNESS -> alias ->
+filter -> clip -> level -> pitch -> log-mel, over the padded clip (the reference pads to 30 s before it augments).  AirAbsorption
+and Mp3Compression stay unbuilt.  Timestamps are untouched.
 """
 from __future__ import annotations
 
@@ -58,6 +66,7 @@ from whisper_finetune.data.filters import FilterAug, identity_sos
 from whisper_finetune.data.gpu_frontend import (HOP_LENGTH, N_FFT, N_FRAMES, N_SAMPLES, SAMPLE_RATE, GpuFrontend, check_rate,
                                                 check_stretch_range, draw_clip_params, mel_filters)
 from whisper_finetune.data.utils import ExtremesFrequencyMasking, TimeWarpAugmenter, pad_or_trim
+from whisper_finetune.data.mix_fx import MixAug, STAGES as MIX_STAGES, check_table as check_mix_table, load_bank, pack_bank, records_from_table as bg_records_from_table
 from whisper_finetune.data.office_fx import OfficeAug, STAGES as OFFICE_STAGES, check_table as check_office_table
 from whisper_finetune.data.rate_fx import RateAug, check_table as check_rate_table
 from whisper_finetune.data.wave_fx import STAGES as WAVE_STAGES, WaveAug, active_rows, check_records, records_from_table
@@ -65,6 +74,7 @@ from whisper_finetune.data.wave_fx import STAGES as WAVE_STAGES, WaveAug, active
 CHUNK_LENGTH = 30
 _TS = re.compile(r"(<\|[123]?[0-9]\.[0-9][0-9]\|>)")  # <|0.00|> .. <|30.00|>
 _FILTERS = {}
+_BANKS = {}  # the per-clip form's noise banks: (id of the MixAug, device) -> DeviceBank
 
 
 def pitch_rows(audio, semitones, lengths=None):
@@ -105,9 +115,52 @@ def office_rows(audio, n, office):
     return audio
 
 
-def apply_wave_stages(audio, n, sos, fx, rate=None, lengths=None, office=None):
+class DeviceBank:
+    """The noise bank of a MixAug on one device: the entries back to back f32 [total], their offsets i64 [K + 1] and the lengths
+    as host integers.  A bank at another rate (`bank_sample_rate`) is resampled ONCE, entry by entry, through gpu_frontend.resample."""
+
+    def __init__(self, mix_aug: MixAug, device):
+        from whisper_finetune.data.gpu_frontend import resample
+
+        src = mix_aug.sample_rate if mix_aug.bank_sample_rate is None else mix_aug.bank_sample_rate
+        entries = load_bank(mix_aug.bank, src)
+        if src != mix_aug.sample_rate:
+            parts = [resample(e, src, device) for e in entries]
+            self.lengths = [int(t.shape[0]) for t in parts]
+            self.bank = torch.cat(parts).contiguous()
+            self.off = torch.tensor(np.concatenate([[0], np.cumsum(self.lengths)]), dtype=torch.int64).to(device)
+        else:
+            bank, off = pack_bank(entries)
+            self.lengths = [int(e.shape[0]) for e in entries]
+            self.bank, self.off = torch.from_numpy(bank).to(device), torch.from_numpy(off).to(device)
+        if self.lengths != list(mix_aug.lengths):
+            raise RuntimeError(f"noise bank: the device holds entries of {self.lengths} samples, the draws were made for {list(mix_aug.lengths)}")
+
+
+def background_rows(audio, n, mix):
+    """BACKGROUND on audio f32 [B, ld] (device), in place: mix = (the checked mix table f64 [B, 6], DeviceBank or None)."""
+    from whisper_finetune.engine import kernels as K
+
+    table, bank = mix
+    if bool(table[:, 0].any()):
+        K.bg_mix(audio, bank.bank, bank.off, bg_records_from_table(table), n, out=audio, lengths=bank.lengths)
+    return audio
+
+
+def loudness_rows(audio, n, mix):
+    """LOUDNESS on audio f32 [B, ld] (device), in place: the rows with loud_on are brought to their targets."""
+    from whisper_finetune.engine import kernels as K
+
+    table = mix[0]
+    if bool(table[:, 4].any()):
+        K.loudness(audio, SAMPLE_RATE, np.where(table[:, 4] != 0, table[:, 5], np.nan), n, out=audio)
+    return audio
+
+
+def apply_wave_stages(audio, n, sos, fx, rate=None, lengths=None, office=None, mix=None):
     """The audio-domain stages behind the stretch on audio f32 [B, ld] (device), in the reference's Compose order:
-    CRUSH -> ROOM -> NOISE -> ALIAS -> filter -> CLIP -> LEVEL -> PITCH.  n: i32 [B] on the device or None; sos: f64 [B, 4, 6] or
+    CRUSH -> ROOM -> BACKGROUND -> NOISE -> LOUDNESS -> ALIAS -> filter -> CLIP -> LEVEL -> PITCH (mix: None, or the checked mix
+    table f64 [B, 6] of data/mix_fx.py with the DeviceBank of its background rows; both of its stages run in place).  n: i32 [B] on the device or None; sos: f64 [B, 4, 6] or
     None; fx: checked wave-effect records [B] (data/wave_fx.py) or None; rate: the checked rate-effect table f64 [B, 4]
     (data/rate_fx.py) or None; lengths: the rows' lengths as host integers (what n holds; None with n None); office: the checked
     office table f64 [B, 2 + cap] (data/office_fx.py) or None.  A stage with no active row launches nothing.
@@ -116,8 +169,12 @@ def apply_wave_stages(audio, n, sos, fx, rate=None, lengths=None, office=None):
 
     if office is not None:
         audio = office_rows(audio, n, office)
+    if mix is not None:
+        background_rows(audio, n, mix)
     if fx is not None:
         K.wave_fx(audio, fx, "noise", n, out=audio)
+    if mix is not None:
+        loudness_rows(audio, n, mix)
     if rate is not None and bool(rate[:, 0].any()):
         audio = K.alias(audio, rate[:, 1], n, SAMPLE_RATE)  # out of place; a "none" row (rate 0) is copied
     if sos is not None:
@@ -167,7 +224,8 @@ class AudioDataset(Dataset):
     with `filter_aug` one more field behind those, the clip's filter as sos f64 [4, 6] (identity sections = "do not filter");
     with `wave_aug` one more field behind the filter, the clip's wave effects as a table row f64 [14] (data/wave_fx.py);
     with `rate_aug` one more field behind the wave effects, the clip's rate effects as a table row f64 [4] (data/rate_fx.py);
-    with `office_aug` one more field behind the rate effects, the clip's office effects as a table row f64 [2 + cap] (data/office_fx.py).
+    with `office_aug` one more field behind the rate effects, the clip's office effects as a table row f64 [2 + cap] (data/office_fx.py);
+    with `mix_aug` one more field behind the office effects, the clip's mix effects as a table row f64 [6] (data/mix_fx.py).
 
     apply_baseline_aug: the rate is drawn as audiomentations draws it — Python's `random` module, one `random.random()` gate against
     p = 1.0, then `random.uniform(min_rate, max_rate)` (BaseWaveformTransform.randomize_parameters, then TimeStretch's).  That order is
@@ -185,6 +243,10 @@ class AudioDataset(Dataset):
     office_aug: None, or a mapping of data/office_fx.py OfficeAug's groups (`crush`, `room`, each None or a mapping of its keywords; a
     missing group is off).  The parameters are drawn after the rate effects, with Python's `random`, and the room's impulse response
     is designed in the worker.  It is NOT `apply_office_aug`, which stays refused (mp3 compression is not built).
+    mix_aug: None, or a mapping of data/mix_fx.py MixAug's groups (`background`, `loudness`, each None or a mapping of its keywords; a
+    missing group is off; `background` needs `bank`).  The parameters are drawn after the office effects, with Python's `random`,
+    for the padded clip of 480000 samples; the dataset keeps the bank's entry lengths only.  It is NOT `apply_advanced_aug`, which
+    stays refused (air absorption is not built).
 
     hu_dataset: indexable records {"audio": {"array", optional "sampling_rate"}, "text", "language", optional "prompt"}; a record
     whose "sampling_rate" is present and differs from the dataset's `sample_rate` raises ValueError (no mixed rates); tokenizer: whisper-style
@@ -200,6 +262,7 @@ class AudioDataset(Dataset):
     wave_aug = None
     rate_aug = None
     office_aug = None
+    mix_aug = None
 
     def __init__(self, hu_dataset, tokenizer, device=None, no_timestamp_training: bool = False, n_mels: int = 80,
                  max_prompt_length: int = 223, prompt_use_rate: float = 0.5, no_timestamps_rate: float = 0.5,
@@ -207,7 +270,8 @@ class AudioDataset(Dataset):
                  extremes_spec_augment_params: Optional[dict] = None, apply_baseline_aug: bool = False, apply_office_aug: bool = False,
                  apply_advanced_aug: bool = False, time_stretch_min_rate: float = 0.8, time_stretch_max_rate: float = 1.25,
                  bpe_dropout: float = 0.0, sample_rate: int = SAMPLE_RATE, filter_aug: Optional[dict] = None,
-                 wave_aug: Optional[dict] = None, rate_aug: Optional[dict] = None, office_aug: Optional[dict] = None):
+                 wave_aug: Optional[dict] = None, rate_aug: Optional[dict] = None, office_aug: Optional[dict] = None,
+                 mix_aug: Optional[dict] = None):
         self.sample_rate = check_rate(sample_rate)
         self.n_samples = CHUNK_LENGTH * self.sample_rate  # 30 s at the clips' own rate
         refused = [name for name, on in (("apply_office_aug", apply_office_aug), ("apply_advanced_aug", apply_advanced_aug)) if on]
@@ -215,7 +279,8 @@ class AudioDataset(Dataset):
             raise NotImplementedError(f"{' and '.join(refused)}: the office and advanced audio pipelines (room simulation, mp3 compression, "
                                       "background-noise files, biquad filters, pitch shift) are not implemented; "
                                       "apply_baseline_aug (time stretch) is; the office pipeline's bit crush and room simulation run "
-                                      "behind this project's own option audio_augment.wft_office_aug")
+                                      "behind this project's own option audio_augment.wft_office_aug, the advanced pipeline's "
+                                      "background noise and loudness normalisation behind audio_augment.wft_mix_aug")
         if apply_baseline_aug:
             time_stretch_min_rate, time_stretch_max_rate = check_stretch_range(time_stretch_min_rate, time_stretch_max_rate)
         self.hu_dataset, self.tokenizer, self.n_mels, self.device = hu_dataset, tokenizer, n_mels, device
@@ -238,6 +303,9 @@ class AudioDataset(Dataset):
         if office_aug is not None and (not hasattr(office_aug, "keys") or not set(office_aug.keys()) <= set(OFFICE_STAGES)):
             raise ValueError(f"office_aug must be None or a mapping of OfficeAug's groups {OFFICE_STAGES}, got {office_aug!r}")
         self.office_aug = OfficeAug(sample_rate=SAMPLE_RATE, **dict(office_aug)) if office_aug is not None else None
+        if mix_aug is not None and (not hasattr(mix_aug, "keys") or not set(mix_aug.keys()) <= set(MIX_STAGES)):
+            raise ValueError(f"mix_aug must be None or a mapping of MixAug's groups {MIX_STAGES}, got {mix_aug!r}")
+        self.mix_aug = MixAug(sample_rate=SAMPLE_RATE, **dict(mix_aug)) if mix_aug is not None else None
         if spec_augment:
             self.spec_augment_p = float(spec_augment_params.get("p", 1.0))
             if not 0.0 <= self.spec_augment_p <= 1.0:
@@ -304,6 +372,22 @@ class AudioDataset(Dataset):
         names, row = self.office_aug.draw()
         return check_office_table(row[None]) if any(names.values()) else None
 
+    def _draw_mix(self, device):
+        """The clip's mix effects for the per-clip form: (the checked table f64 [1, 6], the DeviceBank or None), or None without the
+        option or when nothing was drawn."""
+        if self.mix_aug is None:
+            return None
+        names, row = self.mix_aug.draw(N_SAMPLES)
+        if names["background"] is None and not names["loudness"]:
+            return None
+        bank = None
+        if self.mix_aug.lengths is not None:
+            key = (id(self.mix_aug), str(device))
+            if key not in _BANKS:
+                _BANKS[key] = DeviceBank(self.mix_aug, device)
+            bank = _BANKS[key]
+        return check_mix_table(row[None], self.mix_aug.lengths), bank
+
     def _calculate_mel(self, audio_array, next_partial_segment_start: Optional[float], no_timestamps: bool) -> torch.Tensor:
         """Per-clip form: [time stretch] -> [crush] -> [room] -> [noise] -> [alias] -> [filter] -> [clipping] -> [level] -> [pitch] -> log-mel -> cut at a partial segment + minimum-value pad -> [warp -> time mask -> freq mask]
         w.p. p -> extremes masking, every stage a libwft kernel on the device."""
@@ -318,8 +402,8 @@ class AudioDataset(Dataset):
             row = torch.as_tensor(np.asarray(audio_array, dtype=np.float32)).to(dev)[None]
             stretch_rate = self._draw_stretch_rate()
             stretched, n_out = K.time_stretch(row, [stretch_rate])
-            sos, fx, rt, office = self._draw_filter(), self._draw_wave(), self._draw_rate(), self._draw_office()
-            stretched = apply_wave_stages(stretched, n_out, sos, fx, rt, stretched_lengths(row.shape[1], [stretch_rate]), office)
+            sos, fx, rt, office, mix = self._draw_filter(), self._draw_wave(), self._draw_rate(), self._draw_office(), self._draw_mix(dev)
+            stretched = apply_wave_stages(stretched, n_out, sos, fx, rt, stretched_lengths(row.shape[1], [stretch_rate]), office, mix)
             key = (self.n_mels, row.device)
             if key not in _FILTERS:
                 _FILTERS[key] = mel_filters(self.n_mels).to(row.device)
@@ -327,10 +411,13 @@ class AudioDataset(Dataset):
             mel = K.logmel_ragged(stretched, n_out, keep, _FILTERS[key], N_FRAMES)[0]
         else:
             sos, fx, rt, office = self._draw_filter(), self._draw_wave(), self._draw_rate(), self._draw_office()
-            if sos is not None or fx is not None or rt is not None or office is not None:  # the same kernels as GpuMelLoader, on one row
+            mix = None
+            if self.mix_aug is not None:
+                mix = self._draw_mix(self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device()))
+            if sos is not None or fx is not None or rt is not None or office is not None or mix is not None:  # the same kernels as GpuMelLoader, on one row
                 dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
                 row = torch.as_tensor(np.asarray(audio_array, dtype=np.float32)).to(dev)[None].clone()
-                audio_array = apply_wave_stages(row, None, sos, fx, rt, None, office)[0]
+                audio_array = apply_wave_stages(row, None, sos, fx, rt, None, office, mix)[0]
             mel = log_mel_spectrogram(audio_array, n_mels=self.n_mels, device=self.device)
             if no_timestamps and next_partial_segment_start is not None:
                 mel = mel[:, : int(next_partial_segment_start * self.num_frames_per_second)]
@@ -465,6 +552,8 @@ class AudioDataset(Dataset):
             item += (torch.from_numpy(self.rate_aug.draw()[1]),)
         if self.office_aug is not None:
             item += (torch.from_numpy(self.office_aug.draw()[1]),)
+        if self.mix_aug is not None:
+            item += (torch.from_numpy(self.mix_aug.draw(N_SAMPLES)[1]),)
         return item
 
 
@@ -476,7 +565,7 @@ def collate_fn(data):
     if len(cols) == 3:
         return pad_sequence(cols[0], batch_first=True, padding_value=0), y_in, y_out
     out = (torch.stack(cols[0]), y_in, y_out, torch.stack(cols[3]), torch.stack(cols[4]), torch.tensor(cols[5], dtype=torch.int32))
-    return out + tuple(torch.stack(c) for c in cols[6:])  # the time-stretch rates f64 [B], the filters f64 [B, 4, 6], the wave effects f64 [B, 14], the rate effects f64 [B, 4], the office effects f64 [B, 2 + cap]
+    return out + tuple(torch.stack(c) for c in cols[6:])  # the time-stretch rates f64 [B], the filters f64 [B, 4, 6], the wave effects f64 [B, 14], the rate effects f64 [B, 4], the office effects f64 [B, 2 + cap], the mix effects f64 [B, 6]
 
 
 class WarmupDatasetSampler(torch.utils.data.Sampler):
@@ -555,11 +644,15 @@ class GpuMelLoader:
     (the lengths are known on the host as round(480000 / rate): no synchronisation).
 
     Batches of a dataset built with office_aug carry the office effects f64 [B, 2 + cap] as their last field, behind the rate effects:
-    CRUSH (in place) and ROOM (out of place; its output takes the batch's place) run right behind the stretch, in front of NOISE."""
+    CRUSH (in place) and ROOM (out of place; its output takes the batch's place) run right behind the stretch, in front of NOISE.
+
+    Batches of a dataset built with mix_aug carry the mix effects f64 [B, 6] as their LAST field, behind the office effects: BACKGROUND
+    runs behind ROOM and LOUDNESS behind NOISE, both in place.  The noise bank is loaded when the loader is built and stays on the
+    device (entries back to back, f32 [total] with i64 offsets [K + 1]); a batch without an active row launches nothing."""
 
     def __init__(self, loader, frontend: GpuFrontend, training_aug: bool, sample_rate: int = SAMPLE_RATE, stretch: Optional[bool] = None,
                  filter_aug: Optional[bool] = None, wave_aug: Optional[bool] = None, rate_aug: Optional[bool] = None,
-                 office_aug: Optional[bool] = None):
+                 office_aug: Optional[bool] = None, mix_aug: Optional[bool] = None):
         self.loader, self.frontend, self.training_aug = loader, frontend, training_aug
         ds = getattr(loader, "dataset", None)
         if stretch is None and ds is not None:
@@ -574,6 +667,13 @@ class GpuMelLoader:
             office_aug = getattr(ds, "office_aug", None) is not None
         self.stretch, self.filter_aug, self.wave_aug, self.rate_aug = stretch, bool(filter_aug), bool(wave_aug), bool(rate_aug)
         self.office_aug = bool(office_aug)
+        if mix_aug is None:
+            mix_aug = getattr(ds, "mix_aug", None) is not None
+        self.mix_aug = bool(mix_aug)
+        self._mix = getattr(ds, "mix_aug", None) if self.mix_aug else None
+        if self.mix_aug and self._mix is None:
+            raise ValueError("mix_aug=True needs a loader whose dataset was built with mix_aug (it holds the noise bank's description)")
+        self._bank = DeviceBank(self._mix, frontend.device) if self._mix is not None and self._mix.lengths is not None else None
         self._identity = torch.from_numpy(identity_sos())
         self.sample_rate = check_rate(sample_rate)
         self.sampler = getattr(loader, "sampler", None)  # infinite_iter() calls sampler.set_epoch(...)
@@ -595,13 +695,14 @@ class GpuMelLoader:
 
     def _all_fields(self, batch):
         """_fields and, as a fourth item, the checked rate-effect table f64 [B, 4] (numpy) or None (no option, or no row active)."""
-        stretch = (len(batch) == 7 and not self.filter_aug and not self.wave_aug and not self.rate_aug and not self.office_aug) \
+        stretch = (len(batch) == 7 and not self.filter_aug and not self.wave_aug and not self.rate_aug and not self.office_aug and not self.mix_aug) \
             if self.stretch is None else self.stretch
-        if len(batch) != 6 + int(stretch) + int(self.filter_aug) + int(self.wave_aug) + int(self.rate_aug) + int(self.office_aug):
+        if len(batch) != 6 + int(stretch) + int(self.filter_aug) + int(self.wave_aug) + int(self.rate_aug) + int(self.office_aug) + int(self.mix_aug):
             raise ValueError(f"a batch of {len(batch)} fields from a loader with stretch={stretch}, filter_aug={self.filter_aug}"
                              + (f", wave_aug={self.wave_aug}" if self.wave_aug else "")
                              + (f", rate_aug={self.rate_aug}" if self.rate_aug else "")
-                             + (f", office_aug={self.office_aug}" if self.office_aug else ""))
+                             + (f", office_aug={self.office_aug}" if self.office_aug else "")
+                             + (f", mix_aug={self.mix_aug}" if self.mix_aug else ""))
         rates = batch[6] if stretch else None
         sos = batch[6 + int(stretch)] if self.filter_aug else None
         if sos is not None and bool((sos == self._identity).all()):
@@ -619,11 +720,20 @@ class GpuMelLoader:
         return rates, sos, fx, rt
 
     def _office_field(self, batch):
-        """The checked office table f64 [B, 2 + cap] (numpy) of a collated batch, its last field, or None (no option, or no row active)."""
+        """The checked office table f64 [B, 2 + cap] (numpy) of a collated batch, its last field in front of the mix effects, or None
+        (no option, or no row active)."""
         if not self.office_aug:
             return None
-        office = check_office_table(batch[-1])
+        office = check_office_table(batch[-1 - int(self.mix_aug)])
         return office if bool(office[:, :2].any()) else None
+
+    def _mix_field(self, batch):
+        """(The checked mix table f64 [B, 6] (numpy) of a collated batch, its last field, the device bank), or None (no option, or no
+        row active)."""
+        if not self.mix_aug:
+            return None
+        table = check_mix_table(batch[-1], self._mix.lengths)
+        return (table, self._bank) if bool(table[:, 0].any() or table[:, 4].any()) else None
 
     def _stage(self, batch):
         """Issue the batch's H2D copies on the side stream; returns the device tensors and the event that orders them."""
@@ -637,9 +747,9 @@ class GpuMelLoader:
             staged = [t.to(dev, non_blocking=True) for t in (audio, y_in, y_out, params, ext)]
             ev = torch.cuda.Event()
             ev.record(self._copy_stream)
-        return staged, cut, ev, need_aug, rates, sos, fx, rt, self._office_field(batch)
+        return staged, cut, ev, need_aug, rates, sos, fx, rt, self._office_field(batch), self._mix_field(batch)
 
-    def _to_mel(self, staged, cut, ev, need_aug, rates=None, sos=None, fx=None, rt=None, office=None):
+    def _to_mel(self, staged, cut, ev, need_aug, rates=None, sos=None, fx=None, rt=None, office=None, mix=None):
         from whisper_finetune.engine import kernels as K
 
         cur = torch.cuda.current_stream(self.frontend.device)
@@ -655,14 +765,14 @@ class GpuMelLoader:
             # rows' lengths stay on the device; the cut and the minimum-value pad happen inside the ragged log-mel
             stretched, n_out = K.time_stretch(audio, rates)
             stretched = apply_wave_stages(stretched, n_out, sos, fx, rt,
-                                          stretched_lengths(audio.shape[1], rates.tolist()) if rt is not None else None, office)
+                                          stretched_lengths(audio.shape[1], rates.tolist()) if rt is not None else None, office, mix)
             keep = cut.clamp(max=N_FRAMES).to(torch.int32).to(audio.device, non_blocking=True)
             mel = K.logmel_ragged(stretched, n_out, keep, self.frontend.filters, N_FRAMES)
         else:
-            if sos is not None or fx is not None or rt is not None or office is not None:
+            if sos is not None or fx is not None or rt is not None or office is not None or mix is not None:
                 if audio.stride(1) != 1 or not audio.is_contiguous():
                     audio = audio.contiguous()
-                audio = apply_wave_stages(audio, None, sos, fx, rt, None, office)  # in place on the staged (or resampled) copy; alias gives a new one
+                audio = apply_wave_stages(audio, None, sos, fx, rt, None, office, mix)  # in place on the staged (or resampled) copy; alias gives a new one
             mel = self.frontend.log_mel(audio)
             for b in (cut < N_FRAMES).nonzero().flatten().tolist():  # rare: cut at a partial segment, pad with the min value
                 c = int(cut[b])
@@ -678,7 +788,7 @@ class GpuMelLoader:
                 audio, y_in, y_out, params, ext, cut = batch[:6]
                 need_aug = bool(params[:, 0].any() or ext.any())
                 staged = [t.to(dev, non_blocking=True) for t in (audio, y_in, y_out, params, ext)]
-                yield self._to_mel(staged, cut, None, need_aug, *self._all_fields(batch), self._office_field(batch))
+                yield self._to_mel(staged, cut, None, need_aug, *self._all_fields(batch), self._office_field(batch), self._mix_field(batch))
             return
         it = iter(self.loader)
         try:
@@ -701,11 +811,13 @@ def get_dataloader(hu_dataset, tokenizer, batch_size: int = 1, n_mels: int = 80,
                    extremes_spec_augment_params: Optional[dict] = None, apply_baseline_aug: bool = False, apply_office_aug: bool = False,
                    apply_advanced_aug: bool = False, time_stretch_min_rate: float = 0.8, time_stretch_max_rate: float = 1.25,
                    bpe_dropout: float = 0.0, drop_last: bool = False, sample_rate: int = SAMPLE_RATE, filter_aug: Optional[dict] = None,
-                   wave_aug: Optional[dict] = None, rate_aug: Optional[dict] = None, office_aug: Optional[dict] = None):
+                   wave_aug: Optional[dict] = None, rate_aug: Optional[dict] = None, office_aug: Optional[dict] = None,
+                   mix_aug: Optional[dict] = None):
     """`filter_aug`: None, or a mapping of FilterAug's keywords (AudioDataset's docstring): the filter augmentation of a TRAINING loader.
     `wave_aug`: None, or a mapping of WaveAug's groups (AudioDataset's docstring): noise, clipping and level changes of a TRAINING loader.
     `rate_aug`: None, or a mapping of RateAug's groups (AudioDataset's docstring): aliasing and pitch shift of a TRAINING loader.
     `office_aug`: None, or a mapping of OfficeAug's groups (AudioDataset's docstring): bit crush and room reverb of a TRAINING loader.
+    `mix_aug`: None, or a mapping of MixAug's groups (AudioDataset's docstring): background noise and loudness normalisation of a TRAINING loader.
     `sample_rate`: the rate of every clip of `hu_dataset` (default 16000).  At another rate the clips are padded to
     30 * sample_rate samples and resampled to 16 kHz on the device (GpuMelLoader); without a device the loader yields the padded
     native-rate clips."""
@@ -716,7 +828,7 @@ def get_dataloader(hu_dataset, tokenizer, batch_size: int = 1, n_mels: int = 80,
                       extremes_spec_augment_params=extremes_spec_augment_params, bpe_dropout=bpe_dropout,
                       apply_baseline_aug=apply_baseline_aug, apply_office_aug=apply_office_aug, apply_advanced_aug=apply_advanced_aug,
                       time_stretch_min_rate=time_stretch_min_rate, time_stretch_max_rate=time_stretch_max_rate, sample_rate=sample_rate,
-                      filter_aug=filter_aug, wave_aug=wave_aug, rate_aug=rate_aug, office_aug=office_aug)
+                      filter_aug=filter_aug, wave_aug=wave_aug, rate_aug=rate_aug, office_aug=office_aug, mix_aug=mix_aug)
     if sampler is not None:
         shuffle = False  # DataLoader does not allow both
     loader = DataLoader(ds, batch_size=batch_size, sampler=sampler, shuffle=shuffle, num_workers=num_workers,

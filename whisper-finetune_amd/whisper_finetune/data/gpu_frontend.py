@@ -326,6 +326,71 @@ def bit_crush(audio, bit_depth, device=None):
     return out if a.dim() == 2 else out[0]
 
 
+# ------------------------------------------------------------------------------------------------- mix effects
+# Loudness (ITU-R BS.1770) and background noise (data/mix_fx.py designs and draws them for the loader; include/wft.h "Loudness and
+# background noise" states the arithmetic).
+from whisper_finetune.data import mix_fx as _MF  # noqa: E402
+from whisper_finetune.data.mix_fx import k_weighting  # noqa: E402,F401  (the meter's two biquads as sos f64 [2, 6])
+
+
+def loudness(audio, sample_rate: int = SAMPLE_RATE, device=None):
+    """The integrated loudness of audio in LUFS, on the device (K.loudness: the ITU-R BS.1770 meter, pyloudnorm's
+    Meter(rate).integrated_loudness for one channel, restated).
+
+    audio: f32, 1-D [n] or 2-D [B, n], a tensor or an array; a host input goes to `device` (default: the current GPU) first.
+    sample_rate: an integer multiple of 10 inside [8000, 384000] (ValueError otherwise).  Returns a float64 device tensor, [B] for 2-D
+    input, a scalar for 1-D; -inf for a row without a block over the gates or shorter than 400 ms (pyloudnorm raises there)."""
+    a, rows = _rows(audio, "loudness")
+    _MF.loudness_hop(sample_rate)  # before the device is touched
+    _, stats = K.loudness(_to_device(rows, device), sample_rate)
+    return stats[:, 0].clone() if a.dim() == 2 else stats[0, 0].clone()
+
+
+def loudness_normalize(audio, target_lufs, sample_rate: int = SAMPLE_RATE, device=None):
+    """audio brought to `target_lufs` by one gain per row, on the device (K.loudness: pyloudnorm's normalize.loudness on the meter's
+    reading — audiomentations' LoudnessNormalization; no clipping afterwards).
+
+    audio: f32, 1-D [n] or 2-D [B, n], a tensor or an array; target_lufs: one value or one per row inside [-200, 200], NaN = "leave
+    the row as it is" (ValueError otherwise).  A row that reads -inf is copied.  Returns a new device tensor of the input's shape."""
+    a, rows = _rows(audio, "loudness_normalize")
+    _MF.loudness_hop(sample_rate)
+    t = K._row_values(target_lufs, rows.shape[0], "loudness_normalize", "targets")
+    out, _ = K.loudness(_to_device(rows, device), sample_rate, t)
+    return out if a.dim() == 2 else out[0]
+
+
+def mix_background(audio, noise, snr_db=None, absolute_rms_db=None, offset=0, device=None):
+    """audio with background noise added at a signal-to-noise ratio or at an absolute RMS level, on the device (K.bg_mix:
+    audiomentations' AddBackgroundNoise, restated; a noise shorter than the audio repeats, a silent one leaves the row as it is).
+
+    audio: f32, 1-D [n] or 2-D [B, n], a tensor or an array.  noise: ONE mono float32 recording for every row (1-D, a tensor or an
+    array) or a ragged list of B recordings.  Exactly one of snr_db / absolute_rms_db: one value in dB or one per row (NaN = "leave
+    the row as it is").  offset: one integer or one per row, where the segment starts inside the noise; it must lie inside the
+    recording and is pulled back to m - n when the recording of m samples is longer than the audio's n (so the segment never wraps),
+    and to 0 when it is not.  ValueError otherwise.  Returns a new device tensor of the input's shape."""
+    a, rows = _rows(audio, "mix_background")
+    B = rows.shape[0]
+    if (snr_db is None) == (absolute_rms_db is None):
+        raise ValueError("mix_background: give exactly one of snr_db and absolute_rms_db")
+    kind = _MF.KIND_ID["snr" if absolute_rms_db is None else "absolute"]
+    db = K._row_values(snr_db if absolute_rms_db is None else absolute_rms_db, B, "mix_background", "dB values")
+    off = K._row_values(offset, B, "mix_background", "offsets")
+    entries = _MF.load_bank(list(noise) if isinstance(noise, (list, tuple)) else [noise])
+    if len(entries) not in (1, B):
+        raise ValueError(f"mix_background: {len(entries)} noise recordings for {B} rows")
+    on = ~np.isnan(db)
+    table = _MF.none_table(B)
+    table[:, 0] = np.where(on, float(kind), 0.0)
+    table[:, 1] = np.arange(B) if len(entries) == B else 0
+    table[:, 2], table[:, 3] = off, np.where(on, db, 0.0)
+    lengths = [e.shape[0] for e in entries]
+    rec = _MF.records_from_table(_MF.check_table(table, lengths))  # before the device is touched
+    rows = _to_device(rows, device)
+    bank, bank_off = _MF.pack_bank(entries)
+    out, _ = K.bg_mix(rows, torch.from_numpy(bank).to(rows.device), torch.from_numpy(bank_off).to(rows.device), rec, lengths=lengths)
+    return out if a.dim() == 2 else out[0]
+
+
 from whisper_finetune.data.transforms import FrequencyMasking, TimeMasking, draw_mask_span  # noqa: E402,F401
 
 

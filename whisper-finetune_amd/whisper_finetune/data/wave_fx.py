@@ -17,7 +17,8 @@ Deviations from the reference's recipe, all of them deliberate:
   * PitchShift's slot in the level group is dropped here (its quarter of the gate is simply "nothing"); the pitch shift has a gate of its
     own in data/rate_fx.py, independent of this group.
   * clipping sits outside the filter group's OneOf: a clip may be filtered AND clipped, which the reference never does.
-  * background-noise files, LoudnessNormalization and AirAbsorption need files or libraries and are not built; Aliasing and PitchShift
+  * AirAbsorption (its coefficient table cannot be restated without audiomentations) is not built; background noise (over a bank of
+    .npy recordings) and LoudnessNormalization live in data/mix_fx.py (csrc/mix.hip), with gates of their own; Aliasing and PitchShift
     are resampling at a per-row rate and live in data/rate_fx.py (csrc/rate.hip).
 """
 from __future__ import annotations

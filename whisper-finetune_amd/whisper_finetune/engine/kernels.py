@@ -1705,6 +1705,152 @@ def bitcrush(audio, bits, n=None, *, out=None):
     return out
 
 
+def _mix_rows(audio, out, who: str):
+    """The shared checks of loudness / bg_mix on audio and out -> audio with usable strides (ValueError before the device is touched)."""
+    audio = _rate_rows(audio, who)
+    B, n_max = audio.shape
+    if audio.stride(1) != 1 or (B > 1 and audio.stride(0) < n_max):
+        if out is audio:
+            raise ValueError(f"{who}: an in-place call needs rows with unit column stride that do not overlap")
+        audio = audio.contiguous()
+    if out is not None and out is not audio:
+        if not torch.is_tensor(out) or out.dtype != F32 or tuple(out.shape) != (B, n_max) or out.stride(1) != 1 or (B > 1 and out.stride(0) < n_max):
+            raise ValueError(f"{who}: out must be f32 [{B}, {n_max}] with unit column stride and rows that do not overlap")
+    return audio
+
+
+def loudness(audio, sample_rate: int = 16000, target=None, n=None, *, out=None):
+    """The ITU-R BS.1770 integrated loudness of every row and, with a target, the gain that brings the row to it
+    (wft_loudness_f32, include/wft.h "Loudness and background noise": pyloudnorm's meter and normalize.loudness, restated).
+
+    audio f32 [B, ld] on the device (stride(1) == 1); sample_rate: an integer multiple of 10 inside [8000, 384000]; target: None
+    (measure only), or one value in LUFS or one per row as HOST numbers, NaN = "leave the row as it is" (not measured either);
+    n i32 [B] on the device (row b covers its first n[b] samples) or None.  out: None (a new tensor), `audio` itself (in place) or an
+    f32 [B, ld] tensor that does not overlap `audio` (ignored without a target).
+    -> (out or None, stats f64 [B, 4] on the device = LUFS, relative gate, blocks over both gates, gain).  A row without a block
+    over both gates, or shorter than 400 ms, reads -inf and is copied.  When no row has a target and an output is wanted nothing is
+    launched.  Every host-side check raises ValueError before the device is touched."""
+    import numpy as np
+
+    from whisper_finetune.data import mix_fx as MF
+
+    measure = target is None
+    audio = _mix_rows(audio, None if measure else out, "loudness")
+    B, n_max = audio.shape
+    hop = MF.loudness_hop(sample_rate)
+    sos = MF.k_weighting(sample_rate)
+    tg = md = None
+    if target is not None:
+        t = _row_values(target, B, "loudness", "targets")
+        on = ~np.isnan(t)
+        if not bool(np.all(np.abs(t[on]) <= MF.DB_LIMIT)):
+            raise ValueError(f"loudness: a target must lie inside [-{MF.DB_LIMIT}, {MF.DB_LIMIT}] LUFS (NaN: leave the row), got {t.tolist()}")
+        t = np.where(on, t, 0.0)
+    _chk(audio, F32, "audio")  # (every ValueError above comes before the device is touched)
+    n = _lengths(n, B, audio.device, "loudness", "n")
+    if not measure and out is not None and out.device != audio.device:
+        raise ValueError("loudness: audio and out must live on the same GPU")
+    if not measure and not bool(on.any()):  # nothing to launch
+        stats = torch.tensor([[-math.inf, -math.inf, 0.0, 1.0]], dtype=torch.float64, device=audio.device).repeat(B, 1)
+        if out is audio:
+            return audio, stats
+        if out is None:
+            out = torch.empty((B, n_max), dtype=F32, device=audio.device)
+        out.copy_(audio)
+        if n is not None:
+            out.masked_fill_(torch.arange(n_max, device=audio.device)[None] >= n.clamp(0, n_max)[:, None], 0.0)
+        return out, stats
+    if target is not None:
+        tg = torch.from_numpy(t).to(audio.device)
+        md = torch.from_numpy(on.astype(np.int32)).to(audio.device)
+    lib = L.load()
+    nbytes = lib.wft_loudness_workspace_bytes(B, n_max, hop)
+    if nbytes < 0:
+        raise ValueError(f"loudness: {B} rows of {n_max} samples at hop {hop} are not supported by wft_loudness_f32")
+    if not measure and out is None:
+        out = torch.empty((B, n_max), dtype=F32, device=audio.device)
+    stats = torch.empty((B, 4), dtype=torch.float64, device=audio.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=audio.device)
+    ld_in = audio.stride(0) if B > 1 else max(audio.stride(0), n_max)
+    ld_out = 0 if measure else (out.stride(0) if B > 1 else max(out.stride(0), n_max))
+    L.check(lib.wft_loudness_f32(_p(audio), ld_in, _p(n), n_max, sos.ctypes.data, hop, _p(tg), _p(md), None if measure else _p(out), ld_out,
+                                 _p(stats), _p(ws), nbytes, B, L.stream_ptr()), "wft_loudness_f32")
+    return (None if measure else out), stats
+
+
+def bg_records(rec, B: int, lengths):
+    """rec -> checked wft_bg_rec records [B] (data/mix_fx.py RECORD_DTYPE).  rec: a numpy structured array [B] of that dtype.
+    lengths: the bank's entry lengths.  ValueError: a kind outside 0..2; on a row with a kind an entry outside the bank, an offset
+    outside its entry, a dB value that is not finite or beyond +-200."""
+    import numpy as np
+
+    from whisper_finetune.data import mix_fx as MF
+
+    a = np.asarray(rec)
+    if a.dtype != MF.RECORD_DTYPE or a.shape != (B,):
+        raise ValueError(f"bg_mix: {B} rows need {B} records of data/mix_fx.py RECORD_DTYPE, got {a.dtype} {tuple(a.shape)}")
+    table = MF.none_table(B)
+    table[:, 0], table[:, 1], table[:, 2], table[:, 3] = a["kind"], a["entry"], a["offset"], a["db"]
+    return MF.records_from_table(MF.check_table(table, lengths))
+
+
+def bg_mix(audio, bank, bank_off, rec, n=None, *, out=None, lengths=None):
+    """A scaled entry of a noise bank added to every row (wft_bg_mix_f32, include/wft.h "Loudness and background noise":
+    audiomentations' AddBackgroundNoise, restated).
+
+    audio f32 [B, ld] on the device (stride(1) == 1); bank f32 [total] and bank_off i64 [K + 1] on the same device (data/mix_fx.py
+    pack_bank); rec: the rows' records on the HOST (bg_records states the form; kind 0 = the row is copied); n i32 [B] on the device
+    or None; lengths: the entry lengths as host integers (None: read back from bank_off, one small copy).  out: None (a new tensor),
+    `audio` itself (in place) or an f32 [B, ld] tensor that does not overlap `audio`.
+    -> (out, stats f64 [B, 3] on the device = clean RMS, noise RMS, scale).  When no row has a kind nothing is launched.
+    Every host-side check raises ValueError before the device is touched."""
+    import numpy as np
+
+    from whisper_finetune.data import mix_fx as MF
+
+    audio = _mix_rows(audio, out, "bg_mix")
+    B, n_max = audio.shape
+    if not torch.is_tensor(bank) or bank.dtype != F32 or bank.dim() != 1 or bank.numel() < 1 or not bank.is_contiguous():
+        raise ValueError("bg_mix: bank must be a contiguous float32 tensor [total]")
+    if not torch.is_tensor(bank_off) or bank_off.dtype != torch.int64 or bank_off.dim() != 1 or bank_off.numel() < 2 or not bank_off.is_contiguous():
+        raise ValueError("bg_mix: bank_off must be a contiguous int64 tensor [K + 1]")
+    K_ = bank_off.numel() - 1
+    if lengths is None:
+        off = bank_off.detach().cpu().numpy()
+        if int(off[0]) != 0 or int(off[-1]) != bank.numel() or bool(np.any(np.diff(off) < 1)):
+            raise ValueError("bg_mix: bank_off must rise from 0 to the bank's size in steps of at least 1")
+        lengths = np.diff(off)
+    if len(lengths) != K_:
+        raise ValueError(f"bg_mix: {len(lengths)} lengths for a bank of {K_} entries")
+    r = bg_records(rec, B, lengths)
+    _chk(audio, F32, "audio")  # (every ValueError above comes before the device is touched)
+    n = _lengths(n, B, audio.device, "bg_mix", "n")
+    if bank.device != audio.device or bank_off.device != audio.device or (out is not None and out.device != audio.device):
+        raise ValueError("bg_mix: audio, bank, bank_off and out must live on the same GPU")
+    if not bool((r["kind"] != 0).any()):  # nothing to launch
+        stats = torch.zeros((B, 3), dtype=torch.float64, device=audio.device)
+        if out is audio:
+            return audio, stats
+        if out is None:
+            out = torch.empty((B, n_max), dtype=F32, device=audio.device)
+        out.copy_(audio)
+        if n is not None:
+            out.masked_fill_(torch.arange(n_max, device=audio.device)[None] >= n.clamp(0, n_max)[:, None], 0.0)
+        return out, stats
+    lib = L.load()
+    nbytes = lib.wft_bg_mix_workspace_bytes(B, n_max)
+    if out is None:
+        out = torch.empty((B, n_max), dtype=F32, device=audio.device)
+    rec_d = torch.from_numpy(r.view("u1").reshape(B, MF.RECORD_DTYPE.itemsize).copy()).to(audio.device)
+    stats = torch.empty((B, 3), dtype=torch.float64, device=audio.device)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=audio.device)
+    ld_in = audio.stride(0) if B > 1 else max(audio.stride(0), n_max)
+    ld_out = out.stride(0) if B > 1 else max(out.stride(0), n_max)
+    L.check(lib.wft_bg_mix_f32(_p(audio), ld_in, _p(n), n_max, _p(bank), _p(bank_off), K_, _p(rec_d), _p(out), ld_out, _p(stats), _p(ws),
+                               nbytes, B, L.stream_ptr()), "wft_bg_mix_f32")
+    return out, stats
+
+
 def mel_to_tmajor(mel, c_pad: int):
     _chk(mel, F32, "mel")
     mel = mel.contiguous()

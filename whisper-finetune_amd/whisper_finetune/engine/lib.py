@@ -173,6 +173,15 @@ FX_NONE, FX_GAUSSIAN_NOISE, FX_GAUSSIAN_SNR = 0, 1, 2  # noise_kind
 FX_CLIPPING = 1  # clip_kind
 FX_GAIN, FX_GAIN_TRANSITION, FX_SHIFT = 1, 2, 3  # level_kind
 
+class BgRec(C.Structure):
+    """Mirror of wft_bg_rec (include/wft.h "Loudness and background noise"): one row's background-noise record, 24 bytes;
+    data/mix_fx.py RECORD_DTYPE is the numpy form of the same layout."""
+
+    _fields_ = [("kind", C.c_int32), ("entry", C.c_int32), ("offset", C.c_int64), ("db", C.c_double)]
+
+
+BG_NONE, BG_SNR, BG_ABSOLUTE = 0, 1, 2  # wft_bg_rec kind
+
 EPI_NONE, EPI_GELU, EPI_DGELU, EPI_GELU_GRAD, EPI_MUL_AUX, EPI_GELU_GRAD8, EPI_MUL_AUX8 = 0, 1, 2, 3, 4, 5, 6
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); this table is also what
@@ -276,6 +285,10 @@ SIGNATURES = {
     "wft_fir_conv_workspace_bytes": [C.c_int, C.c_int],
     "wft_fir_conv_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, C.c_int, c_vp, c_i64, c_vp, c_i64, C.c_int, c_vp],
     "wft_bitcrush_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, C.c_int, c_vp],
+    "wft_loudness_workspace_bytes": [C.c_int, c_i64, C.c_int],
+    "wft_loudness_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, C.c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, C.c_int, c_vp],
+    "wft_bg_mix_workspace_bytes": [C.c_int, c_i64],
+    "wft_bg_mix_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, C.c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, C.c_int, c_vp],
     "wft_adamw_step": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float,
                        C.c_float, C.c_float, C.c_float, c_vp, c_vp],
     "wft_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],
@@ -309,7 +322,7 @@ _RESTYPES = {"wft_last_error": C.c_char_p, "wft_version": C.c_char_p, "wft_layer
              "wft_attn_decode_beam_workspace_bytes": c_i64,
              "wft_dtw_workspace_bytes": c_i64, "wft_time_stretch_workspace_bytes": c_i64,
              "wft_sos_filter_workspace_bytes": c_i64, "wft_wave_fx_workspace_bytes": c_i64,
-             "wft_fir_conv_workspace_bytes": c_i64}
+             "wft_fir_conv_workspace_bytes": c_i64, "wft_loudness_workspace_bytes": c_i64, "wft_bg_mix_workspace_bytes": c_i64}
 
 _lib = None
 

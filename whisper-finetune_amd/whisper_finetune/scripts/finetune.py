@@ -264,7 +264,9 @@ def main(config: dict):
     # stretch or filter; audio_augment.wft_wave_aug (also this project's own: a mapping of data/wave_fx.py WaveAug's groups) switches on
     # additive noise, clipping and level changes, which no dev loader applies either; audio_augment.wft_rate_aug (a mapping of
     # data/rate_fx.py RateAug's groups) switches on aliasing and the pitch shift in the same way; audio_augment.wft_office_aug (a mapping of
-    # data/office_fx.py OfficeAug's groups) the office pipeline's bit crush and room reverb
+    # data/office_fx.py OfficeAug's groups) the office pipeline's bit crush and room reverb; audio_augment.wft_mix_aug (a mapping of
+    # data/mix_fx.py MixAug's groups) the advanced pipeline's background noise (over a noise bank kept on the device) and loudness
+    # normalisation
     aa = aug.get("audio_augment", {})
     n_mels = rt.unwrap_model(model).dims.n_mels
     loader_kw = dict(n_mels=n_mels, no_timestamp_training=d_cfg.get("no_timestamp_training", False),
@@ -280,7 +282,7 @@ def main(config: dict):
                                   time_stretch_min_rate=aa.get("time_stretch", {}).get("min_rate", 0.8),
                                   time_stretch_max_rate=aa.get("time_stretch", {}).get("max_rate", 1.25),
                                   filter_aug=aa.get("wft_filter_aug"), wave_aug=aa.get("wft_wave_aug"), rate_aug=aa.get("wft_rate_aug"),
-                                  office_aug=aa.get("wft_office_aug"),
+                                  office_aug=aa.get("wft_office_aug"), mix_aug=aa.get("wft_mix_aug"),
                                   bpe_dropout=aug.get("bpe_dropout", 0.0), drop_last=drop_last, **loader_kw)
     dev_loaders = {name: get_dataloader(ds, tokenizer, batch_size=d_cfg.get("batch_size_eval", d_cfg["batch_size"]), shuffle=False,
                                         num_workers=d_cfg.get("eval_num_workers", 0), **{**loader_kw, "no_timestamp_training": True,
