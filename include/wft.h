@@ -1130,6 +1130,50 @@ int wft_bg_mix_f32(const float* in, int64_t ld_in, const int32_t* n, int64_t n_m
                    const wft_bg_rec* rec, float* out, int64_t ld_out, double* stats, void* workspace, int64_t workspace_bytes, int B,
                    void* stream);
 
+/* ------------------------------------------------- PCM decode (audio files) */
+/* The sample data of audio files — the `data` chunk of a WAV file, or headerless PCM — to mono f32 over a ragged batch of
+ * recordings, ONE launch (csrc/pcm.hip; DESIGN.md §3 "Audio files").  The header is parsed on the host (data/audio_io.py
+ * parse_wav); the bytes go to the device as they are in the file.  Conventions of libsndfile and scipy.io.wavfile; neither is a
+ * dependency.
+ *
+ * raw: device bytes, ANY alignment; rows: device table of B records, 8-byte aligned; out f32: row b at out + b * ld_out,
+ * ld_out >= n_max; 1 <= B <= 65535; 1 <= n_max <= 2^30; raw_bytes >= 1.  Row b decodes `frames` frames of `channels` interleaved
+ * little-endian samples that start at raw + byte_off:
+ *   1. every channel sample becomes an exact fp64 value:
+ *        WFT_PCM_U8     (b - 128) / 128                    WFT_PCM_S16LE  v / 2^15
+ *        WFT_PCM_S24LE  v / 2^23, three bytes sign-extended WFT_PCM_S32LE  v / 2^31
+ *        WFT_PCM_F32LE, WFT_PCM_F64LE  the value as it is
+ *        WFT_PCM_ALAW, WFT_PCM_ULAW    G.711 expanded to its 16-bit integer in integer arithmetic (no table), then / 2^15:
+ *          u-law: u = ~code; t = (((u & 15) << 3) + 132) << ((u >> 4) & 7); v = (u & 128) ? 132 - t : t - 132
+ *                 (0x00 -> -32124, 0x80 -> +32124, 0x7F and 0xFF -> 0);
+ *          A-law: a = code ^ 0x55; s = (a >> 4) & 7; t = (a & 15) << 4; t = s == 0 ? t + 8 : (t + 264) << (s - 1);
+ *                 v = (a & 128) ? t : -t  (0x55 -> -8, 0xD5 -> +8, 0x2A -> -32256, 0xAA -> +32256).
+ *   2. channel >= 0 takes that channel's value; channel == -1 adds the values in channel order 0 .. C - 1 in fp64 and divides the
+ *      sum by C in fp64 (a division, not a multiplication by a reciprocal).
+ *   3. ONE rounding, fp64 -> f32, to nearest even: F32LE mono or picked comes out bit for bit (finite values, infinities and f32
+ *      subnormals); NaN stays NaN, its payload is unpinned.
+ *   4. out[b, j] = 0 for frames <= j < n_max; columns n_max .. ld_out - 1 are never written.
+ * A row's bits depend on its own bytes and its table row only — not on B, its batch partners or the launch.
+ * Memory safety: the table is device memory, so the kernel checks every row itself: a row decodes as frames = 0 (all zeros) when
+ * format is outside the enum, channels outside 1..8, channel outside -1..channels-1, frames outside 0..n_max, byte_off < 0 or
+ * byte_off + frames * frame_bytes > raw_bytes.  Global loads are 16-byte loads of aligned 16-byte granules; a byte outside
+ * [raw, raw + raw_bytes) is touched only inside a granule that also holds a byte of the row's frames.
+ * wft_pcm_decode_tile(): the output frames per workgroup (the seams the tests walk over).
+ * WFT_ERR_ARG, nothing launched: a null raw / rows / out, raw_bytes < 1, B or n_max outside its range, ld_out < n_max, rows not
+ * 8-byte or out not 4-byte aligned.                                                                                             */
+enum { WFT_PCM_U8 = 0, WFT_PCM_S16LE, WFT_PCM_S24LE, WFT_PCM_S32LE, WFT_PCM_F32LE, WFT_PCM_F64LE, WFT_PCM_ALAW, WFT_PCM_ULAW };
+typedef struct {       /* one row, 32 bytes, in DEVICE memory */
+  int64_t byte_off;    /*  0: first byte of the row's first frame inside raw; any alignment */
+  int32_t frames;      /*  8: frames to decode */
+  int32_t channels;    /* 12: 1..8, interleaved */
+  int32_t format;      /* 16: WFT_PCM_* */
+  int32_t channel;     /* 20: -1 = mean of all channels; 0..channels-1 = that channel */
+  int32_t reserved[2]; /* 24: 0 */
+} wft_pcm_row;
+int wft_pcm_decode_tile(void);
+int wft_pcm_decode_f32(const uint8_t* raw, int64_t raw_bytes, const wft_pcm_row* rows, float* out, int64_t ld_out, int64_t n_max,
+                       int B, void* stream);
+
 /* ---------------------------------------------------------------- AdamW */
 /* torch.optim.AdamW single-tensor step over a flat f32 range
  * (model/optimizer.py:240-262 → optimizer.step() in model_utils.py:122).

@@ -84,8 +84,12 @@
          absolute, in place, over a synthetic bank of four entries) on [32, 480000] and [96, 480000] with every row active, beside
          K.sos_filter at two sections (the same recurrence, with its outputs stored), the log-mel and torch's copy of the same batch.
          No threshold is set.  (--parts mix --out profiles/decode_bench_mix.jsonl)
+  pcm      the audio-file decoder (--batches is not used): wft_pcm_decode_f32 on 32 and 96 clips of 30 s, as S16LE stereo at 48 kHz and
+         as u-law mono at 8 kHz, beside a device-to-device copy that moves the same number of bytes (in plus out), decode + resample
+         beside resample alone, and the host path it replaces (numpy convert + downmix, then the host-to-device copy of f32) as wall
+         time.  No threshold is set.  (--parts pcm --out profiles/decode_bench_pcm.jsonl)
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample,stretch,filter,wavefx,rate,office,mix] [--batches 1,8,32] [--out FILE]
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample,stretch,filter,wavefx,rate,office,mix,pcm] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -1238,6 +1242,82 @@ def bench_mix(batches):
         emit(out_rec)
 
 
+def bench_pcm(batches):
+    """wft_pcm_decode_f32 on 32 and 96 clips of 30 s, as S16LE stereo at 48 kHz and as u-law mono at 8 kHz: ms per call of the decode
+    launch beside a device-to-device copy that moves the same number of bytes (in plus out), decode + resample beside resample
+    alone, and the host path it replaces (numpy convert + downmix, then the host-to-device copy of f32) as wall time."""
+    import numpy as np
+
+    from whisper_finetune.data import audio_io as AIO
+
+    lib = L.load()
+    ulaw = np.zeros(256, dtype=np.float32)
+    for code in range(256):
+        u = ~code & 0xFF
+        t = (((u & 0x0F) << 3) + 0x84) << ((u & 0x70) >> 4)
+        ulaw[code] = ((0x84 - t) if u & 0x80 else (t - 0x84)) / 32768.0
+    for fmt, ch, rate in (("s16le", 2, 48000), ("ulaw", 1, 8000)):
+        frames = 30 * rate
+        fb = ch * AIO.SAMPLE_BYTES[AIO.FORMAT_ID[fmt]]
+        for B in (32, 96):
+            rng = np.random.default_rng(B)
+            host = rng.integers(0, 256, B * frames * fb, dtype=np.uint8)
+            raw = torch.from_numpy(host).to(DEV)
+            rows = [(b * frames * fb, frames, ch, fmt, "mean") for b in range(B)]
+            rec, n_max = AIO.pcm_rows(rows, int(raw.numel()))
+            table = torch.from_numpy(rec.view("u1").reshape(B, 32).copy()).to(DEV)
+            out = torch.empty((B, frames), dtype=torch.float32, device=DEV)
+            traffic = int(raw.numel()) + out.numel() * 4
+            a = torch.empty(traffic // 2, dtype=torch.uint8, device=DEV)
+            c = torch.empty_like(a)
+            res16 = K.resample(out, rate, 16000)
+
+            def launch():
+                L.check(lib.wft_pcm_decode_f32(C.c_void_p(raw.data_ptr()), int(raw.numel()), C.c_void_p(table.data_ptr()), C.c_void_p(out.data_ptr()),
+                                               frames, frames, B, L.stream_ptr()), "wft_pcm_decode_f32")
+
+            arms = {"decode": launch, "decode_wrapper": lambda: K.pcm_decode(raw, rec, n_max, out=out), "copy_same_bytes": lambda: c.copy_(a),
+                    "decode_resample": lambda: (launch(), K.resample(out, rate, 16000, out=res16)),
+                    "resample": lambda: K.resample(out, rate, 16000, out=res16)}
+            res = ab(arms, rounds=5, iters=5)
+
+            def host_path():
+                t0 = time.perf_counter()
+                clips = []
+                for b in range(B):
+                    seg = host[b * frames * fb:(b + 1) * frames * fb]
+                    if fmt == "s16le":
+                        clips.append((seg.view("<i2").reshape(frames, ch).astype(np.float32) / 32768.0).mean(axis=1))
+                    else:
+                        clips.append(ulaw[seg])
+                t1 = time.perf_counter()
+                d = torch.from_numpy(np.stack(clips)).to(DEV)
+                torch.cuda.synchronize()
+                return (t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3, d
+
+            host_path()
+            conv_ms, h2d_ms, _ = host_path()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            torch.from_numpy(host).to(DEV)
+            torch.cuda.synchronize()
+            raw_h2d_ms = (time.perf_counter() - t0) * 1e3
+            out_rec = dict(part="pcm", format=fmt, channels=ch, rate=rate, B=B, frames=frames, raw_bytes=int(raw.numel()), out_bytes=out.numel() * 4,
+                           note="ms per call, medians of 5 alternating rounds of 5 calls; decode: the wft_pcm_decode_f32 launch on a table that is "
+                                "already on the device; decode_wrapper: K.pcm_decode (host row checks and the table upload included); copy_same_bytes: "
+                                "torch's device-to-device copy of (raw_bytes + out_bytes) / 2 bytes, which reads and writes as many bytes as the decode; "
+                                "*_gbps: (raw_bytes + out_bytes) / time; host_*: the path this replaces, wall time of one pass on the host's CPU "
+                                "(numpy convert + downmix per clip in float32, then stack + pageable host-to-device copy of the f32 batch); raw_h2d: "
+                                "the pageable host-to-device copy of the file bytes, which the device path pays instead")
+            for name, (med, mn, spread) in res.items():
+                out_rec[name + "_ms"], out_rec[name + "_min_ms"], out_rec[name + "_spread"] = round(med, 4), round(mn, 4), round(spread, 3)
+            out_rec["decode_gbps"] = round(traffic / (res["decode"][0] * 1e-3) / 1e9, 1)
+            out_rec["copy_same_bytes_gbps"] = round(traffic / (res["copy_same_bytes"][0] * 1e-3) / 1e9, 1)
+            out_rec["host_convert_ms"], out_rec["host_f32_h2d_ms"], out_rec["raw_h2d_ms"] = round(conv_ms, 1), round(h2d_ms, 1), round(raw_h2d_ms, 1)
+            emit(out_rec)
+            del raw, out, a, c, res16
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="attn,gemm,e2e")
@@ -1251,7 +1331,7 @@ def main():
     for part in a.parts.split(","):
         {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": lambda b: (bench_gemm_stream(b), bench_gemm_stream_q8(b)), "e2e_step": bench_e2e_step,
          "gemm_i8": bench_gemm_i8, "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align, "transcribe": bench_transcribe, "resample": bench_resample,
-         "stretch": bench_stretch, "filter": bench_filter, "wavefx": bench_wavefx, "rate": bench_rate, "office": bench_office, "mix": bench_mix}[part](batches)
+         "stretch": bench_stretch, "filter": bench_filter, "wavefx": bench_wavefx, "rate": bench_rate, "office": bench_office, "mix": bench_mix, "pcm": bench_pcm}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

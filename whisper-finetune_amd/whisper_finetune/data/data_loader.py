@@ -54,7 +54,7 @@ from __future__ import annotations
 
 import random
 import re
-from typing import Iterator, List, Optional, Sequence, Tuple
+from typing import Iterator, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -117,12 +117,26 @@ def office_rows(audio, n, office):
 
 class DeviceBank:
     """The noise bank of a MixAug on one device: the entries back to back f32 [total], their offsets i64 [K + 1] and the lengths
-    as host integers.  A bank at another rate (`bank_sample_rate`) is resampled ONCE, entry by entry, through gpu_frontend.resample."""
+    as host integers.  A bank at another rate (`bank_sample_rate`) is resampled ONCE, entry by entry, through gpu_frontend.resample;
+    a {"wav_dir": path} bank is gpu_frontend.load_audio over its files at the loader's rate (one copy of the file bytes, one decode
+    launch, every file resampled from its own rate)."""
 
     def __init__(self, mix_aug: MixAug, device):
         from whisper_finetune.data.gpu_frontend import resample
 
         src = mix_aug.sample_rate if mix_aug.bank_sample_rate is None else mix_aug.bank_sample_rate
+        if isinstance(mix_aug.bank, Mapping) and "wav_dir" in mix_aug.bank:  # .wav files: decoded, downmixed and resampled on the device
+            from whisper_finetune.data.gpu_frontend import load_audio
+            from whisper_finetune.data.mix_fx import wav_bank
+
+            files, channel, _ = wav_bank(mix_aug.bank)
+            parts = load_audio(files, sample_rate=mix_aug.sample_rate, channel=channel, device=device)
+            self.lengths = [int(t.shape[0]) for t in parts]
+            self.bank = torch.cat(parts).contiguous()
+            self.off = torch.tensor(np.concatenate([[0], np.cumsum(self.lengths)]), dtype=torch.int64).to(device)
+            if self.lengths != list(mix_aug.lengths):
+                raise RuntimeError(f"noise bank: the device holds entries of {self.lengths} samples, the draws were made for {list(mix_aug.lengths)}")
+            return
         entries = load_bank(mix_aug.bank, src)
         if src != mix_aug.sample_rate:
             parts = [resample(e, src, device) for e in entries]

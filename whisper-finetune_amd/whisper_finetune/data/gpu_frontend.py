@@ -13,6 +13,7 @@ run reproduces the reference's augmentation decisions exactly.
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -389,6 +390,109 @@ def mix_background(audio, noise, snr_db=None, absolute_rms_db=None, offset=0, de
     bank, bank_off = _MF.pack_bank(entries)
     out, _ = K.bg_mix(rows, torch.from_numpy(bank).to(rows.device), torch.from_numpy(bank_off).to(rows.device), rec, lengths=lengths)
     return out if a.dim() == 2 else out[0]
+
+
+# ------------------------------------------------------------------------------------------------- audio files
+# WAV recordings and headerless PCM, decoded and downmixed on the device (data/audio_io.py parses the header on the host;
+# include/wft.h "PCM decode" states the arithmetic).
+from whisper_finetune.data import audio_io as _AIO  # noqa: E402
+from whisper_finetune.data.audio_io import WavInfo, parse_wav  # noqa: E402,F401
+
+
+def _device(device):
+    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def decode_pcm(raw, format, channels: int = 1, channel="mean", frames=None, byte_offset: int = 0, device=None):
+    """Headerless PCM -> mono f32 [frames] on the device (K.pcm_decode, one launch).
+
+    raw: `bytes`, a `memoryview`, a uint8 array or a uint8 tensor (a host input goes to `device`, default the current GPU, as it is:
+    1 to 8 bytes per sample).  format: "u8", "s16le", "s24le", "s32le", "f32le", "f64le", "alaw" or "ulaw"; channels: 1..8,
+    interleaved; channel: "mean" (the fp64 mean of the channels) or the index of one channel; frames: how many frames to decode
+    (None: all whole frames behind byte_offset); byte_offset: where the first frame starts, any alignment.  Integer formats are
+    scaled by their full range (s16 / 2^15, ...: libsndfile's and scipy's convention).  ValueError before the device is touched."""
+    if torch.is_tensor(raw):
+        buf = raw
+        if buf.dtype != torch.uint8 or buf.dim() != 1:
+            raise ValueError(f"decode_pcm: a tensor must be uint8 [nbytes], got {buf.dtype} {tuple(buf.shape)}")
+    else:
+        try:
+            buf = torch.from_numpy(np.frombuffer(memoryview(raw).cast("B"), dtype=np.uint8).copy())
+        except TypeError:
+            raise ValueError(f"decode_pcm: raw must be bytes, a memoryview, a uint8 array or a uint8 tensor, got {type(raw).__name__}") from None
+    fmt = _AIO.format_id(format)
+    if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)) or not 1 <= channels <= _AIO.MAX_CHANNELS:
+        raise ValueError(f"decode_pcm: channels must be an integer inside [1, {_AIO.MAX_CHANNELS}], got {channels!r}")
+    if isinstance(byte_offset, bool) or not isinstance(byte_offset, (int, np.integer)) or byte_offset < 0:
+        raise ValueError(f"decode_pcm: byte_offset must be a non-negative integer, got {byte_offset!r}")
+    fb = int(channels) * _AIO.SAMPLE_BYTES[fmt]
+    if frames is None:
+        frames = (int(buf.numel()) - int(byte_offset)) // fb
+    if isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or frames < 1:
+        raise ValueError(f"decode_pcm: at least one whole frame is needed, got frames = {frames!r}")
+    rows, n_max = _AIO.pcm_rows([(int(byte_offset), int(frames), int(channels), fmt, channel)], int(buf.numel()))  # before the device is touched
+    buf = buf.contiguous().to(_device(device) if (device is not None or not buf.is_cuda) else buf.device)
+    return K.pcm_decode(buf, rows, n_max)[0]
+
+
+def _decode_files(sources, channel, device, who: str):
+    """WAV sources (paths or bytes) -> (their mono f32 recordings at their own rates as device tensors, their WavInfo): every payload
+    in ONE host byte buffer, one host-to-device copy, one wft_pcm_decode_f32 launch.  A recording that holds a sample that is not
+    finite raises ValueError with its source named."""
+    infos, parts, total = [], [], 0
+    for k, src in enumerate(sources):
+        if not isinstance(src, (str, bytes, bytearray, memoryview)) and not hasattr(src, "__fspath__"):
+            raise ValueError(f"{who}: source {k} must be a path or the bytes of a WAV file, got {type(src).__name__}")
+        info = parse_wav(src)
+        payload = _AIO.read_payload(src, info)
+        infos.append(info)
+        parts.append((total, payload))
+        total = (total + payload.shape[0] + 15) // 16 * 16  # every payload starts on a 16-byte granule of the buffer
+    rows = [(off, info.frames, info.channels, info.format, _AIO.channel_id(channel, info.channels)) for (off, _), info in zip(parts, infos)]
+    rec, n_max = _AIO.pcm_rows(rows, total)
+    host = np.zeros(total, dtype=np.uint8)
+    for off, payload in parts:
+        host[off:off + payload.shape[0]] = payload
+    dev = _device(device)
+    out = K.pcm_decode(torch.from_numpy(host).to(dev), rec, n_max)
+    finite = torch.isfinite(out).all(dim=1).cpu().tolist()
+    for k, ok in enumerate(finite):
+        if not ok:
+            src = sources[k]
+            name = repr(os.fspath(src)) if isinstance(src, (str, os.PathLike)) else f"source {k} ({len(src)} bytes)"
+            raise ValueError(f"{who}: {name} holds a sample that is not finite")
+    return [out[k, :info.frames] for k, info in enumerate(infos)], infos
+
+
+def load_audio(sources, sample_rate: int = SAMPLE_RATE, channel="mean", device=None, return_info: bool = False):
+    """WAV files -> mono f32 recordings at `sample_rate` Hz on the device.
+
+    sources: one path or the `bytes` of one file, or a list of them (data/audio_io.py parse_wav says what is read: RIFF/WAVE with
+    integer PCM, IEEE float, A-law or u-law, 1 to 8 channels).  channel: "mean" or the index of one channel (it must exist in every
+    file).  All payloads go to the device in ONE host-to-device copy, as the bytes of the file, and ONE wft_pcm_decode_f32 launch
+    decodes them; files at another rate are then resampled (K.resample), the files of equal rate and length together, so every
+    result is bit-equal to decoding and resampling that file alone.  A recording with a sample that is not finite raises ValueError
+    naming it.  -> one tensor [n] for one source, a list for a list; with return_info=True (recordings, WavInfo or list of WavInfo)."""
+    single = isinstance(sources, (str, bytes, bytearray, memoryview)) or hasattr(sources, "__fspath__")
+    srcs = [sources] if single else list(sources)
+    if not srcs:
+        raise ValueError("load_audio: at least one source is needed")
+    rate = check_rate(sample_rate)
+    rows, infos = _decode_files(srcs, channel, device, "load_audio")
+    out = [None] * len(srcs)
+    groups = {}
+    for k, info in enumerate(infos):
+        if info.sample_rate == rate:
+            out[k] = rows[k].clone()
+        else:
+            groups.setdefault((info.sample_rate, info.frames), []).append(k)
+    for (src_rate, _), ks in groups.items():
+        res = K.resample(torch.stack([rows[k] for k in ks]), src_rate, rate)
+        for i, k in enumerate(ks):
+            out[k] = res[i] if len(ks) > 1 else res[0]
+    if return_info:
+        return (out[0], infos[0]) if single else (out, infos)
+    return out[0] if single else out
 
 
 from whisper_finetune.data.transforms import FrequencyMasking, TimeMasking, draw_mask_span  # noqa: E402,F401

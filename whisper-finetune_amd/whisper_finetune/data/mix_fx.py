@@ -18,7 +18,8 @@ Deviations from the reference's recipe, all of them deliberate:
   * the offset into a noise entry is drawn as an integer number of samples; audiomentations draws it in seconds.
   * a clip shorter than one 400 ms block is copied; pyloudnorm raises.
   * the meter's block count is stated in integers (pyloudnorm rounds a float).
-  * no `noise_transform`; the bank is mono `.npy` float32 arrays (no audio file decoding), optionally resampled once on the device.
+  * no `noise_transform`; the bank is mono `.npy` float32 arrays, optionally resampled once on the device, or a directory of `.wav`
+    files ({"wav_dir": path}: decoded, downmixed and resampled on the device, data/audio_io.py).
   * pyloudnorm and audiomentations are not dependencies: the methods are restated from their definitions, parity with their binaries
     is unpinned.
 """
@@ -103,8 +104,13 @@ def synthetic_bank(K: int, sample_rate: int = 16000, seed: int = 0):
 def load_bank(bank, sample_rate: int = 16000):
     """The noise bank as a list of mono float32 arrays.  bank: a directory of `.npy` files (taken in sorted name order), a list of
     arrays, or {"synthetic": K[, "seed": s]} (synthetic_bank at `sample_rate`).  ValueError: an empty bank, an entry of length 0, a
-    non-finite sample, an array that is not 1-D float32."""
+    non-finite sample, an array that is not 1-D float32.  A {"wav_dir": path[, "channel": c]} bank has no host form (its files are
+    decoded on the device: data_loader.DeviceBank): it is checked and then refused here; bank_lengths serves it."""
     if isinstance(bank, Mapping):
+        if "wav_dir" in bank:
+            wav_bank(bank)
+            raise ValueError("noise bank: a wav_dir bank is decoded on the device (data_loader.DeviceBank, gpu_frontend.load_audio); "
+                             "bank_lengths reads its lengths from the headers")
         if not set(bank.keys()) <= {"synthetic", "seed"} or "synthetic" not in bank:
             raise ValueError(f"noise bank: a mapping must be {{'synthetic': K[, 'seed': s]}}, got {dict(bank)!r}")
         seed = bank.get("seed", 0)
@@ -144,9 +150,35 @@ def resampled_length(m: int, orig: int, new: int) -> int:
     return -((-m * new) // orig)
 
 
+def wav_bank(bank):
+    """{"wav_dir": path[, "channel": c]} -> (the directory's `.wav` files in name order, channel, their headers): audio_io.parse_wav
+    reads the headers only.  ValueError: what audio_io.wav_dir_files and parse_wav refuse (the file named), a channel a file lacks."""
+    from whisper_finetune.data import audio_io as AIO
+
+    files, channel = AIO.wav_dir_files(bank)
+    infos = []
+    for f in files:
+        try:
+            info = AIO.parse_wav(f)
+        except ValueError as e:
+            raise ValueError(f"noise bank: {f!r}: {e}") from None
+        if channel != "mean" and int(channel) >= info.channels:
+            raise ValueError(f"noise bank: {f!r}: channel {int(channel)} does not exist in a file of {info.channels} channels")
+        infos.append(info)
+    return files, channel, infos
+
+
 def bank_lengths(bank, sample_rate: int = 16000, bank_sample_rate=None):
     """The entry lengths at `sample_rate` (what a loader worker needs for its draws); the bank is loaded once for its checks.
-    bank_sample_rate: the rate of the bank's recordings when it differs (they are resampled once on the device: GpuMelLoader)."""
+    bank_sample_rate: the rate of the bank's recordings when it differs (they are resampled once on the device: GpuMelLoader).
+    A {"wav_dir": ...} bank: every file has its own rate in its header (bank_sample_rate must be None); the lengths come from the
+    headers and resampled_length, no payload is read."""
+    if isinstance(bank, Mapping) and "wav_dir" in bank:
+        if bank_sample_rate is not None:
+            raise ValueError("noise bank: a wav_dir bank takes every file's rate from its header; bank_sample_rate must not be given")
+        if isinstance(sample_rate, bool) or not isinstance(sample_rate, int) or not 1000 <= sample_rate <= 384000:
+            raise ValueError(f"noise bank: sample_rate must be an integer inside [1000, 384000], got {sample_rate!r}")
+        return [int(resampled_length(i.frames, i.sample_rate, sample_rate)) for i in wav_bank(bank)[2]]
     src = sample_rate if bank_sample_rate is None else bank_sample_rate
     if isinstance(src, bool) or not isinstance(src, int) or not 1000 <= src <= 384000:
         raise ValueError(f"noise bank: bank_sample_rate must be an integer inside [1000, 384000], got {bank_sample_rate!r}")
@@ -224,7 +256,8 @@ class MixAug:
     """MixAug(sample_rate, background=None | {p, kinds, bank, bank_sample_rate, min/max_snr_db, min/max_absolute_rms_db},
     loudness=None | {p, min_lufs, max_lufs}); a missing group is off, `{}` = the defaults (the background group needs `bank`):
     p = DEFAULT_P (the reference's marginal rates 0.3 and 0.075), kinds ("absolute", "snr"), the reference's arguments (absolute
-    -30..-10 dB, snr 2..4 dB) and audiomentations' LoudnessNormalization defaults (-31..-13 LUFS).  bank: what load_bank takes; only
+    -30..-10 dB, snr 2..4 dB) and audiomentations' LoudnessNormalization defaults (-31..-13 LUFS).  bank: what load_bank takes, or
+    {"wav_dir": path[, "channel": c]} (a directory of `.wav` files, every file at the rate of its header; no bank_sample_rate); only
     the entry lengths at `sample_rate` are kept (`lengths`), the recordings go to the device once (GpuMelLoader reads `bank` and
     `bank_sample_rate` back from here).
 

@@ -1851,6 +1851,35 @@ def bg_mix(audio, bank, bank_off, rec, n=None, *, out=None, lengths=None):
     return out, stats
 
 
+def pcm_decode(raw, table_rows, n_max=None, out=None):
+    """File bytes -> mono f32 rows, one launch for a ragged batch (wft_pcm_decode_f32, include/wft.h "PCM decode").
+
+    raw: uint8 [nbytes] on the device, contiguous, at any alignment (a view into a larger buffer is fine).  table_rows: the rows on
+    the HOST, (byte_off, frames, channels, format, channel) each — format a name of data/audio_io.py FORMATS or its WFT_PCM_*
+    number, channel "mean" / -1 or 0..channels-1 — or an array of audio_io.ROW_DTYPE.  n_max: the output width (None: the largest
+    frame count).  out: None (a new tensor) or f32 [B, n_max] on raw's device with unit column stride and rows that do not overlap.
+    -> out f32 [B, n_max]: row b holds its decoded frames, zeros behind them.  Every row is checked on the host with the conditions
+    the kernel clamps with (audio_io.pcm_rows): ValueError before the device is touched."""
+    from whisper_finetune.data import audio_io as AIO
+
+    if not torch.is_tensor(raw) or raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < 1 or raw.stride(0) != 1:
+        raise ValueError("pcm_decode: raw must be a contiguous uint8 tensor [nbytes] with at least one byte")
+    rec, n_max = AIO.pcm_rows(table_rows, int(raw.numel()), n_max)
+    B = rec.shape[0]
+    if out is not None and (not torch.is_tensor(out) or out.dtype != F32 or tuple(out.shape) != (B, n_max) or out.stride(1) != 1
+                            or (B > 1 and out.stride(0) < n_max)):
+        raise ValueError(f"pcm_decode: out must be f32 [{B}, {n_max}] with unit column stride and rows that do not overlap")
+    _chk(raw, torch.uint8, "raw")  # (every ValueError above comes before the device is touched)
+    if out is not None and out.device != raw.device:
+        raise ValueError("pcm_decode: raw and out must live on the same GPU")
+    if out is None:
+        out = torch.empty((B, n_max), dtype=F32, device=raw.device)
+    rows_d = torch.from_numpy(rec.view("u1").reshape(B, AIO.ROW_DTYPE.itemsize).copy()).to(raw.device)
+    ld_out = out.stride(0) if B > 1 else max(out.stride(0), n_max)
+    L.check(L.load().wft_pcm_decode_f32(_p(raw), int(raw.numel()), _p(rows_d), _p(out), ld_out, n_max, B, L.stream_ptr()), "wft_pcm_decode_f32")
+    return out
+
+
 def mel_to_tmajor(mel, c_pad: int):
     _chk(mel, F32, "mel")
     mel = mel.contiguous()

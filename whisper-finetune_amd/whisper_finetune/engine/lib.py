@@ -289,6 +289,8 @@ SIGNATURES = {
     "wft_loudness_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, C.c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, C.c_int, c_vp],
     "wft_bg_mix_workspace_bytes": [C.c_int, c_i64],
     "wft_bg_mix_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, C.c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, C.c_int, c_vp],
+    "wft_pcm_decode_tile": [],
+    "wft_pcm_decode_f32": [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, C.c_int, c_vp],
     "wft_adamw_step": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float,
                        C.c_float, C.c_float, C.c_float, c_vp, c_vp],
     "wft_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],

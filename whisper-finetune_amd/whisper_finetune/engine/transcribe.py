@@ -2,8 +2,9 @@
 
 Upstream's `whisper.decoding.detect_language` and the window loop of `whisper.transcribe.transcribe`, restated on the window decoders
 of engine/decode/ (openai-whisper is not a dependency: parity with its binary is unpinned).  Ids go in and ids come out — no
-tokenizer, no audio file decoding: `audio` is mono f32, at 16 kHz or at the `sample_rate` it is declared with (then it is resampled
-on the device first: data/gpu_frontend.py `resample`, csrc/audio.hip `wft_resample_f32`).
+tokenizer: `audio` is mono f32, at 16 kHz or at the `sample_rate` it is declared with (then it is resampled on the device first:
+data/gpu_frontend.py `resample`, csrc/audio.hip `wft_resample_f32`), or a WAV file as a path or `bytes`, decoded and downmixed on
+the device at the rate of its header (data/audio_io.py `parse_wav`, csrc/pcm.hip `wft_pcm_decode_f32`).
 
 Device stages (csrc/transcribe.hip, include/wft.h "Language detection and long-form windows"): `wft_lang_probs` is the tail of
 detect_language, `wft_mel_windows` cuts one zero-padded 30 s window per batch row out of the packed long log-mels; the long log-mel
@@ -198,6 +199,11 @@ def _per_recording(sot_sequence, n: int) -> list:
     return rows
 
 
+def _is_file(a) -> bool:
+    """An entry of `audio` that names or holds a WAV file: a path (str / PathLike) or the bytes of the file."""
+    return isinstance(a, (str, bytes)) or hasattr(a, "__fspath__")
+
+
 def _to_list(v):
     return v.tolist() if hasattr(v, "tolist") else list(v)
 
@@ -296,7 +302,7 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
                suppress_first: Sequence[int] = (), max_initial_timestamp_index: Optional[int] = 50, sync_every: int = 8, step: str = "eager",
                weights: str = "bf16", filters: Optional[torch.Tensor] = None, sample_rate=SAMPLE_RATE, word_timestamps: bool = False, split_words=None,
                prepend_punctuations: str = D.PREPEND_PUNCTUATIONS, append_punctuations: str = D.APPEND_PUNCTUATIONS,
-               hallucination_silence_threshold: Optional[float] = None, _decode=None, _detect=None, _align=None,
+               hallucination_silence_threshold: Optional[float] = None, audio_channel="mean", _decode=None, _detect=None, _align=None,
                _frames: Optional[Sequence[int]] = None) -> list:
     """Upstream's `transcribe()` over one recording or a list of them -> one dict per recording, in input order:
       "language": the detected language token id (None without `language_tokens`), "language_probs": f32 [n_lang] or None,
@@ -307,7 +313,12 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
     audio: one 1-D f32 tensor / array, or a list of them with ragged lengths, at `sample_rate` Hz: one integer for all recordings
     or one per recording, each inside [1000, 384000] (default 16000).  A recording at another rate than 16 kHz is resampled on the
     device (data.gpu_frontend.resample: one wft_resample_f32 launch) before its long log-mel, so its content_frames =
-    ceil(len * 16000 / rate) // 160; at 16 kHz nothing runs differently.  sot_sequence: one sequence for all
+    ceil(len * 16000 / rate) // 160; at 16 kHz nothing runs differently.  An entry may also be a WAV file: a `str` / `PathLike`
+    path or the `bytes` of the file (data/audio_io.py parse_wav says what is read).  The file entries of a call are decoded and
+    downmixed on the device in one launch (data.gpu_frontend: wft_pcm_decode_f32; `audio_channel`: "mean" or the index of one
+    channel), each at the rate of its header, and then go the way of an array declared at that rate — so the result is bit-equal
+    to a call with the decoded arrays and `sample_rate=[...]`.  With a file entry `sample_rate` must be left at its default
+    (ValueError otherwise); array entries of the same list are at 16 kHz.  sot_sequence: one sequence for all
     recordings or one per recording, e.g. (sot, language, task); with `language_tokens` the language is detected on each recording's
     first window (`detect_language`, sot = sot_sequence[0]) and replaces sot_sequence[1] of that recording.  Ids in, ids out:
     `text_of` (ids -> str) is needed only for `compression_ratio_threshold` and for the blank-text rule below.  `no_speech`: the id
@@ -374,7 +385,9 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
     _check_mode(model, "transcribe")
     D._check_mode(model, "transcribe", step, sync_every, weights)
     single = isinstance(audio, torch.Tensor) and audio.dim() == 1 or (not isinstance(audio, (list, tuple)) and getattr(audio, "ndim", 0) == 1)
+    single = single or _is_file(audio)
     audios = [audio] if single else list(audio)
+    files = [k for k, a in enumerate(audios) if _is_file(a)]
     n = len(audios)
     if n < 1:
         raise ValueError("transcribe needs at least one recording")
@@ -399,6 +412,9 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
         raise ValueError(f"sot_sequence of {max(len(s) for s in sots)} ids leaves no room to generate inside n_text_ctx = {n_ctx}")
     from ..data.gpu_frontend import check_rate
 
+    if files and (isinstance(sample_rate, bool) or not isinstance(sample_rate, int) or sample_rate != SAMPLE_RATE):
+        raise ValueError("sample_rate must be left at its default when an entry of audio is a file: a file's rate comes from its header "
+                         "(array entries of the same list are at 16 kHz)")
     if isinstance(sample_rate, (list, tuple)) or getattr(sample_rate, "ndim", 0) == 1:
         rates = [check_rate(r) for r in sample_rate]
         if len(rates) != n:
@@ -423,6 +439,12 @@ def transcribe(model, audio, *, sot_sequence, eot: int, timestamp_begin: Optiona
             from ..data.gpu_frontend import mel_filters
 
             filters = mel_filters(model.dims.n_mels).to(model.device)
+        if files:  # one copy of the file bytes, one decode launch; every file then goes on at the rate of its header
+            from ..data.gpu_frontend import _decode_files
+
+            decoded, infos = _decode_files([audios[k] for k in files], audio_channel, filters.device, "transcribe")
+            for k, a, info in zip(files, decoded, infos):
+                audios[k], rates[k] = a, check_rate(info.sample_rate)
         if any(r != SAMPLE_RATE for r in rates):
             from ..data.gpu_frontend import resample
 

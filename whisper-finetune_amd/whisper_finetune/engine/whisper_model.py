@@ -558,7 +558,8 @@ class Whisper(nn.Module):
         """Upstream's `transcribe()` over one recording or a ragged list of them, ids in and ids out (engine/transcribe.py
         transcribe has the keywords and states the loop; parity with the upstream binary is unpinned).  Recordings are mono f32 at
         16 kHz, or at `sample_rate=` Hz (one integer, or one per recording): those are resampled to 16 kHz on the device first
-        (wft_resample_f32).  The long log-mel once per
+        (wft_resample_f32).  An entry may also be a WAV file, as a path or `bytes`: it is decoded and downmixed on the device
+        (wft_pcm_decode_f32, `audio_channel=`) at the rate of its header; `sample_rate=` must then be left at its default.  The long log-mel once per
         recording, then 30 s windows — cut on the device (wft_mel_windows), decoded with `decode_with_fallback`, advanced by the
         timestamp tokens — with the recordings that are still running batched side by side -> one dict per recording
         ("language", "language_probs", "segments", "tokens", "windows", "truncated").  `word_timestamps=True` with `split_words=`
