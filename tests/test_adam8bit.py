@@ -2,7 +2,11 @@
 
 PARITY UNPINNED: bitsandbytes is not vendored in the reference and not installed here, and the reference's tests hold no vector for
 it.  The oracle (oracle/adam8bit_oracle.py) restates the published block-wise dynamic-quantisation scheme; these tests pin what ANY
-implementation of that scheme must satisfy (CPU), and the HIP kernel against the restatement (GPU)."""
+implementation of that scheme must satisfy (CPU), and the HIP kernel against the restatement (GPU).
+
+The kernel test here is the multi-step trajectory check; the per-element checks of wft_mt_adamw8 (exact codes and absmax for the
+encoder, the decoder and the whole update, bounds per element for p, guarded and unaligned buffers) are tests/_adam8_cases.py,
+tests/test_adam8_host.py and tests/test_adam8_gpu.py."""
 import numpy as np
 import pytest
 import torch
