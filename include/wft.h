@@ -1174,6 +1174,46 @@ int wft_pcm_decode_tile(void);
 int wft_pcm_decode_f32(const uint8_t* raw, int64_t raw_bytes, const wft_pcm_row* rows, float* out, int64_t ld_out, int64_t n_max,
                        int B, void* stream);
 
+/* ---------------------------------------------------------------- Edit counts */
+/* Hits, substitutions, deletions and insertions of the Levenshtein alignment of a ragged batch of (reference, hypothesis) pairs,
+ * ONE launch (csrc/edit.hip; DESIGN.md §3 "Edit counts"): the evaluator's WER / CER (jiwer.wer / jiwer.cer in the reference,
+ * eval/evaluator.py:105-106) and how the errors split.
+ *
+ * A pair is a reference r[0..n) and a hypothesis h[0..m) of int32 symbols; only equality of symbols matters (every int32 value is a
+ * symbol, negative ones and the two extremes included).  Cell (i, j), 0 <= i <= n, 0 <= j <= m, holds a triple (S, D, I) with cost
+ * S + D + I:
+ *   (0, 0) = (0, 0, 0);  (i, 0) = (0, i, 0);  (0, j) = (0, 0, j);
+ *   (i, j) takes the cheapest of three candidates, in this priority on equal cost:
+ *     1. diagonal:  the triple of (i-1, j-1), with S + 1 if r[i-1] != h[j-1];
+ *     2. deletion:  the triple of (i-1, j), with D + 1;
+ *     3. insertion: the triple of (i, j-1), with I + 1.
+ *   A later candidate replaces an earlier one only when it is strictly cheaper.
+ * The result is (H, S, D, I) of cell (n, m) with H = n - S - D.  It follows that S + D + I is the Levenshtein distance (unique),
+ * H + S + D = n and H + S + I = m.  The split into S, D and I is the one this priority selects: jiwer / rapidfuzz may pick another
+ * optimal alignment — that parity is UNPINNED; the rates (S + D + I) / n are pinned.
+ *
+ * sym: device int32 [n_sym], n_sym >= 1; rows: device table of P records, 8-byte aligned; out int32: out[p * ld_out + 0..3] =
+ * H, S, D, I of pair p, ld_out >= 4, no other element of out is written; 1 <= P <= 2^20; 1 <= max_len <= wft_edit_max_len() = 4096
+ * (the cap per side; the launch's LDS is sized from max_len, so pass the longest side of the batch, not the cap).
+ * A row's counts depend on its own symbols and its table row only — not on P, its batch partners or max_len.
+ * Memory safety: the table is device memory, so the kernel checks every row itself: a row writes -1 four times and reads no symbol
+ * when ref_len or hyp_len lies outside [0, max_len], an offset is negative, or offset + length > n_sym.  No table can make the
+ * kernel read outside [sym, sym + n_sym).
+ * wft_edit_threads(): the threads of a workgroup = the cells of a diagonal computed per pass (the seams the tests walk over).
+ * WFT_ERR_ARG, nothing launched: a null sym / rows / out, n_sym < 1, P or max_len outside its range, ld_out < 4, rows not 8-byte or
+ * sym / out not 4-byte aligned.                                                                                                  */
+typedef struct {        /* one pair, 32 bytes, in DEVICE memory */
+  int64_t ref_off;      /*  0: first symbol of the reference inside sym */
+  int64_t hyp_off;      /*  8: first symbol of the hypothesis inside sym */
+  int32_t ref_len;      /* 16: 0 .. max_len */
+  int32_t hyp_len;      /* 20: 0 .. max_len */
+  int32_t reserved[2];  /* 24: 0 */
+} wft_edit_row;
+int wft_edit_max_len(void);
+int wft_edit_threads(void);
+int wft_edit_counts_i32(const int32_t* sym, int64_t n_sym, const wft_edit_row* rows, int32_t* out, int64_t ld_out, int P,
+                        int max_len, void* stream);
+
 /* ---------------------------------------------------------------- AdamW */
 /* torch.optim.AdamW single-tensor step over a flat f32 range
  * (model/optimizer.py:240-262 → optimizer.step() in model_utils.py:122).

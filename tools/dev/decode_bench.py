@@ -88,8 +88,12 @@
          as u-law mono at 8 kHz, beside a device-to-device copy that moves the same number of bytes (in plus out), decode + resample
          beside resample alone, and the host path it replaces (numpy convert + downmix, then the host-to-device copy of f32) as wall
          time.  No threshold is set.  (--parts pcm --out profiles/decode_bench_pcm.jsonl)
+  edit     WER / CER scoring (--batches is not used): P = 32 and P = 2 048 utterances of 20, 60 and 90 words; the Python Levenshtein loops
+         the evaluator ran per utterance (metrics.wer + metrics.cer, wall time on the host's CPU) beside word_error_counts +
+         char_error_counts on the GPU (packing and both copies included) and the wft_edit_counts_i32 launches alone on resident
+         tables.  No threshold is set.  (--parts edit --out profiles/decode_bench_edit.jsonl)
 
-  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample,stretch,filter,wavefx,rate,office,mix,pcm] [--batches 1,8,32] [--out FILE]
+  python tools/dev/decode_bench.py [--parts attn,gemm,e2e,gemm_stream,e2e_step,gemm_i8,beam,ts,sample,align,transcribe,resample,stretch,filter,wavefx,rate,office,mix,pcm,edit] [--batches 1,8,32] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -1318,6 +1322,79 @@ def bench_pcm(batches):
             del raw, out, a, c, res16
 
 
+def bench_edit(batches):
+    """WER / CER scoring of P = 32 and P = 2 048 utterances of 20, 60 and 90 words (synthetic transcripts over a 2 000-word vocabulary,
+    every 7th word of the hypothesis replaced): host_parent = metrics.wer + metrics.cer per pair, the Python Levenshtein loops the
+    evaluator ran per utterance, as wall time on this machine's CPU; device = word_error_counts + char_error_counts on the GPU, packing
+    and both copies included; kernel = the two wft_edit_counts_i32 launches alone on resident tables."""
+    import numpy as np
+
+    from whisper_finetune.eval import metrics as M
+
+    lib = L.load()
+    rng = np.random.default_rng(0)
+    letters = np.array(list("abcdefghijklmnopqrstuvwxyz"))
+    vocab = sorted({"".join(rng.choice(letters, size=int(rng.integers(3, 10)))) for _ in range(2400)})[:2000]
+    HOST_PAIRS = 32  # the host loops cost the same per pair whatever P is: they are timed on 32 pairs and scaled to P
+
+    def resident(refs, hyps):
+        ids, flat, rows = {}, [], []
+        for r, h in zip(refs, hyps):
+            rows.append((len(flat), len(flat) + len(r), len(r), len(h)))
+            flat.extend(ids.setdefault(x, len(ids)) for x in r)
+            flat.extend(ids.setdefault(x, len(ids)) for x in h)
+        rec, max_len = K.edit_rows(np.asarray(rows, dtype=np.int64), len(flat))
+        sym = torch.tensor(flat, dtype=torch.int32, device=DEV)
+        table = torch.from_numpy(rec.view("u1").reshape(len(rows), 32).copy()).to(DEV)
+        out = torch.empty((len(rows), 4), dtype=torch.int32, device=DEV)
+        return lambda: L.check(lib.wft_edit_counts_i32(C.c_void_p(sym.data_ptr()), int(sym.numel()), C.c_void_p(table.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                       4, len(rows), max_len, L.stream_ptr()), "wft_edit_counts_i32"), out
+
+    for words in (20, 60, 90):
+        host_ms = None
+        for P in (32, 2048):
+            prng = np.random.default_rng(words)
+            refs, hyps = [], []
+            for _ in range(P):
+                r = [vocab[i] for i in prng.integers(0, len(vocab), size=words)]
+                h = [vocab[int(prng.integers(0, len(vocab)))] if k % 7 == 6 else w for k, w in enumerate(r)]
+                refs.append(" ".join(r))
+                hyps.append(" ".join(h))
+            chars = sum(len(r) for r in refs) / P
+            if host_ms is None:  # (the first 32 pairs of both P are the same strings)
+                ts = []
+                for _ in range(3):
+                    t0 = time.perf_counter()
+                    for r, h in zip(refs[:HOST_PAIRS], hyps[:HOST_PAIRS]):
+                        M.wer(r, h)
+                        M.cer(r, h)
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                host_ms = statistics.median(ts)
+            launch_w, out_w = resident([r.split() for r in refs], [h.split() for h in hyps])
+            launch_c, out_c = resident([list(r.strip()) for r in refs], [list(h.strip()) for h in hyps])
+
+            def device():
+                return M.word_error_counts(hyps, refs, DEV), M.char_error_counts(hyps, refs, DEV)
+
+            w, c = device()
+            launch_w(), launch_c()
+            assert np.array_equal(w, out_w.cpu().numpy()) and np.array_equal(c, out_c.cpu().numpy())
+            for k in range(min(P, 4)):  # the device's integers give the parent's floats
+                assert int(w[k, 1:].sum()) / int(w[k, :3].sum()) == M.wer(refs[k], hyps[k]) and int(c[k, 1:].sum()) / int(c[k, :3].sum()) == M.cer(refs[k], hyps[k])
+            res = ab({"device": device, "kernel": lambda: (launch_w(), launch_c())}, rounds=5, iters=3)
+            rec = dict(part="edit", words=words, chars=round(chars, 1), P=P, host_pairs_timed=HOST_PAIRS,
+                       note="ms per batch of P utterances. host_parent: metrics.wer + metrics.cer per pair (the Python loops of the parent's evaluator), wall time "
+                            "on this machine's CPU, median of 3 passes over 32 pairs, scaled by P / 32 (the loops cost the same per pair whatever P is); "
+                            "device: word_error_counts + char_error_counts on the GPU — tokenising, the id dict, one packed host-to-device copy, one launch and "
+                            "one copy back for each of the two; kernel: the two wft_edit_counts_i32 launches alone on resident tables; device and kernel: "
+                            "medians of 5 alternating rounds of 3 calls")
+            rec["host_parent_ms"] = round(host_ms * P / HOST_PAIRS, 2)
+            for name, (med, mn, spread) in res.items():
+                rec[name + "_ms"], rec[name + "_min_ms"], rec[name + "_spread"] = round(med, 4), round(mn, 4), round(spread, 3)
+            rec["host_over_device"] = round(rec["host_parent_ms"] / res["device"][0], 1)
+            emit(rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="attn,gemm,e2e")
@@ -1331,7 +1408,8 @@ def main():
     for part in a.parts.split(","):
         {"attn": bench_attn, "gemm": bench_gemm, "e2e": bench_e2e, "gemm_stream": lambda b: (bench_gemm_stream(b), bench_gemm_stream_q8(b)), "e2e_step": bench_e2e_step,
          "gemm_i8": bench_gemm_i8, "beam": bench_beam, "ts": bench_ts, "sample": bench_sample, "align": bench_align, "transcribe": bench_transcribe, "resample": bench_resample,
-         "stretch": bench_stretch, "filter": bench_filter, "wavefx": bench_wavefx, "rate": bench_rate, "office": bench_office, "mix": bench_mix, "pcm": bench_pcm}[part](batches)
+         "stretch": bench_stretch, "filter": bench_filter, "wavefx": bench_wavefx, "rate": bench_rate, "office": bench_office, "mix": bench_mix, "pcm": bench_pcm,
+         "edit": bench_edit}[part](batches)
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text("".join(json.dumps(r) + "\n" for r in OUT))

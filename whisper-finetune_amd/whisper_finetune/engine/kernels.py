@@ -1880,6 +1880,80 @@ def pcm_decode(raw, table_rows, n_max=None, out=None):
     return out
 
 
+EDIT_MAX_LEN = 4096   # wft_edit_max_len(): symbols per side of a pair
+EDIT_MAX_PAIRS = 1 << 20
+
+
+def _edit_row_dtype():
+    import numpy as np
+
+    return np.dtype([("ref_off", "<i8"), ("hyp_off", "<i8"), ("ref_len", "<i4"), ("hyp_len", "<i4"), ("reserved", "<i4", (2,))])
+
+
+EDIT_ROW_DTYPE = _edit_row_dtype()  # numpy form of wft_edit_row (lib.EditRow), 32 bytes
+
+
+def edit_rows(rows, n_sym: int, max_len=None):
+    """A pair table -> (records of EDIT_ROW_DTYPE [P], max_len), checked with the conditions wft_edit_counts_i32 refuses a row with.
+
+    rows: integers [P, 4], (ref_off, hyp_off, ref_len, hyp_len) each, or an EDIT_ROW_DTYPE array.  max_len: the longest side the
+    launch is sized for (None: the longest side of the table, at least 1).  ValueError: no pair or more than 2^20, a length outside
+    0..max_len, a negative offset, offset + length > n_sym, max_len outside 1..4096, n_sym < 1."""
+    import numpy as np
+
+    if isinstance(rows, np.ndarray) and rows.dtype == EDIT_ROW_DTYPE:
+        rec = np.ascontiguousarray(rows).reshape(-1).copy()
+    else:
+        arr = np.asarray(rows)
+        if arr.ndim != 2 or arr.shape[1] != 4 or arr.dtype.kind not in "iu":
+            raise ValueError(f"edit_counts: rows must be integers [P, 4] of (ref_off, hyp_off, ref_len, hyp_len), got shape {arr.shape} of {arr.dtype}")
+        arr = arr.astype(np.int64)
+        if arr.shape[0] and (np.abs(arr[:, 2:]) >= (1 << 31)).any():
+            raise ValueError("edit_counts: a length does not fit its 32-bit field")
+        rec = np.zeros(arr.shape[0], dtype=EDIT_ROW_DTYPE)
+        rec["ref_off"], rec["hyp_off"], rec["ref_len"], rec["hyp_len"] = arr[:, 0], arr[:, 1], arr[:, 2], arr[:, 3]
+    P = rec.shape[0]
+    if not 1 <= P <= EDIT_MAX_PAIRS:
+        raise ValueError(f"edit_counts: 1 to 2^20 pairs per call, got {P}")
+    if isinstance(n_sym, bool) or not isinstance(n_sym, (int, np.integer)) or n_sym < 1:
+        raise ValueError(f"edit_counts: sym must hold at least one symbol, got {n_sym!r}")
+    if max_len is None:
+        max_len = max(1, int(rec["ref_len"].max()), int(rec["hyp_len"].max()))
+    if isinstance(max_len, bool) or not isinstance(max_len, (int, np.integer)) or not 1 <= max_len <= EDIT_MAX_LEN:
+        raise ValueError(f"edit_counts: max_len must be an integer inside [1, {EDIT_MAX_LEN}], got {max_len!r}")
+    for off, ln in (("ref_off", "ref_len"), ("hyp_off", "hyp_len")):
+        o, n = rec[off].astype(np.int64), rec[ln].astype(np.int64)
+        bad = (n < 0) | (n > max_len) | (o < 0) | (o > n_sym - n)
+        if bad.any():
+            p = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"edit_counts: pair {p}: {off} {int(o[p])} with {ln} {int(n[p])} is outside sym [0, {n_sym}) or 0..max_len = {max_len}")
+    return rec, int(max_len)
+
+
+def edit_counts(sym, rows, max_len=None, rows_d=None):
+    """(H, S, D, I) of every (reference, hypothesis) pair, one launch for a ragged batch (wft_edit_counts_i32, include/wft.h "Edit counts").
+
+    sym: int32 [n_sym] on the device, contiguous: the symbols of every reference and hypothesis.  rows: the pairs on the HOST (see
+    edit_rows).  max_len: the longest side the launch is sized for (None: the table's own).  rows_d: None (the table is copied to
+    the device here) or a contiguous int32 [8 P] tensor on sym's device that already holds the records of `rows` — a caller that
+    packs table and symbols into one host buffer pays one copy instead of two (eval/metrics.py edit_counts_batch).
+    -> int32 [P, 4] on sym's device.
+    Every row is checked on the host with the conditions the kernel refuses it with: ValueError before the device is touched."""
+    if not torch.is_tensor(sym) or sym.dtype != torch.int32 or sym.dim() != 1 or sym.numel() < 1 or sym.stride(0) != 1:
+        raise ValueError("edit_counts: sym must be a contiguous int32 tensor [n_sym] with at least one symbol")
+    rec, max_len = edit_rows(rows, int(sym.numel()), max_len)
+    _chk(sym, torch.int32, "sym")
+    P = rec.shape[0]
+    if rows_d is None:
+        rows_d = torch.from_numpy(rec.view("u1").reshape(P, EDIT_ROW_DTYPE.itemsize).copy()).to(sym.device)
+    elif (not torch.is_tensor(rows_d) or rows_d.dtype != torch.int32 or rows_d.dim() != 1 or rows_d.numel() != 8 * P or rows_d.stride(0) != 1
+          or rows_d.device != sym.device or rows_d.data_ptr() % 8):
+        raise ValueError(f"edit_counts: rows_d must be a contiguous, 8-byte aligned int32 tensor [{8 * P}] on sym's device")
+    out = torch.empty((P, 4), dtype=torch.int32, device=sym.device)
+    L.check(L.load().wft_edit_counts_i32(_p(sym), int(sym.numel()), _p(rows_d), _p(out), 4, P, max_len, L.stream_ptr()), "wft_edit_counts_i32")
+    return out
+
+
 def mel_to_tmajor(mel, c_pad: int):
     _chk(mel, F32, "mel")
     mel = mel.contiguous()

@@ -182,6 +182,14 @@ class BgRec(C.Structure):
 
 BG_NONE, BG_SNR, BG_ABSOLUTE = 0, 1, 2  # wft_bg_rec kind
 
+
+class EditRow(C.Structure):
+    """Mirror of wft_edit_row (include/wft.h "Edit counts"): one (reference, hypothesis) pair, 32 bytes; engine/kernels.py
+    EDIT_ROW_DTYPE is the numpy form of the same layout."""
+
+    _fields_ = [("ref_off", c_i64), ("hyp_off", c_i64), ("ref_len", C.c_int32), ("hyp_len", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 EPI_NONE, EPI_GELU, EPI_DGELU, EPI_GELU_GRAD, EPI_MUL_AUX, EPI_GELU_GRAD8, EPI_MUL_AUX8 = 0, 1, 2, 3, 4, 5, 6
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); this table is also what
@@ -291,6 +299,9 @@ SIGNATURES = {
     "wft_bg_mix_f32": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, C.c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, C.c_int, c_vp],
     "wft_pcm_decode_tile": [],
     "wft_pcm_decode_f32": [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, C.c_int, c_vp],
+    "wft_edit_max_len": [],
+    "wft_edit_threads": [],
+    "wft_edit_counts_i32": [c_vp, c_i64, c_vp, c_vp, c_i64, C.c_int, C.c_int, c_vp],
     "wft_adamw_step": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float,
                        C.c_float, C.c_float, C.c_float, c_vp, c_vp],
     "wft_sumsq_f32": [c_vp, c_i64, c_vp, c_vp],

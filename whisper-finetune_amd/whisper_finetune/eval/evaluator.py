@@ -3,8 +3,10 @@ evaluate_single_dataset (:29-131), evaluate_multiple_datasets (:134-183), log_me
 
 The forward is the engine's teacher-forced pass.  Differences that do not change results: the per-token
 reductions (argmax, NLL, log-prob, entropy, confidence) come from one fused kernel over the bf16 logits instead
-of materialising fp32 [B, S, V] logits plus four softmax passes, and predictions are copied to the host ONCE
-per batch instead of once per sample."""
+of materialising fp32 [B, S, V] logits plus four softmax passes, predictions are copied to the host ONCE
+per batch instead of once per sample, and WER / CER of the whole dataset come from one `wft_edit_counts_i32` launch
+after the loader loop (jiwer per utterance in the reference), which also yields the substitution / deletion /
+insertion counts and the corpus-level rates."""
 from __future__ import annotations
 
 from typing import Dict, List, Tuple
@@ -13,8 +15,8 @@ import numpy as np
 import torch
 
 import whisper_finetune.runtime as rt
-from whisper_finetune.eval.metrics import (DatasetMetrics, PerUtteranceMetrics, aggregate_dataset_metrics, cer,
-                                           compute_macro_average, compute_token_metrics, token_metrics_from_stats, wer)
+from whisper_finetune.eval.metrics import (DatasetMetrics, PerUtteranceMetrics, aggregate_dataset_metrics, compute_macro_average,
+                                           compute_token_metrics, edit_counts_batch, token_metrics_from_stats)
 from whisper_finetune.eval.utils import VOCAB_SPECS, decode_prefix_len, normalize_text
 
 
@@ -121,6 +123,31 @@ def _fallback_config(t_config: dict) -> dict:
     return out
 
 
+def _score_utterances(pending, device) -> List[PerUtteranceMetrics]:
+    """WER / CER and the error counts of a whole dataset from its normalised (prediction, reference) pairs: the word pairs and the
+    character pairs of every utterance go through ONE edit_counts_batch call — on a GPU one packed copy, one wft_edit_counts_i32
+    launch and one copy back instead of two Python Levenshtein loops per utterance; a model on the CPU takes the host function.
+    wer = (S + D + I) / (H + S + D): the integers metrics.wer divides, so the floats are the same bits.  An utterance whose normalised
+    reference is empty scores 0.0, carries no counts and stays out of the corpus totals."""
+    scored = [k for k, (_, ref, *_rest) in enumerate(pending) if ref]
+    for k in scored:
+        if not pending[k][1].split():
+            raise ValueError("one or more references are empty strings")  # what metrics.wer says of a blank reference
+    refs = [pending[k][1].split() for k in scored] + [list(pending[k][1].strip()) for k in scored]
+    hyps = [pending[k][0].split() for k in scored] + [list(pending[k][0].strip()) for k in scored]
+    counts = edit_counts_batch(refs, hyps, device).tolist() if scored else []
+    at = {k: (tuple(counts[q]), tuple(counts[len(scored) + q])) for q, k in enumerate(scored)}
+    out = []
+    for k, (pred_n, true_n, nll, lp, ent, conf, ok) in enumerate(pending):
+        if k in at:
+            (wh, ws, wd, wi), (ch, cs, cd, ci) = at[k]
+            out.append(PerUtteranceMetrics(pred_n, true_n, (ws + wd + wi) / (wh + ws + wd), (cs + cd + ci) / (ch + cs + cd), nll, lp, ent, conf, ok,
+                                           word_counts=at[k][0], char_counts=at[k][1]))
+        else:
+            out.append(PerUtteranceMetrics(pred_n, true_n, 0.0, 0.0, nll, lp, ent, conf, ok))
+    return out
+
+
 @torch.no_grad()
 def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict, tokenizer=None) -> DatasetMetrics:
     model = rt.unwrap_model(model)
@@ -142,7 +169,7 @@ def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict
         tokenizer = _default_tokenizer()
     specials = set(tokenizer.special_tokens.values())
     spec = VOCAB_SPECS["v0"]
-    per_utt: List[PerUtteranceMetrics] = []
+    pending = []  # (prediction, reference, the five token statistics) per utterance: WER / CER are scored once, after the loop
     decode_mode = t_config.get("wft_eval_decode")
     if decode_mode not in (None, "greedy", "beam_search", "fallback"):
         raise ValueError(f'wft_eval_decode: "greedy", "beam_search" or "fallback" (absent = the teacher-forced argmax), got {decode_mode!r}')
@@ -206,14 +233,13 @@ def evaluate_single_dataset(model, dataloader, dataset_name: str, t_config: dict
                 nll, lp, ent, conf, ok = token_metrics_from_stats(fused[1][i], pred_host[i], y_host[i])
             else:
                 nll, lp, ent, conf, ok = compute_token_metrics(logits[i], y_out[i], pred[i])
-            per_utt.append(PerUtteranceMetrics(pred_n, true_n, wer(true_n, pred_n) if true_n else 0.0,
-                                               cer(true_n, pred_n) if true_n else 0.0, nll, lp, ent, conf, ok))
+            pending.append((pred_n, true_n, nll, lp, ent, conf, ok))
     if decode_mode is not None and decode_step == "graph":
         # the captured steps pin a KV cache and the cross keys / values per batch size: nothing of that stays behind for training
         from whisper_finetune.engine import decode as _decode
 
         _decode.release_graphs(model)
-    return aggregate_dataset_metrics(per_utt, dataset_name)
+    return aggregate_dataset_metrics(_score_utterances(pending, device), dataset_name)
 
 
 @torch.no_grad()
@@ -237,6 +263,9 @@ def log_metrics_to_wandb(dataset_metrics: Dict[str, DatasetMetrics], macro_metri
     for name, m in dataset_metrics.items():
         for key in ("wer", "cer", "mean_token_nll", "avg_log_prob", "mean_token_entropy", "ece", "num_samples"):
             data[f"{prefix}/{name}/{key}"] = getattr(m, key)
+        for key in ("corpus_wer", "corpus_cer", "word_sub_rate", "word_del_rate", "word_ins_rate"):
+            if getattr(m, key, None) is not None:
+                data[f"{prefix}/{name}/{key}"] = getattr(m, key)
     for key, val in macro_metrics.items():
         data[f"{prefix}/{key}"] = val
     rt.log(data, step=step)
