@@ -691,9 +691,8 @@ class LinearFn(torch.autograd.Function):
         ctx.pre_is_aux8 = pre_codes is not None
         ctx.save_for_backward(x, pre_codes if pre_codes is not None else gelu_pre, None if aux8 is not None else out_pre, *params)
         if cfg.gelu_out:
-            ctx.mark_non_differentiable(y)
-            if aux8 is not None:
-                ctx.mark_non_differentiable(aux8)
+            # (ONE call: a second mark_non_differentiable replaces the first, which left `act` differentiable in the one-byte form)
+            ctx.mark_non_differentiable(*((y,) if aux8 is None else (y, aux8)))
             return out_pre, y, aux8
         return y
 
